@@ -10,6 +10,11 @@ kernel-map build (hash + probe + per-offset bucketing + mask sort) + AB forward 
 through the SparseConv3d module under bf16 autocast, then (N > 1) one RCCL all-reduce of the weight/bias
 gradients.  Inputs (coordinates, features, grad_out, fp32 master weights) are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0 (see README / DESIGN.md §Measurement).
+
+A plain run sets up, warms up, times the K steps and prints the headline.  `--full` adds the in-step per-kernel and
+roofline figures, the map-cached step, the secondary workloads, the CPU baseline and (N > 1) the all-reduce diagnosis.
+`--dump-outputs DIR` writes what the last timed step computed (a fixed sample of the output features and input-feature
+gradient, the weight and bias gradients) as float32 .npy files, for comparing two builds output for output.
 """
 import argparse
 import gc
@@ -307,9 +312,61 @@ def secondary_configs(dev, args):
     return out
 
 
+def headline(args, world, N, value, ms_per_step, second_half):
+    """The result line of a plain run: the headline figure of the timed steps and what the workload was, nothing measured
+    beyond them (`report` adds the `--full` figures to it)."""
+    return {
+        "metric": "M active voxels/sec fwd+bwd, SparseConv3d 64→128 k=3, 1/2/4/8 MI355X",  # = BASELINE.json:metric
+        "value": round(value, 3),
+        "unit": "M voxels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle_steps": args.settle,
+        "ms_per_step": round(ms_per_step, 4),
+        "second_half": second_half,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic",
+        "config": {
+            "workload": f"configs[1]: one {N}-voxel {'uniform (U)' if args.scene == 'uniform' else 'surface-like (S, secondary)'} scene per GPU, SparseConv3d 64->128 k=3, bf16 autocast, "
+                        "kernel-map build + AB fwd + ABt dgrad + AtB wgrad per step",
+            "voxels_per_gpu": N, "coord_order": args.coord_order, "parallelism": f"dp{world} (scene-sharded, grad all-reduce)" + ("" if world == 1 else "; N > 1 has run under gloo on CPU only before this launch (no earlier RCCL measurement exists)"),
+        },
+        "step_includes": "kernel-map build, forward, dgrad, wgrad + bias gradient, SGD parameter update (so both packed bf16 "
+                         "weight images are rebuilt every step)",
+    }
+
+
+def dump_outputs(out_dir, y, feats, conv, rows=65536, seed=0):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 .npy files - the output features and the
+    input-feature gradient on a fixed seeded sample of `rows` rows (the same rows in every run of the same arguments), the
+    output coordinates of those rows, and the whole weight and bias gradients.  ~52 MB at the defaults."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = y.batched_features.batched_tensor
+    n = out.shape[0]
+    pick = np.sort(np.random.default_rng(seed).choice(n, size=min(rows, n), replace=False))
+    idx = torch.from_numpy(pick).to(out.device)
+    arrays = {
+        "out_features": out.index_select(0, idx),
+        "out_coords": y.coordinate_tensor.index_select(0, idx),
+        "grad_features": feats.grad.index_select(0, idx),
+        "grad_weight": conv.weight.grad,
+        "grad_bias": conv.bias.grad,
+    }
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    assert total <= 64_000_000, f"--dump-outputs wrote {total} bytes, over the 64 MB budget"
+
+
 def report(args, dev, world, coords, feats, grad_out, offsets, conv, params, N, value, ms_per_step, second_half):
-    """Rank 0: per-kernel timing IN THE STEP (HIP events on the launch stream between the four phases of an unrolled step,
-    so every kernel meets the cache state it meets in the module step), roofline figures, secondary configs, CPU baseline."""
+    """Rank 0, `--full`: per-kernel timing IN THE STEP (HIP events on the launch stream between the four phases of an unrolled
+    step, so every kernel meets the cache state it meets in the module step), roofline figures, secondary configs, CPU baseline."""
     from warpconvnet_amd import _lib
     from warpconvnet_amd.geometry.coords.search.torch_discrete import generate_kernel_map
     from warpconvnet_amd.geometry.types.voxels import Voxels
@@ -438,26 +495,9 @@ def report(args, dev, world, coords, feats, grad_out, offsets, conv, params, N, 
 
     t_cached = time_events(cached_step, it)
     total_bytes = sum(ab.values())
-    result = {
-        "metric": "M active voxels/sec fwd+bwd, SparseConv3d 64\u2192128 k=3, 1/2/4/8 MI355X",  # = BASELINE.json:metric
-        "value": round(value, 3),
-        "unit": "M voxels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "settle_steps": args.settle,
-        "ms_per_step": round(ms_per_step, 4),
-        "second_half": second_half,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic",
-        "config": {
-            "workload": f"configs[1]: one {N}-voxel {'uniform (U)' if args.scene == 'uniform' else 'surface-like (S, secondary)'} scene per GPU, SparseConv3d 64->128 k=3, bf16 autocast, "
-                        "kernel-map build + AB fwd + ABt dgrad + AtB wgrad per step",
-            "voxels_per_gpu": N, "pairs_per_scene": L, "coord_order": args.coord_order, "parallelism": f"dp{world} (scene-sharded, grad all-reduce)" + ("" if world == 1 else "; N > 1 has run under gloo on CPU only before this launch (no earlier RCCL measurement exists)"),
-        },
+    result = headline(args, world, N, value, ms_per_step, second_half)
+    result["config"]["pairs_per_scene"] = L
+    result.update({
         "roofline": {
             "bound": "hbm", "kernel": names[dom_key], "phase": dom_key, "achieved": dom["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": dom["frac"], "compulsory_frac": dom["compulsory_frac"], "traffic": traffic, "traffic_static": traffic is not None,
@@ -466,8 +506,6 @@ def report(args, dev, world, coords, feats, grad_out, offsets, conv, params, N, 
             "timing": "HIP events on the launch stream between the phases of an unrolled step (map build -> fwd -> wgrad -> dgrad), "
                       "i.e. in-step; the rocprofv3 trace of this command is the newest profiles/r*_kernel_trace_stats.md",
         },
-        "step_includes": "kernel-map build, forward, dgrad, wgrad + bias gradient, SGD parameter update (so both packed bf16 "
-                         "weight images are rebuilt every step)",
         "roofline_all": {names[k]: entry(k) for k in ("fwd", "dgrad", "wgrad", "kmap")},
         "phases_ms": {"kmap": round(t_kmap, 4), "fwd_kernel": round(tk_fwd, 4), "dgrad_kernel": round(tk_dgrad, 4),
                       "wgrad_kernels": round(tk_wgrad, 4), "sum": round(sum(in_step), 4)},
@@ -475,7 +513,7 @@ def report(args, dev, world, coords, feats, grad_out, offsets, conv, params, N, 
         "whole_step_compulsory_hbm_frac": round(sum(comp.values()) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
         "map_cached": {"value": round(N / (t_cached * 1e-3) / 1e6, 3), "unit": "M voxels/s", "ms_per_step": round(t_cached, 4),
                        "note": "same step with the kernel map taken from the geometry's cache (fwd + dgrad + wgrad only)"},
-    }
+    })
     if world == 1 and not args.no_secondary:
         try:
             result["secondary"] = secondary_configs(dev, args)
@@ -507,10 +545,11 @@ def build_workload(args, dev, rank, conv_kwargs=None):
     return coords, feats, grad_out, offsets, conv, [p for p in conv.parameters()]
 
 
-def make_step(dev, world, coords, feats, grad_out, offsets, conv, params, attach=None):
+def make_step(dev, world, coords, feats, grad_out, offsets, conv, params, attach=None, keep=None):
     """The timed step, exactly as `main` runs it: fresh geometry -> kernel map rebuilt -> forward -> backward (dgrad + wgrad) ->
     (N > 1) the flat-bucket gradient all-reduce launched from the autograd hook of the last gradient.  `attach(voxels)` lets
-    the CPU test (tests/test_dist_gloo.py: gloo, explicit backend) supply an oracle-built kernel map; None on the GPU."""
+    the CPU test (tests/test_dist_gloo.py: gloo, explicit backend) supply an oracle-built kernel map; None on the GPU.
+    `keep` (a dict, `--dump-outputs` only): the step leaves its output geometry in `keep["y"]`."""
     from warpconvnet_amd.dist import GradientBuckets
     from warpconvnet_amd.geometry.types.voxels import Voxels
 
@@ -532,6 +571,8 @@ def make_step(dev, world, coords, feats, grad_out, offsets, conv, params, attach
         else:
             y = conv(x)
         y.batched_features.batched_tensor.backward(grad_out)
+        if keep is not None:
+            keep["y"] = y
         if buckets is not None:
             buckets.finish()
         # the parameter update of a training step (plain SGD, lr 1e-6): bumps the parameters' version counters, so the packed
@@ -626,9 +667,16 @@ def parse_args(argv=None):
                     help="extra untimed steps in front of the warm-up (reported as settle_steps): a fresh process on a fresh box "
                          "runs its first ~60 steps at cold clocks / first-use allocator cost")
     ap.add_argument("--voxels", type=int, default=1_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry: in-step per-kernel times and roofline "
+                         "figures, the map-cached step, the secondary workloads, the CPU baseline and (N > 1) the all-reduce "
+                         "diagnosis.  Off: set up, warm up, time the steps, print the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (output features, gradients) to DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000)  # the whole configs[1] scene: ~10-15 s of CPU work
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the surface-scene / MinkUNet-14 / PointConv secondary timings")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="(--full) skip the surface-scene / MinkUNet-14 / PointConv secondary timings")
     ap.add_argument("--coord-order", choices=["generator", "block"], default="generator",
                     help="generator: rows in the order the reference's generator emits them (the headline workload); "
                          "block: the same scene with rows sorted by 16^3 block then x,y,z (what a voxelised scan looks like) - "
@@ -636,7 +684,10 @@ def parse_args(argv=None):
     ap.add_argument("--scene", choices=["uniform", "surface"], default="uniform",
                     help="uniform: the reference-style generator U the metric is quoted on; surface: generator S of "
                          "SURVEY.md §8d (ScanNet-like sheets, ~2x the pairs per voxel) - a secondary workload")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -665,18 +716,25 @@ def main():
     gc.collect()
     gc.freeze()
     # N > 1: persistent flat gradient bucket, the all-reduce is launched from the autograd hook of the last gradient
-    step, _ = make_step(dev, world, coords, feats, grad_out, offsets, conv, params)
+    keep = {} if args.dump_outputs else None
+    step, _ = make_step(dev, world, coords, feats, grad_out, offsets, conv, params, keep=keep)
     elapsed, ms_half = timed_loop(step, args, dev, world)
     second_half = {"value": round(N * world / (ms_half * 1e-3) / 1e6, 3), "ms_per_step": round(ms_half, 4),
                    "steps": args.steps - args.steps // 2,
                    "note": "rank 0's last K/2 timed steps between two HIP events (steady state; the headline value covers all K)"}
     ms_per_step = elapsed / args.steps * 1e3
     value = N * world * args.steps / elapsed / 1e6
+    if keep is not None and rank == 0:
+        # before `--full` runs anything else: its figures run steps of their own, which overwrite the gradients
+        dump_outputs(args.dump_outputs, keep.pop("y"), feats, conv)
 
-    diag = multi_gpu_diag(dev, rank, world, params) if world > 1 else None
+    diag = multi_gpu_diag(dev, rank, world, params) if world > 1 and args.full else None
     result = None
     if rank == 0:
-        result = report(args, dev, world, coords, feats, grad_out, offsets, conv, params, N, value, ms_per_step, second_half)
+        if args.full:
+            result = report(args, dev, world, coords, feats, grad_out, offsets, conv, params, N, value, ms_per_step, second_half)
+        else:
+            result = headline(args, world, N, value, ms_per_step, second_half)
         if diag is not None:
             result["multi_gpu"] = diag
     if world > 1:

@@ -10,7 +10,7 @@ fi
 for scene in $SCENES; do
 for cs in $MODES; do
   f=gpurun_out/ab/bench_${scene}_cs$cs.json
-  WARPCONVNET_AMD_GEMM_CS=$cs python bench.py --steps 40 --warmup 5 --no-secondary --no-cpu-baseline --scene $scene > $f 2> gpurun_out/ab/bench_${scene}_cs$cs.err
+  WARPCONVNET_AMD_GEMM_CS=$cs python bench.py --full --steps 40 --warmup 5 --no-secondary --no-cpu-baseline --scene $scene > $f 2> ${f%.json}.err
   python - "$f" "$scene cs=$cs" <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/prof
   echo "== parity $lib"; WARPCONVNET_AMD_LIB=$PWD/warpconvnet_amd/csrc/$lib python -m pytest tests/test_gpu_conv.py -x -q -k "mfma or oracle or golden or compact" 2>&1 | tail -2
 done
 [ -n "$COUNTERS_ONLY" ] || bash tools/ab_libs.sh "uniform surface" 2 - libwcn_abl_pair.so libwcn_abl_wfirst.so
-CMD="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+CMD="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
 for lib in - libwcn_abl_pair.so libwcn_abl_wfirst.so; do
   tag=$(basename $lib .so); [ "$lib" = "-" ] && tag=shipped
   if [ "$lib" = "-" ]; then unset WARPCONVNET_AMD_LIB; else export WARPCONVNET_AMD_LIB=$PWD/warpconvnet_amd/csrc/$lib; fi

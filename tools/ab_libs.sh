@@ -6,7 +6,7 @@ for scene in $SCENES; do for r in $(seq $ROUNDS); do for lib in "$@"; do
   tag=$(basename $lib .so)
   f=gpurun_out/ab/libs_${scene}_${tag}_$r.json
   if [ "$lib" = "-" ]; then unset WARPCONVNET_AMD_LIB; else export WARPCONVNET_AMD_LIB=$PWD/warpconvnet_amd/csrc/$lib; fi
-  python bench.py --steps 60 --warmup 5 --no-secondary --no-cpu-baseline --scene $scene > $f 2> ${f%.json}.err
+  python bench.py --full --steps 60 --warmup 5 --no-secondary --no-cpu-baseline --scene $scene > $f 2> ${f%.json}.err
   python - "$f" "$scene $tag" <<'PY'
 import json,sys
 try:

@@ -111,7 +111,7 @@ def traffic(fetch_db, write_db):
     # (round 3: the 64 -> 128 forward and the 128 -> 64 dgrad run the channel-split kernels, template <T, CO, RBW, WR, MINW>)
     keys = {"fwd": "gather_gemm_cs_kernelIDF16bLi128E", "dgrad": "gather_gemm_cs_kernelIDF16bLi64E",
             "wgrad": "wgrad_mfma_kernelIDF16bLi64ELi128ELb1"}
-    out = {"unit": "bytes per launch", "fetch_correction": 2.0, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `python bench.py --steps 20 --warmup 5 --no-cpu-baseline`"}
+    out = {"unit": "bytes per launch", "fetch_correction": 2.0, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline`"}
     for name, sub in keys.items():
         fk = [v for k, v in f.items() if sub in k]
         wk = [v for k, v in w.items() if sub in k]
