@@ -602,6 +602,30 @@ int wcn_conv_bn_backward_ld(const void* grad_out, int64_t grad_out_ld, const voi
                             int32_t cin, int32_t cout, int32_t num_offsets, int32_t dtype, void* bn_workspace,
                             size_t bn_workspace_bytes, wcn_stream_t stream);
 
+/* ---- block-diagonal ("varlen") multi-head attention over a packed qkv tensor ----------------------------------------------
+ * The attention core of PatchAttention (reference nn/modules/attention.py:496 calls flash_attn_varlen_qkvpacked_func through
+ * nn/functional/flash_attn_utils.py:15-82); same contract without dropout, causal mask or window.  `qkv` [total, 3, heads,
+ * head_dim] contiguous (slot 0 = Q, 1 = K, 2 = V), `cu_seqlens` int32 [num_seqs + 1], device: sequence s is the rows
+ * [cu[s], cu[s+1]), a row attends to the rows of its own sequence only.  `max_seqlen` >= every length (it sizes the grid; the
+ * host never reads cu_seqlens).  Rows outside every sequence are not written.
+ *   wcn_attn_varlen_supported        host-only: 1 if head_dim in {16, 32, 64} and dtype is WCN_F16 / WCN_BF16.
+ *   wcn_attn_varlen_workspace_bytes  host-only: the backward's fp32 [total, heads] workspace (delta = rowsum(dO * O)).
+ *   wcn_attn_varlen_fwd              out [total, heads, head_dim] (dtype), lse [total, heads] fp32 = ln sum_k exp(scale q.k).
+ *   wcn_attn_varlen_bwd              dqkv [total, 3, heads, head_dim] (dtype) from dout / out [total, heads, head_dim] and the
+ *                                    forward's lse; every row of every sequence written exactly once, fixed-order sums (two
+ *                                    calls give bit-identical dqkv).
+ * Arguments are checked before any launch: unsupported head_dim / dtype -> WCN_ERROR_UNSUPPORTED_CONFIG; heads < 1,
+ * max_seqlen < 0, negative sizes, null pointers with total > 0, a short workspace -> WCN_ERROR_INVALID_PARAMETERS. */
+int wcn_attn_varlen_supported(int32_t head_dim, int32_t dtype);
+size_t wcn_attn_varlen_workspace_bytes(int64_t total, int32_t heads);
+int wcn_attn_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, int64_t num_seqs, int64_t total, int32_t heads,
+                        int32_t head_dim, int32_t max_seqlen, float softmax_scale, int32_t dtype, void* out, float* lse,
+                        wcn_stream_t stream);
+int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, const float* lse, const int32_t* cu_seqlens,
+                        int64_t num_seqs, int64_t total, int32_t heads, int32_t head_dim, int32_t max_seqlen,
+                        float softmax_scale, int32_t dtype, void* dqkv, void* workspace, size_t workspace_bytes,
+                        wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

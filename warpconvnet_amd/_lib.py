@@ -235,6 +235,18 @@ SIGNATURES = {
                                                                c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                                c_size_t, c_void_p],
     ),
+    "wcn_attn_varlen_supported": (c_int, [c_int32, c_int32]),
+    "wcn_attn_varlen_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "wcn_attn_varlen_fwd": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p,
+         c_void_p],
+    ),
+    "wcn_attn_varlen_bwd": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_float,
+         c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "wcn_mfma_wgrad_bias_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_conv_wgrad_bias": (
         c_int,

@@ -1,3 +1,4 @@
+from .attention import BatchedLinear, FeedForward, LayerNorm, PatchAttention, TransformerBlock
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
 from .mlp import MLPBlock
@@ -10,4 +11,5 @@ from .sparse_conv_depth import SparseDepthwiseConv2d, SparseDepthwiseConv3d, Spa
 
 __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Sequential", "SparseConv2d", "SparseConv3d", "SpatiallySparseConv",
            "SparseDepthwiseConv2d", "SparseDepthwiseConv3d", "SpatiallySparseDepthwiseConv",
-           "BatchNorm", "NormalizationBase", "FusedSparseConvBlock", "GlobalPool", "SparseMaxPool", "SparseMinPool", "SparsePool", "SparseUnpool"]
+           "BatchNorm", "NormalizationBase", "FusedSparseConvBlock", "GlobalPool", "SparseMaxPool", "SparseMinPool", "SparsePool", "SparseUnpool",
+           "BatchedLinear", "FeedForward", "LayerNorm", "PatchAttention", "TransformerBlock"]
