@@ -120,6 +120,29 @@ def _hip_gather(inp: Tensor, weight: Tensor, tbl: Tensor, n_out: int, K: int, fl
     return out
 
 
+def _dgrad_duplicates(g: Tensor, w: Tensor, tbl: Tensor, n: int) -> Tensor:
+    """fp32 input gradient of a SUBMANIFOLD map over repeated coordinates (odd kernel, stride 1) on the gather kernel, in a
+    fixed summation order.  Every row of a coordinate has the same neighbours (the smallest row - the "winner" - of each
+    neighbouring coordinate) and only winners appear as inputs, so with ``g'[v] = sum of g over the rows at v's coordinate``
+    the gradient of a winner row is the k-flipped gather ``dx[i] = sum_k g'[nbr[i][K-1-k]] * w[k]`` and every other row gets
+    zero (the dense-weight counterpart is ``hip_gemm._dgrad_duplicates``).  ``g'`` is itself a gather: a table of the rows of
+    each winner's coordinate in ascending order, against unit weights."""
+    K, C = w.shape
+    dev = g.device
+    winner = tbl[:, K // 2].long()  # centre neighbour of a row: the winner of its own coordinate
+    order = torch.sort(winner, stable=True).indices
+    counts = torch.bincount(winner, minlength=n)
+    m = int(counts.max())
+    start = torch.cumsum(counts, 0) - counts
+    grouped = winner[order]
+    rows = torch.full((n, _lib.lib().wcn_kmap_row_pitch(m)), -1, dtype=torch.int32, device=dev)
+    rows[grouped, torch.arange(n, device=dev) - start[grouped]] = order.to(torch.int32)
+    gsum = _hip_gather(g.float(), torch.ones((m, C), dtype=torch.float32, device=dev), rows, n, m, False)
+    dx = _hip_gather(gsum, w.float().contiguous(), tbl, n, K, True)
+    keep = (winner == torch.arange(n, device=dev)).unsqueeze(1)
+    return torch.where(keep, dx, torch.zeros((), dtype=dx.dtype, device=dev))
+
+
 def _implicit_depthwise_forward_logic(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult, num_out_coords: int,
                                       compute_dtype: Optional[torch.dtype] = None) -> Tensor:
     dt = compute_dtype or in_features.dtype
@@ -141,9 +164,12 @@ def _implicit_depthwise_backward_logic(grad_output: Tensor, in_features: Tensor,
     fwd_tbl = _tables(kernel_map, n_in, n_out)
     dx = dw = None
     if needs[0]:
-        if getattr(kernel_map, "_has_duplicates", False):
-            # repeated coordinates (degenerate input): several output rows pair with one input row per offset, which the
-            # one-slot-per-(row, offset) tables cannot express -> scatter-add over the pair lists (reference formulation)
+        if getattr(kernel_map, "_dup_symmetric", False):
+            dx = _dgrad_duplicates(g, w, fwd_tbl, n_in)
+        elif getattr(kernel_map, "_has_duplicates", False):
+            # repeated coordinates under an even kernel (degenerate input): several output rows pair with one input row per
+            # offset, which the one-slot-per-(row, offset) tables cannot express -> scatter-add over the pair lists (reference
+            # formulation; atomic, so not bit-reproducible)
             dxf = torch.zeros(n_in, C, dtype=torch.float32, device=dev)
             for k in range(K):
                 in_map, out_map = kernel_map[k]
