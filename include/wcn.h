@@ -626,6 +626,49 @@ int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, cons
                         float softmax_scale, int32_t dtype, void* dqkv, void* workspace, size_t workspace_bytes,
                         wcn_stream_t stream);
 
+/* ---- sparse resampling over a CHILD TABLE (ABI 6, additions only) -----------------------------------------------------------
+ * Space-to-channel / channel-to-space / subdivide / up- and down-sampling / prune of sparse VAEs and generative decoders
+ * (reference, pure torch: nn/modules/sparse_resample.py:44-287, nn/modules/prune.py, nn/functional/sparse_ops.py:33-65).
+ * `tbl` [n_parent][pitch] int32: tbl[p][col] = the fine row that is a child of coarse row p, or -1; n_per = factor^3 children,
+ * factor in {2, 3, 4} (and factor = n_per = 1: the compaction of prune); larger factors -> WCN_ERROR_UNSUPPORTED_CONFIG.
+ * The CHANNEL slot of the child at (x, y, z) is the reference's s = (x mod f) + f (y mod f) + f^2 (z mod f)
+ * (sparse_resample.py:202-203).  `slot_order` names the column order of the table: WCN_SLOT_X_FASTEST col = s (tables of
+ * wcn_resample_expand), WCN_SLOT_Z_FASTEST col = ((x mod f) f + (y mod f)) f + (z mod f) - the kernel-offset order of
+ * wcn_cells_stride_emit and of a kernel map with kernel_size == stride == f (pitch = wcn_kmap_row_pitch(n_per)).
+ * Feature rows are `dtype` (f32 / f16 / bf16), any channels >= 1: 16-B pieces when channels * sizeof(T) is a multiple of 16 and
+ * the buffers are 16-B aligned, single elements otherwise.  Pure copies: deterministic, no atomics, bit-exact.
+ *   wcn_resample_pack    dst [n_parent][n_per * channels]: dst[p][s*C .. (s+1)*C) = src[tbl[p][col(s)]] or 0 where the child
+ *                        is absent - ONE pass, the zeros are written by the same kernel (the reference fills zeros, then
+ *                        scatters).  Forward of space-to-channel, backward of channel-to-space / prune.  src [n_src][channels].
+ *   wcn_resample_unpack  dst [n_dst][channels]: dst[tbl[p][col(s)]] = src[p][s*C .. (s+1)*C) for every present child; rows of
+ *                        dst no entry names are not written.  Forward of channel-to-space / prune, backward of
+ *                        space-to-channel.  broadcast = 1: src is [n_parent][channels] and every child receives src[p] - the
+ *                        feature side of up-sampling and subdivision; tbl = NULL: the dense subdivision, child s of p is row
+ *                        p * n_per + s.
+ *   wcn_resample_expand  the subdivision a mask describes.  parents [n_parent][4] (b, x, y, z), batch-sorted; mask
+ *                        [n_parent][n_per], mask_dtype 0 / 1 / 2 = wcn_dtype ("non-zero = keep"), 3 = bytes (a bool tensor);
+ *                        NULL = keep all.  Children are ordered by parent row, then ascending column; the child of column
+ *                        j sits at factor * parent + (j % f, j / f % f, j / f^2) (WCN_SLOT_X_FASTEST) or
+ *                        + (j / f^2, j / f % f, j % f) (WCN_SLOT_Z_FASTEST, the order of the reference's SparseSubdivide).
+ *                        Two phases on one workspace (wcn_resample_expand_workspace(n_parent) bytes), selected by the
+ *                        outputs given: out_offsets != NULL: count + exclusive scan, out_offsets [num_batches + 1] =
+ *                        children of the parents with a batch index < b (the last entry is their number M: the ONE host
+ *                        read); child_coords / tbl != NULL: emit child_coords [M][4] and tbl [n_parent][pitch] (col = mask
+ *                        column) from the counts a phase-1 call left in the workspace; `capacity` = rows of child_coords,
+ *                        nothing past it is written.  Both in one call when the caller sizes child_coords by the bound
+ *                        n_parent * n_per. */
+enum wcn_slot_order { WCN_SLOT_X_FASTEST = 0, WCN_SLOT_Z_FASTEST = 1 };
+int wcn_resample_pack(const void* src, const int32_t* tbl, int64_t n_src, int64_t n_parent, int32_t channels, int32_t n_per,
+                      int32_t factor, int32_t pitch, int32_t slot_order, int32_t dtype, void* dst, wcn_stream_t stream);
+int wcn_resample_unpack(const void* src, const int32_t* tbl, int64_t n_parent, int64_t n_dst, int32_t channels, int32_t n_per,
+                        int32_t factor, int32_t pitch, int32_t slot_order, int32_t broadcast, int32_t dtype, void* dst,
+                        wcn_stream_t stream);
+size_t wcn_resample_expand_workspace(int64_t n_parent);
+int wcn_resample_expand(const int32_t* parents, const void* mask, int32_t mask_dtype, int64_t n_parent, int32_t n_per,
+                        int32_t factor, int32_t slot_order, int32_t num_batches, void* workspace, size_t workspace_bytes,
+                        int32_t* out_offsets, int64_t capacity, int32_t* child_coords, int32_t* tbl, int32_t pitch,
+                        wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ WCN_ALGO_AUTO, WCN_ALGO_REF, WCN_ALGO_MFMA = 0, 1, 2
 WCN_FLAG_TABLE_FULL, WCN_FLAG_COORD_RANGE, WCN_FLAG_PAIR_OVERFLOW, WCN_FLAG_DUPLICATE_COORD = 1, 2, 4, 8
 WCN_FLAG_NEED_STRICT = 16
 WCN_FLAG_ROW_OVERFLOW = 32
+WCN_SLOT_X_FASTEST, WCN_SLOT_Z_FASTEST = 0, 1  # column order of a child table (csrc/resample.hip)
+WCN_MASK_U8 = 3  # mask_dtype of wcn_resample_expand: a bool / uint8 mask
 
 _I32P = c_void_p  # all pointers travel as void*
 _3I = c_int32 * 3
@@ -247,6 +249,13 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_float,
          c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_resample_pack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                  c_void_p, c_void_p]),
+    "wcn_resample_unpack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_int32, c_void_p, c_void_p]),
+    "wcn_resample_expand_workspace": (c_size_t, [c_int64]),
+    "wcn_resample_expand": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t,
+                                    c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     "wcn_mfma_wgrad_bias_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_conv_wgrad_bias": (
         c_int,
