@@ -1,5 +1,5 @@
 // conv_api.hip - C-ABI entry points of the sparse-conv GEMMs (include/wcn.h); dispatch only.
-#include "wcn_common.h"
+#include "gather_gemm.h"  // the gather-GEMM families: family decision, launchers, weight packer
 
 namespace wcn {
 // conv_ref.hip
@@ -9,24 +9,6 @@ size_t colsum_workspace(int c);
 int colsum(const void* in, int64_t n, int c, int dtype, float* out, void* workspace, size_t workspace_bytes, hipStream_t s);
 int conv_wgrad_ref(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                    const int32_t* offsets, int cin, int cout, int K, int dtype, hipStream_t s);
-// conv_mfma.hip
-bool mfma_gather_supported(int cin, int cout, int K, int dtype);
-bool gather_gemm_cs_supported(int cin, int cout, int K, int dtype);  // conv_mfma_cs.hip
-int conv_gather_gemm_mfma(const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
-                          const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
-                          float* out32, hipStream_t s);
-int pack_weight_mfma(const void* w, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                     hipStream_t s);
-int pack_weight_cs_pair(const float* w, int K, int cin, int cout, int dtype, int flip_dgrad, void* packed_fwd, void* packed_dgrad,
-                        hipStream_t s);
-int pack_weight_mfma_f32(const float* w, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                         hipStream_t s);
-bool mfma_grouped_supported(int cin, int cout, int K, int dtype);
-int conv_gather_gemm_grouped(const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
-                             const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int groups,
-                             int K, int dtype, hipStream_t s);
-int pack_weight_grouped(const void* w, int w_is_f32, int K, int groups, int cin, int cout, int dtype, int transpose, int flip,
-                        void* packed, hipStream_t s);
 // wgrad_mfma.hip
 bool mfma_wgrad_supported(int cin, int cout, int dtype);
 size_t wgrad_mfma_workspace(int K, int cin, int cout);
@@ -72,7 +54,9 @@ int wcn_mfma_wgrad_supported(int32_t cin, int32_t cout, int32_t dtype) {
 size_t wcn_packed_weight_bytes(int32_t num_offsets, int32_t cin, int32_t cout, int32_t dtype, int32_t transpose) {
   (void)transpose;  // cin / cout are the kernel-side roles already (reduce over cin, produce cout)
   if (num_offsets < 1 || cin < 1 || cout < 1 || !dtype_ok(dtype)) return 0;
-  // the channel-split kernels reduce in 64-channel chunks: a trailing 32-channel chunk is zero-padded in the image
+  // Upper bound over the three layouts (gather_gemm_family), whatever the family: the channel-split kernels reduce in
+  // 64-channel chunks and zero-pad a trailing 32-channel chunk in the image, the other two hold cin as it is.  Callers size
+  // their buffers with it and the packers below refuse a smaller one.
   return (size_t)num_offsets * ((cin + 63) / 64 * 64) * cout * dtype_size(dtype);
 }
 
@@ -80,14 +64,14 @@ int wcn_pack_weight(const void* w, int32_t num_offsets, int32_t cin, int32_t cou
                     int32_t flip, void* packed, size_t packed_bytes, wcn_stream_t stream) {
   if (!w || !packed || num_offsets < 1 || cin < 1 || cout < 1) return WCN_ERROR_INVALID_PARAMETERS;
   if (packed_bytes < wcn_packed_weight_bytes(num_offsets, cin, cout, dtype, transpose)) return WCN_ERROR_INVALID_PARAMETERS;
-  return pack_weight_mfma(w, num_offsets, cin, cout, dtype, transpose, flip, packed, (hipStream_t)stream);
+  return pack_weight_mfma(w, 0, num_offsets, cin, cout, dtype, transpose, flip, packed, (hipStream_t)stream);
 }
 
 int wcn_pack_weight_f32(const float* w, int32_t num_offsets, int32_t cin, int32_t cout, int32_t dtype, int32_t transpose,
                         int32_t flip, void* packed, size_t packed_bytes, wcn_stream_t stream) {
   if (!w || !packed || num_offsets < 1 || cin < 1 || cout < 1) return WCN_ERROR_INVALID_PARAMETERS;
   if (packed_bytes < wcn_packed_weight_bytes(num_offsets, cin, cout, dtype, transpose)) return WCN_ERROR_INVALID_PARAMETERS;
-  return pack_weight_mfma_f32(w, num_offsets, cin, cout, dtype, transpose, flip, packed, (hipStream_t)stream);
+  return pack_weight_mfma(w, 1, num_offsets, cin, cout, dtype, transpose, flip, packed, (hipStream_t)stream);
 }
 
 // COMPACT tables (wcn_kmap_build_binned with compact = 1: 16 ints per row, the mask first): the channel-split gather kernels take

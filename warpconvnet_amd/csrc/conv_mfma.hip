@@ -25,120 +25,13 @@
 // or of w^T with k reversed (dgrad of a submanifold map), or of w^T (dgrad with a reverse table).
 // Reference semantics: warpconvnet/nn/functional/sparse_conv/detail/explicit.py:22-57, 60-92; role of
 // _C.mask_gemm.fwd/.dgrad (warpconvnet/csrc/bindings/mask_gemm_bindings.cu:2074-2101).
-#include "wcn_common.h"
+#include "gather_gemm.h"
 
 namespace wcn {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-template <typename T> struct Frag;
-template <> struct Frag<__bf16> {
-  typedef bf16x8 type;
-  static __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Frag<_Float16> {
-  typedef f16x8 type;
-  static __device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 constexpr int kWaves = 4;
 constexpr int kMaxKp = 32;  // table columns staged per pass (one mask word)
 constexpr int kMaxK = 1024;  // kernel volumes up to 32 mask words (5^3 = 125 and 7^3 = 343 included)
-
-#ifdef WCN_PROF
-// dev-only phase stamps (wall clock, 10 ns ticks): [wg][8] = {entry, after perm, after slab, loop end, end, steps}
-__device__ unsigned long long g_prof[8192 * 8];
-__device__ unsigned long long g_prof2[8192 * 4];  // per-WG sums (wave 0): issue, compute, vmcnt wait, barrier (clocks)
-#define WCN_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_prof[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
-#define WCN_STAMPV(i, v) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_prof[blockIdx.x * 8 + (i)] = (v); } while (0)
-#else
-#define WCN_STAMP(i)
-#define WCN_STAMPV(i, v)
-#endif
-
-
-// ---- weight packing --------------------------------------------------------------------------------
-// packed[k][chunk][b][s][lane][j], lane = (h<<5)|m:
-//   ci = chunk*CIC + h*(CIC/2) + 8*s + j
-//   co = ((m>>2)&1)*(CO/2) + 16*b + 4*(m>>3) + (m&3)
-// so that the C fragment of lane (h', n) holds out channels h'*(CO/2) + 16*b + reg, reg = 0..15.
-template <typename T>
-__global__ void pack_weight_kernel(const T* __restrict__ w, T* __restrict__ packed, int K, int cin, int cout, int cic,
-                                   int transpose, int flip) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)K * cin * cout;
-  if (e >= total) return;
-  const int NS = cic / 16, NB = cout / 32, nchunk = cin / cic;
-  int64_t t = e;
-  const int j = (int)(t % 8); t /= 8;
-  const int lane = (int)(t % 64); t /= 64;
-  const int s = (int)(t % NS); t /= NS;
-  const int b = (int)(t % NB); t /= NB;
-  const int chunk = (int)(t % nchunk); t /= nchunk;
-  const int k = (int)t;
-  const int h = lane >> 5, m = lane & 31;
-  const int ci = chunk * cic + h * (cic / 2) + 8 * s + j;
-  const int co = ((m >> 2) & 1) * (cout / 2) + 16 * b + 4 * (m >> 3) + (m & 3);
-  const int kw = flip ? (K - 1 - k) : k;
-  // not transposed: w[kw][ci][co] ([K, cin, cout]); transposed: w is the forward weight [K, cout, cin]
-  const int64_t src = transpose ? (((int64_t)kw * cout + co) * cin + ci) : (((int64_t)kw * cin + ci) * cout + co);
-  packed[e] = w[src];
-}
-
-// the same image straight from the fp32 master weights (round to nearest even, what `.to(bf16 / f16)` does): one launch
-// instead of a cast kernel plus a pack kernel per convolution and direction
-template <typename TD>
-__global__ void pack_weight_cast_kernel(const float* __restrict__ w, TD* __restrict__ packed, int K, int cin, int cout,
-                                        int cic, int transpose, int flip) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)K * cin * cout;
-  if (e >= total) return;
-  const int NS = cic / 16, NB = cout / 32, nchunk = cin / cic;
-  int64_t t = e;
-  const int j = (int)(t % 8); t /= 8;
-  const int lane = (int)(t % 64); t /= 64;
-  const int s = (int)(t % NS); t /= NS;
-  const int b = (int)(t % NB); t /= NB;
-  const int chunk = (int)(t % nchunk); t /= nchunk;
-  const int k = (int)t;
-  const int h = lane >> 5, m = lane & 31;
-  const int ci = chunk * cic + h * (cic / 2) + 8 * s + j;
-  const int co = ((m >> 2) & 1) * (cout / 2) + 16 * b + 4 * (m >> 3) + (m & 3);
-  const int kw = flip ? (K - 1 - k) : k;
-  const int64_t src = transpose ? (((int64_t)kw * cout + co) * cin + ci) : (((int64_t)kw * cin + ci) * cout + co);
-  packed[e] = (TD)w[src];
-}
-
-// grouped weights [K, G, cin, cout] (forward layout; cin / cout per group) -> G packed images back to back, one launch
-template <typename TS, typename TD>
-__global__ void pack_weight_grouped_kernel(const TS* __restrict__ w, TD* __restrict__ packed, int K, int groups, int cin,
-                                           int cout, int cic, int transpose, int flip) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t per_group = (int64_t)K * cin * cout;
-  if (e >= per_group * groups) return;
-  const int grp = (int)(e / per_group);
-  const int NS = cic / 16, NB = cout / 32, nchunk = cin / cic;
-  int64_t t = e - (int64_t)grp * per_group;
-  const int j = (int)(t % 8); t /= 8;
-  const int lane = (int)(t % 64); t /= 64;
-  const int s = (int)(t % NS); t /= NS;
-  const int b = (int)(t % NB); t /= NB;
-  const int chunk = (int)(t % nchunk); t /= nchunk;
-  const int k = (int)t;
-  const int h = lane >> 5, m = lane & 31;
-  const int ci = chunk * cic + h * (cic / 2) + 8 * s + j;
-  const int co = ((m >> 2) & 1) * (cout / 2) + 16 * b + 4 * (m >> 3) + (m & 3);
-  const int64_t kg = (int64_t)(flip ? (K - 1 - k) : k) * groups + grp;
-  // not transposed: w[k][g][ci][co]; transposed: w is the forward weight [K, G, cout, cin] in kernel-side names
-  const int64_t src = transpose ? ((kg * cout + co) * cin + ci) : ((kg * cin + ci) * cout + co);
-  packed[e] = (TD)w[src];
-}
 
 // ---- main kernel -------------------------------------------------------------------------------------
 template <typename T, int CIC, int CO, int RB>
@@ -149,10 +42,8 @@ struct GatherGemm {
   static constexpr int TILE = kWaves * ROWS_PER_WAVE;
   static constexpr int SLAB_ELEMS = CIC * CO;
   static constexpr int SLAB_BYTES = SLAB_ELEMS * 2;
-  static constexpr int DMA_UNITS = SLAB_BYTES / 1024;  // one wave-instruction of LDS-DMA moves 1 KiB
-  static_assert(SLAB_BYTES % 1024 == 0, "weight slab must be a multiple of 1 KiB");
   static constexpr size_t LDS_BYTES = 2 * (size_t)SLAB_BYTES + (size_t)TILE * kMaxKp * 4 + (size_t)TILE * 4 + 64;
-  typedef typename Frag<T>::type frag_t;
+  typedef typename Mfma32<T>::type frag_t;
 };
 
 template <typename T, int CIC, int CO, int RB, bool MULTI>
@@ -191,16 +82,8 @@ __global__ __launch_bounds__(256, 2) void gather_gemm_mfma_kernel(const T* __res
   const int nchunk = cin / CIC;
   const int64_t row0 = (int64_t)blockIdx.x * TILE;
 
-  WCN_STAMP(0);
-  // ---- stage output row ids ----
-  if (tid < TILE) {
-    const int64_t pr = row0 + tid;
-    int32_t r = -1;
-    if (pr < n_out) r = perm ? perm[pr] : (int32_t)pr;
-    s_rows[tid] = r;
-  }
+  stage_row_ids<TILE>(s_rows, perm, row0, n_out);
   __syncthreads();
-  WCN_STAMP(1);
 
   f32x16 acc[NB][RB];
 #pragma unroll
@@ -255,48 +138,28 @@ __global__ __launch_bounds__(256, 2) void gather_gemm_mfma_kernel(const T* __res
   // (one word per 32-row block: a wave also skips the MFMAs of a row block that has no row with the offset)
   if (tid < kWaves * RB) s_wmask[tid] = 0;
   __syncthreads();
-  if (tid < TILE && my_mask) atomicOr(&s_wmask[tid / 32], my_mask);
+  or_row_mask<TILE, 32>(s_wmask, my_mask);
   __syncthreads();
   uint32_t rb_mask[RB];
-  uint32_t wave_mask = 0u, block_mask = 0u;
+  uint32_t wave_mask = 0u;
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
     rb_mask[rb] = __builtin_amdgcn_readfirstlane(s_wmask[wave * RB + rb]);  // wave-uniform: keep it in an SGPR
     wave_mask |= rb_mask[rb];
   }
-#pragma unroll
-  for (int q = 0; q < kWaves * RB; ++q) block_mask |= s_wmask[q];
-  block_mask = __builtin_amdgcn_readfirstlane(block_mask);
-  WCN_STAMP(2);
-  WCN_STAMPV(5, (unsigned long long)__builtin_popcount(block_mask));
+  const uint32_t block_mask = tile_mask<kWaves * RB>(s_wmask);
 
   if (block_mask != 0u) {
-    // ---- helpers ----
-    auto dma_weights = [&](int buf, int k, int chunk) {
-      const T* src = wp + ((int64_t)(kbase + k) * nchunk + chunk) * G::SLAB_ELEMS;
-      char* dst = reinterpret_cast<char*>(s_w) + (size_t)buf * G::SLAB_BYTES;
-#pragma unroll
-      for (int it = 0; it < (G::DMA_UNITS + kWaves - 1) / kWaves; ++it) {
-        const int u = it * kWaves + wave;  // wave-uniform 1-KiB unit
-        if (u < G::DMA_UNITS)
-          glds16(reinterpret_cast<const char*>(src) + u * 1024 + lane * 16,
-                 __builtin_amdgcn_readfirstlane(lds_addr_of(dst + u * 1024)));
-      }
-    };
-    // LDS-DMA completion is tracked by vmcnt; drain it explicitly before every barrier.
-    auto sync_step = [&]() {
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), gfx9 encoding; also resets hipcc's own load scoreboard
-      __syncthreads();
-    };
-    auto gather = [&](frag_t (&bf)[RB][NS], int k, int chunk) {
+    // weight slab of the step by LDS-DMA, then the rows: lane (h, n) pulls its half of the chunk's channels of row n
+    auto fetch = [&](int buf, frag_t (&bf)[RB][NS], int k, int chunk) {
+      const T* slab = wp + ((int64_t)(kbase + k) * nchunk + chunk) * G::SLAB_ELEMS;
+      dma_weights<G::SLAB_BYTES, kWaves>(reinterpret_cast<const char*>(slab),
+                                         reinterpret_cast<char*>(s_w) + (size_t)buf * G::SLAB_BYTES, wave, lane);
       if (!((wave_mask >> k) & 1u)) return;
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb) {
         const int i = wave * RPW + rb * 32 + n;
-        int32_t idx = s_nbr[i * kpw + k];
-#ifdef WCN_ABL_LOCAL
-        if (idx >= 0) idx &= 1023;  // dev ablation: all gathers hit a 128 KB window
-#endif
+        const int32_t idx = s_nbr[i * kpw + k];
         const T* p = in + (int64_t)idx * in_stride + chunk * CIC + h * (CIC / 2);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -325,75 +188,41 @@ __global__ __launch_bounds__(256, 2) void gather_gemm_mfma_kernel(const T* __res
         for (int rb = 0; rb < RB; ++rb) {
           if (RB > 1 && !((rb_mask[rb] >> k) & 1u)) continue;  // wave-uniform: no row of this block has offset k
 #pragma unroll
-          for (int b = 0; b < NB; ++b) acc[b][rb] = Frag<T>::mfma(a_cur[b], bf[rb][s], acc[b][rb]);
+          for (int b = 0; b < NB; ++b) acc[b][rb] = Mfma32<T>::mfma(a_cur[b], bf[rb][s], acc[b][rb]);
         }
 #pragma unroll
         for (int b = 0; b < NB; ++b) a_cur[b] = a_nxt[b];
       }
     };
-    // step iterator over (set bits of block_mask ascending) x (channel chunks)
-    uint32_t rem = block_mask;
-    auto next_step = [&](int& k, int& chunk) -> bool {
-      if (k >= 0 && chunk + 1 < nchunk) { ++chunk; return true; }
-      if (rem == 0u) return false;
-      k = __builtin_ctz(rem);
-      rem &= rem - 1u;
-      chunk = 0;
-      return true;
-    };
-
-#ifdef WCN_PROF
-    unsigned long long pq[4] = {0, 0, 0, 0};
-#endif
+    // double buffered: while step i multiplies from weight buffer b and row registers Bb, the slab and the rows of step i + 1
+    // are in flight into buffer 1 - b; one barrier per step
+    StepIter steps{block_mask, nchunk};
     frag_t B0[RB][NS], B1[RB][NS];
     int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
-    next_step(k0, c0);
-    dma_weights(0, k0, c0);
-    gather(B0, k0, c0);
+    steps.next(k0, c0);
+    fetch(0, B0, k0, c0);
     sync_step();
     bool more = true;
     while (more) {
       // even half-iteration: compute (k0,c0) from buffer 0 while fetching (k1,c1) into buffer 1
       k1 = k0; c1 = c0;
-      const bool has1 = next_step(k1, c1);
-#ifdef WCN_PROF
-      const unsigned long long q0 = clock64();
-#endif
-      if (has1) { dma_weights(1, k1, c1); gather(B1, k1, c1); }
-#ifdef WCN_PROF
-      const unsigned long long q1 = clock64();
-#endif
+      const bool has1 = steps.next(k1, c1);
+      if (has1) fetch(1, B1, k1, c1);
       compute(B0, 0, k0);
-#ifdef WCN_PROF
-      const unsigned long long q2 = clock64();
-#endif
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-#ifdef WCN_PROF
-      const unsigned long long q3 = clock64();
-#endif
-      __syncthreads();
-#ifdef WCN_PROF
-      const unsigned long long q4 = clock64();
-      pq[0] += q1 - q0; pq[1] += q2 - q1; pq[2] += q3 - q2; pq[3] += q4 - q3;
-#endif
+      sync_step();
       if (!has1) break;
       // odd half-iteration
       k0 = k1; c0 = c1;
-      const bool has0 = next_step(k0, c0);
-      if (has0) { dma_weights(0, k0, c0); gather(B0, k0, c0); }
+      const bool has0 = steps.next(k0, c0);
+      if (has0) fetch(0, B0, k0, c0);
       compute(B1, 1, k1);
       sync_step();
       more = has0;
     }
-#ifdef WCN_PROF
-    if (tid == 0 && blockIdx.x < 8192)
-      for (int q = 0; q < 4; ++q) g_prof2[blockIdx.x * 4 + q] = 2 * pq[q];  // only even half-steps are timed
-#endif
   }
   __syncthreads();  // the slab and the mask words are rewritten by the next pass
   }  // word
 
-  WCN_STAMP(3);
   // ---- epilogue: lane (h, n) holds out channels h*CO/2 + 16*b + q of row (rb, n).  Storing that straight to HBM
   // makes every lane write 16-B pieces of its own row (8 partial-line write requests per 128-B line); instead each
   // wave transposes 32 rows at a time through its own LDS stage and writes whole rows with adjacent lanes. ----
@@ -488,17 +317,11 @@ __global__ __launch_bounds__(256, 2) void gather_gemm_mfma_kernel(const T* __res
           const int32_t rr = s_rows[wave * RPW + rb * 32 + row];
           if (rr >= 0) {
             frag_t o = *reinterpret_cast<const frag_t*>(stage + row * kPitch + piece * 16);
-            if (epi.residual) {  // residual rows are read the way the output is written: whole rows, adjacent lanes
+            if (epi.residual) {
               const frag_t rv = __builtin_nontemporal_load(
                   reinterpret_cast<const frag_t*>(reinterpret_cast<const T*>(epi.residual) + (int64_t)rr * out_stride + piece * 8));
-#pragma unroll
-              for (int q = 0; q < 8; ++q) {
-                float f = (float)o[q] + (float)rv[q];
-                if (epi.relu) f = fmaxf(f, 0.f);
-                o[q] = (T)f;
-              }
+              o = add_residual<T>(o, rv, epi.relu);
             }
-            // streamed once: non-temporal, so the output does not push the gathered input out of the caches
             __builtin_nontemporal_store(o, reinterpret_cast<frag_t*>(out + (int64_t)rr * out_stride + piece * 8));
           }
         }
@@ -506,10 +329,6 @@ __global__ __launch_bounds__(256, 2) void gather_gemm_mfma_kernel(const T* __res
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // next block overwrites the stage
     }
   }
-#ifdef WCN_PROF
-  wait_vmcnt<0>();
-  WCN_STAMP(4);
-#endif
 }
 
 template <typename T, int CIC, int CO, int RB>
@@ -519,23 +338,11 @@ static int launch_gather_gemm(const void* in, const void* wp, void* out, const i
   typedef GatherGemm<T, CIC, CO, RB> G;
   const int kp = wcn_kmap_row_pitch(K);
   const int mw = wcn_kmap_mask_words(K);
-  static unsigned long long attr_done = 0ull;  // per device (wcn_common.h)
-  const int rc = once_per_device(attr_done, [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(gather_gemm_mfma_kernel<T, CIC, CO, RB, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(gather_gemm_mfma_kernel<T, CIC, CO, RB, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES) == hipSuccess;
-  });
-  if (rc != WCN_SUCCESS) return rc;
   const dim3 grid((unsigned)ceil_div(n_out, G::TILE), (unsigned)groups);
   const int in_stride = cin * groups, out_stride = CO * groups;
-  if (mw == 1)
-    hipLaunchKernelGGL((gather_gemm_mfma_kernel<T, CIC, CO, RB, false>), grid, dim3(256), G::LDS_BYTES, s, (const T*)in,
-                       (const T*)wp, (T*)out, nbr, mask, perm, epi, n_out, cin, K, kp, mw, out32, in_stride, out_stride);
-  else
-    hipLaunchKernelGGL((gather_gemm_mfma_kernel<T, CIC, CO, RB, true>), grid, dim3(256), G::LDS_BYTES, s, (const T*)in,
-                       (const T*)wp, (T*)out, nbr, mask, perm, epi, n_out, cin, K, kp, mw, out32, in_stride, out_stride);
-  return launch_status();
+  return launch_multi<gather_gemm_mfma_kernel<T, CIC, CO, RB, false>, gather_gemm_mfma_kernel<T, CIC, CO, RB, true>>(
+      mw != 1, grid, G::LDS_BYTES, s, (const T*)in, (const T*)wp, (T*)out, nbr, mask, perm, epi, n_out, cin, K, kp, mw,
+      out32, in_stride, out_stride);
 }
 
 // Output widths 96 / 128 run 32 rows per wave (128-row tiles, 64 / 48 accumulator registers, three workgroups per CU
@@ -555,26 +362,9 @@ static int dispatch_co(int cout, const void* in, const void* wp, void* out, cons
   }
 }
 
-// conv_mfma_cs.hip: channel-split family, gathered rows staged through LDS (round 3)
-bool gather_gemm_cs_supported(int cin, int cout, int K, int dtype);
-int conv_gather_gemm_cs(const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
-                        const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
-                        float* out32, hipStream_t s);
-int pack_weight_cs(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                   hipStream_t s);
-
-// conv_mfma16.hip
-bool mfma16_supported(int cin, int cout, int K, int dtype);
-int conv_gather_gemm16(const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
-                       const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
-                       float* out32, hipStream_t s);
-int pack_weight16(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                  hipStream_t s);
-
 // reduction chunk per step: 64 channels when they divide cin (measured optimum between loads in flight per wave and steps
 // per tile: a 128 -> 64 dgrad with one 128-channel step per offset 317 us, with 32-channel steps 314 us, vs 265 us)
-int mfma_chunk_for(int cin, int cout, int K) {
-  (void)cout; (void)K;
+static int mfma32_chunk(int cin) {
   if (cin % 64 == 0) return 64;
   if (cin % 32 == 0) return 32;
   if (cin % 16 == 0) return 16;
@@ -583,23 +373,29 @@ int mfma_chunk_for(int cin, int cout, int K) {
 
 // channel shapes of the 32x32x16 kernels in this file
 bool mfma32_shape(int cin, int cout) {
-  if (mfma_chunk_for(cin, cout, 1) == 0) return false;
+  if (mfma32_chunk(cin) == 0) return false;
   return cout == 32 || cout == 64 || cout == 96 || cout == 128 || cout == 192 || cout == 256;
 }
 
+// The family a shape goes to: channel-split where it applies (incl. outputs in column blocks: 320 = 5 x 64, 384, 512 ...),
+// else the 16x16x32 kernels (which leave the 32x32x16 shapes alone), else the 32x32x16 kernels of this file.
+GemmFamily gather_gemm_family(int cin, int cout, int K, int dtype) {
+  if (gather_gemm_cs_supported(cin, cout, K, dtype)) return GemmFamily::ChannelSplit;
+  if (mfma16_supported(cin, cout, K, dtype)) return GemmFamily::Mfma16;
+  if (dtype != WCN_F16 && dtype != WCN_BF16) return GemmFamily::None;
+  if (K < 1 || K > kMaxK) return GemmFamily::None;
+  return mfma32_shape(cin, cout) ? GemmFamily::Mfma32 : GemmFamily::None;
+}
+
 bool mfma_gather_supported(int cin, int cout, int K, int dtype) {
-  if (gather_gemm_cs_supported(cin, cout, K, dtype)) return true;  // (incl. outputs in column blocks: 320 = 5 x 64, 384, 512 ...)
-  if (mfma16_supported(cin, cout, K, dtype)) return true;
-  if (dtype != WCN_F16 && dtype != WCN_BF16) return false;
-  if (K < 1 || K > kMaxK) return false;
-  return mfma32_shape(cin, cout);
+  return gather_gemm_family(cin, cout, K, dtype) != GemmFamily::None;
 }
 
 template <typename T>
 static int dispatch_cic(int cin, int cout, const void* in, const void* wp, void* out, const int32_t* nbr,
                         const uint32_t* mask, const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int K, float* out32,
                         hipStream_t s, int groups = 1) {
-  switch (mfma_chunk_for(cin, cout, K)) {
+  switch (mfma32_chunk(cin)) {
     case 64: return dispatch_co<T, 64>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s, groups);
     case 32: return dispatch_co<T, 32>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s, groups);
     case 16: return dispatch_co<T, 16>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s, groups);
@@ -615,86 +411,207 @@ int conv_gather_gemm_grouped(const void* in, const void* wp, void* out, const in
                              const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int groups,
                              int K, int dtype, hipStream_t s) {
   if (groups < 1 || groups > 65535 || !mfma_grouped_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  if (dtype == WCN_BF16)
-    return dispatch_cic<__bf16>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, nullptr, s, groups);
-  return dispatch_cic<_Float16>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, nullptr, s, groups);
+  return dispatch_dtype(dtype, [&](auto t) {
+    return dispatch_cic<decltype(t)>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, nullptr, s, groups);
+  });
 }
-// packed images of all groups for the kernels above (always the 32x32x16 layout), one launch
-int pack_weight_grouped(const void* w, int w_is_f32, int K, int groups, int cin, int cout, int dtype, int transpose, int flip,
-                        void* packed, hipStream_t s);
 
 int conv_gather_gemm_mfma(const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
                           const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
                           float* out32, hipStream_t s) {
-  if (!mfma_gather_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  if (gather_gemm_cs_supported(cin, cout, K, dtype))  // channel-split family (conv_mfma_cs.hip)
-    return conv_gather_gemm_cs(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, dtype, out32, s);
-  if (mfma16_supported(cin, cout, K, dtype))  // 16x16x32 shape: row-shaped gathers (conv_mfma16.hip)
-    return conv_gather_gemm16(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, dtype, out32, s);
-  if (dtype == WCN_BF16) return dispatch_cic<__bf16>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
-  return dispatch_cic<_Float16>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
+  switch (gather_gemm_family(cin, cout, K, dtype)) {
+    case GemmFamily::ChannelSplit:
+      return conv_gather_gemm_cs(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, dtype, out32, s);
+    case GemmFamily::Mfma16:
+      return conv_gather_gemm16(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, dtype, out32, s);
+    case GemmFamily::Mfma32:
+      return dispatch_dtype(dtype, [&](auto t) {
+        return dispatch_cic<decltype(t)>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
+      });
+    case GemmFamily::None: break;
+  }
+  return WCN_ERROR_UNSUPPORTED_CONFIG;
 }
 
-int pack_weight_mfma_f32(const float* w, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                         hipStream_t s) {
-  // the layout of the packed image follows the kernel that will consume it (a pure function of the shape)
-  if (gather_gemm_cs_supported(cin, cout, K, dtype)) return pack_weight_cs(w, 1, K, cin, cout, dtype, transpose, flip, packed, s);
-  if (mfma16_supported(cin, cout, K, dtype)) return pack_weight16(w, 1, K, cin, cout, dtype, transpose, flip, packed, s);
-  const int cic = mfma_chunk_for(cin, cout, K);
-  if (cic == 0 || cout % 32 != 0 || (dtype != WCN_F16 && dtype != WCN_BF16)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  const int64_t total = (int64_t)K * cin * cout;
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  if (dtype == WCN_BF16)
-    hipLaunchKernelGGL(pack_weight_cast_kernel<__bf16>, grid, block, 0, s, w, (__bf16*)packed, K, cin, cout, cic, transpose, flip);
-  else
-    hipLaunchKernelGGL(pack_weight_cast_kernel<_Float16>, grid, block, 0, s, w, (_Float16*)packed, K, cin, cout, cic,
+// ---- weight packing (all three families) ---------------------------------------------------------------------------------
+// A packed image is a permutation of the weight (plus zero padding, channel-split family) in the order the consuming
+// kernel reads its A fragments.  A Layout knows the element count of its image and, for packed element e, the weight
+// element it holds: offset k, group, input channel ci, output channel co (kernel-side roles: reduce over ci, produce co),
+// and whether it exists at all.  Source: w[K][groups][cin][cout], or [K][groups][cout][cin] with `transpose` (the forward
+// weight, packed for a dgrad); `flip` reverses k (dgrad of a submanifold map).
+struct PackIndex { int k, grp, ci, co; bool valid; };
+struct PackShape { int K, cin, cout, groups; };
+
+// 32x32x16 kernels (this file): per group packed[k][chunk][b][s][lane][j], lane = (h<<5)|m:
+//   ci = chunk*CIC + h*(CIC/2) + 8*s + j
+//   co = ((m>>2)&1)*(CO/2) + 16*b + 4*(m>>3) + (m&3)
+// so that the C fragment of lane (h', n) holds out channels h'*(CO/2) + 16*b + reg, reg = 0..15.
+// Grouped weights (cin / cout per group): the images of the groups back to back.
+struct Pack32 : PackShape {
+  int cic;
+  __host__ __device__ int64_t elements() const { return (int64_t)groups * K * cin * cout; }
+  __device__ PackIndex at(int64_t e) const {
+    const int64_t per_group = (int64_t)K * cin * cout;
+    const int NS = cic / 16, NB = cout / 32, nchunk = cin / cic;
+    PackIndex x;
+    x.grp = (int)(e / per_group);
+    int64_t t = e - (int64_t)x.grp * per_group;
+    const int j = (int)(t % 8); t /= 8;
+    const int lane = (int)(t % 64); t /= 64;
+    const int s = (int)(t % NS); t /= NS;
+    const int b = (int)(t % NB); t /= NB;
+    const int chunk = (int)(t % nchunk); t /= nchunk;
+    x.k = (int)t;
+    const int h = lane >> 5, m = lane & 31;
+    x.ci = chunk * cic + h * (cic / 2) + 8 * s + j;
+    x.co = ((m >> 2) & 1) * (cout / 2) + 16 * b + 4 * (m >> 3) + (m & 3);
+    x.valid = true;
+    return x;
+  }
+};
+
+// 16x16x32 kernels (conv_mfma16.hip): packed[k][chunk][c][cb][lane][j], lane = (g<<4)|n:
+//   ci = chunk*CIC + 32*c + 8*g + j          co = (n >> 2)*(CO/4) + 4*cb + (n & 3)
+// so the D fragments of lane (g, n) over cb = 0..CO/16-1 are the CO/4 contiguous output channels [g*CO/4, (g+1)*CO/4).
+struct Pack16 : PackShape {
+  int cic;
+  __host__ __device__ int64_t elements() const { return (int64_t)K * cin * cout; }
+  __device__ PackIndex at(int64_t e) const {
+    const int NC = cic / 32, NCB = cout / 16, nchunk = cin / cic;
+    int64_t t = e;
+    const int j = (int)(t % 8); t /= 8;
+    const int lane = (int)(t % 64); t /= 64;
+    const int cb = (int)(t % NCB); t /= NCB;
+    const int c = (int)(t % NC); t /= NC;
+    const int chunk = (int)(t % nchunk); t /= nchunk;
+    const int g = lane >> 4, n = lane & 15;
+    PackIndex x;
+    x.k = (int)t;
+    x.grp = 0;
+    x.ci = chunk * cic + 32 * c + 8 * g + j;
+    x.co = (n >> 2) * (cout / 4) + 4 * cb + (n & 3);
+    x.valid = true;
+    return x;
+  }
+};
+
+// channel-split kernels (conv_mfma_cs.hip): packed[k][chunk][cs][s][lane][j], lane = (h << 5) | m:
+//   ci = chunk*64 + 16*s + 8*h + j                      (the K index of the MFMA: natural channel order)
+//   co = cs*32 + 16*((m >> 2) & 1) + 4*(m >> 3) + (m & 3)
+// so that the C fragment of lane (h', n) holds output channels cs*32 + 16*h' + reg, reg = 0..15, of row n.  A last chunk
+// of 32 channels is zero-padded to 64.  Outputs wider than 128 channels: `cout / cob` images of `cob` channels behind
+// each other (column block on grid.y of the main kernel), each the image of w[:, :, cb * cob : (cb + 1) * cob].
+struct PackCs : PackShape {
+  int cob;
+  __host__ __device__ int nchunk() const { return (cin + kCsCIC - 1) / kCsCIC; }
+  __host__ __device__ int64_t elements() const { return (int64_t)K * nchunk() * kCsCIC * cout; }
+  __device__ PackIndex at(int64_t e) const {
+    const int WC = cob / 32;
+    const int64_t image = (int64_t)K * nchunk() * kCsCIC * cob;
+    const int cb = (int)(e / image);
+    int64_t t = e - cb * image;
+    const int j = (int)(t % 8); t /= 8;
+    const int lane = (int)(t % 64); t /= 64;
+    const int s = (int)(t % 4); t /= 4;
+    const int cs = (int)(t % WC); t /= WC;
+    const int chunk = (int)(t % nchunk()); t /= nchunk();
+    const int h = lane >> 5, m = lane & 31;
+    PackIndex x;
+    x.k = (int)t;
+    x.grp = 0;
+    x.ci = chunk * kCsCIC + 16 * s + 8 * h + j;
+    x.co = cb * cob + cs * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
+    x.valid = x.ci < cin;
+    return x;
+  }
+};
+
+// TS -> TD: fp32 master weights are rounded to nearest even (what `.to(bf16 / f16)` does) while they are packed - one
+// launch instead of a cast kernel plus a pack kernel per convolution and direction
+template <typename Layout, typename TS, typename TD>
+__device__ __forceinline__ void pack_element(const Layout& L, const TS* __restrict__ w, TD* __restrict__ packed, int64_t e,
+                                             int transpose, int flip) {
+  if (e >= L.elements()) return;
+  const PackIndex x = L.at(e);
+  const int64_t kg = (int64_t)(flip ? (L.K - 1 - x.k) : x.k) * L.groups + x.grp;
+  const int64_t src = transpose ? ((kg * L.cout + x.co) * L.cin + x.ci) : ((kg * L.cin + x.ci) * L.cout + x.co);
+  packed[e] = x.valid ? (TD)w[src] : (TD)0;
+}
+
+template <typename Layout, typename TS, typename TD>
+__global__ void pack_weight_kernel(const Layout L, const TS* __restrict__ w, TD* __restrict__ packed, int transpose, int flip) {
+  pack_element(L, w, packed, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, transpose, flip);
+}
+
+// Both images of a training step in ONE launch: blockIdx.y = 0 the forward image of w [K, cin, cout], 1 the dgrad image
+// (kernel-side roles exchanged: reduce over cout, produce cin; transposed, k-flipped for a submanifold map).  An optimizer step
+// invalidates both at once, so every layer of a network saves a launch per iteration.
+template <typename TD>
+__global__ void pack_weight_cs_pair_kernel(const PackCs fwd, const PackCs dgrad, const float* __restrict__ w,
+                                           TD* __restrict__ packed_fwd, TD* __restrict__ packed_dgrad, int flip_dgrad) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blockIdx.y == 0) pack_element(fwd, w, packed_fwd, e, 0, 0);
+  else pack_element(dgrad, w, packed_dgrad, e, 1, flip_dgrad);
+}
+
+template <typename Layout>
+static int launch_pack(const Layout& L, const void* w, int w_is_f32, int dtype, int transpose, int flip, void* packed,
+                       hipStream_t s) {
+  const dim3 grid((unsigned)ceil_div(L.elements(), 256)), block(256);
+  if (!w_is_f32) {  // bf16 and f16 are both 2-byte moves
+    hipLaunchKernelGGL((pack_weight_kernel<Layout, uint16_t, uint16_t>), grid, block, 0, s, L, (const uint16_t*)w,
+                       (uint16_t*)packed, transpose, flip);
+    return launch_status();
+  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    typedef decltype(t) TD;
+    hipLaunchKernelGGL((pack_weight_kernel<Layout, float, TD>), grid, block, 0, s, L, (const float*)w, (TD*)packed,
                        transpose, flip);
-  return launch_status();
+    return launch_status();
+  });
 }
 
-int pack_weight_mfma(const void* w, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
+// the layout of the packed image follows the kernel that will consume it (a pure function of the shape)
+int pack_weight_mfma(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
                      hipStream_t s) {
-  if (gather_gemm_cs_supported(cin, cout, K, dtype)) return pack_weight_cs(w, 0, K, cin, cout, dtype, transpose, flip, packed, s);
-  if (mfma16_supported(cin, cout, K, dtype)) return pack_weight16(w, 0, K, cin, cout, dtype, transpose, flip, packed, s);
-  const int cic = mfma_chunk_for(cin, cout, K);
-  if (cic == 0 || cout % 32 != 0 || (dtype != WCN_F16 && dtype != WCN_BF16)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  const int64_t total = (int64_t)K * cin * cout;
-  // bf16 and f16 are both 2-byte moves
-  hipLaunchKernelGGL(pack_weight_kernel<uint16_t>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s,
-                     (const uint16_t*)w, (uint16_t*)packed, K, cin, cout, cic, transpose, flip);
-  return launch_status();
+  switch (gather_gemm_family(cin, cout, K, dtype)) {
+    case GemmFamily::ChannelSplit:
+      return launch_pack(PackCs{{K, cin, cout, 1}, cs_col_block(cout)}, w, w_is_f32, dtype, transpose, flip, packed, s);
+    case GemmFamily::Mfma16:
+      return launch_pack(Pack16{{K, cin, cout, 1}, mfma16_chunk(cin, cout)}, w, w_is_f32, dtype, transpose, flip, packed, s);
+    case GemmFamily::Mfma32:
+    case GemmFamily::None: {
+      // (None: a shape no kernel takes - K above the limit, an output width that is not instantiated - is still packed
+      // in the 32x32x16 layout where that layout exists, as it always was; the launcher refuses it.)
+      const int cic = mfma32_chunk(cin);
+      if (cic == 0 || cout % 32 != 0 || (dtype != WCN_F16 && dtype != WCN_BF16)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+      return launch_pack(Pack32{{K, cin, cout, 1}, cic}, w, w_is_f32, dtype, transpose, flip, packed, s);
+    }
+  }
+  return WCN_ERROR_UNSUPPORTED_CONFIG;  // (not reached: the switch names every family)
 }
 
+// grouped weights [K, G, cin, cout] (forward layout; cin / cout per group): always the 32x32x16 layout, one launch
 int pack_weight_grouped(const void* w, int w_is_f32, int K, int groups, int cin, int cout, int dtype, int transpose, int flip,
                         void* packed, hipStream_t s) {
-  const int cic = mfma_chunk_for(cin, cout, K);
-  if (groups < 1 || cic == 0 || !mfma32_shape(cin, cout) || (dtype != WCN_F16 && dtype != WCN_BF16))
+  if (groups < 1 || !mfma32_shape(cin, cout) || (dtype != WCN_F16 && dtype != WCN_BF16)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return launch_pack(Pack32{{K, cin, cout, groups}, mfma32_chunk(cin)}, w, w_is_f32, dtype, transpose, flip, packed, s);
+}
+
+// forward + dgrad images of an fp32 master weight in one launch; both directions must be the channel-split family's shapes
+int pack_weight_cs_pair(const float* w, int K, int cin, int cout, int dtype, int flip_dgrad, void* packed_fwd,
+                        void* packed_dgrad, hipStream_t s) {
+  if (!gather_gemm_cs_supported(cin, cout, K, dtype) || !gather_gemm_cs_supported(cout, cin, K, dtype))
     return WCN_ERROR_UNSUPPORTED_CONFIG;
-  const int64_t total = (int64_t)groups * K * cin * cout;
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  if (w_is_f32) {
-    if (dtype == WCN_BF16)
-      hipLaunchKernelGGL((pack_weight_grouped_kernel<float, __bf16>), grid, block, 0, s, (const float*)w, (__bf16*)packed, K,
-                         groups, cin, cout, cic, transpose, flip);
-    else
-      hipLaunchKernelGGL((pack_weight_grouped_kernel<float, _Float16>), grid, block, 0, s, (const float*)w, (_Float16*)packed,
-                         K, groups, cin, cout, cic, transpose, flip);
-  } else {
-    hipLaunchKernelGGL((pack_weight_grouped_kernel<uint16_t, uint16_t>), grid, block, 0, s, (const uint16_t*)w,
-                       (uint16_t*)packed, K, groups, cin, cout, cic, transpose, flip);
-  }
-  return launch_status();
+  const PackCs fwd{{K, cin, cout, 1}, cs_col_block(cout)}, dgrad{{K, cout, cin, 1}, cs_col_block(cin)};
+  const int64_t total = fwd.elements() > dgrad.elements() ? fwd.elements() : dgrad.elements();
+  const dim3 grid((unsigned)ceil_div(total, 256), 2), block(256);
+  return dispatch_dtype(dtype, [&](auto t) {
+    typedef decltype(t) TD;
+    hipLaunchKernelGGL((pack_weight_cs_pair_kernel<TD>), grid, block, 0, s, fwd, dgrad, w, (TD*)packed_fwd, (TD*)packed_dgrad,
+                       flip_dgrad);
+    return launch_status();
+  });
 }
 
-#ifdef WCN_PROF
 }  // namespace wcn
-extern "C" int wcn_debug_read_prof2(void* dst, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wcn::g_prof2), bytes);
-}
-extern "C" int wcn_debug_read_prof(void* dst, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wcn::g_prof), bytes);
-}
-namespace wcn {
-#endif
-}  // namespace wcn
-

@@ -17,66 +17,21 @@
 // wave-private LDS stage and written as whole lines.
 //
 // Layout of one MFMA (lane l: g = l >> 4, n = l & 15):  A[i = n][k = 8g + j],  B[k = 8g + j][col n],  D[i = 4g + r][col n].
-// Packed weight image (wcn_pack_weight): [offset][chunk][c][cb][lane][j] with
-//     ci = chunk*CIC + 32*c + 8*g + j          co = (n >> 2)*(CO/4) + 4*cb + (n & 3)
-// so the D fragments of lane (g, n) over cb = 0..CO/16-1 are the CO/4 CONTIGUOUS output channels [g*CO/4, (g+1)*CO/4) of
-// output row n.  Channel counts: cin % 32 == 0, cout in {16, 32, 48, 64, 96, 128, 160, 192, 256, 384, 512} (rows per wave
-// shrink as cout grows: 64 up to 128 channels, 32 up to 256, 16 above).
+// The packed weight image (Pack16 in conv_mfma.hip) orders the output channels so that the D fragments of lane (g, n)
+// over cb = 0..CO/16-1 are the CO/4 CONTIGUOUS output channels [g*CO/4, (g+1)*CO/4) of output row n.  Channel counts:
+// cin % 32 == 0, cout in {16, 32, 48, 64, 96, 128, 160, 192, 256, 384, 512} (rows per wave shrink as cout grows: 64 up
+// to 128 channels, 32 up to 256, 16 above).
 // Math: out[r] = sum_k in[nbr[r][k]] . Wp[k]  (fp32 accumulate), Wp = packed image of w (forward), of w^T with k reversed
 // (dgrad of a submanifold map), or of w^T (dgrad with a reverse table).
 // Reference semantics: warpconvnet/nn/functional/sparse_conv/detail/explicit.py:22-57, 60-92; role of
 // _C.mask_gemm.fwd/.dgrad (warpconvnet/csrc/bindings/mask_gemm_bindings.cu:2074-2101).
-#include <cstdlib>
-
-#include "wcn_common.h"
+#include "gather_gemm.h"
 
 namespace wcn {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 m_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 m_f16x8;
-typedef __attribute__((ext_vector_type(4))) float m_f32x4;
-
-template <typename T> struct MFrag;
-template <> struct MFrag<__bf16> {
-  typedef m_bf16x8 type;
-  static __device__ __forceinline__ m_f32x4 mfma(m_bf16x8 a, m_bf16x8 b, m_f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct MFrag<_Float16> {
-  typedef m_f16x8 type;
-  static __device__ __forceinline__ m_f32x4 mfma(m_f16x8 a, m_f16x8 b, m_f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 constexpr int kMWaves = 4;
 constexpr int kMMaxKp = 32;    // table columns staged per pass (one mask word)
 constexpr int kMMaxK = 1024;   // kernel volumes up to 32 mask words
-
-// ---- weight packing ----------------------------------------------------------------------------------
-template <typename TS, typename TD>
-__global__ void pack_weight16_kernel(const TS* __restrict__ w, TD* __restrict__ packed, int K, int cin, int cout, int cic,
-                                     int transpose, int flip) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)K * cin * cout;
-  if (e >= total) return;
-  const int NC = cic / 32, NCB = cout / 16, nchunk = cin / cic;
-  int64_t t = e;
-  const int j = (int)(t % 8); t /= 8;
-  const int lane = (int)(t % 64); t /= 64;
-  const int cb = (int)(t % NCB); t /= NCB;
-  const int c = (int)(t % NC); t /= NC;
-  const int chunk = (int)(t % nchunk); t /= nchunk;
-  const int k = (int)t;
-  const int g = lane >> 4, n = lane & 15;
-  const int ci = chunk * cic + 32 * c + 8 * g + j;
-  const int co = (n >> 2) * (cout / 4) + 4 * cb + (n & 3);
-  const int kw = flip ? (K - 1 - k) : k;
-  // not transposed: w[kw][ci][co] ([K, cin, cout]); transposed: w is the forward weight [K, cout, cin]
-  const int64_t src = transpose ? (((int64_t)kw * cout + co) * cin + ci) : (((int64_t)kw * cin + ci) * cout + co);
-  packed[e] = (TD)w[src];
-}
 
 // ---- main kernel -------------------------------------------------------------------------------------
 template <typename T, int CIC, int CO, int RG>
@@ -86,14 +41,12 @@ struct GG16 {
   static constexpr int RPW = 16 * RG;         // rows per wave
   static constexpr int TILE = kMWaves * RPW;  // rows per workgroup
   static constexpr int SLAB_BYTES = CIC * CO * 2;
-  static constexpr int DMA_UNITS = SLAB_BYTES / 1024;  // one wave-instruction of LDS-DMA moves 1 KiB
-  static_assert(SLAB_BYTES % 1024 == 0, "weight slab must be a multiple of 1 KiB");
   static constexpr int PITCH = CO * 2 + 16;   // epilogue stage row pitch (bytes)
   static constexpr size_t STAGE_BYTES = (size_t)kMWaves * 16 * PITCH;
   static constexpr size_t OFF_NBR = 2 * (size_t)SLAB_BYTES > STAGE_BYTES ? 2 * (size_t)SLAB_BYTES : STAGE_BYTES;
   static constexpr size_t OFF_ROWS = OFF_NBR + (size_t)TILE * kMMaxKp * 4;
   static constexpr size_t LDS_BYTES = OFF_ROWS + (size_t)TILE * 4 + 128;
-  typedef typename MFrag<T>::type frag_t;
+  typedef typename Mfma16<T>::type frag_t;
 };
 
 template <typename T, int CIC, int CO, int RG, bool MULTI>
@@ -121,16 +74,10 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
   // every wave sees the same mix of masks and the per-step barriers do not wait for the one wave whose rows are dense.
   auto grp = [&](int rg) { return ilv ? rg * kMWaves + wave : wave * RG + rg; };
 
-  // ---- output row ids (through the mask-sorted permutation) ----
-  if (tid < TILE) {
-    const int64_t pr = row0 + tid;
-    int32_t r = -1;
-    if (pr < n_out) r = perm ? perm[pr] : (int32_t)pr;
-    s_rows[tid] = r;
-  }
+  stage_row_ids<TILE>(s_rows, perm, row0, n_out);
   __syncthreads();
 
-  m_f32x4 acc[RG][NCB];
+  f32x4 acc[RG][NCB];
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
@@ -150,7 +97,8 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
       if (r >= 0) my_mask = mask[(int64_t)r * mw + word];  // thread tid stages row tid (16-row group tid / 16)
     }
     {
-      // index slab: all row ids first, then all table loads, then all LDS writes (one global round trip)
+      // index slab: all row ids first, then all table loads, then all LDS writes (one global round trip).  Kept in the
+      // kernel, like the staged store below: as shared functions they change the K > 32 kernels' registers and spills.
       const int vec_per_row = kpw >> 2;
       constexpr int kIter = (TILE * (kMMaxKp / 4) + 255) / 256;
       int32_t rr[kIter];
@@ -180,48 +128,34 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
     }
     if (tid < kMWaves * RG) s_gmask[tid] = 0;
     __syncthreads();
-    if (tid < TILE && my_mask) atomicOr(&s_gmask[tid >> 4], my_mask);
+    or_row_mask<TILE, 16>(s_gmask, my_mask);
     __syncthreads();
     uint32_t rg_mask[RG];
-    uint32_t wave_mask = 0u, block_mask = 0u;
+    uint32_t wave_mask = 0u;
 #pragma unroll
     for (int rg = 0; rg < RG; ++rg) {
       rg_mask[rg] = __builtin_amdgcn_readfirstlane(s_gmask[grp(rg)]);  // wave-uniform: keep it in an SGPR
       wave_mask |= rg_mask[rg];
     }
-#pragma unroll
-    for (int q = 0; q < kMWaves * RG; ++q) block_mask |= s_gmask[q];
-    block_mask = __builtin_amdgcn_readfirstlane(block_mask);
+    const uint32_t block_mask = tile_mask<kMWaves * RG>(s_gmask);
 
     if (block_mask != 0u) {
-      auto dma_weights = [&](int buf, int k, int chunk) {
-        const char* src = reinterpret_cast<const char*>(wp) + ((size_t)(kbase + k) * nchunk + chunk) * G::SLAB_BYTES;
-        char* dst = s_w + (size_t)buf * G::SLAB_BYTES;
-#pragma unroll
-        for (int it = 0; it < (G::DMA_UNITS + kMWaves - 1) / kMWaves; ++it) {
-          const int u = it * kMWaves + wave;  // wave-uniform 1-KiB unit
-          if (u < G::DMA_UNITS)
-            glds16(src + u * 1024 + lane * 16, __builtin_amdgcn_readfirstlane(lds_addr_of(dst + u * 1024)));
-        }
-      };
-      // rows of step (k, chunk): lane (g, n) of row group rg pulls channels [32c + 8g, +8) of row n straight into the B
-      // operand - 16 rows per instruction; absent neighbours issue no request.
+      // weight slab of step (k, chunk) by LDS-DMA, then its rows: lane (g, n) of row group rg pulls channels
+      // [32c + 8g, +8) of row n straight into the B operand - 16 rows per instruction; absent neighbours issue no request.
       // (Measured alternative, round 2: ROW-SHAPED loads - lane l takes piece l & 3 of row l >> 2, four adjacent lanes
       // per 64 contiguous bytes, 3x the address-pipeline rate in tools/gather_probe.hip - plus a 16 x 4 lane transpose with
       // four ds_bpermute per fragment in front of the MFMAs: correct, but 64->128 forward 227 vs 212 us and 128->64 dgrad
       // 284 vs 228 us.  The kernel is not bound by the gather path - with every gather redirected into a 128 KB window
       // its time does not change - so the transposes are pure added work.)
-      auto gather = [&](frag_t (&bf)[RG][NC], int k, int chunk) {
+      auto fetch = [&](int buf, frag_t (&bf)[RG][NC], int k, int chunk) {
+        const char* slab = reinterpret_cast<const char*>(wp) + ((size_t)(kbase + k) * nchunk + chunk) * G::SLAB_BYTES;
+        dma_weights<G::SLAB_BYTES, kMWaves>(slab, s_w + (size_t)buf * G::SLAB_BYTES, wave, lane);
         if (!((wave_mask >> k) & 1u)) return;
 #pragma unroll
         for (int rg = 0; rg < RG; ++rg) {
           if (RG > 1 && !((rg_mask[rg] >> k) & 1u)) continue;  // wave-uniform: no row of this group has offset k
           const int32_t idx = s_nbr[(grp(rg) * 16 + n) * kpw + k];
-#ifdef WCN_ABL_LOCAL
-          const T* p = in + (int64_t)(idx & 8191) * cin + chunk * CIC + 8 * g;
-#else
           const T* p = in + (int64_t)idx * cin + chunk * CIC + 8 * g;
-#endif
 #pragma unroll
           for (int c = 0; c < NC; ++c) {
             frag_t v;
@@ -248,46 +182,33 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
 #pragma unroll
             for (int rg = 0; rg < RG; ++rg) {
               if (RG > 1 && !((rg_mask[rg] >> k) & 1u)) continue;  // wave-uniform
-              acc[rg][cb] = MFrag<T>::mfma(a_cur, bt[rg], acc[rg][cb]);
+              acc[rg][cb] = Mfma16<T>::mfma(a_cur, bt[rg], acc[rg][cb]);
             }
             a_cur = a_nxt;
           }
         }
       };
-      // step iterator over (set bits of block_mask ascending) x (channel chunks)
-      uint32_t rem = block_mask;
-      auto next_step = [&](int& k, int& chunk) -> bool {
-        if (k >= 0 && chunk + 1 < nchunk) { ++chunk; return true; }
-        if (rem == 0u) return false;
-        k = __builtin_ctz(rem);
-        rem &= rem - 1u;
-        chunk = 0;
-        return true;
-      };
-      // LDS-DMA completion is tracked by vmcnt; drained explicitly (builtin: also resets hipcc's own load scoreboard)
-      auto sync_step = [&]() {
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), gfx9 encoding
-        __syncthreads();
-      };
+      // double buffered: while step i multiplies from weight buffer b and row registers Bb, the slab and the rows of step i + 1
+      // are in flight into buffer 1 - b; one barrier per step
+      StepIter steps{block_mask, nchunk};
       frag_t B0[RG][NC], B1[RG][NC];
       int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
-      next_step(k0, c0);
-      dma_weights(0, k0, c0);
-      gather(B0, k0, c0);
+      steps.next(k0, c0);
+      fetch(0, B0, k0, c0);
       sync_step();
       bool more = true;
       while (more) {
         // even half-iteration: compute (k0,c0) from buffer 0 while fetching (k1,c1) into buffer 1
         k1 = k0; c1 = c0;
-        const bool has1 = next_step(k1, c1);
-        if (has1) { dma_weights(1, k1, c1); gather(B1, k1, c1); }
+        const bool has1 = steps.next(k1, c1);
+        if (has1) fetch(1, B1, k1, c1);
         compute(B0, 0, k0);
         sync_step();
         if (!has1) break;
         // odd half-iteration
         k0 = k1; c0 = c1;
-        const bool has0 = next_step(k0, c0);
-        if (has0) { dma_weights(0, k0, c0); gather(B0, k0, c0); }
+        const bool has0 = steps.next(k0, c0);
+        if (has0) fetch(0, B0, k0, c0);
         compute(B1, 1, k1);
         sync_step();
         more = has0;
@@ -307,11 +228,8 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
       float* dst = out32 + (int64_t)r * CO + g * CQ;
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        float4 o = make_float4(acc[rg][cb][0], acc[rg][cb][1], acc[rg][cb][2], acc[rg][cb][3]);
-        if (epi.bias) {
-          const float4 bv = reinterpret_cast<const float4*>(epi.bias + g * CQ)[cb];
-          o.x += bv.x; o.y += bv.y; o.z += bv.z; o.w += bv.w;
-        }
+        float4 o = acc4(acc[rg][cb], 0);
+        if (epi.bias) o = epi_bias(o, reinterpret_cast<const float4*>(epi.bias + g * CQ)[cb]);
         reinterpret_cast<float4*>(dst)[cb] = o;
       }
     }
@@ -328,19 +246,13 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
   for (int rg = 0; rg < RG; ++rg) {
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-      float4 o = make_float4(acc[rg][cb][0], acc[rg][cb][1], acc[rg][cb][2], acc[rg][cb][3]);
-      if (epi.bias) {  // + bias[co] in fp32 before the rounding to the storage dtype
-        const float4 bv = reinterpret_cast<const float4*>(epi.bias + g * CQ)[cb];
-        o.x += bv.x; o.y += bv.y; o.z += bv.z; o.w += bv.w;
-      }
-      if (epi.scale) {  // per-channel affine (BatchNorm in inference mode)
-        const float4 sv = reinterpret_cast<const float4*>(epi.scale + g * CQ)[cb];
-        const float4 tv = reinterpret_cast<const float4*>(epi.shift + g * CQ)[cb];
-        o.x = o.x * sv.x + tv.x; o.y = o.y * sv.y + tv.y; o.z = o.z * sv.z + tv.z; o.w = o.w * sv.w + tv.w;
-      }
-      if (epi.relu && !epi.residual) {  // (with a residual the activation follows the add below)
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-      }
+      float4 o = acc4(acc[rg][cb], 0);
+      // + bias[co] in fp32 before the rounding to the storage dtype
+      if (epi.bias) o = epi_bias(o, reinterpret_cast<const float4*>(epi.bias + g * CQ)[cb]);
+      if (epi.scale)
+        o = epi_affine(o, reinterpret_cast<const float4*>(epi.scale + g * CQ)[cb],
+                       reinterpret_cast<const float4*>(epi.shift + g * CQ)[cb]);
+      if (epi.relu && !epi.residual) o = epi_relu(o);  // (with a residual the activation follows the add below)
       typedef __attribute__((ext_vector_type(4))) T t4;
       t4 v;
       v[0] = (T)o.x; v[1] = (T)o.y; v[2] = (T)o.z; v[3] = (T)o.w;
@@ -358,17 +270,11 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
           const int32_t rr = s_rows[grp(rg) * 16 + row];
           if (rr >= 0) {
             frag_t o = *reinterpret_cast<const frag_t*>(stage + row * kPitch + piece * 16);
-            if (epi.residual) {  // residual rows are read the way the output is written: whole rows, adjacent lanes
+            if (epi.residual) {
               const frag_t rv = __builtin_nontemporal_load(
                   reinterpret_cast<const frag_t*>(reinterpret_cast<const T*>(epi.residual) + (int64_t)rr * CO + piece * 8));
-#pragma unroll
-              for (int q = 0; q < 8; ++q) {
-                float f = (float)o[q] + (float)rv[q];
-                if (epi.relu) f = fmaxf(f, 0.f);
-                o[q] = (T)f;
-              }
+              o = add_residual<T>(o, rv, epi.relu);
             }
-            // streamed once: non-temporal, so the output does not push the gathered input out of the caches
             __builtin_nontemporal_store(o, reinterpret_cast<frag_t*>(out + (int64_t)rr * CO + piece * 8));
           }
         }
@@ -383,10 +289,8 @@ __global__ __launch_bounds__(256, 2) void gather_gemm16_kernel(const T* __restri
 // Measured on MI355X (1 M voxels, bf16, round 2) where both apply: 64->128 forward 212 vs 200 us, 128->64 dgrad 228 vs
 // 231 us - a wash, so the older kernels keep their shapes.  (Row-shaped gathers with an LDS or ds_bpermute operand
 // transpose in front of the MFMAs were measured too: 248 / 282 and 227 / 284 us - dropped.)
-bool mfma32_shape(int cin, int cout);  // conv_mfma.hip
-
 // reduction chunk per step: 64 channels when they divide cin and the two weight slabs stay within 64 KB, else 32
-static int chunk16(int cin, int cout) { return (cin % 64 == 0 && 2 * 64 * cout * 2 <= 65536) ? 64 : 32; }
+int mfma16_chunk(int cin, int cout) { return (cin % 64 == 0 && 2 * 64 * cout * 2 <= 65536) ? 64 : 32; }
 
 // Shapes this kernel family takes.  ONE pure function of the shape for the weight packer and the launcher.
 bool mfma16_supported(int cin, int cout, int K, int dtype) {
@@ -406,23 +310,9 @@ static int launch16(const void* in, const void* wp, void* out, const int32_t* nb
                     hipStream_t s) {
   typedef GG16<T, CIC, CO, RG> G;
   const int kp = wcn_kmap_row_pitch(K), mw = wcn_kmap_mask_words(K);
-  static unsigned long long attr_done = 0ull;  // per device (wcn_common.h)
-  const int rc = once_per_device(attr_done, [] {
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(gather_gemm16_kernel<T, CIC, CO, RG, false>),
-                          reinterpret_cast<const void*>(gather_gemm16_kernel<T, CIC, CO, RG, true>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES) == hipSuccess;
-    return ok;
-  });
-  if (rc != WCN_SUCCESS) return rc;
-  const unsigned grid = (unsigned)ceil_div(n_out, G::TILE);
-  if (mw == 1)
-    hipLaunchKernelGGL((gather_gemm16_kernel<T, CIC, CO, RG, false>), dim3(grid), dim3(256), G::LDS_BYTES, s,
-                       (const T*)in, (const T*)wp, (T*)out, nbr, mask, perm, epi, n_out, cin, K, kp, mw, out32, 1);
-  else
-    hipLaunchKernelGGL((gather_gemm16_kernel<T, CIC, CO, RG, true>), dim3(grid), dim3(256), G::LDS_BYTES, s,
-                       (const T*)in, (const T*)wp, (T*)out, nbr, mask, perm, epi, n_out, cin, K, kp, mw, out32, 1);
-  return launch_status();
+  return launch_multi<gather_gemm16_kernel<T, CIC, CO, RG, false>, gather_gemm16_kernel<T, CIC, CO, RG, true>>(
+      mw != 1, dim3((unsigned)ceil_div(n_out, G::TILE)), G::LDS_BYTES, s, (const T*)in, (const T*)wp, (T*)out, nbr, mask,
+      perm, epi, n_out, cin, K, kp, mw, out32, 1);
 }
 
 template <typename T, int CIC>
@@ -457,7 +347,7 @@ template <typename T>
 static int dispatch16(int cin, int cout, const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
                       const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int K, float* out32, hipStream_t s) {
   if (cout > 256) return dispatch16_wide<T>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s);
-  if (chunk16(cin, cout) == 64) return dispatch16_co<T, 64>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s);
+  if (mfma16_chunk(cin, cout) == 64) return dispatch16_co<T, 64>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s);
   return dispatch16_co<T, 32>(cout, in, wp, out, nbr, mask, perm, epi, n_out, cin, K, out32, s);
 }
 
@@ -465,29 +355,9 @@ int conv_gather_gemm16(const void* in, const void* wp, void* out, const int32_t*
                        const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
                        float* out32, hipStream_t s) {
   if (!mfma16_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  if (dtype == WCN_BF16) return dispatch16<__bf16>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
-  return dispatch16<_Float16>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
-}
-
-// packed image for this kernel family; `w` fp32 (w_is_f32) or already in the 16-bit storage dtype
-int pack_weight16(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                  hipStream_t s) {
-  if (!mfma16_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  const int cic = cout > 256 ? 32 : chunk16(cin, cout);
-  const int64_t total = (int64_t)K * cin * cout;
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  if (w_is_f32) {
-    if (dtype == WCN_BF16)
-      hipLaunchKernelGGL((pack_weight16_kernel<float, __bf16>), grid, block, 0, s, (const float*)w, (__bf16*)packed, K, cin,
-                         cout, cic, transpose, flip);
-    else
-      hipLaunchKernelGGL((pack_weight16_kernel<float, _Float16>), grid, block, 0, s, (const float*)w, (_Float16*)packed, K,
-                         cin, cout, cic, transpose, flip);
-  } else {  // bf16 and f16 are both 2-byte moves
-    hipLaunchKernelGGL((pack_weight16_kernel<uint16_t, uint16_t>), grid, block, 0, s, (const uint16_t*)w, (uint16_t*)packed,
-                       K, cin, cout, cic, transpose, flip);
-  }
-  return launch_status();
+  return dispatch_dtype(dtype, [&](auto t) {
+    return dispatch16<decltype(t)>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
+  });
 }
 
 }  // namespace wcn

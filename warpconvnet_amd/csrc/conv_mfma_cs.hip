@@ -30,42 +30,21 @@
 // MaskGemm_forward_64x64x32_1s_flat.h:287-296.
 #include <cstdlib>
 
-#include "wcn_common.h"
+#include "gather_gemm.h"
 
 namespace wcn {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 c_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 c_f16x8;
-typedef __attribute__((ext_vector_type(16))) float c_f32x16;
-
-template <typename T> struct CFrag;
-template <> struct CFrag<__bf16> {
-  typedef c_bf16x8 type;
-  static __device__ __forceinline__ c_f32x16 mfma(c_bf16x8 a, c_bf16x8 b, c_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct CFrag<_Float16> {
-  typedef c_f16x8 type;
-  static __device__ __forceinline__ c_f32x16 mfma(c_f16x8 a, c_f16x8 b, c_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 constexpr int kCsSlabPitch = 28;   // staged table columns (ints): kernel volumes up to 28 (3^3 = 27)
 constexpr int kCsMaxK = 28;
-constexpr int kCsCIC = 64;         // input channels per step (one 128-B row piece)
+// (kCsCIC = 64 input channels per step, one 128-B row piece: gather_gemm.h - the weight packer needs it too)
 
 // Workgroup shape: WC = CO / 32 channel slices x WR row groups waves; a wave holds RBW 32-row blocks of its 32 channels.
 //   CO = 128: RBW 4, WR 1 -> 4 waves, 128-row tile (RBW 2: 64-row tile, half the LDS, twice the weight traffic per row)
 //   CO =  64: RBW 2, WR 2 -> 4 waves, 128-row tile;  RBW 2, WR 1 -> 2 waves, 64-row tile (same weight traffic per row)
 template <int CO, int RBW_, int WR_>
 struct CsCfg {
-#ifdef WCN_CS_PAIR  // ablation build (round 6): two (offset, chunk) steps per barrier, four ring stages - profiles/r06_gemm_limits.md
-  static constexpr int D = 4;
-#else
-  static constexpr int D = 2;                    // ring depth (deeper rings need counted waits)
-#endif
+  static constexpr int D = 2;                    // ring depth (deeper rings need counted waits; two steps per barrier on a
+                                                 // ring of four were measured in round 6 and lost: profiles/r06_gemm_limits.md)
   static constexpr int WC = CO / 32;             // channel slices (waves across the output width)
   static constexpr int WR = WR_;                 // row groups
   static constexpr int RBW = RBW_;               // 32-row blocks per wave
@@ -93,51 +72,7 @@ struct CsCfg {
   static_assert((size_t)TILE * OUT_PITCH <= OFF_ROWS - SLAB_SAVED, "the epilogue stage reuses the ring and the index slab");
 };
 
-// ---- weight packing: [k][chunk][cs][s][lane][j], lane = (h << 5) | m ------------------------------------------------
-//   ci = chunk*64 + 16*s + 8*h + j                      (the K index of the MFMA: natural channel order)
-//   co = cs*32 + 16*((m >> 2) & 1) + 4*(m >> 3) + (m & 3)
-// so that the C fragment of lane (h', n) holds output channels cs*32 + 16*h' + reg, reg = 0..15, of row n.
-// Outputs wider than 128 channels: `cout / cob` images of `cob` channels behind each other (column block on grid.y of the
-// main kernel), each the image of w[:, :, cb * cob : (cb + 1) * cob].
-template <typename TS, typename TD>
-__device__ __forceinline__ void pack_weight_cs_element(const TS* __restrict__ w, TD* __restrict__ packed, int64_t e, int K, int cin,
-                                                       int cout, int cob, int transpose, int flip) {
-  const int WC = cob / 32, nchunk = (cin + kCsCIC - 1) / kCsCIC;  // a last chunk of 32 channels is zero-padded to 64
-  const int64_t image = (int64_t)K * nchunk * kCsCIC * cob;
-  if (e >= image * (cout / cob)) return;
-  const int cb = (int)(e / image);
-  int64_t t = e - cb * image;
-  const int j = (int)(t % 8); t /= 8;
-  const int lane = (int)(t % 64); t /= 64;
-  const int s = (int)(t % 4); t /= 4;
-  const int cs = (int)(t % WC); t /= WC;
-  const int chunk = (int)(t % nchunk); t /= nchunk;
-  const int k = (int)t;
-  const int h = lane >> 5, m = lane & 31;
-  const int ci = chunk * kCsCIC + 16 * s + 8 * h + j;
-  const int co = cb * cob + cs * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
-  const int kw = flip ? (K - 1 - k) : k;
-  // not transposed: w[kw][ci][co] ([K, cin, cout]); transposed: w is the forward weight [K, cout, cin]
-  const int64_t src = transpose ? (((int64_t)kw * cout + co) * cin + ci) : (((int64_t)kw * cin + ci) * cout + co);
-  packed[e] = ci < cin ? (TD)w[src] : (TD)0;
-}
-
-template <typename TS, typename TD>
-__global__ void pack_weight_cs_kernel(const TS* __restrict__ w, TD* __restrict__ packed, int K, int cin, int cout, int cob,
-                                      int transpose, int flip) {
-  pack_weight_cs_element(w, packed, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, K, cin, cout, cob, transpose, flip);
-}
-
-// Both images of a training step in ONE launch: blockIdx.y = 0 the forward image of w [K, cin, cout], 1 the dgrad image
-// (kernel-side roles exchanged: reduce over cout, produce cin; transposed, k-flipped for a submanifold map).  An optimizer step
-// invalidates both at once, so every layer of a network saves a launch per iteration.
-template <typename TD>
-__global__ void pack_weight_cs_pair_kernel(const float* __restrict__ w, TD* __restrict__ packed_fwd, TD* __restrict__ packed_dgrad,
-                                           int K, int cin, int cout, int cob_fwd, int cob_dgrad, int flip_dgrad) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (blockIdx.y == 0) pack_weight_cs_element(w, packed_fwd, e, K, cin, cout, cob_fwd, 0, 0);
-  else pack_weight_cs_element(w, packed_dgrad, e, K, cout, cin, cob_dgrad, 1, flip_dgrad);
-}
+// (Weight image of this family: PackCs in conv_mfma.hip.)
 
 #ifdef WCN_PROF
 // dev build (`make prof`, tools/prof_phases.py): thread 0 of every 4th workgroup stamps its phases - per slot: prologue, step
@@ -161,7 +96,7 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
                                                                 float* __restrict__ out32, int ldc) {
   // ldc: channels of an output (and residual) row; blockIdx.y: the CO-wide column block of it this workgroup produces
   typedef CsCfg<CO, RBW_, WR_> G;
-  typedef typename CFrag<T>::type frag_t;
+  typedef typename Mfma32<T>::type frag_t;
   constexpr int WC = G::WC, RBW = G::RBW, SP = kCsSlabPitch, TILE = G::TILE, NT = G::NT;
   constexpr int kCsStageBytes = G::STAGE_BYTES;
 
@@ -197,12 +132,7 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
 #endif
 
   // ---- output row ids (through the mask-sorted permutation), masks, index slab ----
-  if (tid < TILE) {
-    const int64_t pr = row0 + tid;
-    int32_t r = -1;
-    if (pr < n_out) r = perm ? perm[pr] : (int32_t)pr;
-    s_rows[tid] = r;
-  }
+  stage_row_ids<TILE>(s_rows, perm, row0, n_out);
   if (tid < 8) reinterpret_cast<int4*>(s_zero)[tid] = make_int4(0, 0, 0, 0);
   if (tid < 8) s_wmask[tid] = 0;
   if (last_pieces < 8) {
@@ -252,16 +182,15 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
       reinterpret_cast<int4*>(s_nbr)[e] = vv[t];
     }
   } else {
-    {
-      uint32_t my_mask = 0;
-      if (tid < TILE) {
-        const int32_t r = s_rows[tid];
-        if (r >= 0) my_mask = mask ? mask[r] : 1u;  // (no table: the identity map of a 1 x 1 x 1 kernel, see below)
-        s_mask[tid] = my_mask;
-        if (my_mask) atomicOr(&s_wmask[tid >> 5], my_mask);
-      }
+    uint32_t my_mask = 0;
+    if (tid < TILE) {
+      const int32_t r = s_rows[tid];
+      if (r >= 0) my_mask = mask ? mask[r] : 1u;  // (no table: the identity map of a 1 x 1 x 1 kernel)
+      s_mask[tid] = my_mask;
+      or_row_mask<TILE, 32>(s_wmask, my_mask);
     }
-    // all row ids first, then all table loads, then all LDS writes (one global round trip)
+    // Index slab [TILE][SP] (wider than the table may be: pieces past column kp stay -1): all row ids first, then all
+    // table loads, then all LDS writes (one global round trip)
     constexpr int kVec = SP / 4;  // 16-B pieces per slab row
     constexpr int kIter = (TILE * kVec + NT - 1) / NT;
     int32_t rr[kIter];
@@ -295,12 +224,9 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
   }
   __syncthreads();
   uint32_t rb_mask[RBW];
-  uint32_t block_mask = 0u;
 #pragma unroll
   for (int rb = 0; rb < RBW; ++rb) rb_mask[rb] = __builtin_amdgcn_readfirstlane(s_wmask[rg * RBW + rb]);  // SGPR
-#pragma unroll
-  for (int q = 0; q < G::NBLK; ++q) block_mask |= s_wmask[q];
-  block_mask = __builtin_amdgcn_readfirstlane(block_mask);
+  const uint32_t block_mask = tile_mask<G::NBLK>(s_wmask);
   // the DMA instructions of this wave cover tile rows [DMA_ROWS * wave, DMA_ROWS * (wave + 1)): OR of their blocks' masks (skip empty instructions)
   uint32_t dma_mask = 0u;
 #pragma unroll
@@ -313,7 +239,7 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
 #pragma unroll
   for (int rb = 0; rb < RBW; ++rb) mrow[rb] = s_mask[(rg * RBW + rb) * 32 + n];
 
-  c_f32x16 acc[RBW];
+  f32x16 acc[RBW];
 #pragma unroll
   for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
@@ -386,116 +312,49 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
       const uint32_t sbase = rowaddr + (uint32_t)buf * kCsStageBytes;
       // ONE set of B fragments: the LDS reads of row block rb + 1 are issued behind the MFMAs of block rb and ride under their
       // execution.  (Round 6: the double-buffered set - reads of rb + 1 in front of the MFMAs of rb - cost 27 VGPRs and bought
-      // nothing: forward 204.7 vs 203.6 us, dgrad 222.0 vs 229.0 us WITH the single set, same box; `-DWCN_CS_BDOUBLE`.)
-#ifdef WCN_CS_BDOUBLE
-      frag_t b[2][4];
-      if ((rb_mask[0] >> k) & 1u) load_b(b[0], sbase, 0, k);
-#pragma unroll
-      for (int rb = 0; rb < RBW; ++rb) {
-        if (rb + 1 < RBW && ((rb_mask[rb + 1 < RBW ? rb + 1 : rb] >> k) & 1u)) load_b(b[(rb + 1) & 1], sbase, rb + 1, k);
-        if ((rb_mask[rb] >> k) & 1u) {  // wave-uniform: some row of this block has the offset
-#pragma unroll
-          for (int s = 0; s < 4; ++s) acc[rb] = CFrag<T>::mfma(w[s], b[rb & 1][s], acc[rb]);
-        }
-      }
-#else
+      // nothing: forward 204.7 vs 203.6 us, dgrad 222.0 vs 229.0 us WITH the single set, same box.)
       frag_t b[4];
 #pragma unroll
       for (int rb = 0; rb < RBW; ++rb) {
         if ((rb_mask[rb] >> k) & 1u) {  // wave-uniform: some row of this block has the offset
           load_b(b, sbase, rb, k);
 #pragma unroll
-          for (int s = 0; s < 4; ++s) acc[rb] = CFrag<T>::mfma(w[s], b[s], acc[rb]);
+          for (int s = 0; s < 4; ++s) acc[rb] = Mfma32<T>::mfma(w[s], b[s], acc[rb]);
         }
       }
-#endif
     };
-    // step iterator over (set bits of block_mask ascending) x (channel chunks)
-    uint32_t rem = block_mask;
-    auto next_step = [&](int& k, int& chunk) -> bool {
-      if (k >= 0 && chunk + 1 < nchunk) { ++chunk; return true; }
-      if (rem == 0u) return false;
-      k = __builtin_ctz(rem);
-      rem &= rem - 1u;
-      chunk = 0;
-      return true;
-    };
-    auto sync_step = [&]() {
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), gfx9 encoding; also resets hipcc's own load scoreboard
-      __syncthreads();
-    };
-
-#ifdef WCN_CS_PAIR
-    // TWO steps per barrier: the rows and weight fragments of steps s+2, s+3 are requested while s, s+1 multiply
-    frag_t W0[4], W1[4], W2[4], W3[4];
-    int ka = -1, ca = 0, kb = -1, cb = 0, kc = -1, cc = 0, kd = -1, cd = 0;
-    bool hb, hc, hd;
-    next_step(ka, ca);
-    kb = ka; cb = ca;
-    hb = next_step(kb, cb);
-    issue_rows(0, ka, ca);
-    load_w(W0, ka, ca);
-    if (hb) { issue_rows(1, kb, cb); load_w(W1, kb, cb); }
-    for (;;) {
-      kc = hb ? kb : ka; cc = hb ? cb : ca;
-      hc = hb && next_step(kc, cc);
-      kd = kc; cd = cc;
-      hd = hc && next_step(kd, cd);
-      sync_step();
-      if (hc) { issue_rows(2, kc, cc); load_w(W2, kc, cc); }
-      if (hd) { issue_rows(3, kd, cd); load_w(W3, kd, cd); }
-      compute(W0, 0, ka);
-      if (hb) compute(W1, 1, kb);
-      if (!hc) break;
-      ka = hd ? kd : kc; ca = hd ? cd : cc;
-      const bool ha = hd && next_step(ka, ca);
-      kb = ka; cb = ca;
-      hb = ha && next_step(kb, cb);
-      sync_step();
-      if (ha) { issue_rows(0, ka, ca); load_w(W0, ka, ca); }
-      if (hb) { issue_rows(1, kb, cb); load_w(W1, kb, cb); }
-      compute(W2, 2, kc);
-      if (hd) compute(W3, 3, kd);
-      if (!ha) break;
-    }
-#else
+    // Two steps per barrier (ring of four stages, four weight-fragment sets: 199 VGPRs at CO = 128) were measured in round 6
+    // and ran 377 / 437 us against 205 / 247: profiles/r06_gemm_limits.md.
+    StepIter steps{block_mask, nchunk};
     frag_t Wa[4], Wb[4];
     int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
-    next_step(k0, c0);
+    steps.next(k0, c0);
     CS_PROF(pt1 = CS_CLK());
     issue_rows(0, k0, c0);
     load_w(Wa, k0, c0);
     for (;;) {
       k1 = k0; c1 = c0;
-      const bool has1 = next_step(k1, c1);
+      const bool has1 = steps.next(k1, c1);
       CS_PROF(pa = CS_CLK());
       sync_step();  // stage 0 has landed for every wave; every wave is done reading stage 1
       CS_PROF(pw += CS_CLK() - pa; pa = CS_CLK());
-#ifdef WCN_CS_WFIRST  // ablation build (round 6): the L2-resident weight fragments requested in front of the row DMA
-      if (has1) { load_w(Wb, k1, c1); issue_rows(1, k1, c1); }
-#else
+      // (round 6: the L2-resident weight fragments requested in FRONT of the row DMA changed nothing, 205 / 247 us)
       if (has1) { issue_rows(1, k1, c1); load_w(Wb, k1, c1); }
-#endif
       CS_PROF(pi += CS_CLK() - pa; pa = CS_CLK());
       compute(Wa, 0, k0);
       CS_PROF(pc += CS_CLK() - pa; ++pn);
       if (!has1) break;
       k0 = k1; c0 = c1;
-      const bool has0 = next_step(k0, c0);
+      const bool has0 = steps.next(k0, c0);
       CS_PROF(pa = CS_CLK());
       sync_step();
       CS_PROF(pw += CS_CLK() - pa; pa = CS_CLK());
-#ifdef WCN_CS_WFIRST
-      if (has0) { load_w(Wa, k0, c0); issue_rows(0, k0, c0); }
-#else
       if (has0) { issue_rows(0, k0, c0); load_w(Wa, k0, c0); }
-#endif
       CS_PROF(pi += CS_CLK() - pa; pa = CS_CLK());
       compute(Wb, 1, k1);
       CS_PROF(pc += CS_CLK() - pa; ++pn);
       if (!has0) break;
     }
-#endif
     CS_PROF(pt2 = CS_CLK());
   }
 
@@ -510,9 +369,7 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
       float* dst = out32 + (int64_t)r * ldc + col0 + cbase;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const float4 bv = reinterpret_cast<const float4*>(s_epi + cbase)[v];
-        reinterpret_cast<float4*>(dst)[v] = make_float4(acc[rb][4 * v + 0] + bv.x, acc[rb][4 * v + 1] + bv.y,
-                                                        acc[rb][4 * v + 2] + bv.z, acc[rb][4 * v + 3] + bv.w);
+        reinterpret_cast<float4*>(dst)[v] = epi_bias(acc4(acc[rb], v), reinterpret_cast<const float4*>(s_epi + cbase)[v]);
       }
     }
     return;
@@ -526,8 +383,8 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
       const float4 bv = reinterpret_cast<const float4*>(s_epi + cbase)[v];
       const float4 sv = reinterpret_cast<const float4*>(s_epi + CO + cbase)[v];
       const float4 tv = reinterpret_cast<const float4*>(s_epi + 2 * CO + cbase)[v];
-      float f[4] = {(acc[rb][4 * v + 0] + bv.x) * sv.x + tv.x, (acc[rb][4 * v + 1] + bv.y) * sv.y + tv.y,
-                    (acc[rb][4 * v + 2] + bv.z) * sv.z + tv.z, (acc[rb][4 * v + 3] + bv.w) * sv.w + tv.w};
+      const float4 o = epi_affine(epi_bias(acc4(acc[rb], v), bv), sv, tv);
+      float f[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (epi.relu && !epi.residual) f[j] = fmaxf(f[j], 0.f);  // (with a residual the activation follows the add below)
@@ -570,14 +427,7 @@ __global__ __launch_bounds__(64 * (CO / 32) * WR_, MINW) void gather_gemm_cs_ker
       for (int j = 0; j < kBatch; ++j) {
         if (orow[j] < 0 || piece >= kPieces) continue;
         frag_t o = ov[j];
-        if (epi.residual) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            float f = (float)o[q] + (float)rv[j][q];
-            if (epi.relu) f = fmaxf(f, 0.f);
-            o[q] = (T)f;
-          }
-        }
+        if (epi.residual) o = add_residual<T>(o, rv[j], epi.relu);
         // streamed once: non-temporal, so the output does not push the gathered input out of the caches
         __builtin_nontemporal_store(o, reinterpret_cast<frag_t*>(out + (int64_t)orow[j] * ldc + col0 + piece * 8));
       }
@@ -624,7 +474,7 @@ static int cs_mode() {
 // Width of the column blocks an output of `cout` channels is produced in (0: not this family's).  Up to 128 channels: one
 // block; wider: the widest of 128 / 96 / 64 that divides it (256 = 2 x 128, 192 = 2 x 96, 320 = 5 x 64) - the rows are gathered
 // once per block, which the coarse levels of a U-Net (a few thousand rows, 192 - 512 channels) repay with 2 - 4 x the workgroups.
-static int cs_col_block(int cout) {
+int cs_col_block(int cout) {
   if (cout <= 128) return (cout == 64 || cout == 96 || cout == 128) ? cout : 0;
   if (cout > 1024) return 0;
   return cout % 128 == 0 ? 128 : cout % 96 == 0 ? 96 : cout % 64 == 0 ? 64 : 0;
@@ -646,24 +496,14 @@ static int dispatch_cs(const void* in, const void* wp, void* out, const int32_t*
   // 238 / 272 (twice the weight traffic per row); CO = 64 with 2 waves x 64 rows 256 / 374 vs 4 waves x 128 rows 264 / 378
   // vs 2 waves x 128 rows 275 / 392.
   switch (cs_col_block(cout)) {
-#ifdef WCN_CS_PAIR  // (four ring stages and four weight-fragment sets: one wave per SIMD less)
-    case 64: return launch_cs<T, 64, 2, 1, 3>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-    case 96: return launch_cs<T, 96, 3, 1, 2>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-    case 128: return launch_cs<T, 128, 4, 1, 2>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-#else
     // (CO = 64, round 6 again: 4 waves x 64 rows `<64, 1, 2>` 251.8 us, 2 waves x 96 rows `<64, 3, 1>` 255.8 us, against 221.8)
     case 64: return launch_cs<T, 64, 2, 1, 4>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
     case 96: return launch_cs<T, 96, 3, 1, 3>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);  // 3 waves x 96 rows
     // CO = 128, round 6: 96-row tiles, FOUR workgroups a CU (122 VGPRs with the single B-fragment set, 32.6 KB) instead of 128-row
     // tiles and three (141 VGPRs, 42.3 KB): 197.3 vs 200.3 us in the trace, 0.207 vs 0.212 ms in the step, surface scene 728.6 vs
-    // 730.1 M voxels/s (same box; `-DWCN_CS_RBW4` builds the old shape).  160-row tiles `<T, 128, 5, 1, 3>` - weight fragments per
+    // 730.1 M voxels/s (same box).  160-row tiles `<T, 128, 5, 1, 3>` - weight fragments per
     // row -20 %, 166 VGPRs, 54.2 KB - run 244.6 us: the third workgroup of a CU no longer fits.
-#ifdef WCN_CS_RBW4
-    case 128: return launch_cs<T, 128, 4, 1, 3>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-#else
     case 128: return launch_cs<T, 128, 3, 1, 4>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-#endif
-#endif
     default: return WCN_ERROR_UNSUPPORTED_CONFIG;
   }
 }
@@ -672,45 +512,9 @@ int conv_gather_gemm_cs(const void* in, const void* wp, void* out, const int32_t
                         const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
                         float* out32, hipStream_t s) {
   if (!gather_gemm_cs_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  if (dtype == WCN_BF16) return dispatch_cs<__bf16>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-  return dispatch_cs<_Float16>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
-}
-
-int pack_weight_cs(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,
-                   hipStream_t s) {
-  if (!gather_gemm_cs_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  const int64_t total = (int64_t)K * ((cin + kCsCIC - 1) / kCsCIC) * kCsCIC * cout;  // = wcn_packed_weight_elements
-  const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
-  const int cob = cs_col_block(cout);
-  if (w_is_f32) {
-    if (dtype == WCN_BF16)
-      hipLaunchKernelGGL((pack_weight_cs_kernel<float, __bf16>), grid, block, 0, s, (const float*)w, (__bf16*)packed, K, cin,
-                         cout, cob, transpose, flip);
-    else
-      hipLaunchKernelGGL((pack_weight_cs_kernel<float, _Float16>), grid, block, 0, s, (const float*)w, (_Float16*)packed, K,
-                         cin, cout, cob, transpose, flip);
-  } else {
-    hipLaunchKernelGGL((pack_weight_cs_kernel<uint16_t, uint16_t>), grid, block, 0, s, (const uint16_t*)w, (uint16_t*)packed,
-                       K, cin, cout, cob, transpose, flip);
-  }
-  return launch_status();
-}
-
-// forward + dgrad images of an fp32 master weight in one launch; both directions must be this family's shapes
-int pack_weight_cs_pair(const float* w, int K, int cin, int cout, int dtype, int flip_dgrad, void* packed_fwd, void* packed_dgrad,
-                        hipStream_t s) {
-  if (!gather_gemm_cs_supported(cin, cout, K, dtype) || !gather_gemm_cs_supported(cout, cin, K, dtype))
-    return WCN_ERROR_UNSUPPORTED_CONFIG;
-  const int64_t tot_f = (int64_t)K * ((cin + kCsCIC - 1) / kCsCIC) * kCsCIC * cout;
-  const int64_t tot_d = (int64_t)K * ((cout + kCsCIC - 1) / kCsCIC) * kCsCIC * cin;
-  const dim3 grid((unsigned)ceil_div(tot_f > tot_d ? tot_f : tot_d, 256), 2), block(256);
-  if (dtype == WCN_BF16)
-    hipLaunchKernelGGL((pack_weight_cs_pair_kernel<__bf16>), grid, block, 0, s, w, (__bf16*)packed_fwd, (__bf16*)packed_dgrad, K, cin,
-                       cout, cs_col_block(cout), cs_col_block(cin), flip_dgrad);
-  else
-    hipLaunchKernelGGL((pack_weight_cs_pair_kernel<_Float16>), grid, block, 0, s, w, (_Float16*)packed_fwd, (_Float16*)packed_dgrad,
-                       K, cin, cout, cs_col_block(cout), cs_col_block(cin), flip_dgrad);
-  return launch_status();
+  return dispatch_dtype(dtype, [&](auto t) {
+    return dispatch_cs<decltype(t)>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
+  });
 }
 
 }  // namespace wcn

@@ -15,31 +15,11 @@
 //     (the stem under autocast: rounded to T on the fly, as the cast in front of the vendor GEMM would);
 //   * channel counts that are not multiples of 4 (the 3-channel stem) take guarded element loads / stores.
 // HBM-bound: cin + cout elements per row.
-#include "wcn_common.h"
+#include "gather_gemm.h"
 
 namespace wcn {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 d_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 d_f16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 d_bf16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 d_f16x4;
-typedef __attribute__((ext_vector_type(16))) float d_f32x16;
-
-template <typename T> struct DFrag;
-template <> struct DFrag<__bf16> {
-  typedef d_bf16x8 type;
-  typedef d_bf16x4 half_type;
-  static __device__ __forceinline__ d_f32x16 mfma(d_bf16x8 a, d_bf16x8 b, d_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct DFrag<_Float16> {
-  typedef d_f16x8 type;
-  typedef d_f16x4 half_type;
-  static __device__ __forceinline__ d_f32x16 mfma(d_f16x8 a, d_f16x8 b, d_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
+template <typename T> using dr_half = __attribute__((ext_vector_type(4))) T;  // 4 consecutive channels: one 8-B piece
 
 constexpr int kDrMaxSteps = 8;   // k-steps of 16 channels: cin <= 128
 constexpr int kDrMaxBlocks = 3;  // blocks of 32 output channels: cout <= 96 (four blocks leave one wave per SIMD: 231 us for
@@ -54,7 +34,7 @@ __device__ __forceinline__ void dr_load4(const XT* __restrict__ row, int c0, int
       const float4 v = *reinterpret_cast<const float4*>(row + c0);
       out[0] = (T)v.x; out[1] = (T)v.y; out[2] = (T)v.z; out[3] = (T)v.w;
     } else {
-      typename DFrag<T>::half_type v = *reinterpret_cast<const typename DFrag<T>::half_type*>(row + c0);
+      const dr_half<T> v = *reinterpret_cast<const dr_half<T>*>(row + c0);
       out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; out[3] = v[3];
     }
   } else {
@@ -69,7 +49,7 @@ template <typename T, typename XT, typename WT, int NB>
 __global__ __launch_bounds__(kDrThreads) void dense_rows_kernel(const XT* __restrict__ x, const WT* __restrict__ w, int ldw,
                                                                  int transposed, const float* __restrict__ bias,
                                                                  T* __restrict__ y, int64_t n, int cin, int cout) {
-  typedef typename DFrag<T>::type frag;
+  typedef typename Mfma32<T>::type frag;
   __shared__ frag s_w[NB * kDrMaxSteps * 64];
   const int steps = (cin + 15) >> 4;
   for (int e = threadIdx.x; e < NB * steps * 64; e += kDrThreads) {
@@ -119,7 +99,7 @@ __global__ __launch_bounds__(kDrThreads) void dense_rows_kernel(const XT* __rest
         }
       }
     }
-    d_f32x16 acc[NB];
+    f32x16 acc[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(kDrThreads) void dense_rows_kernel(const XT* __rest
     for (int s = 0; s < kDrMaxSteps; ++s) {
       if (s < steps) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) acc[b] = DFrag<T>::mfma(s_w[(b * kDrMaxSteps + s) * 64 + lane], xs[s], acc[b]);
+        for (int b = 0; b < NB; ++b) acc[b] = Mfma32<T>::mfma(s_w[(b * kDrMaxSteps + s) * 64 + lane], xs[s], acc[b]);
       }
     }
     if (vec16_out) {
@@ -164,10 +144,10 @@ __global__ __launch_bounds__(kDrThreads) void dense_rows_kernel(const XT* __rest
           const int ch = b * 32 + 8 * g + 4 * half;  // channels ch .. ch+3 of this row: registers 4g .. 4g+3
           if (ch >= cout) continue;
           if (vec_out && ch + 4 <= cout) {
-            typename DFrag<T>::half_type o;
+            dr_half<T> o;
 #pragma unroll
             for (int q = 0; q < 4; ++q) o[q] = (T)acc[b][4 * g + q];
-            *reinterpret_cast<typename DFrag<T>::half_type*>(yr + ch) = o;
+            *reinterpret_cast<dr_half<T>*>(yr + ch) = o;
           } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
