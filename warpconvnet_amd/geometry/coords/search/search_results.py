@@ -102,6 +102,12 @@ class IntSearchResult:
         self._on_invalid = None  # called once when validation fails (the convolution evicts the map from its cache)
         self._twin = None  # a map made by exchanging in / out of another one (transposed convolution): that map - its reverse
         #                    tables are this map's forward tables and vice versa, nothing is rebuilt from the pair lists
+        # set by the builder (`torch_discrete.generate_kernel_map`) and by the pooling layer; None everywhere else
+        self._device: Optional[torch.device] = None  # where a map without pair lists yet lives (`_blank`)
+        self._kernel_size: Optional[Tuple[int, ...]] = None
+        self._hashtable = None
+        self._keepalive = None  # workspaces the queued build kernels still read
+        self._pool_swapped: Optional["IntSearchResult"] = None  # coarse -> fine view of a pooling map (`sparse_pool._swapped`)
 
     @property
     def has_tables(self) -> bool:
@@ -134,9 +140,9 @@ class IntSearchResult:
         self._in_maps = self._out_maps = None
         self._offsets = None
         self._lazy_pairs = None
-        self._device = torch.device(device)
         self._num_offsets = num_offsets
         self._init_tables()
+        self._device = torch.device(device)
         self.identity_map_index = None
         return self
 
@@ -168,10 +174,9 @@ class IntSearchResult:
         errors (coordinate range, table capacity), fills offsets / identities / pair lists, and rebuilds the tables if the
         device rejected the first attempt.  Returns True when the device tables were REPLACED - launches made on the old
         ones must be repeated.  Idempotent and free once done; a no-op for every other map."""
-        err = getattr(self, "_validate_error", None)
-        if err is not None:
-            raise err  # the reference raises at every use of a failed build; so does this container
-        fn = getattr(self, "_validate_fn", None)
+        if self._validate_error is not None:
+            raise self._validate_error  # the reference raises at every use of a failed build; so does this container
+        fn = self._validate_fn
         if fn is None or self._validating:
             return False
         self._validating = True
@@ -182,7 +187,7 @@ class IntSearchResult:
             # tables hold defined "no neighbour" rows, its lists do not exist - and says so every time
             self._validate_fn = None
             self._validate_error = e
-            cb, self._on_invalid = getattr(self, "_on_invalid", None), None
+            cb, self._on_invalid = self._on_invalid, None
             if cb is not None:
                 cb()
             raise
@@ -195,7 +200,7 @@ class IntSearchResult:
 
     def _ensure_pairs(self):
         self.validate()
-        fn = getattr(self, "_lazy_pairs", None)
+        fn = self._lazy_pairs
         if fn is not None:
             self._lazy_pairs = None
             self._in_maps, self._out_maps = fn()

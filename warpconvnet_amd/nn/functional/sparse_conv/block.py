@@ -28,7 +28,6 @@ from torch.autograd import Function
 
 from warpconvnet_amd import _lib
 from warpconvnet_amd.dist import claim_grad_slot
-from warpconvnet_amd.geometry.coords.search.torch_discrete import reverse_tables
 from warpconvnet_amd.nn.functional.normalizations import _workspace as _bn_workspace
 from warpconvnet_amd.nn.functional.normalizations import bn_module_state
 
@@ -143,10 +142,8 @@ class _ConvBnAct(Function):
         stream = _lib.stream_handle(dev)
         km, M, cin, cout, K, code = plan.km, plan.num_out, plan.cin, plan.cout, plan.K, plan.code
         # (forward and dgrad image in one launch when this step has a backward; k-flip of the latter predicted as in hip_forward)
-        ks = getattr(km, "_kernel_size", None)
-        guess = (bool(km._symmetric) if getattr(km, "_validate_fn", None) is None
-                 else bool(ks is not None and all(int(k) % 2 == 1 for k in ks) and km._num_in == km._num_out))
-        wp = hip_gemm.pack_weight(w, False, False, dtype=x.dtype, dgrad_flip=guess if ctx.needs_input_grad[0] else None)
+        wp = hip_gemm.pack_weight(w, False, False, dtype=x.dtype,
+                                  dgrad_flip=hip_gemm.predict_dgrad_flip(km) if ctx.needs_input_grad[0] else None)
         y = torch.empty((M, cout), dtype=x.dtype, device=dev)
         xp, wpp, yp = _lib.ptr(x), _lib.ptr(wp), _lib.ptr(y)
 
@@ -203,10 +200,7 @@ class _ConvBnAct(Function):
         tbl = msk = perm = wpd = dx = None
         flip = False
         if need_dx:
-            if km._symmetric:
-                (tbl, msk), perm, flip = hip_gemm.own_tables(km, cout, cin, K, y.dtype), km._perm, True
-            else:
-                tbl, msk, perm = reverse_tables(km, plan.num_in)
+            tbl, msk, perm, flip = hip_gemm.dgrad_tables(km, plan.num_in, cout, cin, K, y.dtype)
             wpd = hip_gemm.pack_weight(w, True, flip, dtype=y.dtype)
             dx = torch.empty((plan.num_in, cin), dtype=y.dtype, device=dev)
         dw = wws = None

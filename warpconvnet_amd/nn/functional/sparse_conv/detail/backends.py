@@ -7,6 +7,7 @@ Same plug-in interface as the reference (`warpconvnet/nn/functional/sparse_conv/
 ``auto`` (static shape-class choice between the two HIP paths).
 """
 import dataclasses
+import functools
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, Optional, Tuple
 
@@ -69,61 +70,43 @@ def _bwd_explicit(ctx: BwdCtx):
                                          ctx.device, needs_input_grad=tuple(ctx.needs_input_grad[:2]))
 
 
-def _make_hip_fwd(algo: str) -> FwdFn:
-    def fn(ctx: FwdCtx):
-        dt = ctx.compute_dtype or ctx.in_features.dtype
-        # (an fp32 master weight stays as it is when the MFMA kernel takes the shape: its packed image is rounded from it)
-        w = ctx.weight if hip_gemm.master_weight_ok(dt, ctx.weight, algo, False) else ctx.weight.to(dt)
-        out = hip_gemm.hip_forward(ctx.in_features.to(dt), w, ctx.kernel_map, ctx.num_out_coords, algo, bias=ctx.bias,
-                                   want_dgrad_image=ctx.needs_dgrad)
-        return out.to(ctx.in_features.dtype) if ctx.compute_dtype is not None else out
-
-    return fn
+def _hip_fwd(algo: str, ctx: FwdCtx):
+    dt = ctx.compute_dtype or ctx.in_features.dtype
+    # (an fp32 master weight stays as it is when the MFMA kernel takes the shape: its packed image is rounded from it)
+    w = ctx.weight if hip_gemm.master_weight_ok(dt, ctx.weight, algo, False) else ctx.weight.to(dt)
+    out = hip_gemm.hip_forward(ctx.in_features.to(dt), w, ctx.kernel_map, ctx.num_out_coords, algo, bias=ctx.bias,
+                               want_dgrad_image=ctx.needs_dgrad)
+    return out.to(ctx.in_features.dtype) if ctx.compute_dtype is not None else out
 
 
-def _make_hip_bwd(algo: str) -> BwdFn:
-    def fn(ctx: BwdCtx):
-        dt = ctx.compute_dtype or ctx.in_features.dtype
-        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dy = ctx.grad_output.to(dt)
-        dx = dw = None
-        # Weight gradient FIRST, input gradient second (round 5): the forward has just gathered every row of x; the weight gradient
-        # gathers them again and finds more of them in the 256 MB Infinity Cache before dgrad streams 1 GB of dy rows through
-        # it, and dgrad then finds dy warm - 1 069 -> 1 084 M voxels/s on the headline step (three A/B rounds on one box; wgrad
-        # 246 -> 248 us, dgrad 249 -> 238 us in-step).  The fused conv -> BatchNorm node keeps dgrad first: there dy has just been
-        # written by the BatchNorm backward, and MinkUNet-14 measured the same either way.
-        if need_dw:
-            # the bias gradient rides along only if it is the column sum of the very tensor autograd handed us
-            fuse_db = ctx.want_bias_grad and dy.dtype == ctx.grad_output.dtype
-            if fuse_db:
-                dw, ctx.bias_grad = hip_gemm.hip_wgrad(ctx.in_features.to(dt), dy, ctx.kernel_map, tuple(ctx.weight.shape),
-                                                       algo, want_bias_grad=True, out=getattr(ctx, "dw_out", None))
-            else:
-                dw = hip_gemm.hip_wgrad(ctx.in_features.to(dt), dy, ctx.kernel_map, tuple(ctx.weight.shape), algo,
-                                        out=getattr(ctx, "dw_out", None))
-            # stays fp32 here: the autograd function casts once to the dtype of the weight it was given
-        if need_dx:
-            w = ctx.weight if hip_gemm.master_weight_ok(dt, ctx.weight, algo, True) else ctx.weight.to(dt)
-            dx = hip_gemm.hip_dgrad(dy, w, ctx.kernel_map, ctx.in_features.shape[0], algo)
-            dx = dx.to(ctx.in_features.dtype)
-        return dx, dw
-
-    return fn
+def _hip_bwd(algo: str, ctx: BwdCtx):
+    dt = ctx.compute_dtype or ctx.in_features.dtype
+    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    dy = ctx.grad_output.to(dt)
+    dx = dw = None
+    # Weight gradient FIRST, input gradient second (round 5): the forward has just gathered every row of x; the weight gradient
+    # gathers them again and finds more of them in the 256 MB Infinity Cache before dgrad streams 1 GB of dy rows through
+    # it, and dgrad then finds dy warm - 1 069 -> 1 084 M voxels/s on the headline step (three A/B rounds on one box; wgrad
+    # 246 -> 248 us, dgrad 249 -> 238 us in-step).  The fused conv -> BatchNorm node keeps dgrad first: there dy has just been
+    # written by the BatchNorm backward, and MinkUNet-14 measured the same either way.
+    if need_dw:
+        # the bias gradient rides along only if it is the column sum of the very tensor autograd handed us
+        fuse_db = ctx.want_bias_grad and dy.dtype == ctx.grad_output.dtype
+        dw = hip_gemm.hip_wgrad(ctx.in_features.to(dt), dy, ctx.kernel_map, tuple(ctx.weight.shape), algo,
+                                want_bias_grad=fuse_db, out=ctx.dw_out)
+        if fuse_db:
+            dw, ctx.bias_grad = dw
+        # stays fp32 here: the autograd function casts once to the dtype of the weight it was given
+    if need_dx:
+        w = ctx.weight if hip_gemm.master_weight_ok(dt, ctx.weight, algo, True) else ctx.weight.to(dt)
+        dx = hip_gemm.hip_dgrad(dy, w, ctx.kernel_map, ctx.in_features.shape[0], algo)
+        dx = dx.to(ctx.in_features.dtype)
+    return dx, dw
 
 
-FORWARD_BACKENDS: Dict[str, FwdFn] = {
-    "explicit_gemm": _fwd_explicit,
-    "hip_ref": _make_hip_fwd("hip_ref"),
-    "hip_mfma": _make_hip_fwd("hip_mfma"),
-    "auto": _make_hip_fwd("auto"),
-}
-
-BACKWARD_BACKENDS: Dict[str, BwdFn] = {
-    "explicit_gemm": _bwd_explicit,
-    "hip_ref": _make_hip_bwd("hip_ref"),
-    "hip_mfma": _make_hip_bwd("hip_mfma"),
-    "auto": _make_hip_bwd("auto"),
-}
+_HIP_ALGOS = ("hip_ref", "hip_mfma", "auto")
+FORWARD_BACKENDS: Dict[str, FwdFn] = {"explicit_gemm": _fwd_explicit, **{a: functools.partial(_hip_fwd, a) for a in _HIP_ALGOS}}
+BACKWARD_BACKENDS: Dict[str, BwdFn] = {"explicit_gemm": _bwd_explicit, **{a: functools.partial(_hip_bwd, a) for a in _HIP_ALGOS}}
 
 
 def _hip_algo(algo: str, t: Tensor) -> bool:
@@ -190,52 +173,50 @@ def _group_slices(t: Tensor, groups: int, g: int) -> Tensor:
     return t[:, g * c : (g + 1) * c].contiguous()
 
 
-def run_forward(algo: str, ctx: FwdCtx):
+def _backend(table: dict, algo: str, direction: str):
     try:
-        fn = FORWARD_BACKENDS[algo]
+        return table[algo]
     except KeyError:
-        raise ValueError(f"Unsupported forward algorithm: {algo}")
+        raise ValueError(f"Unsupported {direction} algorithm: {algo}")
+
+
+def _checked(algo: str, tag: str, result):
+    """A backend's result, or the RuntimeError of the non-zero status it returned in its place (first element for a backward)."""
+    status = result[0] if isinstance(result, tuple) else result
+    if isinstance(status, int) and status != 0:
+        raise RuntimeError(f"{algo} {tag} error: {_lib.status_string(status)}")
+    return result
+
+
+def _group_ctx(ctx, g: int, **fields):
+    """Channel groups (weight [K, G, Cin/G, Cout/G], reference sparse_conv.py:147-157): G independent problems on channel
+    slices, same kernel map - the context of group ``g``.  Slices are made contiguous (the kernels take dense [N, C] rows)."""
+    return dataclasses.replace(ctx, in_features=_group_slices(ctx.in_features, ctx.groups, g),
+                               weight=ctx.weight[:, g].contiguous(), groups=1, **fields)
+
+
+def run_forward(algo: str, ctx: FwdCtx):
+    fn = _backend(FORWARD_BACKENDS, algo, "forward")
     if ctx.groups > 1:
         fast = _grouped_fast_forward(algo, ctx)
         if fast is not None:
             return fast
-        # Channel groups (weight [K, G, Cin/G, Cout/G], reference sparse_conv.py:147-157): G independent problems on
-        # channel slices, same kernel map.  Slices are made contiguous (the kernels take dense [N, C] rows).
-        G = ctx.groups
-        outs = []
-        for g in range(G):
-            sub = dataclasses.replace(
-                ctx, in_features=_group_slices(ctx.in_features, G, g), weight=ctx.weight[:, g].contiguous(), groups=1,
-                bias=None if ctx.bias is None else ctx.bias.reshape(G, -1)[g].contiguous())
-            r = fn(sub)
-            if isinstance(r, int) and r != 0:
-                raise RuntimeError(f"{algo} fwd error: {_lib.status_string(r)}")
-            outs.append(r)
-        return torch.cat(outs, dim=1)
-    result = fn(ctx)
-    if isinstance(result, int) and result != 0:
-        raise RuntimeError(f"{algo} fwd error: {_lib.status_string(result)}")
-    return result
+        bias = None if ctx.bias is None else ctx.bias.reshape(ctx.groups, -1)
+        return torch.cat([_checked(algo, "fwd", fn(_group_ctx(ctx, g, bias=None if bias is None else bias[g].contiguous())))
+                          for g in range(ctx.groups)], dim=1)
+    return _checked(algo, "fwd", fn(ctx))
 
 
 def run_backward(algo: str, ctx: BwdCtx):
-    try:
-        fn = BACKWARD_BACKENDS[algo]
-    except KeyError:
-        raise ValueError(f"Unsupported backward algorithm: {algo}")
+    fn = _backend(BACKWARD_BACKENDS, algo, "backward")
     if ctx.groups > 1:
         fast = _grouped_fast_backward(algo, ctx)
         if fast is not None:
             return fast
-        G = ctx.groups
         dxs, dws, dbs = [], [], []
-        for g in range(G):
-            sub = dataclasses.replace(
-                ctx, grad_output=_group_slices(ctx.grad_output, G, g), in_features=_group_slices(ctx.in_features, G, g),
-                weight=ctx.weight[:, g].contiguous(), groups=1, bias_grad=None)
-            dx, dw = fn(sub)
-            if isinstance(dx, int) and dx != 0:
-                raise RuntimeError(f"{algo} bwd error: {_lib.status_string(dx)}")
+        for g in range(ctx.groups):
+            sub = _group_ctx(ctx, g, grad_output=_group_slices(ctx.grad_output, ctx.groups, g), bias_grad=None)
+            dx, dw = _checked(algo, "bwd", fn(sub))
             dxs.append(dx)
             dws.append(dw)
             dbs.append(sub.bias_grad)
@@ -243,7 +224,4 @@ def run_backward(algo: str, ctx: BwdCtx):
         dw = torch.stack(dws, dim=1) if dws[0] is not None else None  # [K, G, Cin/G, Cout/G]
         ctx.bias_grad = torch.cat(dbs) if all(b is not None for b in dbs) else None
         return dx, dw
-    result = fn(ctx)
-    if isinstance(result[0], int) and result[0] != 0:
-        raise RuntimeError(f"{algo} bwd error: {_lib.status_string(result[0])}")
-    return result
+    return _checked(algo, "bwd", fn(ctx))

@@ -65,35 +65,74 @@ def fp16_safe_cast(t: Tensor) -> Tuple[Tensor, Tensor]:
     return (t * torch.exp2(-exp)).half(), torch.exp2(exp)
 
 
-def _fp32_via_fp16(algo: str, kin: int, kout: int, K: int, dtype: torch.dtype) -> bool:
-    """fp32 features take the fp16-operand fused kernels when the algorithm allows and the shape is covered."""
-    if dtype != torch.float32 or algo == "hip_ref":
-        return False
-    return _gather_ok(kin, kout, K, _lib.WCN_F16)
+def _via_fp16(a: Tensor, b: Tensor, launch) -> Tensor:
+    """fp32 operands through fp16 ones: ``launch(a16, b16)`` (fp32 result) times the product of the two operand scales - an
+    exact power-of-two multiply-back, no host sync."""
+    a16, sa = fp16_safe_cast(a)
+    b16, sb = fp16_safe_cast(b)
+    return launch(a16, b16) * (sa * sb)
 
 
-def resolve_gather_algo(algo: str, cin: int, cout: int, K: int, dtype: torch.dtype) -> int:
-    L = _lib.lib()
-    ok = _gather_ok(cin, cout, K, _lib.dtype_code(dtype))
-    if algo == "hip_ref":
-        return _lib.WCN_ALGO_REF
-    if algo == "hip_mfma":
-        if not ok:
-            raise RuntimeError(f"hip_mfma error: {_lib.status_string(-4)} (cin={cin}, cout={cout}, K={K}, {dtype})")
-        return _lib.WCN_ALGO_MFMA
-    return _lib.WCN_ALGO_MFMA if ok else _lib.WCN_ALGO_REF
+# ---- operand plan: what one product does with its operands ---------------------------------------------------------------------
+# native (the MFMA kernels on the operands as they are), ref (the simple kernels, any channel count / full fp32), fp32 through fp16
+# operands (`_via_fp16`), or zero-padded channels: C in {3, 7, 13, 23, 33, 65}, ... lie outside the MFMA tiles.  The reference
+# covers them with scalar-load tile variants and a zero-filled K tail (`mask_gemm.py:495-541`,
+# `warpgemm_a_loader_precomputed.cuh:176-224`).  Here the operands are padded with zero channels to the next shape the MFMA
+# kernels take and the result is cut back: zeros contribute nothing to any of the three products, so the values are those of the
+# unpadded problem (same fp32 accumulation), at the cost of one padded copy of the operands.
+_NATIVE, _REF, _VIA_FP16, _PADDED = "native", "ref", "via_fp16", "padded"
+_MFMA_COUTS = (16, 32, 48, 64, 96, 128, 160, 192, 256, 384, 512)
 
 
-def resolve_wgrad_algo(algo: str, cin: int, cout: int, dtype: torch.dtype) -> int:
-    L = _lib.lib()
-    ok = _wgrad_ok(cin, cout, _lib.dtype_code(dtype))
-    if algo == "hip_ref":
-        return _lib.WCN_ALGO_REF
-    if algo == "hip_mfma":
-        if not ok:
-            raise RuntimeError(f"hip_mfma wgrad error: {_lib.status_string(-4)} (cin={cin}, cout={cout}, {dtype})")
-        return _lib.WCN_ALGO_MFMA
-    return _lib.WCN_ALGO_MFMA if ok else _lib.WCN_ALGO_REF
+def _code16(dtype: torch.dtype) -> int:
+    return _lib.WCN_F16 if dtype == torch.float32 else _lib.dtype_code(dtype)
+
+
+def _resolve(algo: str, ok: bool, what: str, shape: str):
+    """``(treatment, algorithm code)`` of operands taken as they are; ``ok``: the MFMA kernel's probe for the shape."""
+    if algo == "hip_mfma" and not ok:
+        raise RuntimeError(f"hip_mfma {what}: {_lib.status_string(-4)} ({shape})")
+    return (_NATIVE, _lib.WCN_ALGO_MFMA) if ok and algo != "hip_ref" else (_REF, _lib.WCN_ALGO_REF)
+
+
+@functools.lru_cache(maxsize=None)
+def _gather_plan(algo: str, kin: int, kout: int, K: int, dtype: torch.dtype, on_gpu: bool):
+    """``(treatment, algorithm code, kin, kout as launched)`` of a forward (kin = Cin) or dgrad (kin = Cout: it reduces over Cout
+    and produces Cin) product.  A pure function of its arguments, memoised: asked on every call of every layer."""
+    if algo == "auto" and on_gpu and not _gather_ok(kin, kout, K, _code16(dtype)) and dtype in (torch.float16, torch.bfloat16):
+        # the smallest MFMA shape that contains kin x kout (fp32 features keep full fp32 operands on such shapes instead)
+        kin_p = max(32, (kin + 31) // 32 * 32)
+        for kout_p in _MFMA_COUTS:
+            if kout_p >= kout and _gather_ok(kin_p, kout_p, K, _lib.dtype_code(dtype)):
+                return _PADDED, _lib.WCN_ALGO_MFMA, kin_p, kout_p
+    if dtype == torch.float32 and algo != "hip_ref" and _gather_ok(kin, kout, K, _lib.WCN_F16):
+        return _VIA_FP16, _lib.WCN_ALGO_MFMA, kin, kout
+    return _resolve(algo, _gather_ok(kin, kout, K, _lib.dtype_code(dtype)), "error",
+                    f"cin={kin}, cout={kout}, K={K}, {dtype}") + (kin, kout)
+
+
+@functools.lru_cache(maxsize=None)
+def _wgrad_plan(algo: str, cin: int, cout: int, dtype: torch.dtype, on_gpu: bool):
+    """The same for the weight gradient: its own probe, and both channel counts padded to a multiple of 32 (the padded rows /
+    columns of dw are zero)."""
+    if algo == "auto" and on_gpu and not _wgrad_ok(cin, cout, _code16(dtype)) and dtype != torch.float32:
+        cin_p, cout_p = (cin + 31) // 32 * 32, (cout + 31) // 32 * 32
+        if _wgrad_ok(cin_p, cout_p, _lib.dtype_code(dtype)):
+            return _PADDED, _lib.WCN_ALGO_MFMA, cin_p, cout_p
+    if dtype == torch.float32 and algo != "hip_ref" and _wgrad_ok(cin, cout, _lib.WCN_F16):
+        return _VIA_FP16, _lib.WCN_ALGO_MFMA, cin, cout
+    return _resolve(algo, _wgrad_ok(cin, cout, _lib.dtype_code(dtype)), "wgrad error",
+                    f"cin={cin}, cout={cout}, {dtype}") + (cin, cout)
+
+
+def _fit(t: Optional[Tensor], *widths: int) -> Optional[Tensor]:
+    """``t`` with its trailing dimensions zero-padded up to, or cut back to, ``widths``."""
+    if t is None:
+        return None
+    grow = [w - s for s, w in zip(t.shape[-len(widths):], widths)]
+    if any(g > 0 for g in grow):
+        return torch.nn.functional.pad(t, [p for g in reversed(grow) for p in (0, g)])
+    return t[(..., *map(slice, widths))].contiguous()
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,11 +146,52 @@ def own_tables(kernel_map, kin: int, kout: int, K: int, dtype: torch.dtype, mfma
     (``kernel_map._nbrc``, `csrc/kmap_cells.h`): where the channel-split kernels take the shape they are passed as they are, with
     ``mask`` = None - half the table bytes of the launch and no gather of ``mask[perm[i]]`` (a 128-B line per row).  Everything
     else gets the dense table (expanded from the compact rows on first use) and the mask array."""
-    c = getattr(kernel_map, "_nbrc", None)
+    c = kernel_map._nbrc
     if (mfma and c is not None and dtype in (torch.float16, torch.bfloat16)
             and _compact_ok(kin, kout, K, _lib.dtype_code(dtype))):
         return c, None
     return kernel_map._nbr, kernel_map._mask
+
+
+def dgrad_tables(kernel_map, num_in: int, kin: int, kout: int, K: int, dtype: torch.dtype, mfma: bool = True):
+    """``(table, mask, perm, flip)`` of an input-gradient launch: a submanifold map over distinct coordinates reads its own
+    forward table with the offsets reversed (`own_tables`; ``mfma=False`` - the grouped kernels - always gets the dense table
+    and the mask), every other map its reverse tables."""
+    if kernel_map._symmetric:
+        return (*own_tables(kernel_map, kin, kout, K, dtype, mfma), kernel_map._perm, True)
+    return (*reverse_tables(kernel_map, num_in), False)
+
+
+def predict_dgrad_flip(kernel_map) -> bool:
+    """Will the dgrad weight image of this map be k-flipped (`dgrad_tables`)?  Exact once the map is validated, "same row count,
+    odd kernel" before that - a wrong guess only costs the ordinary dgrad pack in the backward."""
+    if kernel_map._validate_fn is None:
+        return bool(kernel_map._symmetric)
+    ks = kernel_map._kernel_size
+    return bool(ks is not None and all(int(k) % 2 == 1 for k in ks) and kernel_map._num_in == kernel_map._num_out)
+
+
+def _cached_image(weight: Tensor, key, make) -> Tensor:
+    """The packed image ``key`` of ``weight`` from ``weight._wcn_packed`` (``key -> (stamp, image)``), or ``make(keep)[key]``:
+    ``make`` returns ``{key: image}`` - more than one entry when one launch writes several images - and all of them are
+    remembered under the weight's stamp when it is a parameter (``keep``: a leaf that requires grad)."""
+    stamp = (weight._version, weight.data_ptr(), weight.device)
+    cache = getattr(weight, "_wcn_packed", None)
+    hit = None if cache is None else cache.get(key)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    keep = weight.requires_grad and weight.is_leaf
+    images = make(keep)
+    if keep:
+        if cache is None:
+            cache = {}
+            try:
+                weight._wcn_packed = cache
+            except AttributeError:
+                return images[key]
+        for k, image in images.items():
+            cache[k] = (stamp, image)
+    return images[key]
 
 
 @functools.lru_cache(maxsize=None)
@@ -133,51 +213,31 @@ def pack_weight(weight: Tensor, transpose: bool, flip: bool, dtype: Optional[tor
     after such an update.  Temporaries (autocast copies, computed weights) are never remembered: the cache lives and
     dies with the parameter object, there is no global table."""
     K, c_in, c_out = weight.shape
-    kin, kout = (c_out, c_in) if transpose else (c_in, c_out)  # kernel-side channel roles
     dtype = dtype or weight.dtype
     key = (dtype, bool(transpose), bool(flip))
-    stamp = (weight._version, weight.data_ptr(), weight.device)
-    cache = getattr(weight, "_wcn_packed", None)
-    if cache is not None:
-        hit = cache.get(key)
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-    cacheable = weight.requires_grad and weight.is_leaf
-    if (dgrad_flip is not None and not transpose and not flip and cacheable
-            and weight.dtype == torch.float32 and dtype in (torch.float16, torch.bfloat16)
-            and _pair_ok(K, c_in, c_out, _lib.dtype_code(dtype))):
-        # the forward image of a parameter that will need its dgrad image in this step's backward (``dgrad_flip``: whether that
-        # one is k-flipped - the caller's prediction; a wrong one only costs the ordinary pack later): both in ONE launch
-        esz = 2
-        fwd = torch.empty(_lib.lib().wcn_packed_weight_bytes(K, c_in, c_out, _lib.dtype_code(dtype), 0) // esz, dtype=dtype,
-                          device=weight.device)
-        bwd = torch.empty(_lib.lib().wcn_packed_weight_bytes(K, c_out, c_in, _lib.dtype_code(dtype), 1) // esz, dtype=dtype,
-                          device=weight.device)
-        _lib.check(
-            _lib.lib().wcn_pack_weight_f32_pair(_lib.ptr(weight), K, c_in, c_out, _lib.dtype_code(dtype), int(bool(dgrad_flip)),
-                                                _lib.ptr(fwd), fwd.numel() * esz, _lib.ptr(bwd), bwd.numel() * esz,
-                                                _lib.stream_handle(weight.device)),
-            "wcn_pack_weight_f32_pair",
-        )
-        if cache is None:
-            cache = {}
-            try:
-                weight._wcn_packed = cache
-            except AttributeError:
-                return fwd
-        cache[key] = (stamp, fwd)
-        cache[(dtype, True, bool(dgrad_flip))] = (stamp, bwd)
-        return fwd
-    packed = _pack_weight_uncached(weight, K, kin, kout, transpose, flip, dtype)
-    if weight.requires_grad and weight.is_leaf:
-        if cache is None:
-            cache = {}
-            try:
-                weight._wcn_packed = cache
-            except AttributeError:
-                return packed
-        cache[key] = (stamp, packed)
-    return packed
+
+    def make(keep: bool):
+        if (dgrad_flip is not None and not transpose and not flip and keep
+                and weight.dtype == torch.float32 and dtype in (torch.float16, torch.bfloat16)
+                and _pair_ok(K, c_in, c_out, _lib.dtype_code(dtype))):
+            # the forward image of a parameter that will need its dgrad image in this step's backward (``dgrad_flip``: whether that
+            # one is k-flipped - the caller's prediction; a wrong one only costs the ordinary pack later): both in ONE launch
+            esz = 2
+            fwd = torch.empty(_lib.lib().wcn_packed_weight_bytes(K, c_in, c_out, _lib.dtype_code(dtype), 0) // esz, dtype=dtype,
+                              device=weight.device)
+            bwd = torch.empty(_lib.lib().wcn_packed_weight_bytes(K, c_out, c_in, _lib.dtype_code(dtype), 1) // esz, dtype=dtype,
+                              device=weight.device)
+            _lib.check(
+                _lib.lib().wcn_pack_weight_f32_pair(_lib.ptr(weight), K, c_in, c_out, _lib.dtype_code(dtype), int(bool(dgrad_flip)),
+                                                    _lib.ptr(fwd), fwd.numel() * esz, _lib.ptr(bwd), bwd.numel() * esz,
+                                                    _lib.stream_handle(weight.device)),
+                "wcn_pack_weight_f32_pair",
+            )
+            return {key: fwd, (dtype, True, bool(dgrad_flip)): bwd}
+        kin, kout = (c_out, c_in) if transpose else (c_in, c_out)  # kernel-side channel roles
+        return {key: _pack_weight_uncached(weight, K, kin, kout, transpose, flip, dtype)}
+
+    return _cached_image(weight, key, make)
 
 
 def invalidate_packed(obj) -> None:
@@ -185,7 +245,7 @@ def invalidate_packed(obj) -> None:
     updates through ``p.data`` (EMA swaps, ``p.data.copy_``), which no version counter records."""
     params = obj.parameters() if hasattr(obj, "parameters") else obj
     for p in params:
-        for attr in ("_wcn_packed", "_wcn_packed_grouped", "_wcn_pc_packed"):
+        for attr in ("_wcn_packed", "_wcn_pc_packed"):
             if hasattr(p, attr):
                 try:
                     delattr(p, attr)
@@ -213,33 +273,6 @@ def _pack_weight_uncached(weight: Tensor, K: int, kin: int, kout: int, transpose
         "wcn_pack_weight",
     )
     return packed
-
-
-# ---- channel counts outside the MFMA tiles (C in {3, 7, 13, 23, 33, 65}, ...): zero-padded channels --------------------------
-# The reference covers them with scalar-load tile variants and a zero-filled K tail (`mask_gemm.py:495-541`,
-# `warpgemm_a_loader_precomputed.cuh:176-224`).  Here the operands are padded with zero channels to the next shape the
-# MFMA kernels take and the result is cut back: zeros contribute nothing to any of the three products, so the values are
-# those of the unpadded problem (same fp32 accumulation), at the cost of one padded copy of the operands.
-_MFMA_COUTS = (16, 32, 48, 64, 96, 128, 160, 192, 256, 384, 512)
-
-
-def _code16(dtype: torch.dtype) -> int:
-    return _lib.WCN_F16 if dtype == torch.float32 else _lib.dtype_code(dtype)
-
-
-def _pad_plan(kin: int, kout: int, K: int, dtype: torch.dtype):
-    """(kin_padded, kout_padded) of the smallest MFMA gather-GEMM shape that contains kin x kout, or None."""
-    if dtype not in (torch.float16, torch.bfloat16):
-        return None  # fp32 features keep full fp32 operands on the shapes the MFMA kernels do not take natively
-    kin_p = max(32, (kin + 31) // 32 * 32)
-    for kout_p in _MFMA_COUTS:
-        if kout_p >= kout and _gather_ok(kin_p, kout_p, K, _code16(dtype)):
-            return kin_p, kout_p
-    return None
-
-
-def _pad_cols(t: Tensor, width: int) -> Tensor:
-    return t if t.shape[-1] == width else torch.nn.functional.pad(t, (0, width - t.shape[-1]))
 
 
 def master_weight_ok(x_dtype: torch.dtype, weight: Tensor, algo: str, transposed: bool) -> bool:
@@ -296,37 +329,20 @@ def hip_forward(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult
         raise RuntimeError(f"hip forward error: {_lib.status_string(-6)} ({x.dtype} vs {w.dtype})")
     K, cin, cout = w.shape
     assert K == len(kernel_map) and cin == x.shape[1]
-    if algo == "auto" and x.is_cuda and not _gather_ok(cin, cout, K, _code16(x.dtype)):
-        plan = _pad_plan(cin, cout, K, x.dtype)
-        if plan is not None:  # zero-padded channels on the MFMA kernels instead of one thread per output element
-            wp_ = torch.nn.functional.pad(w.to(x.dtype) if w.dtype != x.dtype else w, (0, plan[1] - cout, 0, plan[0] - cin))
-            y = hip_forward(_pad_cols(x, plan[0]), wp_, kernel_map, num_out_coords, algo,
-                            None if bias is None else _pad_cols(bias, plan[1]))
-            return y[:, :cout].contiguous()
+    how, code, cin_p, cout_p = _gather_plan(algo, cin, cout, K, x.dtype, x.is_cuda)
+    if how == _PADDED:  # zero-padded channels on the MFMA kernels instead of one thread per output element
+        x, w, bias = _fit(x, cin_p), _fit(w, cin_p, cout_p), _fit(bias, cout_p)
     attach_tables_from_csr(kernel_map, x.shape[0], num_out_coords)
 
     def launch():
-        if _fp32_via_fp16(algo, cin, cout, K, x.dtype):
-            x16, sx = fp16_safe_cast(x)
-            w16, sw = fp16_safe_cast(w)
-            tb, mk = own_tables(kernel_map, cin, cout, K, torch.float16)
-            y = _gather_gemm(x16, w16, tb, mk, kernel_map._perm, num_out_coords, cin, cout, K,
-                             _lib.WCN_ALGO_MFMA, transposed=False, flip=False, bias=None, f32_out=True)
-            y = y * (sx * sw)  # exact power-of-two multiply-back, no host sync
+        tb, mk = own_tables(kernel_map, cin_p, cout_p, K, torch.float16 if how == _VIA_FP16 else x.dtype,
+                            mfma=code == _lib.WCN_ALGO_MFMA)
+        if how == _VIA_FP16:
+            y = _via_fp16(x, w, lambda x16, w16: _gather_gemm(x16, w16, tb, mk, kernel_map._perm, num_out_coords, cin, cout, K,
+                                                              code, transposed=False, flip=False, f32_out=True))
             return y if bias is None else y + bias
-        code = resolve_gather_algo(algo, cin, cout, K, x.dtype)
-        # prediction of the dgrad image's k-flip (a submanifold map over distinct coordinates): exact once the map is validated,
-        # "same row count, odd kernel" before that - a wrong guess only costs the ordinary dgrad pack in the backward
-        if not want_dgrad_image:
-            guess = None
-        elif getattr(kernel_map, "_validate_fn", None) is None:
-            guess = bool(kernel_map._symmetric)
-        else:
-            ks = getattr(kernel_map, "_kernel_size", None)
-            guess = bool(ks is not None and all(int(k) % 2 == 1 for k in ks) and kernel_map._num_in == kernel_map._num_out)
-        tb, mk = own_tables(kernel_map, cin, cout, K, x.dtype, mfma=code == _lib.WCN_ALGO_MFMA)
-        return _gather_gemm(x, w, tb, mk, kernel_map._perm, num_out_coords, cin, cout, K, code,
-                            transposed=False, flip=False, bias=bias, dgrad_flip=guess)
+        return _gather_gemm(x, w, tb, mk, kernel_map._perm, num_out_coords, cin_p, cout_p, K, code, transposed=False, flip=False,
+                            bias=bias, dgrad_flip=predict_dgrad_flip(kernel_map) if want_dgrad_image else None)
 
     # An optimistic map (built by the convolution itself this very call) has not had its status word read: the forward is
     # queued on its tables FIRST - so the GPU runs mask sort -> forward back to back while the host gets to the status -
@@ -334,7 +350,7 @@ def hip_forward(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult
     y = launch()
     if kernel_map.validate():
         y = launch()
-    return y
+    return _fit(y, cout) if how == _PADDED else y
 
 
 def hip_colsum(t: Tensor) -> Tensor:
@@ -382,7 +398,7 @@ def _dgrad_duplicates(dy: Tensor, w: Tensor, kernel_map: IntSearchResult, num_in
     dyp = torch.zeros((n, dy.shape[1]), dtype=torch.float32, device=dy.device).index_add_(0, winner, dy.float()).to(dy.dtype)
     shadow = IntSearchResult._blank(K, dy.device)  # the same tables, seen as a map without duplicates
     shadow._nbr, shadow._mask, shadow._perm = kernel_map._nbr, kernel_map._mask, kernel_map._perm
-    shadow._nbrc = getattr(kernel_map, "_nbrc", None)
+    shadow._nbrc = kernel_map._nbrc
     shadow._offsets_dev, shadow._offsets = kernel_map._offsets_dev, kernel_map._offsets
     shadow._symmetric, shadow._has_duplicates = True, False
     shadow._in_maps, shadow._out_maps = kernel_map._in_maps, kernel_map._out_maps
@@ -399,31 +415,21 @@ def hip_dgrad(grad_output: Tensor, weight: Tensor, kernel_map: IntSearchResult, 
         raise RuntimeError(f"hip dgrad error: {_lib.status_string(-6)} ({dy.dtype} vs {w.dtype})")
     K, cin, cout = w.shape
     kernel_map.validate()
-    if getattr(kernel_map, "_has_duplicates", False):
-        if getattr(kernel_map, "_dup_symmetric", False) and kernel_map.has_tables and dy.shape[0] == num_in_coords:
+    if kernel_map._has_duplicates:
+        if kernel_map._dup_symmetric and kernel_map.has_tables and dy.shape[0] == num_in_coords:
             return _dgrad_duplicates(dy, w, kernel_map, num_in_coords, algo)
         return _dgrad_pair_lists(dy, w, kernel_map, num_in_coords)
-    if algo == "auto" and dy.is_cuda and not _gather_ok(cout, cin, K, _code16(dy.dtype)):
-        plan = _pad_plan(cout, cin, K, dy.dtype)  # kernel-side roles: reduce over cout, produce cin
-        if plan is not None:
-            wp_ = torch.nn.functional.pad(w.to(dy.dtype) if w.dtype != dy.dtype else w, (0, plan[0] - cout, 0, plan[1] - cin))
-            return hip_dgrad(_pad_cols(dy, plan[0]), wp_, kernel_map, num_in_coords, algo)[:, :cin].contiguous()
+    how, code, cout_p, cin_p = _gather_plan(algo, cout, cin, K, dy.dtype, dy.is_cuda)  # kernel-side roles: reduce over cout
+    if how == _PADDED:
+        dy, w = _fit(dy, cout_p), _fit(w, cin_p, cout_p)
     attach_tables_from_csr(kernel_map, num_in_coords, dy.shape[0])
-    via16 = _fp32_via_fp16(algo, cout, cin, K, dy.dtype)
-    code = _lib.WCN_ALGO_MFMA if via16 else resolve_gather_algo(algo, cout, cin, K, dy.dtype)
-    if kernel_map._symmetric:
-        tbl, mask = own_tables(kernel_map, cout, cin, K, torch.float16 if via16 else dy.dtype, mfma=code == _lib.WCN_ALGO_MFMA)
-        perm, flip = kernel_map._perm, True
-    else:
-        tbl, mask, perm = reverse_tables(kernel_map, num_in_coords)
-        flip = False
-    if via16:
-        g16, sg = fp16_safe_cast(dy)
-        w16, sw = fp16_safe_cast(w)
-        dx = _gather_gemm(g16, w16, tbl, mask, perm, num_in_coords, cout, cin, K, _lib.WCN_ALGO_MFMA, transposed=True,
-                          flip=flip, f32_out=True)
-        return dx * (sg * sw)
-    return _gather_gemm(dy, w, tbl, mask, perm, num_in_coords, cout, cin, K, code, transposed=True, flip=flip)
+    tbl, mask, perm, flip = dgrad_tables(kernel_map, num_in_coords, cout_p, cin_p, K,
+                                         torch.float16 if how == _VIA_FP16 else dy.dtype, mfma=code == _lib.WCN_ALGO_MFMA)
+    if how == _VIA_FP16:
+        return _via_fp16(dy, w, lambda g16, w16: _gather_gemm(g16, w16, tbl, mask, perm, num_in_coords, cout, cin, K, code,
+                                                              transposed=True, flip=flip, f32_out=True))
+    dx = _gather_gemm(dy, w, tbl, mask, perm, num_in_coords, cout_p, cin_p, K, code, transposed=True, flip=flip)
+    return _fit(dx, cin) if how == _PADDED else dx
 
 
 def hip_wgrad(in_features: Tensor, grad_output: Tensor, kernel_map: IntSearchResult, weight_shape, algo: str = "auto",
@@ -441,33 +447,33 @@ def hip_wgrad(in_features: Tensor, grad_output: Tensor, kernel_map: IntSearchRes
     if x.dtype != dy.dtype:
         raise RuntimeError(f"hip wgrad error: {_lib.status_string(-6)} ({x.dtype} vs {dy.dtype})")
     K, cin, cout = weight_shape
-    dev = x.device
-    if algo == "auto" and x.is_cuda and not _wgrad_ok(cin, cout, _code16(x.dtype)):
-        cin_p, cout_p = (cin + 31) // 32 * 32, (cout + 31) // 32 * 32
-        if x.dtype != torch.float32 and _wgrad_ok(cin_p, cout_p, _code16(x.dtype)):  # zero-padded channels: the padded rows / columns of dw are zero
-            r = hip_wgrad(_pad_cols(x, cin_p), _pad_cols(dy, cout_p), kernel_map, (K, cin_p, cout_p), algo, want_bias_grad)
-            dw_p, db = r if want_bias_grad else (r, None)
-            dw_c = dw_p[:, :cin, :cout].contiguous()
-            return (dw_c, None if db is None else db[:cout].contiguous()) if want_bias_grad else dw_c
+    how, code, cin_p, cout_p = _wgrad_plan(algo, cin, cout, x.dtype, x.is_cuda)
+    if how == _PADDED:
+        x, dy = _fit(x, cin_p), _fit(dy, cout_p)
     kernel_map.validate()
-    scale = None
-    if x.dtype == torch.float32 and algo != "hip_ref" and _wgrad_ok(cin, cout, _lib.WCN_F16):
-        x, sx = fp16_safe_cast(x)      # fp16 operands, fp32 accumulate and output; scales multiplied back below
-        dy, sg = fp16_safe_cast(dy)
-        scale = sx * sg
-    if out is not None and scale is None and out.shape == (K, cin, cout) and out.dtype == torch.float32 and out.is_contiguous() \
-            and out.device == dev:
-        dw = out
-    else:
-        dw = torch.empty((K, cin, cout), dtype=torch.float32, device=dev)
+    if how == _VIA_FP16:  # (no bias gradient from this kernel then: it stays an exact fp32 column sum, the caller's)
+        dw = _via_fp16(x, dy, lambda x16, g16: _wgrad_launch(x16, g16, kernel_map, K, cin, cout, code, None, False)[0])
+        return (dw, None) if want_bias_grad else dw
+    if out is not None and (how == _PADDED or out.shape != (K, cin, cout) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != x.device):
+        out = None
+    dw, db = _wgrad_launch(x, dy, kernel_map, K, cin_p, cout_p, code, out, want_bias_grad)
+    if how == _PADDED:
+        dw, db = _fit(dw, cin, cout), _fit(db, cout)
+    return (dw, db) if want_bias_grad else dw
+
+
+def _wgrad_launch(x: Tensor, dy: Tensor, kernel_map: IntSearchResult, K: int, cin: int, cout: int, code: int,
+                  out: Optional[Tensor], want_bias_grad: bool):
+    """-> (dw fp32 [K, cin, cout], written into ``out`` when given; the fp32 column sums of ``dy`` from the same kernel or None)."""
+    dev = x.device
+    dw = out if out is not None else torch.empty((K, cin, cout), dtype=torch.float32, device=dev)
     if kernel_map._offsets_dev is None:
         kernel_map._offsets_dev = kernel_map.offsets.to(device=dev, dtype=torch.int32)
     L = _lib.lib()
-    code = resolve_wgrad_algo(algo, cin, cout, x.dtype)
     ws_bytes = _wgrad_workspace(K, cin, cout, code)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    # (not for fp32 features routed through fp16 operands: the bias gradient then stays an exact fp32 column sum)
-    fuse = (want_bias_grad and scale is None and code == _lib.WCN_ALGO_MFMA and getattr(kernel_map, "_self_exact", False)
+    fuse = (want_bias_grad and code == _lib.WCN_ALGO_MFMA and kernel_map._self_exact
             and x.shape[0] == dy.shape[0] and dy.shape[0] > 0
             and _wgrad_bias_ok(cin, cout, _lib.dtype_code(x.dtype)))
     if fuse:
@@ -486,9 +492,7 @@ def hip_wgrad(in_features: Tensor, grad_output: Tensor, kernel_map: IntSearchRes
                          cout, K, _lib.dtype_code(x.dtype), code, _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev)),
         "wcn_conv_wgrad",
     )
-    if scale is not None:
-        dw = dw * scale
-    return (dw, None) if want_bias_grad else dw
+    return dw, None
 
 
 # ---- channel groups -----------------------------------------------------------------------------------------------
@@ -511,31 +515,21 @@ def _pack_grouped(weight: Tensor, transpose: bool, flip: bool, dtype: torch.dtyp
     """G packed images back to back, one launch; cached on the parameter per version like `pack_weight`."""
     K, G, cg_in, cg_out = weight.shape
     kin, kout = (cg_out, cg_in) if transpose else (cg_in, cg_out)
+
+    def make(keep: bool):
+        w = weight.contiguous()
+        if w.dtype not in (torch.float32, dtype):
+            w = w.to(dtype)
+        packed = torch.empty(w.numel(), dtype=dtype, device=w.device)
+        _lib.check(
+            _lib.lib().wcn_pack_weight_grouped(_lib.ptr(w), int(w.dtype == torch.float32), K, G, kin, kout, _lib.dtype_code(dtype),
+                                               int(transpose), int(flip), _lib.ptr(packed), _lib.stream_handle(w.device)),
+            "wcn_pack_weight_grouped",
+        )
+        return {key: packed}
+
     key = ("grouped", dtype, bool(transpose), bool(flip))
-    stamp = (weight._version, weight.data_ptr(), weight.device)
-    cache = getattr(weight, "_wcn_packed", None)
-    if cache is not None:
-        hit = cache.get(key)
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-    w = weight.contiguous()
-    if w.dtype not in (torch.float32, dtype):
-        w = w.to(dtype)
-    packed = torch.empty(w.numel(), dtype=dtype, device=w.device)
-    _lib.check(
-        _lib.lib().wcn_pack_weight_grouped(_lib.ptr(w), int(w.dtype == torch.float32), K, G, kin, kout, _lib.dtype_code(dtype),
-                                           int(transpose), int(flip), _lib.ptr(packed), _lib.stream_handle(w.device)),
-        "wcn_pack_weight_grouped",
-    )
-    if weight.requires_grad and weight.is_leaf:
-        if cache is None:
-            cache = {}
-            try:
-                weight._wcn_packed = cache
-            except AttributeError:
-                return packed
-        cache[key] = (stamp, packed)
-    return packed
+    return _cached_image(weight, key, make)
 
 
 def _grouped_gather(x: Tensor, packed: Tensor, tbl: Tensor, mask: Tensor, perm: Tensor, n_out: int, kin: int, kout: int,
@@ -571,14 +565,10 @@ def hip_dgrad_grouped(grad_output: Tensor, weight: Tensor, kernel_map: IntSearch
     dy = _prep(grad_output, "grad_output")
     K, G, cg_in, cg_out = weight.shape
     kernel_map.validate()
-    if getattr(kernel_map, "_has_duplicates", False):
+    if kernel_map._has_duplicates:
         return torch.cat([_dgrad_pair_lists(dy[:, g * cg_out : (g + 1) * cg_out], weight[:, g].to(dy.dtype), kernel_map,
                                             num_in_coords) for g in range(G)], dim=1)
     attach_tables_from_csr(kernel_map, num_in_coords, dy.shape[0])
-    if kernel_map._symmetric:
-        tbl, mask, perm, flip = kernel_map._nbr, kernel_map._mask, kernel_map._perm, True
-    else:
-        tbl, mask, perm = reverse_tables(kernel_map, num_in_coords)
-        flip = False
+    tbl, mask, perm, flip = dgrad_tables(kernel_map, num_in_coords, cg_out, cg_in, K, dy.dtype, mfma=False)
     packed = _pack_grouped(weight, True, flip, dy.dtype)
     return _grouped_gather(dy, packed, tbl, mask, perm, num_in_coords, cg_out, cg_in, G, K, None)

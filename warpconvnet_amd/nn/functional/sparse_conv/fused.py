@@ -60,8 +60,7 @@ def hip_forward_fused(in_features: Tensor, weight: Tensor, kernel_map, num_out_c
             raise ValueError(f"residual must be [{num_out_coords}, {cout}], got {tuple(residual.shape)}")
         residual = residual.detach().to(x.dtype).contiguous()
     L = _lib.lib()
-    fused_ok = x.dtype in (torch.float16, torch.bfloat16) and bool(
-        L.wcn_mfma_gather_supported(cin, cout, K, _lib.dtype_code(x.dtype)))
+    fused_ok = x.dtype in (torch.float16, torch.bfloat16) and hip_gemm._gather_ok(cin, cout, K, _lib.dtype_code(x.dtype))
     if not fused_ok:
         y = hip_gemm.hip_forward(x, w, kernel_map, num_out_coords, "auto", bias=bias).float()
         if scale is not None:

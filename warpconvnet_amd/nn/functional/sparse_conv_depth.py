@@ -164,9 +164,9 @@ def _implicit_depthwise_backward_logic(grad_output: Tensor, in_features: Tensor,
     fwd_tbl = _tables(kernel_map, n_in, n_out)
     dx = dw = None
     if needs[0]:
-        if getattr(kernel_map, "_dup_symmetric", False):
+        if kernel_map._dup_symmetric:
             dx = _dgrad_duplicates(g, w, fwd_tbl, n_in)
-        elif getattr(kernel_map, "_has_duplicates", False):
+        elif kernel_map._has_duplicates:
             # repeated coordinates under an even kernel (degenerate input): several output rows pair with one input row per
             # offset, which the one-slot-per-(row, offset) tables cannot express -> scatter-add over the pair lists (reference
             # formulation; atomic, so not bit-reproducible)

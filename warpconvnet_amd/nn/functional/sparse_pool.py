@@ -170,7 +170,7 @@ def sparse_unpool(pooled_voxels: Voxels, unpooled_voxels: Voxels, kernel_size, s
 
 def _swapped(kernel_map: IntSearchResult, num_fine: int) -> IntSearchResult:
     """The coarse->fine view of a fine->coarse map: forward table = the map's reverse table and vice versa (cached)."""
-    sw = getattr(kernel_map, "_pool_swapped", None)
+    sw = kernel_map._pool_swapped
     if sw is None:
         rev_tbl, rev_mask, rev_perm = reverse_tables(kernel_map, num_fine)
         sw = IntSearchResult(kernel_map.out_maps, kernel_map.in_maps, kernel_map.offsets)
