@@ -556,3 +556,101 @@ def test_build_hints_are_explicit_state():
     km3.validate()
     assert km3.in_maps_device.untyped_storage().nbytes() <= 4 * int(km3.offsets[-1]) + 1024
     _check_against_oracle(km3, s, s, (3, 3, 3))
+
+
+@pytest.mark.parametrize("m,K", [(1, 1), (257, 33), (300, 257), (4096 * 256 + 1, 3)])
+def test_offset_scan_of_the_c_abi_at_its_trip_boundaries(m, K):
+    """wcn_kmap_count + wcn_kmap_scan: offsets[k + 1] = pairs of the offsets 0 .. k = cumulative popcount of mask bit k over the
+    rows.  (257, 33): two mask words and a ragged second 256-row tile; (300, 257): the scan of the K totals takes a second
+    256-wide trip; (4096 * 256 + 1, 3): the scan of an offset's tile counts takes a second 4096-count trip."""
+    from warpconvnet_amd import _lib
+
+    rng = np.random.default_rng(1000 * K + m % 1000)
+    bits = rng.random((m, K)) < 0.3
+    mw = (K + 31) // 32
+    words = np.zeros((m, mw), np.uint32)
+    for k in range(K):
+        words[:, k // 32] |= bits[:, k].astype(np.uint32) << np.uint32(k % 32)
+    L = _lib.lib()
+    assert L.wcn_kmap_mask_words(K) == mw
+    mask = torch.from_numpy(words.view(np.int32)).to(_dev())
+    counts = torch.empty(L.wcn_kmap_counts_bytes(m, K), dtype=torch.uint8, device=_dev())
+    offsets = torch.full((K + 1,), -1, dtype=torch.int32, device=_dev())
+    stream = _lib.stream_handle(_dev())
+    _lib.check(L.wcn_kmap_count(_lib.ptr(mask), m, K, _lib.ptr(counts), stream), "count")
+    _lib.check(L.wcn_kmap_scan(_lib.ptr(counts), L.wcn_kmap_num_blocks(m), K, _lib.ptr(offsets), stream), "scan")
+    want = np.concatenate([[0], np.cumsum(bits.sum(0, dtype=np.int64))])
+    np.testing.assert_array_equal(offsets.cpu().numpy().astype(np.int64), want)
+
+
+def test_stride_compaction_across_a_scan_trip():
+    """stride_coords from the cell table on 2048 * 256 + 257 rows: the scan of the 256-row tile counts takes a second trip of
+    2048 tiles, and the boundary in front of the last batch lies in it.  Duplicates and negative coordinates as in
+    test_strided_layers_from_the_cell_table; coordinates and batch offsets bit-exact vs the oracle."""
+    from warpconvnet_amd.geometry.coords.ops.stride import stride_coords
+
+    n, trip = 2048 * 256 + 257, 2048 * 256
+    sizes = (300_000, trip + 100 - 300_000 - 60, 157)  # + 60 duplicated rows in batch 0 = n; batch 2 starts at row trip + 100
+    s = np.concatenate([scene_u(sz, 11 + b, b) for b, sz in enumerate(sizes)], 0)
+    s[:, 1:] -= 7
+    s = np.concatenate([s[: sizes[0]], s[100:160], s[sizes[0] :]], 0).astype(np.int32)
+    assert len(s) == n and np.searchsorted(s[:, 0], 2) > trip
+    want, _ = okmap.stride_coords(s, (2, 2, 2))
+    got, offs = stride_coords(torch.from_numpy(s).to(_dev()), (2, 2, 2), num_batches=3)
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    np.testing.assert_array_equal(offs.numpy(), np.concatenate([[0], np.cumsum(np.bincount(want[:, 0], minlength=3))]))
+
+
+@pytest.mark.parametrize("ksize", [(3, 3, 3), (2, 2, 2), (5, 5, 5), (3, 1, 2)])
+def test_both_lookups_of_the_probe_kernel_on_one_query(ksize):
+    """wcn_kmap_probe (hash table) and wcn_kmap_probe_cells (cell table) are one kernel with two lookups: on the strided scene
+    of test_strided_map_bit_exact, stride (2, 2, 2), both give the oracle's table and masks.  The kernel sizes run 32, 8, 64 and
+    8 lanes per row (row pitch 32, 8, 128, 8).  Voxels at both ends of the 18-bit coordinate range: a probe that leaves the
+    range on one side finds the voxel on the other (the packed key masks, the cell path sign-wraps)."""
+    from warpconvnet_amd import _lib
+    from warpconvnet_amd.geometry.coords.search.packed_hashmap import PackedHashTable
+
+    stride = (2, 2, 2)
+    s = np.concatenate([scene_u(6000, 3, 0), scene_u(5000, 4, 1), scene_u(10, 5, 2)], 0)
+    s[:, 1:] -= 7
+    lo, hi = -(1 << 17), (1 << 17) - 1
+    edge = np.array([[1, hi, 3, 3], [1, lo, 3, 3], [1, 5, hi - 1, lo], [1, 5, lo + 1, hi], [1, hi, hi, hi], [1, lo, lo, lo]], np.int32)
+    s = np.concatenate([s[:11000], edge, s[11000:]], 0).astype(np.int32)  # (batch-sorted)
+    out, _ = okmap.stride_coords(s, stride)
+    r = okmap.kernel_map(s, out, ksize, stride, (1, 1, 1))
+    K, n, m = int(np.prod(ksize)), len(s), len(out)
+    dev, L = _dev(), _lib.lib()
+    stream = _lib.stream_handle(dev)
+    kp, mw = L.wcn_kmap_row_pitch(K), L.wcn_kmap_mask_words(K)
+    assert kp == {27: 32, 8: 8, 125: 128, 6: 8}[K]
+    a, q = torch.from_numpy(s).to(dev), torch.from_numpy(out).to(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    table = PackedHashTable(max(16, 2 * n), device=dev)
+    table._launch_insert(a, status)
+    ws_bytes = L.wcn_kmap_binned_workspace(n, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(n, dtype=torch.int32, device=dev)
+    cstatus = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(L.wcn_kmap_cells_build(_lib.ptr(a), n, n, _lib.ptr(ws), ws_bytes, _lib.ptr(scratch), _lib.ptr(cstatus), stream), "cells")
+    got = []
+    for cells in (False, True):
+        nbr = torch.full((m, kp), -7, dtype=torch.int32, device=dev)
+        mask = torch.full((m, mw), -7, dtype=torch.int32, device=dev)
+        if cells:
+            rc = L.wcn_kmap_probe_cells(_lib.ptr(ws), n, n, _lib.ptr(q), m, _lib.i3(ksize), _lib.i3(stride), _lib.i3((1, 1, 1)),
+                                        _lib.ptr(nbr), _lib.ptr(mask), stream)
+        else:
+            rc = L.wcn_kmap_probe(_lib.ptr(table.slots_tensor), table.capacity, _lib.ptr(q), m, _lib.i3(ksize), _lib.i3(stride),
+                                  _lib.i3((1, 1, 1)), _lib.ptr(nbr), _lib.ptr(mask), stream)
+        _lib.check(rc, "probe")
+        got.append((nbr.cpu().numpy(), mask.cpu().numpy().view(np.uint32)))
+    assert int(status.item()) == 0 and int(cstatus.item()) == 0
+    for nbr, mask in got:
+        np.testing.assert_array_equal(nbr[:, :K].T, r["found"])
+        assert (nbr[:, K:] == -1).all()
+        np.testing.assert_array_equal(mask, r["mask"])
+    np.testing.assert_array_equal(got[0][0], got[1][0])
+    np.testing.assert_array_equal(got[0][1], got[1][1])
+    if ksize == (3, 3, 3):  # out (-65536, 1, 1) * 2 + (-1, 1, 1) = (-131073, 3, 3) is voxel (131071, 3, 3) = row 11000
+        row = np.flatnonzero((out == np.array([1, -(1 << 16), 1, 1])).all(1))
+        assert len(row) == 1 and r["found"][(0 * 3 + 2) * 3 + 2, row[0]] == 11000

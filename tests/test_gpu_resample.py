@@ -419,3 +419,27 @@ def test_decoder_block_end_to_end_bf16():
     errs = [rel_max_err(y_got, y_ref), rel_max_err(gx_got, gx_ref)] + [rel_max_err(a, b) for a, b in zip(gp_got, gp_ref)]
     print("end-to-end rel max errs:", ["%.2e" % e for e in errs])
     assert max(errs) < 2e-2
+
+
+def test_expand_across_a_scan_trip():
+    """wcn_resample_expand on 256 * 256 + 3 parents: 257 tiles of 256 parents, so the scan of the tile counts takes a second
+    256-wide trip, and the last batch starts inside it.  The keep-mask has an all-false stretch of three tiles.  Child
+    coordinates, child table and per-batch offsets equal the numpy restatement (tests/resample_helper.py)."""
+    from warpconvnet_amd.nn.functional.sparse_resample import _expand
+
+    f, P = 2, 256 * 256 + 3
+    g = torch.Generator().manual_seed(5)
+    batch = torch.zeros(P, dtype=torch.int32)
+    batch[30_000:] = 1
+    batch[256 * 256 + 1 :] = 2  # the boundary of the last batch lies in the second trip
+    parents = torch.cat([batch[:, None], torch.randint(-50, 50, (P, 3), generator=g, dtype=torch.int32)], 1)
+    mask = torch.rand(P, f ** 3, generator=g) < 0.4
+    mask[1000:1800] = False  # more than one 256-parent tile without a child
+    want_c, idx, slot = H.children_of_mask(parents, mask, f)
+    coords, tbl, offsets = _expand(parents.to(DEV), mask.to(DEV), f ** 3, f, 0, 3)
+    np.testing.assert_array_equal(coords.cpu().numpy(), want_c.numpy())
+    want_t = torch.full((P, f ** 3), -1, dtype=torch.int32)
+    want_t[idx, slot] = torch.arange(len(idx), dtype=torch.int32)
+    np.testing.assert_array_equal(tbl.cpu().numpy()[:, : f ** 3], want_t.numpy())
+    per_batch = np.bincount(batch[idx].numpy(), minlength=3)
+    np.testing.assert_array_equal(offsets.numpy(), np.concatenate([[0], np.cumsum(per_batch)]))

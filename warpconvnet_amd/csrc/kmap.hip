@@ -9,7 +9,7 @@
 // Reference behaviour being replaced (semantics only, nothing copied):
 //   warpconvnet/csrc/cuhash_hash_table.cu:19-262, cuhash_kernel_map.cu:68-134, 508-599,
 //   mask_data_kernels.cu:23-124, 187-220.
-#include "wcn_common.h"
+#include "kmap_cells.h"
 
 namespace wcn {
 
@@ -58,19 +58,39 @@ __global__ void hash_search_kernel(const Slot* __restrict__ slots, uint32_t capa
 }
 
 // ------------------------------------------------------------------------------------------------
-// probe: nbr[m][kp], mask[m][mw], block_counts[blk][K]
+// probe: nbr[m][kp], mask[m][mw] - ONE kernel for both tables.  A Lookup answers "which row holds voxel (b, x, y, z)":
+//   HashLookup   the 16-B slot table of wcn_hash_insert (pack_key masks the coordinates to 18 bits)
+//   CellLookup   the block-hashed cell table of kmap_cells.h: a block-table lookup (2 MB per million voxels: L2-resident) + one
+//                4-B cell read instead of a probe sequence in a 32 MB slot table.  The block key shifts the coordinates, so
+//                the 18-bit wrap of the packed key is applied first, with the sign
 // ------------------------------------------------------------------------------------------------
-struct ProbeGeom {
-  int kx, ky, kz;  // kernel size
-  int cx, cy, cz;  // centre
-  int sx, sy, sz;  // stride (query = out * stride)
-  int dx, dy, dz;  // dilation
+struct HashLookup {
+  const Slot* slots;
+  uint32_t cmask;
+  __device__ __forceinline__ int operator()(int b, int x, int y, int z) const {
+    return slot_lookup(slots, cmask, pack_key(b, x, y, z));
+  }
 };
 
-template <int LPR>  // lanes per row: 8, 16, 32 or 64
-__global__ __launch_bounds__(kThreads) void kmap_probe_kernel(const Slot* __restrict__ slots, uint32_t capacity_mask,
-                                                              const int4* __restrict__ query, int64_t m, ProbeGeom g,
-                                                              int K, int kp, int mw, int32_t* __restrict__ nbr,
+struct CellLookup {
+  const BSlot* slots;
+  uint32_t cmask;
+  CellTable t;
+  __device__ __forceinline__ int operator()(int b, int x, int y, int z) const {
+    const int xx = (x << (32 - kCoordBits)) >> (32 - kCoordBits);
+    const int yy = (y << (32 - kCoordBits)) >> (32 - kCoordBits);
+    const int zz = (z << (32 - kCoordBits)) >> (32 - kCoordBits);
+    const int id = block_id_of(slots, cmask, make_int4(b, xx, yy, zz));
+    int found = -1;
+    if (id >= 0)  // (cell_of written out: through the helper the kernel compiles to other code - OPTIMISATION_LOG section O)
+      found = t.cells[(int64_t)id * kCells + (((xx & (kBlk - 1)) * kBlk + (yy & (kBlk - 1))) * kBlk + (zz & (kBlk - 1)))];
+    return found;
+  }
+};
+
+template <int LPR, typename Lookup>  // lanes per row: 8, 16, 32 or 64
+__global__ __launch_bounds__(kThreads) void kmap_probe_kernel(Lookup lookup, const int4* __restrict__ query, int64_t m,
+                                                              KernelGeom g, int K, int kp, int mw, int32_t* __restrict__ nbr,
                                                               uint32_t* __restrict__ mask) {
   const int tid = threadIdx.x;
   constexpr int kRowsPerIter = 64 / LPR;
@@ -96,8 +116,7 @@ __global__ __launch_bounds__(kThreads) void kmap_probe_kernel(const Slot* __rest
       int found = -1;
       if (row < m && k_real) {
         const int4 q = query[row];
-        const uint64_t key = pack_key(q.x, q.y * g.sx + ox, q.z * g.sy + oy, q.w * g.sz + oz);
-        found = slot_lookup(slots, capacity_mask, key);
+        found = lookup(q.x, q.y * g.sx + ox, q.z * g.sy + oy, q.w * g.sz + oz);
       }
       if (row < m && k_store) nbr[row * kp + k] = found;
       const unsigned long long ball = __ballot(found >= 0);
@@ -111,6 +130,33 @@ __global__ __launch_bounds__(kThreads) void kmap_probe_kernel(const Slot* __rest
   }
 }
 
+// the argument checks and the launch of both probe entry points; `table` = the caller's table memory (checked with the
+// other buffers, behind the m == 0 exit)
+template <typename Lookup>
+static int launch_probe(const Lookup& lookup, const void* table, const int32_t* query, int64_t m, const int32_t ksize[3],
+                        const int32_t stride[3], const int32_t dilation[3], int32_t* nbr, uint32_t* mask, hipStream_t s) {
+  if (m < 0 || !ksize || !stride || !dilation) return WCN_ERROR_INVALID_PARAMETERS;
+  for (int d = 0; d < 3; ++d)
+    if (ksize[d] < 1 || stride[d] < 1 || dilation[d] < 1) return WCN_ERROR_INVALID_PARAMETERS;
+  const int64_t K64 = (int64_t)ksize[0] * ksize[1] * ksize[2];
+  if (!valid_k(K64)) return WCN_ERROR_PROBLEM_NOT_SUPPORTED;
+  if (m == 0) return WCN_SUCCESS;
+  if (!table || !query || !nbr || !mask) return WCN_ERROR_INVALID_PARAMETERS;
+  const int K = (int)K64, kp = wcn_kmap_row_pitch(K), mw = wcn_kmap_mask_words(K);
+  const KernelGeom g = make_kernel_geom(ksize, stride, dilation);
+  const dim3 grid((unsigned)ceil_div(m, kBlockRows)), block(kThreads);
+#define WCN_PROBE(L) \
+  hipLaunchKernelGGL((kmap_probe_kernel<L, Lookup>), grid, block, 0, s, lookup, (const int4*)query, m, g, K, kp, mw, nbr, mask)
+  switch (lanes_per_row(kp)) {
+    case 8: WCN_PROBE(8); break;
+    case 16: WCN_PROBE(16); break;
+    case 32: WCN_PROBE(32); break;
+    default: WCN_PROBE(64); break;
+  }
+#undef WCN_PROBE
+  return launch_status();
+}
+
 // [n, d] int32 coordinates + batch offsets -> [n, d+1] with the batch index in column 0 (one launch instead of
 // repeat_interleave + fill + cat; reference: warpconvnet/geometry/coords/ops/batch_index.py:90-148)
 __global__ __launch_bounds__(256) void batch_indexed_coords_kernel(const int32_t* __restrict__ coords, int64_t n, int d,
@@ -118,15 +164,7 @@ __global__ __launch_bounds__(256) void batch_indexed_coords_kernel(const int32_t
                                                                    int32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int b = 0;
-  if (num_batches > 1) {  // last batch whose offset is <= i
-    int lo = 0, hi = num_batches;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if ((int64_t)offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    b = lo;
-  }
+  const int b = last_offset_not_above(offsets, num_batches, i);  // last batch whose offset is <= i
   if (d == 3) {
     const int32_t* c = coords + i * 3;
     *reinterpret_cast<int4*>(out + i * 4) = make_int4(b, c[0], c[1], c[2]);
@@ -193,15 +231,6 @@ __global__ void fill_i32_kernel(int32_t* __restrict__ p, int64_t n, int32_t v) {
   if (i < n) p[i] = v;
 }
 
-__device__ __forceinline__ int find_bucket(const int32_t* __restrict__ offsets, int K, int64_t p) {
-  int lo = 0, hi = K;  // largest k with offsets[k] <= p
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (offsets[mid] <= p) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // For every pair p of bucket k: tbl[row_of(p)][k] = other_of(p); mask bit k.  `by_in` selects which map
 // indexes the table (reverse table: by input row; from_csr: by output row).
 __global__ void kmap_pairs_to_table_kernel(const int32_t* __restrict__ in_maps, const int32_t* __restrict__ out_maps,
@@ -209,17 +238,11 @@ __global__ void kmap_pairs_to_table_kernel(const int32_t* __restrict__ in_maps, 
                                            int by_in, int32_t* __restrict__ tbl, uint32_t* __restrict__ mask) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= max_pairs || p >= offsets[K]) return;
-  const int k = find_bucket(offsets, K, p);
+  const int k = last_offset_not_above(offsets, K, p);
   const int i = in_maps[p], o = out_maps[p];
   const int64_t row = by_in ? i : o;
   tbl[row * kp + k] = by_in ? o : i;
   atomicOr(&mask[row * mw + (k >> 5)], 1u << (k & 31));
-}
-
-static inline int lanes_per_row(int kp) {
-  int l = 8;
-  while (l < kp && l < 64) l <<= 1;
-  return l;
 }
 
 }  // namespace wcn
@@ -287,42 +310,20 @@ int32_t wcn_kmap_mask_words(int32_t num_offsets) { return (num_offsets + 31) / 3
 int wcn_kmap_probe(const void* slots, int64_t capacity, const int32_t* query, int64_t m, const int32_t ksize[3],
                    const int32_t stride[3], const int32_t dilation[3], int32_t* nbr, uint32_t* mask,
                    wcn_stream_t stream) {
-  if (!slots || !is_pow2(capacity) || m < 0 || !ksize || !stride || !dilation) return WCN_ERROR_INVALID_PARAMETERS;
-  for (int d = 0; d < 3; ++d)
-    if (ksize[d] < 1 || stride[d] < 1 || dilation[d] < 1) return WCN_ERROR_INVALID_PARAMETERS;
-  const int64_t K64 = (int64_t)ksize[0] * ksize[1] * ksize[2];
-  if (K64 > 4096) return WCN_ERROR_PROBLEM_NOT_SUPPORTED;
-  if (m == 0) return WCN_SUCCESS;
-  if (!query || !nbr || !mask) return WCN_ERROR_INVALID_PARAMETERS;
-  const int K = (int)K64, kp = wcn_kmap_row_pitch(K), mw = wcn_kmap_mask_words(K);
-  ProbeGeom g;
-  g.kx = ksize[0]; g.ky = ksize[1]; g.kz = ksize[2];
-  g.cx = (g.kx & 1) ? g.kx / 2 : 0; g.cy = (g.ky & 1) ? g.ky / 2 : 0; g.cz = (g.kz & 1) ? g.kz / 2 : 0;
-  g.sx = stride[0]; g.sy = stride[1]; g.sz = stride[2];
-  g.dx = dilation[0]; g.dy = dilation[1]; g.dz = dilation[2];
-  const dim3 grid((unsigned)ceil_div(m, kBlockRows)), block(kThreads);
-  const size_t shm = 0;
-  const uint32_t cmask = (uint32_t)(capacity - 1);
-  hipStream_t s = (hipStream_t)stream;
-  switch (lanes_per_row(kp)) {
-    case 8:
-      hipLaunchKernelGGL(kmap_probe_kernel<8>, grid, block, shm, s, (const Slot*)slots, cmask, (const int4*)query, m, g, K,
-                         kp, mw, nbr, mask);
-      break;
-    case 16:
-      hipLaunchKernelGGL(kmap_probe_kernel<16>, grid, block, shm, s, (const Slot*)slots, cmask, (const int4*)query, m, g,
-                         K, kp, mw, nbr, mask);
-      break;
-    case 32:
-      hipLaunchKernelGGL(kmap_probe_kernel<32>, grid, block, shm, s, (const Slot*)slots, cmask, (const int4*)query, m, g,
-                         K, kp, mw, nbr, mask);
-      break;
-    default:
-      hipLaunchKernelGGL(kmap_probe_kernel<64>, grid, block, shm, s, (const Slot*)slots, cmask, (const int4*)query, m, g,
-                         K, kp, mw, nbr, mask);
-      break;
-  }
-  return launch_status();
+  if (!slots || !is_pow2(capacity)) return WCN_ERROR_INVALID_PARAMETERS;
+  return launch_probe(HashLookup{(const Slot*)slots, (uint32_t)(capacity - 1)}, slots, query, m, ksize, stride, dilation, nbr,
+                      mask, (hipStream_t)stream);
+}
+
+// the same map from the cell table of the input coordinates (kmap_cells.h; its owner validated: no TABLE_FULL, duplicate
+// coordinates resolved to the smallest row)
+int wcn_kmap_probe_cells(const void* cells_workspace, int64_t n_in, int64_t max_blocks, const int32_t* query, int64_t m,
+                         const int32_t ksize[3], const int32_t stride[3], const int32_t dilation[3], int32_t* nbr,
+                         uint32_t* mask, wcn_stream_t stream) {
+  if (n_in < 0 || max_blocks < 1) return WCN_ERROR_INVALID_PARAMETERS;
+  const CellTable t = carve_cells(const_cast<void*>(cells_workspace), n_in, max_blocks);
+  return launch_probe(CellLookup{t.slots, (uint32_t)(t.capacity - 1), t}, cells_workspace, query, m, ksize, stride, dilation,
+                      nbr, mask, (hipStream_t)stream);
 }
 
 int wcn_batch_indexed_coords(const int32_t* coords, int64_t n, int32_t num_dims, const int32_t* offsets,
@@ -352,7 +353,7 @@ int wcn_morton_code(const int32_t* coords, int64_t n, int32_t num_dims, const in
 }
 
 int wcn_kmap_transpose(const int32_t* nbr, int64_t m, int32_t num_offsets, int32_t* pair_table, wcn_stream_t stream) {
-  if (m < 0 || num_offsets < 1 || num_offsets > 4096) return WCN_ERROR_INVALID_PARAMETERS;
+  if (m < 0 || !valid_k(num_offsets)) return WCN_ERROR_INVALID_PARAMETERS;
   if (m == 0) return WCN_SUCCESS;
   if (!nbr || !pair_table) return WCN_ERROR_INVALID_PARAMETERS;
   const int kp = wcn_kmap_row_pitch(num_offsets);
@@ -365,7 +366,7 @@ int wcn_kmap_transpose(const int32_t* nbr, int64_t m, int32_t num_offsets, int32
 
 static int pairs_to_table(const int32_t* in_maps, const int32_t* out_maps, const int32_t* offsets, int32_t K,
                           int64_t max_pairs, int64_t rows, int by_in, int32_t* tbl, uint32_t* mask, hipStream_t s) {
-  if (K < 1 || K > 4096 || rows < 0 || max_pairs < 0 || !offsets) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!valid_k(K) || rows < 0 || max_pairs < 0 || !offsets) return WCN_ERROR_INVALID_PARAMETERS;
   if (rows == 0) return WCN_SUCCESS;
   if (!tbl || !mask) return WCN_ERROR_INVALID_PARAMETERS;
   const int kp = wcn_kmap_row_pitch(K), mw = wcn_kmap_mask_words(K);

@@ -78,17 +78,13 @@ __global__ void cell_prepare_kernel(uint4* __restrict__ slots, int64_t capacity,
     const int ly = ddy < 0 ? kBlk - g.hy + ty : ty;
     const int lz = ddz < 0 ? kBlk - g.hz + tz : tz;
     const int X = lx + kBlk * ddx + g.hx, Y = ly + kBlk * ddy + g.hy, Z = lz + kBlk * ddz + g.hz;
-    halo[i] = ((uint32_t)dir << 27) | ((uint32_t)((lx * kBlk + ly) * kBlk + lz) << 16) | (uint32_t)(X * g.px + Y * g.py + Z);
+    halo[i] = ((uint32_t)dir << 27) | ((uint32_t)cell_index(lx, ly, lz) << 16) | (uint32_t)(X * g.px + Y * g.py + Z);
   }
 }
 
 __device__ __forceinline__ void store_cell(int32_t* cell, int row, bool strict) {
   if (strict) __hip_atomic_fetch_min(reinterpret_cast<uint32_t*>(cell), (uint32_t)row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else *cell = row;
-}
-
-__device__ __forceinline__ int cell_of(const int4& c) {
-  return ((c.y & (kBlk - 1)) * kBlk + (c.z & (kBlk - 1))) * kBlk + (c.w & (kBlk - 1));
 }
 
 // PHASE 0: every kInsertSample-th voxel creates its block.  PHASE 1: every voxel stores its cell; blocks the sample
@@ -233,10 +229,9 @@ __global__ __launch_bounds__(256) void cell_finish_kernel(const BSlot* __restric
   for (int64_t i = tid; i < n; i += nthreads) {
     if (mask[i * mw + (mw - 1)] != kMaskDeferred) continue;
     const int4 c = coords[i];
-    const int s = block_find(slots, cmask, pack_key(c.x, c.y >> kBlkShift, c.z >> kBlkShift, c.w >> kBlkShift));
-    const int id = s >= 0 ? slots[s].id : -1;
+    const int id = block_id_of(slots, cmask, c);
     if (id < 0) continue;  // block table overflow: flagged by the insert pass
-    store_cell(t.cells + (int64_t)(id & ~kIdLateBit) * kCells + cell_of(c), (int)i, strict != 0);
+    store_cell(t.cells + (int64_t)id * kCells + cell_of(c), (int)i, strict != 0);
   }
   // neighbour table: one wave per block, lane = direction
   const int lane = threadIdx.x & 63;
@@ -632,12 +627,6 @@ static void launch_cell_table(const CellTable& t, const CellGeom& g, const int4*
   }
 }
 
-static inline int lanes_per_row_b(int kp) {
-  int l = 8;
-  while (l < kp && l < 64) l <<= 1;
-  return l;
-}
-
 }  // namespace wcn
 
 using namespace wcn;
@@ -654,13 +643,15 @@ int wcn_kmap_binned_supported(const int32_t ksize[3], const int32_t dilation[3])
   if (!ksize || !dilation) return 0;
   for (int d = 0; d < 3; ++d) {
     if (ksize[d] < 1 || dilation[d] < 1) return 0;
-    const int c = (ksize[d] & 1) ? ksize[d] / 2 : 0;
-    const int lo = c * dilation[d], hi = (ksize[d] - 1 - c) * dilation[d];
-    if ((lo > hi ? lo : hi) > kMaxHalo) return 0;
   }
+  const int32_t unit[3] = {1, 1, 1};
+  const KernelGeom g = make_kernel_geom(ksize, unit, dilation);
+  if (kernel_halo(g.kx, g.cx, g.dx) > kMaxHalo || kernel_halo(g.ky, g.cy, g.dy) > kMaxHalo ||
+      kernel_halo(g.kz, g.cz, g.dz) > kMaxHalo)
+    return 0;
   const int64_t K = (int64_t)ksize[0] * ksize[1] * ksize[2];
   // the top bit of the last mask word marks rows no block has written yet: it must not be a real offset
-  return (K <= 4096 && (K & 31) != 0) ? 1 : 0;
+  return (valid_k(K) && (K & 31) != 0) ? 1 : 0;
 }
 
 int wcn_kmap_compact_supported(int32_t num_offsets) {
@@ -732,7 +723,7 @@ int wcn_kmap_build_binned(const int32_t* coords, int64_t n, const int32_t ksize[
   if (compact) {
     WCN_CELL_NB(32, true);  // (wcn_kmap_compact_supported: 32 lanes per voxel, one mask word)
   } else {
-    switch (lanes_per_row_b(kp)) {
+    switch (lanes_per_row(kp)) {
       case 8: WCN_CELL_NB(8, false); break;
       case 16: WCN_CELL_NB(16, false); break;
       case 32: WCN_CELL_NB(32, false); break;

@@ -31,14 +31,8 @@ __device__ __noinline__ void repair_row(int64_t row, const int4* __restrict__ co
                                         int kp, int mw, int32_t* __restrict__ nbr, uint32_t* __restrict__ mask,
                                         int32_t* __restrict__ status) {
   const int4 c = coords[row];
-  const int s = block_find(t.slots, cmask, pack_key(c.x, c.y >> kBlkShift, c.z >> kBlkShift, c.w >> kBlkShift));
-  int id = s >= 0 ? t.slots[s].id : -1;
-  if (id >= 0) id &= ~kIdLateBit;
-  int w = -1;
-  if (id >= 0) {
-    const int cell = ((c.y & (kBlk - 1)) * kBlk + (c.z & (kBlk - 1))) * kBlk + (c.w & (kBlk - 1));
-    w = t.cells[(int64_t)id * kCells + cell];
-  }
+  const int id = block_id_of(t.slots, cmask, c);
+  const int w = id >= 0 ? t.cells[(int64_t)id * kCells + cell_of(c)] : -1;
   // kp: ints per table row (the dense pitch, or kCompactPitch | kCompactFlag: a compact row is copied like a dense one)
   const bool compact = kp < 0;
   kp &= 0x7FFFFFFF;
@@ -71,6 +65,7 @@ __global__ __launch_bounds__(kTallyThreads) void kmap_tally_kernel(uint32_t* __r
   }
   if (blockIdx.x == 0 && tid == 0) *ticket = 0;  // consumed by the scan launch behind this one
   constexpr int kTilesPerBlock = kRsTile / kTileRows;  // 8 = waves per workgroup
+  // (one trip: `if (tile < ntile) { ... }` in its place compiles to other code - OPTIMISATION_LOG section O)
   for (int tt = 0; tt < 1; ++tt) {
     const int64_t tile = (int64_t)blockIdx.x * kTilesPerBlock + wave;
     if (tile >= ntile) break;
@@ -114,55 +109,6 @@ __global__ __launch_bounds__(kTallyThreads) void kmap_tally_kernel(uint32_t* __r
   }
 }
 
-// exclusive scan of one row of 32-bit counts by one 256-thread workgroup; returns the row total (all threads)
-__device__ __forceinline__ int scan_row_256(int32_t* __restrict__ c, int64_t n, int* s_wave) {
-  constexpr int kPer = 16;  // 4096 counts per trip: a 1 M-row map is one trip (one memory round trip)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int carry = 0;
-  for (int64_t base = 0; base < n; base += kBkThreads * kPer) {
-    const int64_t i0 = base + (int64_t)tid * kPer;
-    int v[kPer];
-    int sum = 0;
-    // 16-B pieces per lane (rows are 16-B aligned, n is a multiple of 4): a lane-strided 4-B access costs one
-    // texture-addresser slot per lane and element
-#pragma unroll
-    for (int j = 0; j < kPer; j += 4) {
-      int4 q = make_int4(0, 0, 0, 0);
-      if (i0 + j < n) q = *reinterpret_cast<const int4*>(c + i0 + j);
-      v[j] = q.x; v[j + 1] = q.y; v[j + 2] = q.z; v[j + 3] = q.w;
-      sum += q.x + q.y + q.z + q.w;
-    }
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int wave_base = 0, trip_total = 0;
-#pragma unroll
-    for (int w = 0; w < kBkThreads / 64; ++w) {
-      const int q = s_wave[w];
-      if (w < wave) wave_base += q;
-      trip_total += q;
-    }
-    int run = carry + wave_base + incl - sum;
-#pragma unroll
-    for (int j = 0; j < kPer; j += 4) {
-      int4 q;
-      q.x = run; run += v[j];
-      q.y = run; run += v[j + 1];
-      q.z = run; run += v[j + 2];
-      q.w = run; run += v[j + 3];
-      if (i0 + j < n) *reinterpret_cast<int4*>(c + i0 + j) = q;
-    }
-    carry += trip_total;
-    __syncthreads();  // s_wave is rewritten by the next trip
-  }
-  return carry;
-}
-
 // blocks [0, K): offset rows; blocks [K, K + bins / 16): 16 sort digits each (nblk_sort > 0).  `mirror` (may be null):
 // device-accessible pinned HOST buffer [K+2] that receives the offsets and the status word in the same kernel - the host
 // waits for an event behind this launch instead of queueing a separate D2H copy.
@@ -180,7 +126,9 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scan_kernel(int32_t* __restri
     rs_scan_body(dcounts, dtotals, nblk_sort, sort_bins, (int)blockIdx.x - K, reinterpret_cast<char*>(s_cols));
     return;
   }
-  const int total = scan_row_256(counts + (int64_t)blockIdx.x * ntile, ntile, s_wave);
+  // 4096 counts per trip (a 1 M-row map is one trip = one memory round trip), 16-B accesses: the rows are 16-B aligned and
+  // ntile is a multiple of 4 (wcn_kmap_num_blocks)
+  const int total = scan_counts_in_place<kBkThreads, 16>(counts + (int64_t)blockIdx.x * ntile, ntile, s_wave);
   if (tid == 0) {
     // device-scope store + fence + ticket: the workgroup that draws the last ticket sees every total
     __hip_atomic_store(&totals[blockIdx.x], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -195,31 +143,15 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scan_kernel(int32_t* __restri
   for (int base = 0; base < K; base += kBkThreads) {
     const int k = base + tid;
     const int v = k < K ? __hip_atomic_load(&totals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    const int lane = tid & 63, wave = tid >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int wave_base = 0, trip_total = 0;
-#pragma unroll
-    for (int w = 0; w < kBkThreads / 64; ++w) {
-      const int q = s_wave[w];
-      if (w < wave) wave_base += q;
-      trip_total += q;
-    }
+    int trip;
+    const int o = carry + block_excl_scan<kBkThreads>(v, s_wave, &trip) + v;
     if (k < K) {
-      const int o = carry + wave_base + incl;
       offsets[k + 1] = o;
       if (mirror) mirror[k + 1] = o;
     }
-    carry += trip_total;
+    carry += trip;
+    __syncthreads();  // s_wave is rewritten by the next trip
   }
-  __syncthreads();
   if (tid == 0) {
     offsets[0] = 0;
     if (mirror) {
@@ -254,8 +186,32 @@ struct KsArgs {
   int32_t* status;
   int compact;  // nbr holds COMPACT rows (kmap_cells.h); one mask word
 };
+static KsArgs ks_args(const int32_t* nbr, const uint32_t* mask, int64_t m, int32_t K, const int32_t* counts,
+                      const int32_t* offsets, int32_t* in_maps, int32_t* out_maps, int64_t pair_capacity, int32_t* status,
+                      int compact) {
+  KsArgs q;
+  q.compact = compact;
+  q.nbr = nbr; q.mask = mask; q.m = m; q.K = K; q.kp = wcn_kmap_row_pitch(K); q.mw = wcn_kmap_mask_words(K);
+  q.ntile = wcn_kmap_num_blocks(m); q.counts = counts; q.offsets = offsets; q.in_maps = in_maps; q.out_maps = out_maps;
+  q.pair_capacity = pair_capacity; q.status = status;
+  return q;
+}
+
+// one pair to position `pos` of the CSR lists; a position behind the caller's capacity raises `overflow` instead
+__device__ __forceinline__ void place_pair(int32_t* __restrict__ in_maps, int32_t* __restrict__ out_maps, int64_t pos,
+                                           int64_t pair_capacity, int in_row, int out_row, bool& overflow) {
+  if (pos < pair_capacity) {
+    in_maps[pos] = in_row;
+    out_maps[pos] = out_row;
+  } else {
+    overflow = true;
+  }
+}
+
 constexpr size_t kKsLds = (size_t)2 * kStageCap * 4 + 32 * 8 + (size_t)(kBkThreads / 64) * 32 * 12 + 36 * 4 + kStageCap;
 
+// (the body of kmap_scatter_kernel alone; it stays a function of its own because written into the kernel it compiles to
+// other code: 94 VGPRs for 104, 5 waves a SIMD for 4 - not measured, OPTIMISATION_LOG section O)
 __device__ __forceinline__ void kmap_scatter_body(const KsArgs& q, int64_t tile_id, char* smem) {
   const int32_t* __restrict__ nbr = q.nbr;
   const uint32_t* __restrict__ mask = q.mask;
@@ -310,12 +266,7 @@ __device__ __forceinline__ void kmap_scatter_body(const KsArgs& q, int64_t tile_
           tot += c;
         }
       }
-      int incl = tot;
-#pragma unroll
-      for (int d = 1; d < 32; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-      }
+      const int incl = wave_incl_scan<32>(tot);
       if (lane < 32) s_seg[lane] = incl - tot;
       if (lane == 31) s_seg[32] = incl;
       if (lane < kend) s_gbase[lane] = (int64_t)offsets[w * 32 + lane] + counts[(int64_t)(w * 32 + lane) * ntile + tile_id];
@@ -323,6 +274,17 @@ __device__ __forceinline__ void kmap_scatter_body(const KsArgs& q, int64_t tile_
     __syncthreads();
     const int total = s_seg[32];
     const bool staged = total <= kStageCap;
+    // pair (input row `val`, output row r of the wave) of offset b, the `local`-th of the tile: staged behind the offset's
+    // segment start, or straight to the lists.  seg / gbase by reference: read where they are used
+    auto place = [&](int val, int r, int b, int local, const int& seg, const int64_t& gbase) {
+      if (staged) {
+        s_in[seg + local] = val;
+        s_out[seg + local] = (int32_t)(row0 + r);
+        s_bk[seg + local] = (unsigned char)b;
+      } else {
+        place_pair(in_maps, out_maps, gbase + local, pair_capacity, val, (int32_t)(row0 + r), overflow);
+      }
+    };
     if ((64 % cols4) == 0) {
       // 1 / 2 / 4 / 8 pieces per row: a lane holds the SAME four table columns 4c .. 4c+3 in every piece (rows r0 + j * rstep), so
       // everything that depends on the offset alone - the wave's pair count below it, its row bitmap, the staged and the global
@@ -349,21 +311,7 @@ __device__ __forceinline__ void kmap_scatter_body(const KsArgs& q, int64_t tile_
         for (int t = 0; t < 4; ++t) {
           const int b = c * 4 + t;
           if (vals[t] < 0 || b >= kend) continue;
-          const int local = cnt_q[t] + __popcll(ball_q[t] & below);
-          if (staged) {
-            const int at = seg_q[t] + local;
-            s_in[at] = vals[t];
-            s_out[at] = (int32_t)(row0 + r);
-            s_bk[at] = (unsigned char)b;
-          } else {
-            const int64_t pos = gb_q[t] + local;
-            if (pos < pair_capacity) {
-              in_maps[pos] = vals[t];
-              out_maps[pos] = (int32_t)(row0 + r);
-            } else {
-              overflow = true;
-            }
-          }
+          place(vals[t], r, b, cnt_q[t] + __popcll(ball_q[t] & below), seg_q[t], gb_q[t]);
         }
       }
     } else {
@@ -377,20 +325,7 @@ __device__ __forceinline__ void kmap_scatter_body(const KsArgs& q, int64_t tile_
         for (int q = 0; q < 4; ++q) {
           const int b = c * 4 + q;  // offset inside the word
           if (vals[q] < 0 || b >= kend) continue;
-          const int local = s_cnt[wave][b] + __popcll(s_ball[wave][b] & ((1ull << r) - 1ull));
-          if (staged) {
-            s_in[s_seg[b] + local] = vals[q];
-            s_out[s_seg[b] + local] = (int32_t)(row0 + r);
-            s_bk[s_seg[b] + local] = (unsigned char)b;
-          } else {
-            const int64_t pos = s_gbase[b] + local;
-            if (pos < pair_capacity) {
-              in_maps[pos] = vals[q];
-              out_maps[pos] = (int32_t)(row0 + r);
-            } else {
-              overflow = true;
-            }
-          }
+          place(vals[q], r, b, s_cnt[wave][b] + __popcll(s_ball[wave][b] & ((1ull << r) - 1ull)), s_seg[b], s_gbase[b]);
         }
       }
     }
@@ -398,13 +333,7 @@ __device__ __forceinline__ void kmap_scatter_body(const KsArgs& q, int64_t tile_
     if (staged) {
       for (int e = tid; e < total; e += kBkThreads) {
         const int b = s_bk[e];  // (offset of staged entry e, written with it: no search over the segment starts)
-        const int64_t pos = s_gbase[b] + (e - s_seg[b]);
-        if (pos < pair_capacity) {
-          in_maps[pos] = s_in[e];
-          out_maps[pos] = s_out[e];
-        } else {
-          overflow = true;
-        }
+        place_pair(in_maps, out_maps, s_gbase[b] + (e - s_seg[b]), pair_capacity, s_in[e], s_out[e], overflow);
       }
     }
     __syncthreads();  // the next word rewrites the bitmaps and the staging area
@@ -472,12 +401,7 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scatter_compact_kernel(KsArgs
         tot += s_wb[w2][lane].base;
       }
     }
-    int incl = tot;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
+    const int incl = wave_incl_scan<32>(tot);
     if (lane < 32) {
       const int seg = incl - tot;
       s_seg[lane] = seg;
@@ -513,13 +437,7 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scatter_compact_kernel(KsArgs
       if (staged) {
         s_pair[at] = make_uint2((uint32_t)vals[t], (uint32_t)(((wave * 64 + r) << 8) | b));
       } else {
-        const int64_t pos = s_delta[b] + at;
-        if (pos < pair_capacity) {
-          in_maps[pos] = vals[t];
-          out_maps[pos] = (int32_t)(row0 + r);
-        } else {
-          overflow = true;
-        }
+        place_pair(in_maps, out_maps, s_delta[b] + at, pair_capacity, vals[t], (int32_t)(row0 + r), overflow);
       }
     }
   }
@@ -527,6 +445,7 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scatter_compact_kernel(KsArgs
   if (staged) {
     for (int e = tid; e < total; e += kBkThreads) {
       const uint2 pr = s_pair[e];
+      // (place_pair written out: as arguments the two halves of `pr` become one 8-B LDS read - section O of the log)
       const int64_t pos = s_delta[pr.y & 31u] + e;
       if (pos < pair_capacity) {
         in_maps[pos] = (int32_t)pr.x;
@@ -543,8 +462,6 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scatter_kernel(KsArgs q) {
   extern __shared__ char s_ks[];
   kmap_scatter_body(q, blockIdx.x, s_ks);
 }
-
-static inline bool valid_k(int32_t k) { return k >= 1 && k <= 4096; }
 
 static void launch_scatter(const KsArgs& q, hipStream_t s) {
   const dim3 grid((unsigned)ceil_div(q.m, kTileRows)), block(kBkThreads);
@@ -645,10 +562,6 @@ int wcn_kmap_scan_to_host(int32_t* counts, int64_t num_blocks, int32_t num_offse
 
 size_t wcn_kmap_tally_sort_workspace(int64_t m) { return wcn_mask_argsort_workspace(m); }
 
-static KsArgs ks_args(const int32_t* nbr, const uint32_t* mask, int64_t m, int32_t K, const int32_t* counts,
-                      const int32_t* offsets, int32_t* in_maps, int32_t* out_maps, int64_t pair_capacity, int32_t* status,
-                      int compact);
-
 int wcn_kmap_tally_sort(uint32_t* mask, int32_t* nbr, int64_t m, int32_t num_offsets, int32_t* counts, int32_t* offsets,
                         int32_t* status, int32_t* host_mirror, int32_t* perm, void* sort_workspace,
                         size_t sort_workspace_bytes, const int32_t* coords, void* binned_workspace, int64_t binned_n,
@@ -693,17 +606,6 @@ int wcn_kmap_tally_sort(uint32_t* mask, int32_t* nbr, int64_t m, int32_t num_off
     launch_scatter(q, s);
   }
   return launch_status();
-}
-
-static KsArgs ks_args(const int32_t* nbr, const uint32_t* mask, int64_t m, int32_t K, const int32_t* counts,
-                      const int32_t* offsets, int32_t* in_maps, int32_t* out_maps, int64_t pair_capacity, int32_t* status,
-                      int compact) {
-  KsArgs q;
-  q.compact = compact;
-  q.nbr = nbr; q.mask = mask; q.m = m; q.K = K; q.kp = wcn_kmap_row_pitch(K); q.mw = wcn_kmap_mask_words(K);
-  q.ntile = wcn_kmap_num_blocks(m); q.counts = counts; q.offsets = offsets; q.in_maps = in_maps; q.out_maps = out_maps;
-  q.pair_capacity = pair_capacity; q.status = status;
-  return q;
 }
 
 int wcn_kmap_densify(const int32_t* nbr_compact, int64_t m, int32_t num_offsets, int32_t* nbr, wcn_stream_t stream) {

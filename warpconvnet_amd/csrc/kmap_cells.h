@@ -1,5 +1,6 @@
-// kmap_cells.h - the block-hashed cell table shared by the binned builder (kmap_binned.hip) and the tally pass that
-// repairs the rows of duplicate coordinates (kmap.hip).
+// kmap_cells.h - what the kernel-map builders share: the kernel geometry (KernelGeom: centre rule, halo, lanes per row) and
+// the block-hashed cell table (layout, block_id_of / cell_index lookups) of the binned builder (kmap_binned.hip), the probe
+// kernel's cell lookup (kmap.hip), the strided layers (kmap_stride.hip) and the tally pass's duplicate repair (kmap_bucket.hip).
 #pragma once
 
 #include "wcn_common.h"
@@ -43,15 +44,41 @@ struct CellTable {
   size_t bytes;
 };
 
+// kernel offset k = (i*ky + j)*kz + l  ->  (i - cx, j - cy, l - cz) * dilation; a probe's query is out * stride + offset
+struct KernelGeom {
+  int kx, ky, kz;  // kernel size
+  int cx, cy, cz;  // centre
+  int sx, sy, sz;  // stride
+  int dx, dy, dz;  // dilation
+};
+
+// the centre rule: odd sizes are centred, even sizes start at the voxel itself
+static inline KernelGeom make_kernel_geom(const int32_t ksize[3], const int32_t stride[3], const int32_t dilation[3]) {
+  auto centre = [](int ks) { return (ks & 1) ? ks / 2 : 0; };
+  return KernelGeom{ksize[0],  ksize[1],  ksize[2],  centre(ksize[0]), centre(ksize[1]), centre(ksize[2]),
+                    stride[0], stride[1], stride[2], dilation[0],      dilation[1],      dilation[2]};
+}
+
+// max |offset| along one axis
+static inline int kernel_halo(int ks, int c, int d) {
+  const int lo = c * d, hi = (ks - 1 - c) * d;
+  return lo > hi ? lo : hi;
+}
+
+// lanes of a wave that share one table row in the one-lane-per-(row, offset) kernels: 8, 16, 32 or 64
+static inline int lanes_per_row(int kp) {
+  int l = 8;
+  while (l < kp && l < 64) l <<= 1;
+  return l;
+}
+
 struct CellGeom {
-  int kx, ky, kz, cx, cy, cz, dx, dy, dz;
+  int kx, ky, kz, cx, cy, cz, dx, dy, dz;  // of the KernelGeom (stride 1)
   int hx, hy, hz;   // halo per axis (max |offset|)
   int px, py;       // LDS grid pitches (x, y); z pitch 1
   int cells;        // LDS grid size in ints
   int halo_cells;   // entries of the halo gather list
 };
-
-static inline size_t align256c(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static inline int64_t cell_capacity(int64_t max_blocks) {
   int64_t c = 1024;
@@ -63,7 +90,7 @@ static inline CellTable carve_cells(void* ws, int64_t n, int64_t max_blocks) {
   CellTable t;
   char* p = (char*)ws;
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align256c(bytes); return q; };
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align256(bytes); return q; };
   (void)n;
   t.max_blocks = max_blocks;
   t.capacity = cell_capacity(max_blocks);
@@ -78,12 +105,13 @@ static inline CellTable carve_cells(void* ws, int64_t n, int64_t max_blocks) {
 }
 
 static inline CellGeom make_cell_geom(const int32_t ksize[3], const int32_t dilation[3]) {
+  const int32_t unit[3] = {1, 1, 1};
+  const KernelGeom k = make_kernel_geom(ksize, unit, dilation);
   CellGeom g;
-  g.kx = ksize[0]; g.ky = ksize[1]; g.kz = ksize[2];
-  g.cx = (g.kx & 1) ? g.kx / 2 : 0; g.cy = (g.ky & 1) ? g.ky / 2 : 0; g.cz = (g.kz & 1) ? g.kz / 2 : 0;
-  g.dx = dilation[0]; g.dy = dilation[1]; g.dz = dilation[2];
-  auto halo = [](int ks, int c, int d) { const int lo = c * d, hi = (ks - 1 - c) * d; return lo > hi ? lo : hi; };
-  g.hx = halo(g.kx, g.cx, g.dx); g.hy = halo(g.ky, g.cy, g.dy); g.hz = halo(g.kz, g.cz, g.dz);
+  g.kx = k.kx; g.ky = k.ky; g.kz = k.kz;
+  g.cx = k.cx; g.cy = k.cy; g.cz = k.cz;
+  g.dx = k.dx; g.dy = k.dy; g.dz = k.dz;
+  g.hx = kernel_halo(g.kx, g.cx, g.dx); g.hy = kernel_halo(g.ky, g.cy, g.dy); g.hz = kernel_halo(g.kz, g.cz, g.dz);
   const int gx = kBlk + 2 * g.hx, gy = kBlk + 2 * g.hy, gz = kBlk + 2 * g.hz;
   // odd y pitch: the 27 cells a voxel probes then fall into 27 different LDS banks for a 3x3x3 kernel (pitches 11, 110)
   g.py = gz | 1;
@@ -103,6 +131,20 @@ __device__ __forceinline__ int block_find(const BSlot* __restrict__ slots, uint3
     s = (s + 1) & cmask;
   }
   return -1;
+}
+
+// dense id of the block that holds voxel c = (b, x, y, z), or -1
+__device__ __forceinline__ int block_id_of(const BSlot* __restrict__ slots, uint32_t cmask, const int4& c) {
+  const int s = block_find(slots, cmask, pack_key(c.x, c.y >> kBlkShift, c.z >> kBlkShift, c.w >> kBlkShift));
+  if (s < 0) return -1;
+  const int id = slots[s].id;
+  return id < 0 ? -1 : (id & ~kIdLateBit);
+}
+
+// cell inside a block's sub-grid: of block-relative coordinates (0 .. kBlk-1), of a voxel
+__device__ __forceinline__ int cell_index(int x, int y, int z) { return (x * kBlk + y) * kBlk + z; }
+__device__ __forceinline__ int cell_of(const int4& c) {
+  return ((c.y & (kBlk - 1)) * kBlk + (c.z & (kBlk - 1))) * kBlk + (c.w & (kBlk - 1));
 }
 
 }  // namespace wcn

@@ -8,10 +8,8 @@
 //                                    lookup + a few adjacent cell reads per voxel, no insert, no probe sequence; survivors are
 //                                    compacted in row order (ballots + one scan).  With kernel_size == stride the kernel map of
 //                                    the strided convolution is those very cells: emitted in the same pass.
-//   wcn_kmap_probe_cells             any other map between two coordinate sets (kernel 3, stride 2; transposed layers that
-//                                    find no cached forward map): one lane per (output row, offset) as in wcn_kmap_probe, but
-//                                    the probe is a block-table lookup (2 MB per million voxels: L2-resident) + one 4-B cell
-//                                    read instead of a probe sequence in a 32 MB slot table, and nothing is inserted.
+// Any other map between two coordinate sets (kernel 3, stride 2; transposed layers that find no cached forward map) is
+// wcn_kmap_probe_cells: the probe kernel of kmap.hip with the cell-table lookup.
 // Both require the table's owner to have been validated (no TABLE_FULL; duplicate coordinates resolved to the smallest row -
 // strict build or a plain build the tally pass accepted), which the Python side guarantees.
 //
@@ -28,13 +26,6 @@ struct StrideGeom {
   int lx, ly, lz;  // log2 of the stride per axis (0..3)
 };
 
-__device__ __forceinline__ int block_id_of(const BSlot* __restrict__ slots, uint32_t cmask, const int4& c) {
-  const int s = block_find(slots, cmask, pack_key(c.x, c.y >> kBlkShift, c.z >> kBlkShift, c.w >> kBlkShift));
-  if (s < 0) return -1;
-  const int id = slots[s].id;
-  return id < 0 ? -1 : (id & ~kIdLateBit);
-}
-
 // smallest row id among the cells of the coarse cell that holds fine cell (x, y, z) of block `id`
 __device__ __forceinline__ int coarse_min_row(const int32_t* __restrict__ cells, int id, int x, int y, int z,
                                               const StrideGeom& g) {
@@ -44,7 +35,7 @@ __device__ __forceinline__ int coarse_min_row(const int32_t* __restrict__ cells,
   for (int dx = 0; dx < (1 << g.lx); ++dx)
     for (int dy = 0; dy < (1 << g.ly); ++dy)
       for (int dz = 0; dz < (1 << g.lz); ++dz) {
-        const int v = sub[((x0 + dx) * kBlk + (y0 + dy)) * kBlk + (z0 + dz)];
+        const int v = sub[cell_index(x0 + dx, y0 + dy, z0 + dz)];
         if (v >= 0 && v < mn) mn = v;
       }
   return mn;
@@ -86,6 +77,8 @@ __global__ __launch_bounds__(256) void stride_scan_kernel(int32_t* __restrict__ 
                                                           int32_t* __restrict__ out_offsets) {
   __shared__ int s_w[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (the scan of wcn_common.h written out, 8 counts a thread with 4-B accesses: through the helpers the kernel takes one
+  // more VGPR - OPTIMISATION_LOG section O)
   int carry = 0;
   for (int64_t base = 0; base < ntile; base += 256 * 8) {
     int v[8], sum = 0;
@@ -123,11 +116,7 @@ __global__ __launch_bounds__(256) void stride_scan_kernel(int32_t* __restrict__ 
   __syncthreads();
   __threadfence_block();
   for (int b = tid; b <= num_batches; b += 256) {
-    int64_t lo = 0, hi = n;  // first row whose batch index is >= b
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (coords[mid].x < b) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = first_row_of_batch(coords, n, b);
     const int64_t r = b >= num_batches ? n : lo;
     int v;
     if (r >= n) {
@@ -171,58 +160,12 @@ __global__ __launch_bounds__(kStTile) void stride_emit_kernel(const BSlot* __res
   for (int dx = 0; dx < (1 << g.lx); ++dx)
     for (int dy = 0; dy < (1 << g.ly); ++dy)
       for (int dz = 0; dz < (1 << g.lz); ++dz, ++k) {
-        const int v = sub[((x0 + dx) * kBlk + (y0 + dy)) * kBlk + (z0 + dz)];
+        const int v = sub[cell_index(x0 + dx, y0 + dy, z0 + dz)];
         nbr[(int64_t)pos * kp + k] = v;
         if (v >= 0 && k < 32) bits |= 1u << k;
       }
   for (; k < kp; ++k) nbr[(int64_t)pos * kp + k] = -1;
   mask[pos] = bits;
-}
-
-struct CpGeom {
-  int kx, ky, kz, cx, cy, cz, sx, sy, sz, dx, dy, dz;
-};
-
-// one lane per (output row, offset): in = out * stride + offset, looked up in the cell table
-template <int LPR>
-__global__ __launch_bounds__(256) void cells_probe_kernel(const BSlot* __restrict__ slots, uint32_t cmask, CellTable t,
-                                                          const int4* __restrict__ query, int64_t m, CpGeom g, int K,
-                                                          int kp, int mw, int32_t* __restrict__ nbr,
-                                                          uint32_t* __restrict__ mask) {
-  constexpr int kRowsPerIter = 64 / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LPR, rsel = lane / LPR;
-  const int64_t wave_row0 = (int64_t)blockIdx.x * 256 + wave * 64;
-  const int num_chunks = (kp + LPR - 1) / LPR;
-  for (int kc = 0; kc < num_chunks; ++kc) {
-    const int k = kc * LPR + sub;
-    const bool k_real = k < K, k_store = k < kp;
-    const int l = k % g.kz, j = (k / g.kz) % g.ky, i = k / (g.kz * g.ky);
-    const int ox = (i - g.cx) * g.dx, oy = (j - g.cy) * g.dy, oz = (l - g.cz) * g.dz;
-#pragma unroll 4
-    for (int it = 0; it < 64 / kRowsPerIter; ++it) {
-      const int64_t row = wave_row0 + it * kRowsPerIter + rsel;
-      int found = -1;
-      if (row < m && k_real) {
-        const int4 q = query[row];
-        // the 18-bit wrap of the packed key, as the hash path applies it
-        const int x = ((q.y * g.sx + ox) << (32 - kCoordBits)) >> (32 - kCoordBits);
-        const int y = ((q.z * g.sy + oy) << (32 - kCoordBits)) >> (32 - kCoordBits);
-        const int z = ((q.w * g.sz + oz) << (32 - kCoordBits)) >> (32 - kCoordBits);
-        const int id = block_id_of(slots, cmask, make_int4(q.x, x, y, z));
-        if (id >= 0)
-          found = t.cells[(int64_t)id * kCells + (((x & (kBlk - 1)) * kBlk + (y & (kBlk - 1))) * kBlk + (z & (kBlk - 1)))];
-      }
-      if (row < m && k_store) nbr[row * kp + k] = found;
-      const unsigned long long ball = __ballot(found >= 0);
-      if (row < m && sub == 0) {
-        const unsigned long long bits = (LPR == 64) ? ball : ((ball >> (rsel * LPR)) & ((1ull << (LPR & 63)) - 1ull));
-        const int w0 = (kc * LPR) >> 5;
-        if (w0 < mw) mask[row * mw + w0] = (uint32_t)bits;
-        if (LPR == 64 && w0 + 1 < mw) mask[row * mw + w0 + 1] = (uint32_t)(bits >> 32);
-      }
-    }
-  }
 }
 
 static inline int log2_stride(int s) { return s == 1 ? 0 : s == 2 ? 1 : s == 4 ? 2 : s == 8 ? 3 : -1; }
@@ -275,38 +218,6 @@ int wcn_cells_stride_emit(const void* cells_workspace, int64_t n, int64_t max_bl
                      (const BSlot*)t.slots, (uint32_t)(t.capacity - 1), t, (const int4*)coords, n, g,
                      (const unsigned long long*)flags, counts, (int4*)out_coords, first_rows, K, (int)wcn_kmap_row_pitch(K), nbr,
                      mask);
-  return launch_status();
-}
-
-int wcn_kmap_probe_cells(const void* cells_workspace, int64_t n_in, int64_t max_blocks, const int32_t* query, int64_t m,
-                         const int32_t ksize[3], const int32_t stride[3], const int32_t dilation[3], int32_t* nbr,
-                         uint32_t* mask, wcn_stream_t stream) {
-  if (n_in < 0 || m < 0 || max_blocks < 1 || !ksize || !stride || !dilation) return WCN_ERROR_INVALID_PARAMETERS;
-  for (int d = 0; d < 3; ++d)
-    if (ksize[d] < 1 || stride[d] < 1 || dilation[d] < 1) return WCN_ERROR_INVALID_PARAMETERS;
-  const int64_t K64 = (int64_t)ksize[0] * ksize[1] * ksize[2];
-  if (K64 > 4096) return WCN_ERROR_PROBLEM_NOT_SUPPORTED;
-  if (m == 0) return WCN_SUCCESS;
-  if (!cells_workspace || !query || !nbr || !mask) return WCN_ERROR_INVALID_PARAMETERS;
-  const int K = (int)K64, kp = wcn_kmap_row_pitch(K), mw = wcn_kmap_mask_words(K);
-  const CellTable t = carve_cells(const_cast<void*>(cells_workspace), n_in, max_blocks);
-  CpGeom g;
-  g.kx = ksize[0]; g.ky = ksize[1]; g.kz = ksize[2];
-  g.cx = (g.kx & 1) ? g.kx / 2 : 0; g.cy = (g.ky & 1) ? g.ky / 2 : 0; g.cz = (g.kz & 1) ? g.kz / 2 : 0;
-  g.sx = stride[0]; g.sy = stride[1]; g.sz = stride[2];
-  g.dx = dilation[0]; g.dy = dilation[1]; g.dz = dilation[2];
-  const dim3 grid((unsigned)ceil_div(m, 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const BSlot* slots = (const BSlot*)t.slots;
-  const uint32_t cmask = (uint32_t)(t.capacity - 1);
-  int lpr = 8;
-  while (lpr < kp && lpr < 64) lpr <<= 1;
-  switch (lpr) {
-    case 8: hipLaunchKernelGGL(cells_probe_kernel<8>, grid, block, 0, s, slots, cmask, t, (const int4*)query, m, g, K, kp, mw, nbr, mask); break;
-    case 16: hipLaunchKernelGGL(cells_probe_kernel<16>, grid, block, 0, s, slots, cmask, t, (const int4*)query, m, g, K, kp, mw, nbr, mask); break;
-    case 32: hipLaunchKernelGGL(cells_probe_kernel<32>, grid, block, 0, s, slots, cmask, t, (const int4*)query, m, g, K, kp, mw, nbr, mask); break;
-    default: hipLaunchKernelGGL(cells_probe_kernel<64>, grid, block, 0, s, slots, cmask, t, (const int4*)query, m, g, K, kp, mw, nbr, mask); break;
-  }
   return launch_status();
 }
 

@@ -1,6 +1,5 @@
 // mask_sort.h - stable LSD radix argsort of the neighbour masks (descending), hand-written for wave64: the kernel BODIES
-// (shared with kmap_bucket.hip, which counts / scans the first digit inside its tally pass and co-schedules the pair
-// scatter with the later passes) and the launch plan.
+// (shared with kmap_bucket.hip, which counts / scans the first digit inside its tally pass) and the launch plan.
 //
 // perm = rows ordered by DESCENDING mask word 0, ties in ascending row order.  Rows with the same neighbourhood
 // pattern become adjacent, so a wavefront of the gather-GEMM can skip absent offsets.
@@ -231,12 +230,7 @@ __device__ __forceinline__ void rs_scatter_body(const RsArgs& a, int blk, char* 
     int mine = 0;
 #pragma unroll
     for (int j = 0; j < kPerT; ++j) mine += tt[j];
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
+    const int incl = wave_incl_scan(mine);
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
     int base = incl - mine;

@@ -9,13 +9,11 @@ __global__ __launch_bounds__(kRsThreads) void rs_kernel(RsArgs a) {
   rs_body<ROLE>(a, blockIdx.x, s_rs);
 }
 
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 SortPlan sort_plan(void* workspace, int64_t n, int num_bits, bool tile_order) {
   SortPlan p;
   p.nblk = (int)ceil_div(n > 0 ? n : 1, kRsTile);
   char* ws = (char*)workspace;
-  const size_t seg = al256((size_t)(n > 0 ? n : 1) * 8);
+  const size_t seg = align256((size_t)(n > 0 ? n : 1) * 8);
   p.pbuf[0] = (uint2*)ws;
   p.pbuf[1] = (uint2*)(ws ? ws + seg : nullptr);
   p.counts = (int32_t*)(ws ? ws + 2 * seg : nullptr);
@@ -32,7 +30,7 @@ SortPlan sort_plan(void* workspace, int64_t n, int num_bits, bool tile_order) {
     p.passes = (num_bits + kRsBits - 1) / kRsBits;
     p.shift0 = 0;
   }
-  p.bytes = 2 * seg + al256((size_t)kRsMaxBins * (p.nblk + 1) * 4) + 256;
+  p.bytes = 2 * seg + align256((size_t)kRsMaxBins * (p.nblk + 1) * 4) + 256;
   return p;
 }
 

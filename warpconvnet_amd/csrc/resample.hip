@@ -127,28 +127,6 @@ __device__ __forceinline__ bool mask_keeps(const void* mask, int mask_dtype, int
   }
 }
 
-// exclusive scan of one int per thread over the workgroup; returns the thread's prefix, *total = the workgroup's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* total) {
-  __shared__ int s_w[kRsThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kRsThreads / 64; ++w) {
-    if (w < wave) base += s_w[w];
-    tot += s_w[w];
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(kRsThreads) void expand_count_kernel(const void* __restrict__ mask, int mask_dtype, int64_t P,
                                                                   int n_per, int32_t* __restrict__ cnt,
                                                                   int32_t* __restrict__ tile) {
@@ -158,8 +136,9 @@ __global__ __launch_bounds__(kRsThreads) void expand_count_kernel(const void* __
     for (int s = 0; s < n_per; ++s) c += mask_keeps(mask, mask_dtype, p * n_per + s) ? 1 : 0;
     cnt[p] = c;
   }
+  __shared__ int s_w[kRsThreads / 64];
   int total;
-  block_excl_scan(c, &total);
+  block_excl_scan<kRsThreads>(c, s_w, &total);
   if (threadIdx.x == 0) tile[blockIdx.x] = total;
 }
 
@@ -169,12 +148,13 @@ __global__ __launch_bounds__(kRsThreads) void expand_scan_kernel(int32_t* __rest
                                                                  const int32_t* __restrict__ cnt, int64_t P,
                                                                  const int4* __restrict__ parents, int num_batches,
                                                                  int32_t* __restrict__ out_offsets) {
+  __shared__ int s_w[kRsThreads / 64];
   int carry = 0;
   for (int64_t base = 0; base < T; base += kRsThreads) {
     const int64_t e = base + threadIdx.x;
     const int v = e < T ? tile[e] : 0;
     int total;
-    const int excl = block_excl_scan(v, &total);
+    const int excl = block_excl_scan<kRsThreads>(v, s_w, &total);
     if (e < T) tile[e] = carry + excl;
     carry += total;
     __syncthreads();
@@ -182,11 +162,7 @@ __global__ __launch_bounds__(kRsThreads) void expand_scan_kernel(int32_t* __rest
   if (threadIdx.x == 0) tile[T] = carry;
   __syncthreads();
   for (int b = threadIdx.x; b <= num_batches; b += kRsThreads) {
-    int64_t lo = 0, hi = P;  // first parent whose batch index is >= b
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (parents[mid].x < b) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = first_row_of_batch(parents, P, b);
     const int64_t r = b >= num_batches ? P : lo;
     int v = carry;
     if (r < P) {
@@ -205,8 +181,9 @@ __global__ __launch_bounds__(kRsThreads) void expand_emit_kernel(const int4* __r
                                                                  int32_t* __restrict__ tbl, int pitch) {
   const int64_t p = (int64_t)blockIdx.x * kRsThreads + threadIdx.x;
   const int c = p < P ? cnt[p] : 0;
+  __shared__ int s_w[kRsThreads / 64];
   int total;
-  int64_t pos = (int64_t)tile[blockIdx.x] + block_excl_scan(c, &total);
+  int64_t pos = (int64_t)tile[blockIdx.x] + block_excl_scan<kRsThreads>(c, s_w, &total);
   if (p >= P) return;
   const int4 pc = parents[p];
   const int f2 = factor * factor;

@@ -93,6 +93,96 @@ inline int launch_status() {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline bool valid_k(int64_t num_offsets) { return num_offsets >= 1 && num_offsets <= 4096; }  // kernel volumes the library takes
+
+// ---- prefix sums (wave64) -------------------------------------------------------------------------------------------------
+// inclusive scan over the first WIDTH (64 or 32) lanes of a wave; with 32 the upper half's results are unspecified
+template <int WIDTH = 64>
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < WIDTH; d <<= 1) {
+    const int up = __shfl_up(v, d);
+    if (lane >= d) v += up;
+  }
+  return v;
+}
+
+// exclusive scan of one int per thread over a workgroup of THREADS; *total = the workgroup's sum (all threads).  `s_wave`:
+// THREADS / 64 ints of LDS - the caller puts a barrier in front of its next use
+template <int THREADS>
+__device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int incl = wave_incl_scan(v);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / 64; ++w) {
+    const int q = s_wave[w];
+    if (w < wave) base += q;
+    tot += q;
+  }
+  *total = tot;
+  return base + incl - v;
+}
+
+// exclusive scan of n counts in place by ONE workgroup of THREADS, THREADS * PER counts a trip; returns their sum (all
+// threads).  16-B accesses: `counts` is 16-B aligned and n a multiple of 4 (a lane-strided 4-B access costs one
+// texture-addresser slot per lane and element).
+template <int THREADS, int PER>
+__device__ __forceinline__ int scan_counts_in_place(int32_t* __restrict__ counts, int64_t n, int* s_wave) {
+  static_assert(PER % 4 == 0, "whole int4 pieces");
+  int carry = 0;
+  for (int64_t base = 0; base < n; base += THREADS * PER) {
+    const int64_t i0 = base + (int64_t)threadIdx.x * PER;
+    int v[PER];
+    int sum = 0;
+#pragma unroll
+    for (int j = 0; j < PER; j += 4) {
+      int4 q = make_int4(0, 0, 0, 0);
+      if (i0 + j < n) q = *reinterpret_cast<const int4*>(counts + i0 + j);
+      v[j] = q.x; v[j + 1] = q.y; v[j + 2] = q.z; v[j + 3] = q.w;
+      sum += q.x + q.y + q.z + q.w;
+    }
+    int trip;
+    int run = carry + block_excl_scan<THREADS>(sum, s_wave, &trip);
+#pragma unroll
+    for (int j = 0; j < PER; j += 4) {
+      int4 q;
+      q.x = run; run += v[j];
+      q.y = run; run += v[j + 1];
+      q.z = run; run += v[j + 2];
+      q.w = run; run += v[j + 3];
+      if (i0 + j < n) *reinterpret_cast<int4*>(counts + i0 + j) = q;
+    }
+    carry += trip;
+    __syncthreads();  // s_wave is rewritten by the next trip
+  }
+  return carry;
+}
+
+// ---- bisections -----------------------------------------------------------------------------------------------------------
+// first row whose batch index (coords[.].x) is >= b; rows are batch-sorted
+__device__ __forceinline__ int64_t first_row_of_batch(const int4* __restrict__ coords, int64_t n, int b) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (coords[mid].x < b) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// largest k in [0, K) with offsets[k] <= p (offsets ascending, offsets[0] <= p; K = 1 reads nothing)
+__device__ __forceinline__ int last_offset_not_above(const int32_t* __restrict__ offsets, int K, int64_t p) {
+  int lo = 0, hi = K;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offsets[mid] <= p) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 
 // Per-device one-time setup (kernel attributes are per device context): bit d of `done` = device d is set up.  The only
 // process-wide state of the library, idempotent: a lost race or a device index above 63 just repeats the setup call.
