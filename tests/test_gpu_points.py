@@ -512,3 +512,123 @@ def test_pointconv_backward_bitwise_repeatable_when_deterministic():
         assert torch.equal(u, v)  # parameter gradients: fixed-order partial sums in both modes
     c, _ = grads(False)
     assert (a - c).abs().max() <= 1e-4 * max(1.0, float(c.abs().max()))
+
+
+def _assert_matches_fp64(out, want, grads, want_grads, params, ref_params):
+    """The metrics of `test_pointconv_fused_edge_kernel_vs_fp64` that hold for every entry: output rows, relative Frobenius
+    error of the data gradients, max error over max magnitude of every parameter gradient."""
+    torch.testing.assert_close(out.detach().cpu().double(), want.detach(), rtol=1e-4, atol=1e-4)
+    for got, wantg in zip(grads, want_grads):
+        err = float((got.cpu().double() - wantg).norm() / wantg.norm())
+        print(f"data gradient: relative Frobenius error {err:.2e}")
+        assert err < 1e-3
+    for (name, p), (_, pr) in zip(params, ref_params):
+        err = float((p.grad.cpu().double() - pr.grad).abs().max()) / (float(pr.grad.abs().max()) + 1e-12)
+        print(f"{name}: relative max error {err:.2e}")
+        assert err < 1e-3, f"{name}: relative max error {err:.2e}"
+
+
+def test_pointconv_peredge_backward_linear_shortcut_relpos_partial_tile():
+    """The per-edge (deterministic) backward at the smallest size that takes its corner paths together: 5 + 5 + 3 = 13 edge
+    channels into 12 -> Linear shortcut; widths that are no multiple of 4 -> the channel-by-channel gather with the
+    relative-position columns; 37 points x 4 neighbours = 148 edges -> four full 32-edge tiles and one of 20.  Two
+    deterministic runs are bitwise equal, the parameter gradients (fixed-order sums in both modes) bitwise equal to the
+    atomic mode's, the input gradient within fp32 summation error of it, and everything agrees with the fp64 evaluation op
+    by op on the same neighbour lists."""
+    import copy
+
+    from warpconvnet_amd.geometry.coords.search.search_configs import RealSearchConfig
+    from warpconvnet_amd.geometry.types.points import Points
+    from warpconvnet_amd.nn.functional import point_conv as fpc
+    from warpconvnet_amd.nn.modules import PointConv
+    from warpconvnet_amd.ops.reductions import row_reduction
+
+    dev = _dev()
+    n, cin, cout, k = 37, 5, 12, 4
+    g = torch.Generator().manual_seed(37)
+    coords = torch.rand(n, 3, generator=g) * 2.0
+    feats = torch.randn(n, cin, generator=g)
+    dy = torch.randn(n, cout, generator=g)
+    cfg = RealSearchConfig(mode="knn", knn_k=k)
+    torch.manual_seed(5)
+    conv = PointConv(cin, cout, cfg, reductions=("mean",), use_rel_pos=True)
+    ref = copy.deepcopy(conv).double()
+    conv = conv.to(dev)
+    assert isinstance(conv.edge_transform_mlp.shortcut, torch.nn.Linear)
+    offsets = torch.tensor([0, n])
+    calls = []
+    orig = fpc._FusedEdge.apply
+
+    def grads(deterministic):
+        conv.zero_grad(set_to_none=True)
+        x = feats.to(dev).requires_grad_(True)
+        prev = torch.are_deterministic_algorithms_enabled()
+        torch.use_deterministic_algorithms(deterministic)
+        fpc._FusedEdge.apply = lambda *a: (calls.append(a[13] is not None), orig(*a))[1]  # a[13]: in_xyz, the edge MLP's call
+        try:
+            out = conv(Points(coords.to(dev), x, offsets=offsets)).feature_tensor
+            out.backward(dy.to(dev))
+        finally:
+            fpc._FusedEdge.apply = orig
+            torch.use_deterministic_algorithms(prev)
+        return out.detach(), x.grad.clone(), [p.grad.clone() for p in conv.parameters()]
+
+    _, a, pa = grads(True)
+    _, b, pb = grads(True)
+    out, c, pc = grads(False)  # last: conv's .grad fields hold the atomic mode's gradients below
+    assert sum(calls) == 3, "the fused edge kernel was not used"
+    assert torch.equal(a, b), "deterministic input gradient differs between two runs"
+    for u, v, w in zip(pa, pb, pc):
+        assert torch.equal(u, v) and torch.equal(u, w)
+    assert (a - c).abs().max() <= 1e-4 * max(1.0, float(c.abs().max()))
+
+    nb = Points(coords.to(dev), feats.to(dev), offsets=offsets)
+    nb = nb.neighbors(query_coords=nb.batched_coordinates, search_args=cfg)
+    idx = nb.neighbor_indices.cpu().view(-1)
+    xr = feats.double().requires_grad_(True)
+    edge = torch.cat([xr[idx], xr.repeat_interleave(k, dim=0), (coords[idx] - coords.repeat_interleave(k, dim=0)).double()], 1)
+    want = ref.out_transform_mlp(row_reduction(ref.edge_transform_mlp(edge), torch.arange(0, n * k + 1, k), reduction="mean"))
+    want.backward(dy.double())
+    _assert_matches_fp64(out, want, [a, c], [xr.grad, xr.grad], conv.named_parameters(), ref.named_parameters())
+
+
+@pytest.mark.parametrize("cout", [16, 12])
+def test_pointconv_fused_edge_hand_built_ragged_lists(cout):
+    """Ragged lists written by hand through `fused_point_conv_edge(..., row_splits=)`: an empty first list, a 33-edge list
+    that straddles tiles 0 and 1, an empty list in the middle, a short last list in a partial tile; identity (8 + 8 -> 16)
+    and Linear (-> 12) shortcut.  Against the fp64 evaluation op by op; the rows of the empty lists are exactly zero in the
+    output and in the query-feature gradient."""
+    import copy
+
+    from warpconvnet_amd.nn.functional import point_conv as fpc
+    from warpconvnet_amd.nn.modules.mlp import MLPBlock
+
+    dev = _dev()
+    n_in, cin, cq, hid = 50, 8, 8, 16
+    splits = torch.tensor([0, 0, 33, 33, 40])
+    counts = splits[1:] - splits[:-1]
+    m, n_edges = counts.numel(), int(splits[-1])
+    g = torch.Generator().manual_seed(cout)
+    feats = torch.randn(n_in, cin, generator=g)
+    qfeats = torch.randn(m, cq, generator=g)
+    nbr = torch.randint(0, n_in, (n_edges,), generator=g)
+    dy = torch.randn(m, cout, generator=g)
+    torch.manual_seed(cout)
+    mlp = MLPBlock(cin + cq, cout, hid)
+    ref = copy.deepcopy(mlp).double()
+    mlp = mlp.to(dev)
+    assert isinstance(mlp.shortcut, torch.nn.Identity if cout == cin + cq else torch.nn.Linear)
+
+    x, q = feats.to(dev).requires_grad_(True), qfeats.to(dev).requires_grad_(True)
+    assert fpc.fused_edge_supported(mlp, x, q, 0, 1, "mean")
+    out = fpc.fused_point_conv_edge(mlp, x, q, nbr.to(dev), 1, "mean", row_splits=splits)
+    out.backward(dy.to(dev))
+
+    xr, qr = feats.double().requires_grad_(True), qfeats.double().requires_grad_(True)
+    e = ref(torch.cat([xr[nbr], qr.repeat_interleave(counts, dim=0)], 1))
+    want = torch.stack([e[s:t].mean(0) if t > s else e.new_zeros(cout) for s, t in zip(splits[:-1], splits[1:])])
+    want.backward(dy.double())
+    _assert_matches_fp64(out, want, [x.grad, q.grad], [xr.grad, qr.grad], mlp.named_parameters(), ref.named_parameters())
+    empty = counts == 0
+    assert int(empty.sum()) == 2
+    assert not out.detach().cpu()[empty].any() and not q.grad.cpu()[empty].any()

@@ -6,20 +6,28 @@
 // [M*k, C] edge tensors in HBM between every one of those steps; here an edge never leaves the chip:
 //
 //   x_e = [in_feats[nbr[e]] | q_feats[q(e)] | in_xyz[nbr[e]] - q_xyz[q(e)]]          gathered into registers
-//   h   = ReLU(LN1(W1 x_e + b1)),  o = LN2(W2 h + b2) + x_e,  out[q] = sum|mean_e o   (forward)
-//   and the whole backward of that chain, recomputing the forward per tile               (backward)
+//   h   = ReLU(LN1(W1 x_e + b1)),  o = LN2(W2 h + b2) + shortcut(x_e),  out[q] = sum|mean_e o   (forward)
+//   and the whole backward of that chain, recomputing the forward per tile                       (backward)
 //
-// Work decomposition ("tensor parallel workgroup"): a workgroup of 4 waves walks 32-edge tiles (32 / k queries).  Every
-// wave holds the tile's x; wave w owns hidden channels [w*HID/4, (w+1)*HID/4) through the whole chain, so the weight
-// gradient blocks it accumulates (its rows of dW1 / dW2) live in registers for the lifetime of the kernel.  All GEMMs
-// are v_mfma_f32_32x32x2_f32 in the TRANSPOSED form (rows = channels, columns = the 32 edges):
+// Both kernels walk 32-edge tiles, for uniform lists (1 << log2k edges a query) and ragged ones (a query id per edge).
+// All GEMMs are v_mfma_f32_32x32x2_f32 in the TRANSPOSED form (rows = channels, columns = the 32 edges):
 //   * a result tile puts edge e in lane e / e+32 and 16 channels in registers, channel sigma(r, h) = 8*(r/4) + 4*h + r%4;
 //   * that is exactly a B operand (k-pair = channels sigma(r,0), sigma(r,1)) of the next GEMM, so GEMM1 -> LN -> ReLU ->
-//     GEMM2 and the whole data-gradient chain run register to register, the permutation folded into the packed weights;
+//     GEMM2 and the whole data-gradient chain run register to register, the permutation folded into the packed weights.
+//
+// pointconv_fwd_wave_kernel - the forward of every list kind.  One tile per WAVE: a wave owns all hidden channels of its
+//   tile, LayerNorm reduces over registers + one lane swap, nothing is exchanged between the waves.  The operand images
+//   (P1, P2, tables, Linear shortcut) sit in LDS once per persistent workgroup.
+// pointconv_bwd_kernel - the backward of every list kind ("tensor parallel workgroup").  One tile per workgroup of 4
+//   waves: every wave holds the tile's x, wave w owns hidden channels [w*HID/4, (w+1)*HID/4) through the whole chain, so
+//   the weight-gradient blocks it accumulates (its rows of dW1 / dW2) live in registers for the lifetime of the kernel.
 //   * LayerNorm reduces over registers + one lane swap + a 1-KiB exchange between the waves;
 //   * only the weight-gradient GEMMs (reduction over edges) need the other orientation: the operands take one trip
-//     through a wave-private LDS tile [channel][edge].
-// Weights are read as A operands straight from a packed image in global memory (L1/L2 resident, 16 B per lane).
+//     through a wave-private LDS tile [channel][edge];
+//   * the forward operands (P1, P2) stay in registers, the transposed images (P2T, P1T) in LDS; the Linear shortcut's
+//     transposed image is read from global memory (L1/L2 resident, 16 B per lane).
+#include <type_traits>
+
 #include "wcn_common.h"
 
 namespace wcn {
@@ -28,8 +36,7 @@ namespace {
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr int kPcWaves = 4;
-constexpr bool kWRegs = false;  // backward: the transposed weight operands (dH, dX GEMMs) in registers too
+constexpr int kPcWaves = 4;  // waves of a backward workgroup
 constexpr int kPitch = 36;  // floats per row of the [channel][32 edges] LDS tiles: b128 reads of 8 lanes hit 32 banks
 
 __host__ __device__ constexpr int sigma(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
@@ -64,26 +71,27 @@ struct PC {
   static constexpr int OFF_PST = OFF_PS + EIN * CO;   // [NBX][NB2][4][64][4]     dX A:       Ws[c = 32cb+i][out = 32b+sigma(r,h)]
   static constexpr int OFF_TS = OFF_PST + EIN * CO;   // [NB2][2][16]             bs
   static constexpr int PACKED = OFF_TS + NB2 * 32;
-  // Linear shortcut: wave w computes output block w % NB2 over its 1/PARTS of the reduction
-  static constexpr int PARTS = kPcWaves / NB2, SPW = KS1 / PARTS;
-  static_assert(NB2 == 1 || NB2 == 2 || NB2 == 4, "shortcut split");
-  static constexpr int WSB = (NBX * NB2 + kPcWaves - 1) / kPcWaves;  // dWs blocks per wave
-  // LDS (floats)
+  // LDS of the forward (floats): the images it reads, P1 | P2 | T1 | T2 | PS | TS
+  static constexpr int LDS_FLOATS_WAVE = OFF_P2T + (NB1 + NB2) * 96 + EIN * CO + NB2 * 32;
+  static constexpr int WSB = (NBX * NB2 + kPcWaves - 1) / kPcWaves;  // backward: dWs blocks per wave
+  // LDS of the backward (floats)
   static constexpr int L_TAB = 0;                             // [NB1 + NB2][3][2][16] bias / LayerNorm tables (copy of T1, T2)
-  static constexpr int L_TX = (NB1 + NB2) * 96;               // [EIN][kPitch]      x, channel-major (identity shortcut, dW1 A)
+  static constexpr int L_TX = (NB1 + NB2) * 96;               // [EIN][kPitch]      x, channel-major (dW1 / dWs A)
   static constexpr int L_TH = L_TX + EIN * kPitch;            // [HID][kPitch]      per wave: H, later dHpre, channel-major
-  static constexpr int L_TB = L_TH + HID * kPitch;            // [CO][kPitch]       dOpre channel-major / forward output tile
+  static constexpr int L_TB = L_TH + HID * kPitch;            // [CO][kPitch]       dOpre channel-major
   static constexpr int L_PO = L_TB + CO * kPitch;             // [4][NBP][16][64]   partial tiles exchanged between the waves
   static constexpr int L_ST = L_PO + kPcWaves * NBP * 1024;   // [2][4][32][2]      LayerNorm partial sums
   static constexpr int L_DXT = L_ST + 2 * kPcWaves * 64;      // [32][EIN+1]        dX, edge-major; before that dy channel-major [CO][kPitch]
   static constexpr int DXT_FLOATS = ((32 * (EIN + 1) > CO * kPitch ? 32 * (EIN + 1) : CO * kPitch) + 3) & ~3;
   static constexpr int L_DOUT = L_DXT + DXT_FLOATS;           // [32][CO] grad_out rows of the tile's queries ([32][CO+1] per edge when ragged)
   static constexpr int L_JT = L_DOUT + 32 * (CO + 1);         // [32] int           neighbour ids, then [32] int query ids (ragged lists)
-  static constexpr int L_WT = L_JT + 64;                      // [HID*CO + EIN*HID]  backward: P2T | P1T operand images
+  static constexpr int L_WT = L_JT + 64;                      // [HID*CO + EIN*HID]  P2T | P1T operand images
   static constexpr int LDS_FLOATS = L_WT + HID * CO + EIN * HID;
   static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
-  static constexpr int LDS_FLOATS_FWD = L_DXT - HID * kPitch + PARTS * CO * kPitch;  // forward: ... + shortcut partial tiles
 };
+// the two layouts of the instantiated shape, pinned: a slip in an offset above fails here
+static_assert(PC<64, 128, 64>::LDS_FLOATS * 4 == 157312, "backward LDS layout");
+static_assert(PC<64, 128, 64>::LDS_FLOATS_WAVE * 4 == 84480, "forward LDS layout");
 
 struct PcArgs {
   const float* in_feats;  // [n_in][cin]
@@ -117,22 +125,21 @@ __host__ __device__ inline int64_t grad_floats(int ein_t, int hid_t, int co_t, i
   return (int64_t)hid_t * ein_t + 3 * hid_t + (int64_t)co_t * hid_t + 3 * co_t + (lin_sc ? (int64_t)co_t * ein_t + co_t : 0);
 }
 
-template <int EIN, int HID, int CO, bool BWD, bool LIN, bool RAG>
-__global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const PcArgs a) {
+template <int EIN, int HID, int CO, bool LIN, bool RAG>
+__global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
   typedef PC<EIN, HID, CO> P;
   constexpr int KS1 = P::KS1, HB = P::HB, NB2 = P::NB2, NBX = P::NBX, NBP = P::NBP;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* tX = smem + P::L_TX;
   float* tH = smem + P::L_TH;
-  float* tB = smem + (BWD ? P::L_TB : P::L_TH);                      // forward: no tH, everything moves up
-  float* po = smem + (BWD ? P::L_PO : P::L_PO - HID * kPitch);
-  float* st = smem + (BWD ? P::L_ST : P::L_ST - HID * kPitch);
+  float* tB = smem + P::L_TB;
+  float* po = smem + P::L_PO;
+  float* st = smem + P::L_ST;
   float* dxt = smem + P::L_DXT;
-  float* tD = dxt;                                                    // backward: dy channel-major, dead before dxt is written
-  float* tS = smem + P::L_DXT - HID * kPitch;                         // forward: [PARTS][CO][kPitch] shortcut partial tiles
+  float* tD = dxt;  // dy channel-major (Linear shortcut), dead before dxt is written
   float* dout = smem + P::L_DOUT;
   int32_t* jt = reinterpret_cast<int32_t*>(smem + P::L_JT);
-  int32_t* qt = BWD ? jt + 32 : reinterpret_cast<int32_t*>(smem + P::L_ST - HID * kPitch + 256);  // forward: the unused half of st
+  int32_t* qt = jt + 32;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, e = lane & 31;
   const int k = 1 << a.log2k, nq = 32 >> a.log2k;
@@ -144,45 +151,42 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
   float* thw = tH + w * HB * 32 * kPitch;  // this wave's rows of tH
   const float* tab = smem + P::L_TAB;
   for (int i = tid; i < (P::NB1 + NB2) * 96; i += 256) smem[P::L_TAB + i] = a.packed[P::OFF_T1 + i];
-  if (BWD)  // the transposed weight images (A operands of the dH and dX GEMMs) live in LDS: no global round trip per tile
-    for (int i = tid; i < (P::OFF_T1 - P::OFF_P2T) / 4; i += 256)
-      reinterpret_cast<f32x4*>(smem + P::L_WT)[i] = pk4[P::OFF_P2T / 4 + i];
+  // the transposed weight images (A operands of the dH and dX GEMMs) live in LDS: no global round trip per tile
+  for (int i = tid; i < (P::OFF_T1 - P::OFF_P2T) / 4; i += 256)
+    reinterpret_cast<f32x4*>(smem + P::L_WT)[i] = pk4[P::OFF_P2T / 4 + i];
   __syncthreads();
   const f32x4* pkT4 = reinterpret_cast<const f32x4*>(smem + P::L_WT) - P::OFF_P2T / 4;  // same indexing as pk4
 
-  // persistent parameter-gradient accumulators (backward)
+  // persistent parameter-gradient accumulators
   f32x16 dW1a[NBX][HB], dW2a[HB][NB2];
   float dg1a[HB][16], dbe1a[HB][16], db1a[HB][16];
   float dg2a[NB2 * 4], dbe2a[NB2 * 4], db2a[NB2 * 4];  // this wave's quarter: items (b*16 + r) with (b*16+r) % 4 == w
   f32x16 dWsa[LIN ? P::WSB : 1];                                 // Linear shortcut: blocks (cb, b) with (cb*NB2 + b) % 4 == w
-  if (BWD) {
 #pragma unroll
-    for (int cb = 0; cb < NBX; ++cb)
-#pragma unroll
-      for (int t = 0; t < HB; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) dW1a[cb][t][q] = 0.f;
+  for (int cb = 0; cb < NBX; ++cb)
 #pragma unroll
     for (int t = 0; t < HB; ++t)
 #pragma unroll
-      for (int b = 0; b < NB2; ++b)
+      for (int q = 0; q < 16; ++q) dW1a[cb][t][q] = 0.f;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) dW2a[t][b][q] = 0.f;
+  for (int t = 0; t < HB; ++t)
 #pragma unroll
-    for (int t = 0; t < HB; ++t)
+    for (int b = 0; b < NB2; ++b)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dg1a[t][r] = dbe1a[t][r] = db1a[t][r] = 0.f;
+      for (int q = 0; q < 16; ++q) dW2a[t][b][q] = 0.f;
 #pragma unroll
-    for (int i = 0; i < NB2 * 4; ++i) dg2a[i] = dbe2a[i] = db2a[i] = 0.f;
+  for (int t = 0; t < HB; ++t)
 #pragma unroll
-    for (int jb = 0; jb < (LIN ? P::WSB : 1); ++jb)
+    for (int r = 0; r < 16; ++r) dg1a[t][r] = dbe1a[t][r] = db1a[t][r] = 0.f;
 #pragma unroll
-      for (int q = 0; q < 16; ++q) dWsa[jb][q] = 0.f;
-  }
+  for (int i = 0; i < NB2 * 4; ++i) dg2a[i] = dbe2a[i] = db2a[i] = 0.f;
+#pragma unroll
+  for (int jb = 0; jb < (LIN ? P::WSB : 1); ++jb)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dWsa[jb][q] = 0.f;
 
-  // ---- this wave's weight operands never change: they stay in registers for the whole kernel ----
+  // ---- this wave's forward weight operands never change: they stay in registers for the whole kernel ----
   float wA1[HB][KS1], wA2[HB][NB2][16];
-  float wA2T[BWD && kWRegs ? HB : 1][NB2][16], wA1T[BWD && kWRegs ? HB : 1][NBX][16];
 #pragma unroll
   for (int t = 0; t < HB; ++t) {
     const int blk = w * HB + t;
@@ -200,33 +204,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
         const f32x4 av = pk4[P::OFF_P2 / 4 + ((blk * NB2 + b) * 4 + r4) * 64 + lane];
 #pragma unroll
         for (int d = 0; d < 4; ++d) wA2[t][b][4 * r4 + d] = av[d];
-        if (BWD && kWRegs) {
-          const f32x4 tv = pk4[P::OFF_P2T / 4 + ((blk * NB2 + b) * 4 + r4) * 64 + lane];
-#pragma unroll
-          for (int d = 0; d < 4; ++d) wA2T[t][b][4 * r4 + d] = tv[d];
-        }
       }
-    if (BWD && kWRegs) {
-#pragma unroll
-      for (int cb = 0; cb < NBX; ++cb)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          const f32x4 tv = pk4[P::OFF_P1T / 4 + ((blk * NBX + cb) * 4 + r4) * 64 + lane];
-#pragma unroll
-          for (int d = 0; d < 4; ++d) wA1T[t][cb][4 * r4 + d] = tv[d];
-        }
-    }
-  }
-
-  // Linear shortcut (forward): this wave's slice of Ws^T, output block sc_b, reduction steps [sc_p*SPW, +SPW)
-  const int sc_b = w % NB2, sc_p = w / NB2;
-  float wS[LIN ? P::SPW : 1];
-  if (!BWD && LIN) {
-#pragma unroll
-    for (int i = 0; i < P::SPW; ++i) {
-      const int sI = sc_p * P::SPW + i;
-      wS[i] = a.packed[P::OFF_PS + ((sc_b * (KS1 / 4) + (sI >> 2)) * 64 + lane) * 4 + (sI & 3)];
-    }
   }
 
   // ---- software pipeline over tiles: the rows of tile i+1 are requested right after GEMM1 of tile i has consumed x,
@@ -238,6 +216,9 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
     j = valid ? a.nbr[E] : 0;
   };
   float x[KS1];
+  // x_e of one edge: 16-B loads where four channels lie inside one feature row, else channel by channel (row tails,
+  // relative positions).  Written out here and in the wave kernel: as one shared function it changes the register
+  // allocation of all eight instances (docs/OPTIMISATION_LOG.md, section P).
   auto gather_x = [&](bool valid, int64_t q, int32_t j) {
     const float* fi = a.in_feats + (int64_t)j * a.cin;
     const float* fq = a.q_feats + q * a.cq;
@@ -278,25 +259,23 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
     // ---- A. stage the tile: neighbour ids, grad_out rows, channel-major copy of x ----
     const bool valid = v_cur;
     if (w == 0 && h == 0) qt[e] = valid ? (int32_t)q_cur : -1;
-    if (BWD) {
-      if (w == 0 && h == 0) jt[e] = valid ? j_cur : -1;
-      if (ragged) {  // grad_out row of every edge's query, scaled (pitch CO + 1: lanes = edges read one column)
-        for (int i = tid; i < 32 * CO; i += 256) {
-          const int ee = i / CO, ch = i - ee * CO;
-          const int64_t Ee = tile * 32 + ee;
-          float v = 0.f;
-          if (Ee < n_edges && ch < a.co_t) {
-            const int64_t qv = a.edge_q[Ee];
-            v = a.grad_out[qv * a.co_t + ch] * (a.q_scale ? a.q_scale[qv] : a.scale);
-          }
-          dout[ee * (CO + 1) + ch] = v;
+    if (w == 0 && h == 0) jt[e] = valid ? j_cur : -1;
+    if (ragged) {  // grad_out row of every edge's query, scaled (pitch CO + 1: lanes = edges read one column)
+      for (int i = tid; i < 32 * CO; i += 256) {
+        const int ee = i / CO, ch = i - ee * CO;
+        const int64_t Ee = tile * 32 + ee;
+        float v = 0.f;
+        if (Ee < n_edges && ch < a.co_t) {
+          const int64_t qv = a.edge_q[Ee];
+          v = a.grad_out[qv * a.co_t + ch] * (a.q_scale ? a.q_scale[qv] : a.scale);
         }
-      } else {
-        for (int i = tid; i < nq * CO; i += 256) {
-          const int ql = i / CO, ch = i - ql * CO;
-          const int64_t qq = tile * nq + ql;
-          dout[i] = (qq < a.n_query && ch < a.co_t) ? a.grad_out[qq * a.co_t + ch] * a.scale : 0.f;
-        }
+        dout[ee * (CO + 1) + ch] = v;
+      }
+    } else {
+      for (int i = tid; i < nq * CO; i += 256) {
+        const int ql = i / CO, ch = i - ql * CO;
+        const int64_t qq = tile * nq + ql;
+        dout[i] = (qq < a.n_query && ch < a.co_t) ? a.grad_out[qq * a.co_t + ch] * a.scale : 0.f;
       }
     }
 #pragma unroll
@@ -311,23 +290,6 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
       for (int r = 0; r < 16; ++r) acc1[t][r] = 0.f;
 #pragma unroll
       for (int s = 0; s < KS1; ++s) acc1[t] = mfma(wA1[t][s], x[s], acc1[t]);
-    }
-    if (!BWD && LIN) {  // Linear shortcut partial: Os^T[block sc_b] over this wave's reduction steps
-      f32x16 osc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) osc[r] = 0.f;
-#pragma unroll
-      for (int i = 0; i < P::SPW; ++i) {
-        // x[sc_p * SPW + i]: the index is wave-uniform but not a constant -> select over the (few) parts
-        float xv = 0.f;
-#pragma unroll
-        for (int pp = 0; pp < P::PARTS; ++pp) xv = (sc_p == pp) ? x[pp * P::SPW + i] : xv;
-        osc = mfma(wS[i], xv, osc);
-      }
-      const float* tsb = a.packed + P::OFF_TS + sc_b * 32 + h * 16;
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        tS[(sc_p * CO + 32 * sc_b + sigma(r, h)) * kPitch + e] = osc[r] + (sc_p == 0 ? tsb[r] : 0.f);
     }
     // x is consumed: next tile's rows, and the ids of the tile after it
     v_cur = v_nxt; q_cur = q_nxt; j_cur = j_nxt;
@@ -372,7 +334,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
       for (int r = 0; r < 16; ++r) {
         xh1[t][r] = (acc1[t][r] - mu1) * rstd1;
         H[t][r] = fmaxf(xh1[t][r] * t1[32 + r] + t1[64 + r], 0.f);
-        if (BWD) thw[(t * 32 + sigma(r, h)) * kPitch + e] = H[t][r];
+        thw[(t * 32 + sigma(r, h)) * kPitch + e] = H[t][r];
       }
     }
 
@@ -397,7 +359,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
     }
     __syncthreads();  // 2: po
 
-    float xh2[NB2][16];  // normalised GEMM2 output; the forward turns it into y in place
+    float xh2[NB2][16];  // normalised GEMM2 output
     float mu2, rstd2;
     {
       float s1b = 0.f, s2b = 0.f;
@@ -429,58 +391,7 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
         for (int r = 0; r < 16; ++r) xh2[b][r] = (xh2[b][r] - mu2) * rstd2;
     }
 
-    if (!BWD) {
-      // ---- forward tail: + identity shortcut, reduce over the k edges of every query ----
-#pragma unroll
-      for (int b = 0; b < NB2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (((b * 16 + r) & 3) == w) {
-            const int ch = 32 * b + sigma(r, h);
-            const float* t2 = tab + (P::NB1 + b) * 96 + h * 16;
-            float sc = 0.f;
-            if (LIN) {
-#pragma unroll
-              for (int pp = 0; pp < P::PARTS; ++pp) sc += tS[(pp * CO + ch) * kPitch + e];
-            } else if (ch < EIN) {
-              sc = tX[ch * kPitch + e];
-            }
-            tB[ch * kPitch + e] = xh2[b][r] * t2[32 + r] + t2[64 + r] + sc;
-          }
-      __syncthreads();  // 3: tB
-      if (ragged) {
-        // segments of equal query id inside the tile; a list may continue in the next tile, so every segment is ADDED to
-        // its (zero-filled) output row.  Thread (part, ch): 32 / parts consecutive edges, flush when the query changes.
-        constexpr int kParts = 256 / CO > 0 ? 256 / CO : 1, kEdges = 32 / kParts;
-        const int ch = tid % CO, part = tid / CO;
-        if (part < kParts && ch < a.co_t) {
-          float acc = 0.f;
-          int32_t qprev = -1;
-          for (int ee = part * kEdges; ee < (part + 1) * kEdges; ++ee) {
-            const int32_t qv = qt[ee];
-            if (qv != qprev) {
-              if (qprev >= 0) unsafeAtomicAdd(a.out + (int64_t)qprev * a.co_t + ch, acc * (a.q_scale ? a.q_scale[qprev] : a.scale));
-              acc = 0.f;
-              qprev = qv;
-            }
-            if (qv >= 0) acc += tB[ch * kPitch + ee];
-          }
-          if (qprev >= 0) unsafeAtomicAdd(a.out + (int64_t)qprev * a.co_t + ch, acc * (a.q_scale ? a.q_scale[qprev] : a.scale));
-        }
-      } else {
-        for (int i = tid; i < nq * CO; i += 256) {
-          const int ql = i / CO, ch = i - ql * CO;
-          const int64_t qq = tile * nq + ql;
-          float s = 0.f;
-          for (int kk = 0; kk < k; ++kk) s += tB[ch * kPitch + ql * k + kk];
-          if (qq < a.n_query && ch < a.co_t) a.out[qq * a.co_t + ch] = s * a.scale;
-        }
-      }
-      __syncthreads();  // 4: LDS is rewritten by the next tile
-      continue;
-    }
-
-    // ---- backward: dy -> LayerNorm2 -> dOpre ----
+    // ---- the forward is recomputed; from here on backward: dy -> LayerNorm2 -> dOpre ----
     float dOpre[NB2][16], dy[NB2][16];
     {
       const int ql = e >> a.log2k;
@@ -527,14 +438,9 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
           const f32x4* pa = pkT4 + P::OFF_P2T / 4 + (((w * HB + t) * NB2 + b) * 4) * 64 + lane;
 #pragma unroll
           for (int r4 = 0; r4 < 4; ++r4) {
-            if (kWRegs) {
+            const f32x4 av = pa[r4 * 64];
 #pragma unroll
-              for (int d = 0; d < 4; ++d) dh = mfma(wA2T[t][b][4 * r4 + d], dOpre[b][4 * r4 + d], dh);
-            } else {
-              const f32x4 av = pa[r4 * 64];
-#pragma unroll
-              for (int d = 0; d < 4; ++d) dh = mfma(av[d], dOpre[b][4 * r4 + d], dh);
-            }
+            for (int d = 0; d < 4; ++d) dh = mfma(av[d], dOpre[b][4 * r4 + d], dh);
           }
         }
 #pragma unroll
@@ -602,14 +508,9 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
         const f32x4* pa = pkT4 + P::OFF_P1T / 4 + (((w * HB + t) * NBX + cb) * 4) * 64 + lane;
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-          if (kWRegs) {
+          const f32x4 av = pa[r4 * 64];
 #pragma unroll
-            for (int d = 0; d < 4; ++d) dx = mfma(wA1T[t][cb][4 * r4 + d], dHpre[t][4 * r4 + d], dx);
-          } else {
-            const f32x4 av = pa[r4 * 64];
-#pragma unroll
-            for (int d = 0; d < 4; ++d) dx = mfma(av[d], dHpre[t][4 * r4 + d], dx);
-          }
+          for (int d = 0; d < 4; ++d) dx = mfma(av[d], dHpre[t][4 * r4 + d], dx);
         }
       }
       if (LIN) {  // + Ws dy: the (cb, b) blocks are spread over the waves, the partial-tile sum adds them up
@@ -692,7 +593,9 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
         if (jj >= 0) unsafeAtomicAdd(a.d_in + (int64_t)jj * a.cin + c, dxt[ee * (EIN + 1) + c]);  // hardware fp32 add, no CAS loop
       }
     }
-    if (ragged) {  // query-side gradient: segments as in the forward reduction, added to the (zero-filled) rows
+    if (ragged) {
+      // query-side gradient: segments of equal query id inside the tile; a list may continue in the next tile, so every
+      // segment is ADDED to its (zero-filled) row.  Thread (part, c): 8 consecutive edges, flush when the query changes.
       for (int i = tid; i < 4 * a.cq; i += 256) {
         const int part = i / a.cq, c = i - part * a.cq;
         float acc = 0.f;
@@ -720,84 +623,82 @@ __global__ __launch_bounds__(256, BWD ? 1 : 2) void pointconv_edge_kernel(const 
     __syncthreads();  // 6: LDS is rewritten by the next tile
   }
 
-  if (BWD) {
-    // ---- this workgroup's parameter-gradient partials (every true element is written: the reduce kernel sums them) ----
-    float* base = a.partial + (int64_t)blockIdx.x * grad_floats(a.ein_t, a.hid_t, a.co_t, LIN);
-    float* pW1 = base;
-    float* pb1 = pW1 + (int64_t)a.hid_t * a.ein_t;
-    float* pg1 = pb1 + a.hid_t;
-    float* pbe1 = pg1 + a.hid_t;
-    float* pW2 = pbe1 + a.hid_t;
-    float* pb2 = pW2 + (int64_t)a.co_t * a.hid_t;
-    float* pg2 = pb2 + a.co_t;
-    float* pbe2 = pg2 + a.co_t;
-    float* pWs = pbe2 + a.co_t;  // [co][ein], then dbs [co]  (Linear shortcut)
-    float* pbs = pWs + (int64_t)a.co_t * a.ein_t;
+  // ---- this workgroup's parameter-gradient partials (every true element is written: the reduce kernel sums them) ----
+  float* base = a.partial + (int64_t)blockIdx.x * grad_floats(a.ein_t, a.hid_t, a.co_t, LIN);
+  float* pW1 = base;
+  float* pb1 = pW1 + (int64_t)a.hid_t * a.ein_t;
+  float* pg1 = pb1 + a.hid_t;
+  float* pbe1 = pg1 + a.hid_t;
+  float* pW2 = pbe1 + a.hid_t;
+  float* pb2 = pW2 + (int64_t)a.co_t * a.hid_t;
+  float* pg2 = pb2 + a.co_t;
+  float* pbe2 = pg2 + a.co_t;
+  float* pWs = pbe2 + a.co_t;  // [co][ein], then dbs [co]  (Linear shortcut)
+  float* pbs = pWs + (int64_t)a.co_t * a.ein_t;
 #pragma unroll
-    for (int t = 0; t < HB; ++t) {
-      const int hid0 = 32 * (w * HB + t);
+  for (int t = 0; t < HB; ++t) {
+    const int hid0 = 32 * (w * HB + t);
 #pragma unroll
-      for (int cb = 0; cb < NBX; ++cb)
+    for (int cb = 0; cb < NBX; ++cb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {  // dW1a[cb][t][r] at lane (h, e): W1 grad (c = 32cb + sigma(r,h), hid = hid0 + e)
-          const int c = 32 * cb + sigma(r, h), hid = hid0 + e;
-          if (c < a.ein_t && hid < a.hid_t) pW1[(int64_t)hid * a.ein_t + c] = dW1a[cb][t][r];
-        }
-#pragma unroll
-      for (int b = 0; b < NB2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {  // dW2a[t][b][r] at lane (h, e): W2 grad (hid = hid0 + sigma(r,h), out = 32b + e)
-          const int hid = hid0 + sigma(r, h), oc = 32 * b + e;
-          if (hid < a.hid_t && oc < a.co_t) pW2[(int64_t)oc * a.hid_t + hid] = dW2a[t][b][r];
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float vg = half_sum32(dg1a[t][r]), vb = half_sum32(dbe1a[t][r]), vc = half_sum32(db1a[t][r]);
-        const int hid = hid0 + sigma(r, h);
-        if (e == 0 && hid < a.hid_t) {
-          pg1[hid] = vg;
-          pbe1[hid] = vb;
-          pb1[hid] = vc;
-        }
+      for (int r = 0; r < 16; ++r) {  // dW1a[cb][t][r] at lane (h, e): W1 grad (c = 32cb + sigma(r,h), hid = hid0 + e)
+        const int c = 32 * cb + sigma(r, h), hid = hid0 + e;
+        if (c < a.ein_t && hid < a.hid_t) pW1[(int64_t)hid * a.ein_t + c] = dW1a[cb][t][r];
       }
-    }
 #pragma unroll
     for (int b = 0; b < NB2; ++b)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (((b * 16 + r) & 3) == w) {
-          const int i = (b * 16 + r) >> 2;
-          const float vg = half_sum32(dg2a[i]), vb = half_sum32(dbe2a[i]), vc = half_sum32(db2a[i]);
-          const int oc = 32 * b + sigma(r, h);
-          if (e == 0 && oc < a.co_t) {
-            pg2[oc] = vg;
-            pbe2[oc] = vb;
-            pb2[oc] = vc;
-            if (LIN) pbs[oc] = vb;  // d bs = sum of dy = d LN2.bias
-          }
+      for (int r = 0; r < 16; ++r) {  // dW2a[t][b][r] at lane (h, e): W2 grad (hid = hid0 + sigma(r,h), out = 32b + e)
+        const int hid = hid0 + sigma(r, h), oc = 32 * b + e;
+        if (hid < a.hid_t && oc < a.co_t) pW2[(int64_t)oc * a.hid_t + hid] = dW2a[t][b][r];
+      }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float vg = half_sum32(dg1a[t][r]), vb = half_sum32(dbe1a[t][r]), vc = half_sum32(db1a[t][r]);
+      const int hid = hid0 + sigma(r, h);
+      if (e == 0 && hid < a.hid_t) {
+        pg1[hid] = vg;
+        pbe1[hid] = vb;
+        pb1[hid] = vc;
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NB2; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (((b * 16 + r) & 3) == w) {
+        const int i = (b * 16 + r) >> 2;
+        const float vg = half_sum32(dg2a[i]), vb = half_sum32(dbe2a[i]), vc = half_sum32(db2a[i]);
+        const int oc = 32 * b + sigma(r, h);
+        if (e == 0 && oc < a.co_t) {
+          pg2[oc] = vg;
+          pbe2[oc] = vb;
+          pb2[oc] = vc;
+          if (LIN) pbs[oc] = vb;  // d bs = sum of dy = d LN2.bias
         }
-    if (LIN) {
+      }
+  if (LIN) {
 #pragma unroll
-      for (int jb = 0; jb < P::WSB; ++jb) {
-        const int id = jb * kPcWaves + w;
-        if (id < NBX * NB2) {
-          const int cb = id / NB2, b = id - cb * NB2;
+    for (int jb = 0; jb < P::WSB; ++jb) {
+      const int id = jb * kPcWaves + w;
+      if (id < NBX * NB2) {
+        const int cb = id / NB2, b = id - cb * NB2;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {  // dWsa[jb][r] at lane (h, e): Ws grad (c = 32cb + sigma(r,h), out = 32b + e)
-            const int c = 32 * cb + sigma(r, h), oc = 32 * b + e;
-            if (c < a.ein_t && oc < a.co_t) pWs[(int64_t)oc * a.ein_t + c] = dWsa[jb][r];
-          }
+        for (int r = 0; r < 16; ++r) {  // dWsa[jb][r] at lane (h, e): Ws grad (c = 32cb + sigma(r,h), out = 32b + e)
+          const int c = 32 * cb + sigma(r, h), oc = 32 * b + e;
+          if (c < a.ein_t && oc < a.co_t) pWs[(int64_t)oc * a.ein_t + c] = dWsa[jb][r];
         }
       }
     }
   }
 }
 
-// Forward for uniform lists, one 32-edge tile per WAVE: nothing to exchange between the waves of a workgroup (every wave
-// owns all hidden channels of its tile), so there is no barrier in the loop and two waves per SIMD overlap each other's
-// gathers, LayerNorm arithmetic and MFMA chains.  The operand images sit in LDS once per (persistent) workgroup.  The
-// tensor-parallel kernel above stays for the backward (its point is the register-resident weight gradients) and for
-// ragged lists.  EIN = 64: lane half h holds x channels [32h, 32h + 32), so the identity shortcut is one lane swap.
+// Forward for uniform and ragged lists, one 32-edge tile per WAVE: nothing to exchange between the waves of a workgroup
+// (every wave owns all hidden channels of its tile), so there is no barrier in the loop and two waves per SIMD overlap each
+// other's gathers, LayerNorm arithmetic and MFMA chains.  The operand images sit in LDS once per (persistent) workgroup.
+// The tensor-parallel decomposition above is the backward's alone: its point is the register-resident weight gradients.
+// EIN = 64: lane half h holds x channels [32h, 32h + 32), so the identity shortcut is one lane swap.
 template <int EIN, int HID, int CO, bool LIN, bool RAG>
 __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs a) {
   typedef PC<EIN, HID, CO> P;
@@ -846,7 +747,7 @@ __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs
       j_nxt = (tile + nwaves < ntiles && En < n_edges) ? a.nbr[En] : 0;
     }
     float x[KS1];
-    {
+    {  // the gather of the backward kernel (gather_x), q clamped for the lanes past the last edge
       const float* fi = a.in_feats + (int64_t)j * a.cin;
       const float* fq = a.q_feats + (q < 0 ? 0 : q) * a.cq;
       const bool vec = ((a.cin | a.cq) & 3) == 0;
@@ -1014,6 +915,29 @@ struct PackArgs {
   int ein_t, hid_t, co_t;
   float* packed;
 };
+// One element of a packed image, decoded from its offset inside the image.  `i` is the MFMA row of the A operand (lane
+// % 32), `blk` the index over the leading dimensions; the k index of the operand is
+//   TFrag  [blk][r4][lane][4]:     channel sigma(4*r4 + d, lane / 32) of a 32-block - a result register of the GEMM in front
+//   KFrag  [blk][s4][lane][4]:     channel (lane / 32) * KS1 + 4*s4 + d            - an x register
+struct TFrag { int i, sg, blk; };
+struct KFrag { int i, c, blk; };
+__device__ __forceinline__ TFrag decode_tfrag(int o) {
+  const int d = o & 3, lane = (o >> 2) & 63, r4 = (o >> 8) & 3;
+  return {lane & 31, sigma(4 * r4 + d, lane >> 5), o >> 10};
+}
+template <int KS1>
+__device__ __forceinline__ KFrag decode_kfrag(int o) {
+  const int d = o & 3, lane = (o >> 2) & 63, rest = o >> 8;
+  return {lane & 31, (lane >> 5) * KS1 + 4 * (rest % (KS1 / 4)) + d, rest / (KS1 / 4)};
+}
+// [blk][ROWS][2][16] table (ROWS = 3: bias, LayerNorm weight, LayerNorm bias): row and channel 32*blk + sigma(r, h)
+struct TabElem { int row, ch; };
+template <int ROWS>
+__device__ __forceinline__ TabElem decode_tab(int o) {
+  const int r = o & 15, hh = (o >> 4) & 1, rows = o >> 5;
+  return {rows % ROWS, 32 * (rows / ROWS) + sigma(r, hh)};
+}
+
 template <int EIN, int HID, int CO>
 __global__ void pointconv_pack_kernel(const PackArgs p) {
   typedef PC<EIN, HID, CO> P;
@@ -1022,53 +946,35 @@ __global__ void pointconv_pack_kernel(const PackArgs p) {
   auto W1 = [&](int c, int hid) { return (c < p.ein_t && hid < p.hid_t) ? p.w1[(int64_t)hid * p.ein_t + c] : 0.f; };
   auto W2 = [&](int hid, int oc) { return (hid < p.hid_t && oc < p.co_t) ? p.w2[(int64_t)oc * p.hid_t + hid] : 0.f; };
   auto WS = [&](int c, int oc) { return (p.ws && c < p.ein_t && oc < p.co_t) ? p.ws[(int64_t)oc * p.ein_t + c] : 0.f; };
+  auto tab = [&](const float* src, int ch, int width) { return (ch < width && src) ? src[ch] : 0.f; };
   float v = 0.f;
   if (idx < P::OFF_P2) {  // P1 [blk][s4][lane][4]
-    const int d = idx & 3, lane = (idx >> 2) & 63, rest = idx >> 8;
-    const int s4 = rest % (P::KS1 / 4), blk = rest / (P::KS1 / 4);
-    v = W1((lane >> 5) * P::KS1 + 4 * s4 + d, 32 * blk + (lane & 31));
+    const KFrag f = decode_kfrag<P::KS1>(idx - P::OFF_P1);
+    v = W1(f.c, 32 * f.blk + f.i);
   } else if (idx < P::OFF_P2T) {  // P2 [blk][b][r4][lane][4]
-    const int i2 = idx - P::OFF_P2;
-    const int d = i2 & 3, lane = (i2 >> 2) & 63, r4 = (i2 >> 8) & 3, rest = i2 >> 10;
-    const int b = rest % P::NB2, blk = rest / P::NB2;
-    v = W2(32 * blk + sigma(4 * r4 + d, lane >> 5), 32 * b + (lane & 31));
-  } else if (idx < P::OFF_P1T) {  // P2T
-    const int i2 = idx - P::OFF_P2T;
-    const int d = i2 & 3, lane = (i2 >> 2) & 63, r4 = (i2 >> 8) & 3, rest = i2 >> 10;
-    const int b = rest % P::NB2, blk = rest / P::NB2;
-    v = W2(32 * blk + (lane & 31), 32 * b + sigma(4 * r4 + d, lane >> 5));
+    const TFrag f = decode_tfrag(idx - P::OFF_P2);
+    v = W2(32 * (f.blk / P::NB2) + f.sg, 32 * (f.blk % P::NB2) + f.i);
+  } else if (idx < P::OFF_P1T) {  // P2T [blk][b][r4][lane][4]
+    const TFrag f = decode_tfrag(idx - P::OFF_P2T);
+    v = W2(32 * (f.blk / P::NB2) + f.i, 32 * (f.blk % P::NB2) + f.sg);
   } else if (idx < P::OFF_T1) {  // P1T [blk][cb][r4][lane][4]
-    const int i2 = idx - P::OFF_P1T;
-    const int d = i2 & 3, lane = (i2 >> 2) & 63, r4 = (i2 >> 8) & 3, rest = i2 >> 10;
-    const int cb = rest % P::NBX, blk = rest / P::NBX;
-    v = W1(32 * cb + (lane & 31), 32 * blk + sigma(4 * r4 + d, lane >> 5));
+    const TFrag f = decode_tfrag(idx - P::OFF_P1T);
+    v = W1(32 * (f.blk % P::NBX) + f.i, 32 * (f.blk / P::NBX) + f.sg);
   } else if (idx < P::OFF_T2) {  // T1 [blk][3][2][16]
-    const int i2 = idx - P::OFF_T1;
-    const int r = i2 & 15, hh = (i2 >> 4) & 1, which = (i2 >> 5) % 3, blk = i2 / 96;
-    const int ch = 32 * blk + sigma(r, hh);
-    const float* src = which == 0 ? p.b1 : which == 1 ? p.g1 : p.be1;
-    v = (ch < p.hid_t && src) ? src[ch] : 0.f;
-  } else if (idx < P::OFF_PS) {
-    const int i2 = idx - P::OFF_T2;
-    const int r = i2 & 15, hh = (i2 >> 4) & 1, which = (i2 >> 5) % 3, b = i2 / 96;
-    const int ch = 32 * b + sigma(r, hh);
-    const float* src = which == 0 ? p.b2 : which == 1 ? p.g2 : p.be2;
-    v = (ch < p.co_t && src) ? src[ch] : 0.f;
+    const TabElem t = decode_tab<3>(idx - P::OFF_T1);
+    v = tab(t.row == 0 ? p.b1 : t.row == 1 ? p.g1 : p.be1, t.ch, p.hid_t);
+  } else if (idx < P::OFF_PS) {  // T2 [b][3][2][16]
+    const TabElem t = decode_tab<3>(idx - P::OFF_T2);
+    v = tab(t.row == 0 ? p.b2 : t.row == 1 ? p.g2 : p.be2, t.ch, p.co_t);
   } else if (idx < P::OFF_PST) {  // PS [b][s4][lane][4]
-    const int i2 = idx - P::OFF_PS;
-    const int d = i2 & 3, lane = (i2 >> 2) & 63, rest = i2 >> 8;
-    const int s4 = rest % (P::KS1 / 4), b = rest / (P::KS1 / 4);
-    v = WS((lane >> 5) * P::KS1 + 4 * s4 + d, 32 * b + (lane & 31));
+    const KFrag f = decode_kfrag<P::KS1>(idx - P::OFF_PS);
+    v = WS(f.c, 32 * f.blk + f.i);
   } else if (idx < P::OFF_TS) {  // PST [cb][b][r4][lane][4]
-    const int i2 = idx - P::OFF_PST;
-    const int d = i2 & 3, lane = (i2 >> 2) & 63, r4 = (i2 >> 8) & 3, rest = i2 >> 10;
-    const int b = rest % P::NB2, cb = rest / P::NB2;
-    v = WS(32 * cb + (lane & 31), 32 * b + sigma(4 * r4 + d, lane >> 5));
+    const TFrag f = decode_tfrag(idx - P::OFF_PST);
+    v = WS(32 * (f.blk / P::NB2) + f.i, 32 * (f.blk % P::NB2) + f.sg);
   } else {  // TS [b][2][16]
-    const int i2 = idx - P::OFF_TS;
-    const int r = i2 & 15, hh = (i2 >> 4) & 1, b = i2 >> 5;
-    const int ch = 32 * b + sigma(r, hh);
-    v = (ch < p.co_t && p.bs) ? p.bs[ch] : 0.f;
+    const TabElem t = decode_tab<1>(idx - P::OFF_TS);
+    v = tab(p.bs, t.ch, p.co_t);
   }
   p.packed[idx] = v;
 }
@@ -1081,13 +987,19 @@ __global__ void pointconv_grad_reduce_kernel(const float* __restrict__ partial, 
   out[i] = s;
 }
 
-// instantiated shapes: (EIN, HID, CO); channel counts are zero-padded up to the smallest one that fits
-struct Shape { int ein, hid, co; };
-constexpr Shape kShapes[] = {{64, 128, 64}};
-
+// Instantiated shapes (EIN, HID, CO), one line each: f(PC<..>{}) for the shape of that index, false past the last one.
+template <typename F>
+bool with_shape(int index, F&& f) {
+  switch (index) {
+    case 0: f(PC<64, 128, 64>{}); return true;
+    default: return false;
+  }
+}
+// channel counts are zero-padded up to the first shape that fits; -1: none does
 int pick_shape(int ein_t, int hid_t, int co_t) {
-  for (int i = 0; i < (int)(sizeof(kShapes) / sizeof(kShapes[0])); ++i)
-    if (ein_t <= kShapes[i].ein && hid_t <= kShapes[i].hid && co_t <= kShapes[i].co) return i;
+  bool fits = false;
+  for (int i = 0; with_shape(i, [&](auto p) { fits = ein_t <= p.EIN && hid_t <= p.HID && co_t <= p.CO; }); ++i)
+    if (fits) return i;
   return -1;
 }
 int log2_exact(int k) {
@@ -1100,53 +1012,48 @@ int bwd_grid(int64_t n_query, int k) {
   return (int)(tiles < 256 ? tiles : 256);  // one persistent workgroup per CU
 }
 
-template <int EIN, int HID, int CO, bool BWD, bool LIN, bool RAG>
-int launch_edge_lin(const PcArgs& a, int grid, hipStream_t s) {
-  typedef PC<EIN, HID, CO> P;
-  static unsigned long long attr_done = 0ull;
-  const int rc = once_per_device(attr_done, [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(pointconv_edge_kernel<EIN, HID, CO, BWD, LIN, RAG>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (BWD ? P::LDS_FLOATS : P::LDS_FLOATS_FWD) * 4) == hipSuccess;
-  });
-  if (rc != WCN_SUCCESS) return rc;
-  hipLaunchKernelGGL((pointconv_edge_kernel<EIN, HID, CO, BWD, LIN, RAG>), dim3(grid), dim3(256),
-                     (BWD ? P::LDS_FLOATS : P::LDS_FLOATS_FWD) * 4, s, a);
-  return launch_status();
+// The two runtime flags of a launch as template flags: f(bool_constant<LIN>, bool_constant<RAG>).
+template <typename F>
+int with_lin_rag(const PcArgs& a, F&& f) {
+  if (a.edge_q) return a.lin_sc ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
+  return a.lin_sc ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
 }
 
-template <int EIN, int HID, int CO>
-int launch_fwd_wave(const PcArgs& a, hipStream_t s) {
-  typedef PC<EIN, HID, CO> P;
-  constexpr int kLds = (P::OFF_P2T + (P::NB1 + P::NB2) * 96 + EIN * CO + P::NB2 * 32) * 4;
-  static unsigned long long attr_done = 0ull;
-  const int rc = once_per_device(attr_done, [] {
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(pointconv_fwd_wave_kernel<EIN, HID, CO, false, false>),
-                          reinterpret_cast<const void*>(pointconv_fwd_wave_kernel<EIN, HID, CO, true, false>),
-                          reinterpret_cast<const void*>(pointconv_fwd_wave_kernel<EIN, HID, CO, false, true>),
-                          reinterpret_cast<const void*>(pointconv_fwd_wave_kernel<EIN, HID, CO, true, true>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) == hipSuccess;
-    return ok;
+// Launches kernel_of(lin, rag), the <LIN, RAG> instance of a kernel for the flags of `a`; the instance's dynamic-LDS limit
+// is raised on its first launch on a device (the static below exists once per instance).
+template <typename KernelOf>
+int launch_lin_rag(const PcArgs& a, KernelOf kernel_of, int grid, int threads, int lds_bytes, hipStream_t s) {
+  return with_lin_rag(a, [&](auto lin, auto rag) {
+    void (*const kernel)(PcArgs) = kernel_of(lin, rag);
+    static unsigned long long attr_done = 0ull;
+    const int rc = once_per_device(attr_done, [&] {
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 lds_bytes) == hipSuccess;
+    });
+    if (rc != WCN_SUCCESS) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds_bytes, s, a);
+    return launch_status();
   });
-  if (rc != WCN_SUCCESS) return rc;
+}
+
+template <typename P>
+int launch_fwd_wave(const PcArgs& a, hipStream_t s) {
   const int64_t edges = a.edge_q ? a.n_edges : (a.n_query << a.log2k);
   const int64_t tiles = (edges + 31) / 32;
   const int64_t wgs = (tiles + 7) / 8;
   const int grid = (int)(wgs < 256 ? wgs : 256);  // one persistent 8-wave workgroup per CU
-#define WCN_PCW(L, R) hipLaunchKernelGGL((pointconv_fwd_wave_kernel<EIN, HID, CO, L, R>), dim3(grid), dim3(512), kLds, s, a)
-  if (a.edge_q) { if (a.lin_sc) WCN_PCW(true, true); else WCN_PCW(false, true); }
-  else { if (a.lin_sc) WCN_PCW(true, false); else WCN_PCW(false, false); }
-#undef WCN_PCW
-  return launch_status();
+  const auto kernel_of = [](auto lin, auto rag) {
+    return pointconv_fwd_wave_kernel<P::EIN, P::HID, P::CO, decltype(lin)::value, decltype(rag)::value>;
+  };
+  return launch_lin_rag(a, kernel_of, grid, 512, P::LDS_FLOATS_WAVE * 4, s);
 }
 
-template <int EIN, int HID, int CO, bool BWD>
-int launch_edge(const PcArgs& a, int grid, hipStream_t s) {
-  if (a.edge_q)
-    return a.lin_sc ? launch_edge_lin<EIN, HID, CO, BWD, true, true>(a, grid, s)
-                    : launch_edge_lin<EIN, HID, CO, BWD, false, true>(a, grid, s);
-  return a.lin_sc ? launch_edge_lin<EIN, HID, CO, BWD, true, false>(a, grid, s)
-                  : launch_edge_lin<EIN, HID, CO, BWD, false, false>(a, grid, s);
+template <typename P>
+int launch_bwd(const PcArgs& a, int grid, hipStream_t s) {
+  const auto kernel_of = [](auto lin, auto rag) {
+    return pointconv_bwd_kernel<P::EIN, P::HID, P::CO, decltype(lin)::value, decltype(rag)::value>;
+  };
+  return launch_lin_rag(a, kernel_of, grid, 256, P::LDS_FLOATS * 4, s);
 }
 
 }  // namespace
@@ -1164,10 +1071,9 @@ int wcn_pointconv_supported(int32_t cin, int32_t cq, int32_t nrel, int32_t hidde
 }
 
 int64_t wcn_pointconv_packed_floats(int32_t ein, int32_t hidden, int32_t cout) {
-  switch (pick_shape(ein, hidden, cout)) {
-    case 0: return PC<64, 128, 64>::PACKED;
-    default: return 0;
-  }
+  int64_t floats = 0;
+  with_shape(pick_shape(ein, hidden, cout), [&](auto p) { floats = p.PACKED; });
+  return floats;
 }
 
 int64_t wcn_pointconv_grad_floats(int32_t ein, int32_t hidden, int32_t cout, int32_t linear_shortcut) {
@@ -1185,13 +1091,11 @@ int wcn_pointconv_pack(const float* w1, const float* b1, const float* g1, const 
   if (!w1 || !w2 || !packed) return WCN_ERROR_INVALID_PARAMETERS;
   const PackArgs p{w1, b1, g1, be1, w2, b2, g2, be2, ws, bs, ein, hidden, cout, packed};
   hipStream_t s = (hipStream_t)stream;
-  switch (pick_shape(ein, hidden, cout)) {
-    case 0:
-      hipLaunchKernelGGL((pointconv_pack_kernel<64, 128, 64>), dim3((PC<64, 128, 64>::PACKED + 255) / 256), dim3(256), 0, s, p);
-      break;
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
-  return launch_status();
+  const bool launched = with_shape(pick_shape(ein, hidden, cout), [&](auto shape) {
+    typedef decltype(shape) P;
+    hipLaunchKernelGGL((pointconv_pack_kernel<P::EIN, P::HID, P::CO>), dim3((P::PACKED + 255) / 256), dim3(256), 0, s, p);
+  });
+  return launched ? launch_status() : WCN_ERROR_UNSUPPORTED_CONFIG;
 }
 
 static int fill_args(PcArgs& a, const float* in_feats, const float* q_feats, const float* in_xyz, const float* q_xyz,
@@ -1210,15 +1114,21 @@ static int fill_args(PcArgs& a, const float* in_feats, const float* q_feats, con
   return WCN_SUCCESS;
 }
 
+// ragged lists: the query of every edge, the per-query reduction scale (or NULL) and the number of edges
+static int set_ragged(PcArgs& a, const int32_t* edge_q, const float* q_scale, int64_t n_edges) {
+  if (!edge_q || n_edges < 0) return WCN_ERROR_INVALID_PARAMETERS;
+  a.edge_q = edge_q; a.q_scale = q_scale; a.n_edges = n_edges;
+  return WCN_SUCCESS;
+}
+
 static int run_forward(PcArgs& a, float* out, hipStream_t s) {
   if (!out) return WCN_ERROR_INVALID_PARAMETERS;
   const int64_t edges = a.edge_q ? a.n_edges : (a.n_query << a.log2k);
   if (a.n_query == 0 || edges == 0) return WCN_SUCCESS;
   a.out = out;
-  switch (pick_shape(a.ein_t, a.hid_t, a.co_t)) {
-    case 0: return launch_fwd_wave<64, 128, 64>(a, s);  // one tile per wave (1.19 vs 1.87 ms for the tensor-parallel kernel)
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  int rc = WCN_ERROR_UNSUPPORTED_CONFIG;
+  with_shape(pick_shape(a.ein_t, a.hid_t, a.co_t), [&](auto shape) { rc = launch_fwd_wave<decltype(shape)>(a, s); });
+  return rc;
 }
 
 static int run_backward(PcArgs& a, const float* grad_out, float* d_in, float* d_q, float* d_params, void* workspace,
@@ -1232,12 +1142,9 @@ static int run_backward(PcArgs& a, const float* grad_out, float* d_in, float* d_
     return hipMemsetAsync(d_params, 0, gf * sizeof(float), s) == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
   a.grad_out = grad_out; a.d_in = d_in; a.d_q = d_q; a.partial = (float*)workspace;
   const int grid = bwd_grid(edges, 1);
-  int rc2;
-  switch (pick_shape(a.ein_t, a.hid_t, a.co_t)) {
-    case 0: rc2 = launch_edge<64, 128, 64, true>(a, grid, s); break;
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
-  if (rc2 != WCN_SUCCESS) return rc2;
+  int rc = WCN_ERROR_UNSUPPORTED_CONFIG;
+  with_shape(pick_shape(a.ein_t, a.hid_t, a.co_t), [&](auto shape) { rc = launch_bwd<decltype(shape)>(a, grid, s); });
+  if (rc != WCN_SUCCESS) return rc;
   hipLaunchKernelGGL(pointconv_grad_reduce_kernel, dim3((unsigned)((gf + 255) / 256)), dim3(256), 0, s,
                      (const float*)workspace, grid, gf, d_params);
   return launch_status();
@@ -1296,8 +1203,7 @@ int wcn_pointconv_edge_forward_ragged(const float* in_feats, const float* q_feat
   const int rc = fill_args(a, in_feats, q_feats, in_xyz, q_xyz, nbr, n_query, 1, cin, cq, nrel, packed, hidden, cout, eps1,
                            eps2, 0, linear_shortcut);
   if (rc != WCN_SUCCESS) return rc;
-  if (!edge_q || n_edges < 0) return WCN_ERROR_INVALID_PARAMETERS;
-  a.edge_q = edge_q; a.q_scale = q_scale; a.n_edges = n_edges;
+  if (const int rr = set_ragged(a, edge_q, q_scale, n_edges)) return rr;
   return run_forward(a, out, (hipStream_t)stream);
 }
 
@@ -1311,8 +1217,7 @@ int wcn_pointconv_edge_backward_ragged(const float* in_feats, const float* q_fea
   const int rc = fill_args(a, in_feats, q_feats, in_xyz, q_xyz, nbr, n_query, 1, cin, cq, nrel, packed, hidden, cout, eps1,
                            eps2, 0, linear_shortcut);
   if (rc != WCN_SUCCESS) return rc;
-  if (!edge_q || n_edges < 0) return WCN_ERROR_INVALID_PARAMETERS;
-  a.edge_q = edge_q; a.q_scale = q_scale; a.n_edges = n_edges;
+  if (const int rr = set_ragged(a, edge_q, q_scale, n_edges)) return rr;
   return run_backward(a, grad_out, d_in, d_q, d_params, workspace, workspace_bytes, (hipStream_t)stream);
 }
 

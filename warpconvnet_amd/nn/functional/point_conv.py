@@ -69,6 +69,17 @@ def _packed_params(mlp: nn.Module, parts) -> Tensor:
     return packed
 
 
+def _edge_args(in_feats, q_feats, in_xyz, q_xyz, nbr, edge_q, q_scale, packed, dims):
+    """The arguments every edge entry point of ``include/wcn.h`` starts with, in front of its output / gradient pointers:
+    uniform lists ``(.., M, k, .., mean, lin)``, ragged lists ``(.., edge_q, q_scale, E, M, .., lin)``."""
+    M, k, cin, cq, nrel, hid, co, eps1, eps2, mean, lin = dims
+    gathered = tuple(_lib.ptr(t) for t in (in_feats, q_feats, in_xyz, q_xyz, nbr))
+    mlp = (cin, cq, nrel, _lib.ptr(packed), hid, co, eps1, eps2)
+    if edge_q is None:
+        return gathered + (M, k) + mlp + (mean, lin)
+    return gathered + (_lib.ptr(edge_q), _lib.ptr(q_scale), nbr.numel(), M) + mlp + (lin,)
+
+
 class _FusedEdge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, in_feats, q_feats, w1, b1, g1, be1, w2, b2, g2, be2, ws, bs, packed, in_xyz, q_xyz, nbr, k, eps1, eps2,
@@ -79,21 +90,15 @@ class _FusedEdge(torch.autograd.Function):
         M, cin, cq = q_feats.shape[0], in_feats.shape[1], q_feats.shape[1]
         nrel = 0 if in_xyz is None else 3
         hid, co = w1.shape[0], w2.shape[0]
-        lin = int(ws is not None)
-        if edge_q is None:
-            out = torch.empty(M, co, dtype=torch.float32, device=dev)
-            _lib.check(L.wcn_pointconv_edge_forward(
-                _lib.ptr(in_feats), _lib.ptr(q_feats), _lib.ptr(in_xyz), _lib.ptr(q_xyz), _lib.ptr(nbr), M, k, cin, cq, nrel,
-                _lib.ptr(packed), hid, co, eps1, eps2, int(mean), lin, _lib.ptr(out), _lib.stream_handle(dev)),
-                "wcn_pointconv_edge_forward")
-        else:  # ragged lists: segments are added to zero-filled rows
-            out = torch.zeros(M, co, dtype=torch.float32, device=dev)
-            _lib.check(L.wcn_pointconv_edge_forward_ragged(
-                _lib.ptr(in_feats), _lib.ptr(q_feats), _lib.ptr(in_xyz), _lib.ptr(q_xyz), _lib.ptr(nbr), _lib.ptr(edge_q),
-                _lib.ptr(q_scale), nbr.numel(), M, cin, cq, nrel, _lib.ptr(packed), hid, co, eps1, eps2, lin, _lib.ptr(out),
-                _lib.stream_handle(dev)), "wcn_pointconv_edge_forward_ragged")
+        dims = (M, k, cin, cq, nrel, hid, co, eps1, eps2, int(mean), int(ws is not None))
+        ragged = edge_q is not None
+        name = "wcn_pointconv_edge_forward_ragged" if ragged else "wcn_pointconv_edge_forward"
+        # ragged lists: segments are added to zero-filled rows
+        out = (torch.zeros if ragged else torch.empty)(M, co, dtype=torch.float32, device=dev)
+        _lib.check(getattr(L, name)(*_edge_args(in_feats, q_feats, in_xyz, q_xyz, nbr, edge_q, q_scale, packed, dims),
+                                    _lib.ptr(out), _lib.stream_handle(dev)), name)
         ctx.save_for_backward(in_feats, q_feats, packed, in_xyz, q_xyz, nbr, edge_q, q_scale)
-        ctx.dims = (M, k, cin, cq, nrel, hid, co, eps1, eps2, int(mean), lin)
+        ctx.dims = dims
         ctx.has = (b1 is not None, b2 is not None, bs is not None)
         return out
 
@@ -106,46 +111,31 @@ class _FusedEdge(torch.autograd.Function):
         ein = cin + cq + nrel
         grad_out = grad_out.contiguous().float()
         grads = torch.empty(L.wcn_pointconv_grad_floats(ein, hid, co, lin), dtype=torch.float32, device=dev)
-        if edge_q is None and torch.are_deterministic_algorithms_enabled():
-            # bitwise-reproducible input gradient: per-edge rows by plain stores, then the rows of every input point added in
-            # ascending edge order (stable sort of the neighbour ids + CSR segment sum) - no fp32 atomics anywhere
+        ragged = edge_q is not None
+        # bitwise-reproducible input gradient (uniform lists): per-edge rows by plain stores, then the rows of every input
+        # point added in ascending edge order (stable sort of the neighbour ids + CSR segment sum) - no fp32 atomics anywhere
+        per_edge = not ragged and torch.are_deterministic_algorithms_enabled()
+        name = "wcn_pointconv_edge_backward" + ("_ragged" if ragged else "_peredge" if per_edge else "")
+        # input-gradient target: [M * k, cin] rows the kernel stores, or the zero-filled d_in its atomics add to
+        d_in = torch.empty(M * k, cin, dtype=torch.float32, device=dev) if per_edge else torch.zeros_like(in_feats)
+        # uniform lists: every d_q row is stored once; ragged lists: list segments are added to zero-filled rows
+        d_q = (torch.zeros_like if ragged else torch.empty_like)(q_feats)
+        lists, length = (nbr.numel(), 1) if ragged else (M, k)
+        ws_bytes = L.wcn_pointconv_backward_workspace(lists, length, ein, hid, co, lin)
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        _lib.check(getattr(L, name)(*_edge_args(in_feats, q_feats, in_xyz, q_xyz, nbr, edge_q, q_scale, packed, ctx.dims),
+                                    _lib.ptr(grad_out), _lib.ptr(d_in), _lib.ptr(d_q), _lib.ptr(grads), _lib.ptr(ws), ws_bytes,
+                                    _lib.stream_handle(dev)), name)
+        if per_edge:
             from warpconvnet_amd.ops.reductions import row_reduction
 
-            d_q = torch.empty_like(q_feats)
-            d_edge = torch.empty(M * k, cin, dtype=torch.float32, device=dev)
-            ws_bytes = L.wcn_pointconv_backward_workspace(M, k, ein, hid, co, lin)
-            ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
-            _lib.check(L.wcn_pointconv_edge_backward_peredge(
-                _lib.ptr(in_feats), _lib.ptr(q_feats), _lib.ptr(in_xyz), _lib.ptr(q_xyz), _lib.ptr(nbr), M, k, cin, cq, nrel,
-                _lib.ptr(packed), hid, co, eps1, eps2, mean, lin, _lib.ptr(grad_out), _lib.ptr(d_edge), _lib.ptr(d_q),
-                _lib.ptr(grads), _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev)), "wcn_pointconv_edge_backward_peredge")
             ids = nbr.reshape(-1).long()
             valid = ids >= 0
             order = torch.sort(torch.where(valid, ids, torch.full_like(ids, in_feats.shape[0])), stable=True).indices
             counts = torch.bincount(ids[valid], minlength=in_feats.shape[0])
             splits = torch.zeros(in_feats.shape[0] + 1, dtype=torch.int64, device=dev)
             splits[1:] = counts.cumsum(0)
-            d_in = row_reduction(d_edge[order[: int(splits[-1])]], splits, "sum")
-        elif edge_q is None:
-            d_in = torch.zeros_like(in_feats)
-            d_q = torch.empty_like(q_feats)
-            ws_bytes = L.wcn_pointconv_backward_workspace(M, k, ein, hid, co, lin)
-            ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
-            _lib.check(L.wcn_pointconv_edge_backward(
-                _lib.ptr(in_feats), _lib.ptr(q_feats), _lib.ptr(in_xyz), _lib.ptr(q_xyz), _lib.ptr(nbr), M, k, cin, cq, nrel,
-                _lib.ptr(packed), hid, co, eps1, eps2, mean, lin, _lib.ptr(grad_out), _lib.ptr(d_in), _lib.ptr(d_q),
-                _lib.ptr(grads), _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev)), "wcn_pointconv_edge_backward")
-        else:
-            d_in = torch.zeros_like(in_feats)
-            d_q = torch.zeros_like(q_feats)
-            E = nbr.numel()
-            ws_bytes = L.wcn_pointconv_backward_workspace(E, 1, ein, hid, co, lin)
-            ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
-            _lib.check(L.wcn_pointconv_edge_backward_ragged(
-                _lib.ptr(in_feats), _lib.ptr(q_feats), _lib.ptr(in_xyz), _lib.ptr(q_xyz), _lib.ptr(nbr), _lib.ptr(edge_q),
-                _lib.ptr(q_scale), E, M, cin, cq, nrel, _lib.ptr(packed), hid, co, eps1, eps2, lin, _lib.ptr(grad_out),
-                _lib.ptr(d_in), _lib.ptr(d_q), _lib.ptr(grads), _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev)),
-                "wcn_pointconv_edge_backward_ragged")
+            d_in = row_reduction(d_in[order[: int(splits[-1])]], splits, "sum")
         o = 0
 
         def take(n, shape):
