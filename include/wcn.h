@@ -669,6 +669,52 @@ int wcn_resample_expand(const int32_t* parents, const void* mask, int32_t mask_d
                         int32_t* out_offsets, int64_t capacity, int32_t* child_coords, int32_t* tbl, int32_t pitch,
                         wcn_stream_t stream);
 
+/* ---- Q/K prologue of sparse voxel self-attention: qk-RMSNorm, coordinate RoPE, cast (ABI 7, additions only) ------------------
+ * What the reference's SparseMultiHeadAttention runs between `to_qkv` and the attention core
+ * (nn/modules/sparse_dit_attention.py:249-262: unbind -> MultiHeadRMSNorm -> SparseRotaryPositionEmbedder -> stack) and its
+ * fused rotation (nn/functional/fused_rope.py:30,55 -> csrc/fused_rope_kernel.cu), as one pass over `qkv` [total, 3, heads,
+ * head_dim] contiguous (slot 0 = Q, 1 = K, 2 = V); head_dim even, <= 256.
+ * The rotation: a head is head_dim / 2 pairs (x[2j], x[2j+1]); pair j < rot_pairs = 3 * num_freqs turns by the angle
+ * pos[a] * freqs[f], a = j / num_freqs, f = j % num_freqs, pos[a] = float(coord[a]) - origin[a] + bias (fp32, one rounding
+ * per operation); out = (x0 cos - x1 sin, x0 sin + x1 cos), `conjugate` = 1 negates sin (the inverse rotation).  Pairs
+ * j >= rot_pairs and the whole V slot pass through.  The reference's two conventions are two settings: fused_rope_qkv is
+ * origin = column minimum, bias = 1, freqs = theta; SparseRotaryPositionEmbedder is origin = NULL, bias = 0,
+ * freqs[i] = f0 / f1^(i / F).
+ *   wcn_rope_table                   table [total, 3 * num_freqs, 2] fp32 = (cos, sin), with the accurate sincosf.  `coords`
+ *                                    [total, 3] int32 (coords_float = 0) or fp32 (1); `origin` device float[3] or NULL (= 0);
+ *                                    `freqs` device float[num_freqs], 6 * num_freqs <= 256.
+ *   wcn_qk_prologue_supported        host-only: 1 if head_dim is even, 2..256, in_dtype is f32 / f16 / bf16 and out_dtype
+ *                                    f16 / bf16.
+ *   wcn_qk_prologue_workspace_bytes  host-only: the backward's workspace (fp32 partial sums of the gamma gradients).
+ *   wcn_qk_prologue_fwd              out [total, 3, heads, head_dim] (out_dtype: f16 / bf16; an f32 input is cast here).
+ *                                    gamma_q, gamma_k [heads, head_dim] fp32, both or neither: each (token, head) of Q and
+ *                                    K becomes x / max(|x|_2, 1e-12) * gamma[h] * sqrt(head_dim) in fp32, not rounded before
+ *                                    the rotation, and inv_norm [total, 2, heads] fp32 = 1 / max(|x|_2, 1e-12) is written for
+ *                                    the backward.  `table` NULL with rot_pairs = 0: no rotation.  Neither: a cast copy.
+ *   wcn_qk_prologue_bwd              dqkv [total, 3, heads, head_dim] (in_dtype) from dout (dout_dtype: f16 / bf16).  Without
+ *                                    gammas it is the forward on dout with conjugate = 1 (`qkv`, `inv_norm`, `dgamma_*`,
+ *                                    `workspace` unused).  With them: dy = un-rotated dout, u = gamma sqrt(D) dy,
+ *                                    xh = x inv_norm, dx = (u - xh (xh . u)) inv_norm (u * 1e12 where the norm was clamped),
+ *                                    dgamma_q / dgamma_k [heads, head_dim] fp32 = sum_t sqrt(D) xh dy through per-row-group
+ *                                    partial sums in `workspace` and a fixed-order second pass: no float atomics, two calls
+ *                                    give bit-identical dqkv and dgamma.
+ * 16-byte pieces per lane when head_dim is a multiple of 8 (f16 / bf16 on both sides) or 4 (an f32 side) and the buffers
+ * are 16-B aligned, one pair per lane otherwise.  Arguments are checked before any launch: a dtype outside the above, an odd
+ * head_dim or head_dim > 256 -> WCN_ERROR_UNSUPPORTED_CONFIG; negative sizes, heads < 1, 2 * rot_pairs > head_dim, one gamma
+ * without the other, total * 3 * heads > INT32_MAX, null pointers with total > 0, a buffer not aligned to one pair, a short
+ * workspace -> WCN_ERROR_INVALID_PARAMETERS; total == 0 -> WCN_SUCCESS without a launch. */
+int wcn_rope_table(const void* coords, int32_t coords_float, int64_t total, const float* origin, float bias,
+                   const float* freqs, int32_t num_freqs, float* table, wcn_stream_t stream);
+int wcn_qk_prologue_supported(int32_t head_dim, int32_t in_dtype, int32_t out_dtype);
+size_t wcn_qk_prologue_workspace_bytes(int64_t total, int32_t heads, int32_t head_dim);
+int wcn_qk_prologue_fwd(const void* qkv, int32_t in_dtype, int64_t total, int32_t heads, int32_t head_dim, const float* table,
+                        int32_t rot_pairs, int32_t conjugate, const float* gamma_q, const float* gamma_k, void* out,
+                        int32_t out_dtype, float* inv_norm, wcn_stream_t stream);
+int wcn_qk_prologue_bwd(const void* dout, int32_t dout_dtype, const void* qkv, int32_t in_dtype, int64_t total, int32_t heads,
+                        int32_t head_dim, const float* table, int32_t rot_pairs, const float* gamma_q, const float* gamma_k,
+                        const float* inv_norm, void* dqkv, float* dgamma_q, float* dgamma_k, void* workspace,
+                        size_t workspace_bytes, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

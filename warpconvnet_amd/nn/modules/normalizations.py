@@ -1,6 +1,7 @@
 """Normalisation modules over ``Geometry`` features (reference `nn/modules/normalizations.py:30-68`)."""
 from typing import Union
 
+import torch
 import torch.nn as nn
 from torch import Tensor
 
@@ -38,3 +39,17 @@ class BatchNorm(NormalizationBase):
 
     def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1):
         super().__init__(nn.BatchNorm1d(num_features, eps=eps, momentum=momentum))
+
+
+class MultiHeadRMSNorm(nn.Module):
+    """RMS norm per attention head (reference `nn/modules/normalizations.py:226-245`): ``x`` [..., heads, dim] ->
+    ``x / max(|x|_2, 1e-12) * gamma * sqrt(dim)`` in fp32, returned in the input dtype.  Called on its own this is plain
+    torch; ``SparseMultiHeadAttention`` hands ``gamma`` to the fused Q/K prologue kernel instead."""
+
+    def __init__(self, dim: int, heads: int):
+        super().__init__()
+        self.scale = dim ** 0.5
+        self.gamma = nn.Parameter(torch.ones(heads, dim))
+
+    def forward(self, x: Tensor) -> Tensor:
+        return (nn.functional.normalize(x.float(), dim=-1) * self.gamma * self.scale).to(x.dtype)
