@@ -715,6 +715,46 @@ int wcn_qk_prologue_bwd(const void* dout, int32_t dout_dtype, const void* qkv, i
                         const float* inv_norm, void* dqkv, float* dgamma_q, float* dgamma_k, void* workspace,
                         size_t workspace_bytes, wcn_stream_t stream);
 
+/* ---- adaLN modulation and gated residual of a sparse transformer block (ABI 8, additions only) ------------------------------
+ * The per-voxel glue of the reference's ModulatedSparseTransformerBlock (nn/modules/sparse_dit.py:108-123, a dozen
+ * element-wise torch passes per branch) as one streaming pass per direction.  With b = the segment of row t
+ * (cu[b] <= t < cu[b+1]; `cu` int32 [num_segs + 1] on the device, empty segments allowed, never read on the host):
+ *     x1 = x + h * gate[b]                            with `h` and `gate`   (NULL, NULL: x1 = x, nothing written)
+ *     y  = LN(x1) * (1 + scale[b]) + shift[b]         with `shift` and `scale` (NULL, NULL: no y)
+ * LN has no affine parameters, the biased variance and `eps`.  `x`, `h`, `x1`, `y` are [rows, channels] contiguous in
+ * `dtype` (f32 / f16 / bf16); `gate`, `shift`, `scale` are fp32 [num_segs, channels] views with the common row pitch
+ * `mod_ld` floats (chunks of one [num_segs, 6 * channels] tensor).  All arithmetic is fp32 with one rounding to the output
+ * dtype: y comes from the fp32 x1, not from its rounded value; the variance is two-pass (mean, then squared deviations).
+ *   wcn_adaln_supported        host-only: 1 if channels is a multiple of 8 in 8..2048 and dtype is f32 / f16 / bf16.
+ *   wcn_adaln_workspace_bytes  host-only: the backward's workspace, (ceil(rows / 64) + num_segs) * 3 * channels floats.
+ *   wcn_adaln_fwd              writes x1 (with h, gate), y and stats [rows, 2] fp32 = (mean, rstd) (with shift, scale).
+ *   wcn_adaln_bwd              `dy` (with `scale`, `stats` and the forward's `x`) selects the norm, `h` (with `gate`) the
+ *                              gated residual; `dx1` = the gradient that reaches x1 directly, or NULL (required without
+ *                              dy).  x1 = x + h gate[b] is formed again in fp32 (the forward's bits, not its rounded
+ *                              output), xhat = (x1 - mean) rstd, g = dy (1 + scale[b]):
+ *                                  dx = dx1 + rstd (g - mean_c(g) - xhat mean_c(g xhat))      (`dx` may be NULL without dy)
+ *                                  dh = dx gate[b],   dgate[b] = sum_{t in b} dx h,
+ *                                  dshift[b] = sum_{t in b} dy,   dscale[b] = sum_{t in b} dy xhat
+ *                              dgate / dshift / dscale fp32 [num_segs, channels] with the row pitch `dmod_ld`, zeros for a
+ *                              segment without rows.  The sums go through per-(64-row chunk, segment) partial slots in
+ *                              `workspace` and a fixed-order second pass: no float atomics, two calls give bit-identical
+ *                              results.
+ * Arguments are checked before any launch: channels / dtype outside the above -> WCN_ERROR_UNSUPPORTED_CONFIG; negative
+ * sizes, rows > INT32_MAX, neither use selected, one pointer of a pair without the other, a pointer the selected use needs
+ * missing, mod_ld / dmod_ld < channels, mod_ld not a multiple of 4, a short workspace, row buffers / mod views / workspace
+ * not 16-B aligned -> WCN_ERROR_INVALID_PARAMETERS.  rows == 0 or num_segs == 0 -> WCN_SUCCESS without a kernel (the
+ * backward still zero-fills dgate / dshift / dscale); the use is still told from the pointers, so a caller whose empty
+ * buffers have no address decides these cases itself. */
+int wcn_adaln_supported(int32_t channels, int32_t dtype);
+size_t wcn_adaln_workspace_bytes(int64_t rows, int64_t num_segs, int32_t channels);
+int wcn_adaln_fwd(const void* x, const void* h, const float* gate, const float* shift, const float* scale, int64_t mod_ld,
+                  const int32_t* cu, int64_t num_segs, int64_t rows, int32_t channels, float eps, int32_t dtype, void* x1,
+                  void* y, float* stats, wcn_stream_t stream);
+int wcn_adaln_bwd(const void* dx1, const void* dy, const void* x, const void* h, const float* gate, const float* scale,
+                  int64_t mod_ld, const float* stats, const int32_t* cu, int64_t num_segs, int64_t rows, int32_t channels,
+                  int32_t dtype, void* dx, void* dh, float* dgate, float* dshift, float* dscale, int64_t dmod_ld,
+                  void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,18 @@ SIGNATURES = {
         [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_adaln_supported": (c_int, [c_int32, c_int32]),
+    "wcn_adaln_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "wcn_adaln_fwd": (
+        c_int,
+        [c_void_p] * 5 + [c_int64, c_void_p, c_int64, c_int64, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p, c_void_p,
+                          c_void_p],
+    ),
+    "wcn_adaln_bwd": (
+        c_int,
+        [c_void_p] * 6 + [c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32] + [c_void_p] * 5 +
+        [c_int64, c_void_p, c_size_t, c_void_p],
+    ),
     "wcn_resample_pack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_void_p, c_void_p]),
     "wcn_resample_unpack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

@@ -1,0 +1,481 @@
+// adaln.hip - the per-voxel glue of an adaLN-modulated sparse transformer block (reference: nn/modules/sparse_dit.py:108-123
+// runs it as a dozen element-wise torch passes per branch: x.float(), the norm, the cast back, three t[batch_index] gathers
+// that write [T, C] copies of the per-batch vectors, 1 +, two multiplies, two adds).  One row-streaming kernel family per
+// direction, two compile-time switches:
+//   RES   x1 = x + h * gate[b]                         (the gated residual; x1 is written, rounded once)
+//   NORM  y  = LN(x1) * (1 + scale[b]) + shift[b]      (LN without affine parameters, biased variance, from the fp32 x1)
+// so that NORM alone opens a block, RES + NORM sits between the attention and the MLP, and RES alone closes it.  b is the
+// segment of the row: cu[b] <= t < cu[b+1], cu int32 [B + 1] on the device, empty segments allowed, never read on the host.
+// shift / scale / gate are fp32 [B, C] views with one row pitch (chunks of one [B, 6C] tensor).
+//
+// Launch shape.  A row is C / 8 pieces of 8 elements (one 16-B load of f16 / bf16, two of f32).  G = the power of two >=
+// min(C / 8, 64) lanes stand side by side on a row and hold it in registers, NCH = ceil(C / 8 / G) <= 4 pieces each; 64 / G
+// rows share a wave.  Sums over a row go across its G lanes with an xor butterfly (every lane ends with the same bits).
+// The variance is two-pass: the mean, then the sums of the deviations and of their squares - the first corrects the mean's
+// own rounding, which at |mean| >> sigma is what limits xhat.
+//   forward   the lane groups stride over the rows; writes stats [T, 2] = (mean, rstd) for the backward.
+//   backward  reads x, not the rounded x1 the forward wrote: x1 = x + h * gate[b] is formed again in fp32, so xhat is the
+//             forward's at the same bytes per element.  Lane group u owns the chunk of kAdaChunk consecutive rows u and
+//             keeps the column sums of dgate / dshift / dscale in registers.  Where the segment changes inside the chunk,
+//             and at its end, the sums go to the partial slot u + b: every (chunk, segment) pair with a row has its own
+//             slot, slots grow along the rows, and segment b
+//             owns the contiguous slots [cu[b] / R + b, (cu[b+1] - 1) / R + b].  adaln_final_kernel adds each segment's
+//             slots in a fixed order.  No float atomics, no zero-filled workspace: two runs are bit-identical.
+#include <limits.h>
+
+#include "wcn_common.h"
+
+namespace wcn {
+
+constexpr int kAdaThreads = 256;
+constexpr int kAdaChunk = 64;        // rows of one backward chunk
+constexpr int kAdaMaxChannels = 2048;
+constexpr int kAdaFwdBlocks = 4096;  // the forward's grid is capped here; its lane groups stride over the rows
+
+template <typename T> struct alignas(16) AdaVec8 { T v[8]; };
+
+template <typename T>
+__device__ __forceinline__ void ada_ld8(const T* __restrict__ p, float (&f)[8]) {
+  if constexpr (sizeof(T) == 4) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+  } else {
+    const AdaVec8<T> v = *reinterpret_cast<const AdaVec8<T>*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (float)v.v[e];
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void ada_st8(T* __restrict__ p, const float (&f)[8]) {
+  if constexpr (sizeof(T) == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
+    *reinterpret_cast<float4*>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
+  } else {
+    AdaVec8<T> v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v.v[e] = (T)f[e];
+    *reinterpret_cast<AdaVec8<T>*>(p) = v;
+  }
+}
+
+// sum over the G = 1 << glog lanes of a group; every lane of the group receives the same bits
+__device__ __forceinline__ float ada_group_sum(float v, int glog) {
+  for (int m = 0; m < glog; ++m) v += __shfl_xor(v, 1 << m);
+  return v;
+}
+
+struct AdaGeom {
+  int64_t rows;   // T
+  int64_t units;  // lane groups of the launch: the forward's stride over the rows, the backward's chunks
+  int64_t mod_ld;
+  int channels, num_segs, glog;
+  float eps;
+};
+
+template <typename T, int NCH, bool NORM, bool RES>
+__global__ __launch_bounds__(kAdaThreads) void adaln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ h,
+                                                                const float* __restrict__ gate, const float* __restrict__ shift,
+                                                                const float* __restrict__ scale, const int32_t* __restrict__ cu,
+                                                                T* __restrict__ x1, T* __restrict__ y,
+                                                                float* __restrict__ stats, const AdaGeom g) {
+  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
+  const int64_t unit = v >> g.glog;
+  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
+  const int C = g.channels, nvec = C >> 3;
+  const float fc = (float)C;
+
+  // every lane of a wave walks the same number of trips: the butterfly needs its partners
+  for (int64_t t0 = 0; t0 < g.rows; t0 += g.units) {
+    const int64_t t = t0 + unit;
+    const bool act = t < g.rows;
+    const int b = act ? last_offset_not_above(cu, g.num_segs, t) : 0;
+    float f[NCH][8];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (act && c < nvec) {
+        const int64_t at = t * C + c * 8;
+        ada_ld8(x + at, f[k]);
+        if constexpr (RES) {
+          float hv[8], gv[8];
+          ada_ld8(h + at, hv);
+          ada_ld8(gate + b * g.mod_ld + c * 8, gv);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[k][e] += hv[e] * gv[e];
+          ada_st8(x1 + at, f[k]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += f[k][e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[k][e] = 0.f;
+      }
+    }
+    if constexpr (NORM) {
+      float mean = ada_group_sum(s, g.glog) / fc;  // a division: a constant row's mean is the constant, exactly
+      float sd = 0.f, ss = 0.f;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        const bool m = act && gl + k * G < nvec;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = m ? f[k][e] - mean : 0.f;
+          f[k][e] = d;
+          sd += d;
+          ss += d * d;
+        }
+      }
+      const float delta = ada_group_sum(sd, g.glog) / fc;  // what the rounded mean missed
+      ss = ada_group_sum(ss, g.glog) / fc;
+      const float var = fmaxf(ss - delta * delta, 0.f);
+      const float rstd = 1.0f / sqrtf(var + g.eps);
+      mean += delta;
+      if (act && gl == 0) *reinterpret_cast<float2*>(stats + 2 * t) = make_float2(mean, rstd);
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        const int c = gl + k * G;
+        if (act && c < nvec) {
+          float sc[8], sh[8], o[8];
+          ada_ld8(scale + b * g.mod_ld + c * 8, sc);
+          ada_ld8(shift + b * g.mod_ld + c * 8, sh);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - delta) * rstd * (1.0f + sc[e]) + sh[e];
+          ada_st8(y + t * C + c * 8, o);
+        }
+      }
+    }
+  }
+}
+
+// partial [slots][3][C]: 0 = dgate, 1 = dshift, 2 = dscale
+template <typename T, int NCH, bool NORM, bool RES>
+__global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restrict__ dx1, const T* __restrict__ dy,
+                                                                const T* __restrict__ x, const T* __restrict__ h,
+                                                                const float* __restrict__ gate, const float* __restrict__ scale,
+                                                                const float* __restrict__ stats, const int32_t* __restrict__ cu,
+                                                                T* __restrict__ dx, T* __restrict__ dh,
+                                                                float* __restrict__ partial, const AdaGeom g) {
+  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
+  const int64_t unit = v >> g.glog;
+  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
+  const int C = g.channels, nvec = C >> 3;
+  const float inv_c = 1.0f / (float)C;
+  const bool live = unit < g.units;
+  const bool has_dx1 = dx1 != nullptr;  // the same in every lane
+
+  float a_gate[RES ? NCH : 1][8], a_shift[NORM ? NCH : 1][8], a_scale[NORM ? NCH : 1][8];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if constexpr (RES) a_gate[k][e] = 0.f;
+      if constexpr (NORM) { a_shift[k][e] = 0.f; a_scale[k][e] = 0.f; }
+    }
+
+  // the lane's sums -> slot unit + seg, then zero
+  auto flush = [&](int seg) {
+    float* p = partial + (unit + seg) * 3 * (int64_t)C;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (c < nvec) {
+        if constexpr (RES) ada_st8(p + c * 8, a_gate[k]);
+        if constexpr (NORM) { ada_st8(p + C + c * 8, a_shift[k]); ada_st8(p + 2 * C + c * 8, a_scale[k]); }
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if constexpr (RES) a_gate[k][e] = 0.f;
+        if constexpr (NORM) { a_shift[k][e] = 0.f; a_scale[k][e] = 0.f; }
+      }
+    }
+  };
+
+  int b = -1;              // segment of the rows summed so far; -1: none yet
+  int64_t next = 0;        // cu[b + 1], or never
+#pragma unroll 1
+  for (int i = 0; i < kAdaChunk; ++i) {
+    const int64_t t = unit * kAdaChunk + i;
+    const bool act = live && t < g.rows;
+    if (act) {
+      int nb = b;
+      if (nb < 0) {
+        nb = last_offset_not_above(cu, g.num_segs, t);
+        next = nb + 1 < g.num_segs ? (int64_t)cu[nb + 1] : LLONG_MAX;
+      } else {
+        while (t >= next) {  // ends at the last segment at the latest
+          ++nb;
+          next = nb + 1 < g.num_segs ? (int64_t)cu[nb + 1] : LLONG_MAX;
+        }
+      }
+      if (nb != b) {
+        if (b >= 0) flush(b);
+        b = nb;
+      }
+    }
+    const int bb = b < 0 ? 0 : b;
+    float gd[NCH][8], xh[NCH][8];  // g = dy (1 + scale); xhat
+    float hk[NORM && RES ? NCH : 1][8];
+    float mean = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
+    if constexpr (NORM) {
+      if (act) {
+        const float2 st = *reinterpret_cast<const float2*>(stats + 2 * t);
+        mean = st.x;
+        rstd = st.y;
+      }
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        const int c = gl + k * G;
+        if (act && c < nvec) {
+          const int64_t at = t * C + c * 8;
+          float xv[8], sc[8];
+          ada_ld8(dy + at, gd[k]);
+          ada_ld8(x + at, xv);
+          if constexpr (RES) {  // what LN read is the forward's fp32 x1, formed again with the same operations
+            float gv[8];
+            ada_ld8(h + at, hk[k]);
+            ada_ld8(gate + bb * g.mod_ld + c * 8, gv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xv[e] += hk[k][e] * gv[e];
+          }
+          ada_ld8(scale + bb * g.mod_ld + c * 8, sc);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float d = gd[k][e];
+            xh[k][e] = (xv[e] - mean) * rstd;
+            a_shift[k][e] += d;
+            a_scale[k][e] += d * xh[k][e];
+            gd[k][e] = d * (1.0f + sc[e]);
+            s1 += gd[k][e];
+            s2 += gd[k][e] * xh[k][e];
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { gd[k][e] = 0.f; xh[k][e] = 0.f; }
+        }
+      }
+      s1 = ada_group_sum(s1, g.glog) * inv_c;
+      s2 = ada_group_sum(s2, g.glog) * inv_c;
+    }
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (act && c < nvec) {
+        const int64_t at = t * C + c * 8;
+        float r[8];
+        if (has_dx1) {
+          ada_ld8(dx1 + at, r);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) r[e] = 0.f;
+        }
+        if constexpr (NORM) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) r[e] += rstd * (gd[k][e] - s1 - xh[k][e] * s2);
+        }
+        if (NORM || dx != nullptr) ada_st8(dx + at, r);
+        if constexpr (RES) {
+          float hv[8], gv[8], o[8];
+          if constexpr (NORM) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) hv[e] = hk[k][e];
+          } else {
+            ada_ld8(h + at, hv);
+          }
+          ada_ld8(gate + bb * g.mod_ld + c * 8, gv);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            o[e] = r[e] * gv[e];
+            a_gate[k][e] += r[e] * hv[e];
+          }
+          ada_st8(dh + at, o);
+        }
+      }
+    }
+  }
+  if (b >= 0) flush(b);
+}
+
+// second level of the column sums: 32 columns x 8 slot slices per workgroup, one segment and one of the three sums each;
+// both levels in a fixed order.  A segment without rows gets zeros.
+__global__ __launch_bounds__(256) void adaln_final_kernel(const float* __restrict__ partial, const int32_t* __restrict__ cu,
+                                                          int64_t rows, int C, float* __restrict__ dgate,
+                                                          float* __restrict__ dshift, float* __restrict__ dscale,
+                                                          int64_t out_ld) {
+  __shared__ float s[8][33];
+  const int which = blockIdx.z;
+  float* out = which == 0 ? dgate : which == 1 ? dshift : dscale;
+  if (out == nullptr) return;  // the whole workgroup
+  const int64_t b = blockIdx.x;
+  const int cl = threadIdx.x & 31, q = threadIdx.x >> 5;
+  const int col = blockIdx.y * 32 + cl;
+  int64_t lo = cu[b], hi = cu[b + 1];
+  lo = lo < 0 ? 0 : lo > rows ? rows : lo;
+  hi = hi < 0 ? 0 : hi > rows ? rows : hi;
+  float sum = 0.f;
+  if (col < C && hi > lo) {
+    const int64_t first = lo / kAdaChunk + b, last = (hi - 1) / kAdaChunk + b;
+    for (int64_t sl = first + q; sl <= last; sl += 8) sum += partial[(sl * 3 + which) * C + col];
+  }
+  s[q][cl] = sum;
+  __syncthreads();
+  if (q == 0 && col < C) {
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) tot += s[i][cl];
+    out[b * out_ld + col] = tot;
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+static bool ada_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+static AdaGeom ada_geom(int64_t rows, int64_t num_segs, int channels, int64_t mod_ld, float eps) {
+  AdaGeom g;
+  const int nvec = channels / 8;
+  g.glog = 0;
+  while ((1 << g.glog) < nvec && g.glog < 6) ++g.glog;
+  g.rows = rows;
+  g.units = 0;
+  g.mod_ld = mod_ld;
+  g.channels = channels;
+  g.num_segs = (int)num_segs;
+  g.eps = eps;
+  return g;
+}
+static int ada_nch(const AdaGeom& g) { return (int)ceil_div(g.channels / 8, 1 << g.glog); }
+
+// Shared argument checks.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing to launch.
+static int ada_check(int64_t rows, int64_t num_segs, int32_t channels, int32_t dtype, bool norm, bool res, bool paired,
+                     int64_t mod_ld) {
+  if (rows < 0 || num_segs < 0) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!wcn_adaln_supported(channels, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if ((!norm && !res) || !paired) return WCN_ERROR_INVALID_PARAMETERS;
+  if (rows > INT32_MAX || num_segs > INT32_MAX) return WCN_ERROR_INVALID_PARAMETERS;  // cu is int32
+  if (mod_ld < channels || mod_ld % 4 != 0) return WCN_ERROR_INVALID_PARAMETERS;      // 16-B pieces of the fp32 rows
+  return rows == 0 || num_segs == 0 ? 1 : WCN_SUCCESS;
+}
+
+template <typename T, bool NORM, bool RES>
+static int ada_fwd_t(const void* x, const void* h, const float* gate, const float* shift, const float* scale,
+                     const int32_t* cu, void* x1, void* y, float* stats, AdaGeom g, hipStream_t s) {
+  const int64_t per_block = kAdaThreads >> g.glog;
+  int64_t blocks = ceil_div(g.rows, per_block);
+  if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
+  g.units = blocks * per_block;
+#define WCN_ADA_FWD(NCH)                                                                                               \
+  hipLaunchKernelGGL((adaln_fwd_kernel<T, NCH, NORM, RES>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)x, \
+                     (const T*)h, gate, shift, scale, cu, (T*)x1, (T*)y, stats, g)
+  switch (ada_nch(g)) {
+    case 1: WCN_ADA_FWD(1); break;
+    case 2: WCN_ADA_FWD(2); break;
+    case 3: WCN_ADA_FWD(3); break;
+    default: WCN_ADA_FWD(4); break;
+  }
+#undef WCN_ADA_FWD
+  return launch_status();
+}
+
+template <typename T, bool NORM, bool RES>
+static int ada_bwd_t(const void* dx1, const void* dy, const void* x, const void* h, const float* gate, const float* scale,
+                     const float* stats, const int32_t* cu, void* dx, void* dh, float* partial, AdaGeom g, hipStream_t s) {
+  g.units = ceil_div(g.rows, kAdaChunk);
+  const int64_t blocks = ceil_div(g.units, kAdaThreads >> g.glog);
+#define WCN_ADA_BWD(NCH)                                                                                                  \
+  hipLaunchKernelGGL((adaln_bwd_kernel<T, NCH, NORM, RES>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)dx1, \
+                     (const T*)dy, (const T*)x, (const T*)h, gate, scale, stats, cu, (T*)dx, (T*)dh, partial, g)
+  switch (ada_nch(g)) {
+    case 1: WCN_ADA_BWD(1); break;
+    case 2: WCN_ADA_BWD(2); break;
+    case 3: WCN_ADA_BWD(3); break;
+    default: WCN_ADA_BWD(4); break;
+  }
+#undef WCN_ADA_BWD
+  return launch_status();
+}
+
+// the three uses of one dtype
+#define WCN_ADA_USES(FN, T, ...)                                      \
+  (norm && res ? FN<T, true, true>(__VA_ARGS__)                       \
+               : norm ? FN<T, true, false>(__VA_ARGS__) : FN<T, false, true>(__VA_ARGS__))
+#define WCN_ADA_DTYPES(FN, ...)                                                           \
+  (dtype == WCN_F32 ? WCN_ADA_USES(FN, float, __VA_ARGS__)                                \
+                    : dtype == WCN_F16 ? WCN_ADA_USES(FN, _Float16, __VA_ARGS__) : WCN_ADA_USES(FN, __bf16, __VA_ARGS__))
+
+}  // namespace wcn
+
+using namespace wcn;
+
+int wcn_adaln_supported(int32_t channels, int32_t dtype) {
+  return channels >= 8 && channels % 8 == 0 && channels <= kAdaMaxChannels &&
+                 (dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16)
+             ? 1
+             : 0;
+}
+
+size_t wcn_adaln_workspace_bytes(int64_t rows, int64_t num_segs, int32_t channels) {
+  if (rows <= 0 || num_segs <= 0 || channels < 1) return 0;
+  return (size_t)(ceil_div(rows, kAdaChunk) + num_segs) * 3 * (size_t)channels * sizeof(float);
+}
+
+int wcn_adaln_fwd(const void* x, const void* h, const float* gate, const float* shift, const float* scale, int64_t mod_ld,
+                  const int32_t* cu, int64_t num_segs, int64_t rows, int32_t channels, float eps, int32_t dtype, void* x1,
+                  void* y, float* stats, wcn_stream_t stream) {
+  const bool res = h != nullptr || gate != nullptr, norm = shift != nullptr || scale != nullptr;
+  const bool paired = (h != nullptr) == (gate != nullptr) && (shift != nullptr) == (scale != nullptr);
+  int st = ada_check(rows, num_segs, channels, dtype, norm, res, paired, mod_ld);
+  if ((st == WCN_SUCCESS || st == 1) && !(eps >= 0.f)) st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!x || !cu || (res && !x1) || (norm && (!y || !stats))) st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!ada_aligned(x, 16) || !ada_aligned(h, 16) || !ada_aligned(gate, 16) || !ada_aligned(shift, 16) ||
+             !ada_aligned(scale, 16) || !ada_aligned(x1, 16) || !ada_aligned(y, 16) || !ada_aligned(stats, 8) ||
+             !ada_aligned(cu, 4))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
+  const AdaGeom g = ada_geom(rows, num_segs, channels, mod_ld, eps);
+  return WCN_ADA_DTYPES(ada_fwd_t, x, h, gate, shift, scale, cu, x1, y, stats, g, (hipStream_t)stream);
+}
+
+int wcn_adaln_bwd(const void* dx1, const void* dy, const void* x, const void* h, const float* gate, const float* scale,
+                  int64_t mod_ld, const float* stats, const int32_t* cu, int64_t num_segs, int64_t rows, int32_t channels,
+                  int32_t dtype, void* dx, void* dh, float* dgate, float* dshift, float* dscale, int64_t dmod_ld,
+                  void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
+  const bool res = h != nullptr || gate != nullptr, norm = dy != nullptr || scale != nullptr;
+  const bool paired = (h != nullptr) == (gate != nullptr) && (dy != nullptr) == (scale != nullptr);
+  int st = ada_check(rows, num_segs, channels, dtype, norm, res, paired, mod_ld);
+  if ((st == WCN_SUCCESS || st == 1) &&
+      (dmod_ld < channels || workspace_bytes < wcn_adaln_workspace_bytes(rows, num_segs, channels)))
+    st = WCN_ERROR_INVALID_PARAMETERS;
+  if ((st == WCN_SUCCESS || st == 1) && num_segs > 0 && ((res && !dgate) || (norm && (!dshift || !dscale))))
+    st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!cu || !workspace || (!norm && !dx1) || (norm && (!x || !stats || !dx)) || (res && !dh)) st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!ada_aligned(dx1, 16) || !ada_aligned(dy, 16) || !ada_aligned(x, 16) || !ada_aligned(h, 16) ||
+             !ada_aligned(gate, 16) || !ada_aligned(scale, 16) || !ada_aligned(stats, 8) || !ada_aligned(cu, 4) ||
+             !ada_aligned(dx, 16) || !ada_aligned(dh, 16) || !ada_aligned(dgate, 4) || !ada_aligned(dshift, 4) ||
+             !ada_aligned(dscale, 4) || !ada_aligned(workspace, 16))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (st == 1) {  // no rows: every segment's sums are zero, and no kernel runs
+    if (num_segs > 0) {
+      float* outs[3] = {res ? dgate : nullptr, norm ? dshift : nullptr, norm ? dscale : nullptr};
+      for (float* o : outs)
+        if (o && hipMemset2DAsync(o, (size_t)dmod_ld * sizeof(float), 0, (size_t)channels * sizeof(float), (size_t)num_segs,
+                                  s) != hipSuccess)
+          return WCN_ERROR_KERNEL_EXECUTION;
+    }
+    return WCN_SUCCESS;
+  }
+  if (st != WCN_SUCCESS) return st;
+  const AdaGeom g = ada_geom(rows, num_segs, channels, mod_ld, 0.f);
+  float* partial = (float*)workspace;
+  st = WCN_ADA_DTYPES(ada_bwd_t, dx1, dy, x, h, gate, scale, stats, cu, dx, dh, partial, g, s);
+  if (st != WCN_SUCCESS) return st;
+  hipLaunchKernelGGL(adaln_final_kernel, dim3((unsigned)num_segs, (unsigned)ceil_div(channels, 32), 3), dim3(256), 0, s,
+                     (const float*)partial, cu, rows, channels, res ? dgate : nullptr, norm ? dshift : nullptr,
+                     norm ? dscale : nullptr, dmod_ld);
+  return launch_status();
+}

@@ -2,12 +2,13 @@ from .attention import BatchedLinear, FeedForward, LayerNorm, PatchAttention, Tr
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
 from .mlp import MLPBlock
-from .normalizations import BatchNorm, MultiHeadRMSNorm, NormalizationBase
+from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
 from .point_conv import PointConv
 from .prune import SparsePrune
 from .rope import VoxelRotaryPositionalEmbeddings, suggest_voxel_rope_base
 from .sequential import Sequential
 from .sparse_attention import SparseMultiHeadAttention, SparseRotaryPositionEmbedder
+from .sparse_dit import ModulatedSparseTransformerBlock, SparseFeedForwardNet
 from .sparse_conv import SparseConv2d, SparseConv3d, SpatiallySparseConv
 from .sparse_pool import GlobalPool, SparseMaxPool, SparseMinPool, SparsePool, SparseUnpool
 from .sparse_resample import SparseChannel2Spatial, SparseDownsample, SparseSpatial2Channel, SparseSubdivide, SparseUpsample
@@ -19,4 +20,4 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "BatchedLinear", "FeedForward", "LayerNorm", "PatchAttention", "TransformerBlock",
            "SparseChannel2Spatial", "SparseDownsample", "SparsePrune", "SparseSpatial2Channel", "SparseSubdivide", "SparseUpsample",
            "MultiHeadRMSNorm", "SparseMultiHeadAttention", "SparseRotaryPositionEmbedder", "VoxelRotaryPositionalEmbeddings",
-           "suggest_voxel_rope_base"]
+           "suggest_voxel_rope_base", "LayerNorm32", "ModulatedSparseTransformerBlock", "SparseFeedForwardNet"]

@@ -53,3 +53,12 @@ class MultiHeadRMSNorm(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         return (nn.functional.normalize(x.float(), dim=-1) * self.gamma * self.scale).to(x.dtype)
+
+
+class LayerNorm32(nn.LayerNorm):
+    """``torch.nn.LayerNorm`` that always computes in fp32, then casts back (reference
+    `nn/modules/normalizations.py:196-201`).  Plain torch; ``ModulatedSparseTransformerBlock`` keeps its two as attributes
+    and runs their math inside the fused adaLN kernels."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        return super().forward(x.float()).to(x.dtype)
