@@ -755,6 +755,49 @@ int wcn_adaln_bwd(const void* dx1, const void* dy, const void* x, const void* h,
                   int32_t dtype, void* dx, void* dh, float* dgate, float* dshift, float* dscale, int64_t dmod_ld,
                   void* workspace, size_t workspace_bytes, wcn_stream_t stream);
 
+/* ---- LayerNorm (+ affine) (+ SiLU) and the channel spread / fold of the sparse U-Net blocks (ABI 9, additions only) ---------
+ * The per-voxel glue of the reference's residual blocks (nn/modules/sparse_unet.py: norm(x.float()).to(dtype) -> silu between
+ * two convolutions, five or six [N, C] torch passes per site; h + repeat_interleave(x) / h + reshape(...).mean(-1) at the end)
+ * as one streaming pass per site and direction.
+ *     xhat = (x - mean) * rstd           biased variance, `eps`, fp32, two-pass (mean, then squared deviations)
+ *     z    = xhat * weight + bias        with `weight` and `bias` (NULL, NULL: z = xhat)
+ *     y    = act ? z * sigmoid(z) : z    `act` 0 = none, 1 = SiLU; rounded once, to `dtype`
+ * `x`, `y`, `dy`, `dx` are [rows, channels] contiguous in `dtype` (f32 / f16 / bf16); `weight`, `bias` fp32 [channels].
+ *   wcn_ln_act_supported        host-only: the domain of wcn_adaln_supported (channels a multiple of 8 in 8..2048).
+ *   wcn_ln_act_workspace_bytes  host-only: the backward's workspace with weight / bias, ceil(rows / 64) * 2 * channels floats
+ *                               (without the pair the backward needs none and looks at neither `workspace` argument).
+ *   wcn_ln_act_fwd              writes y and stats [rows, 2] fp32 = (mean, rstd).
+ *   wcn_ln_act_bwd              z is formed again in fp32 from x and stats (not read back from a rounded y), s = sigmoid(z):
+ *                                   g  = dy * (act ? s (1 + z (1 - s)) : 1),   gw = g * weight
+ *                                   dx = rstd (gw - mean_c(gw) - xhat mean_c(gw xhat))
+ *                                   dweight = sum_rows g xhat,   dbias = sum_rows g      fp32 [channels], NULL without the pair
+ *                               The column sums go through one partial slot per 64-row chunk in `workspace` and a fixed-order
+ *                               second pass: no float atomics, no zero-filled workspace, two calls give bit-identical results.
+ * The two skip paths, each the other's gradient (fp32 arithmetic, one rounding, no workspace; `h` may be NULL):
+ *   wcn_channel_spread   out[n, c * r + j] = alpha * x[n, c] (+ h[n, c * r + j])        x [rows, cx]        -> out [rows, cx * r]
+ *   wcn_channel_fold     out[n, c] = alpha * sum_{j < g} x[n, c * g + j] (+ h[n, c])    x [rows, cout * g]  -> out [rows, cout]
+ * The decoder's skip is spread(x, h, r, 1) with the x-gradient fold(dout, NULL, r, 1); the encoder's is fold(x, h, g, 1 / g)
+ * with spread(dout, NULL, g, 1 / g); dh is dout itself.  16-B accesses where the narrow side's channel count (cx / cout) is
+ * a multiple of 8, r / g is 1, 2, 4 or 8 and the pointers are 16-B aligned; any channel count >= 1 and any r, g >= 1 go
+ * through an element kernel.
+ * Arguments are checked before any launch: a dtype or (LN) channel count outside the above, or a spread / fold row wider than
+ * INT32_MAX channels -> WCN_ERROR_UNSUPPORTED_CONFIG; negative sizes (cx, cout, r, g < 1), rows > INT32_MAX, an `act` other
+ * than 0 / 1, one of weight / bias without the other, a required pointer missing with rows > 0 (dweight / dbias / workspace are
+ * required with the pair), a short workspace, a non-finite (or negative) eps, a non-finite alpha, LN buffers not 16-B aligned
+ * -> WCN_ERROR_INVALID_PARAMETERS.  rows == 0 -> WCN_SUCCESS without a launch: nothing is written, a caller that wants zero
+ * dweight / dbias fills them itself. */
+int wcn_ln_act_supported(int32_t channels, int32_t dtype);
+size_t wcn_ln_act_workspace_bytes(int64_t rows, int32_t channels);
+int wcn_ln_act_fwd(const void* x, const float* weight, const float* bias, int64_t rows, int32_t channels, float eps,
+                   int32_t act, int32_t dtype, void* y, float* stats, wcn_stream_t stream);
+int wcn_ln_act_bwd(const void* dy, const void* x, const float* weight, const float* bias, const float* stats, int64_t rows,
+                   int32_t channels, int32_t act, int32_t dtype, void* dx, float* dweight, float* dbias, void* workspace,
+                   size_t workspace_bytes, wcn_stream_t stream);
+int wcn_channel_spread(const void* x, const void* h, int64_t rows, int32_t cx, int32_t r, float alpha, int32_t dtype,
+                       void* out, wcn_stream_t stream);
+int wcn_channel_fold(const void* x, const void* h, int64_t rows, int32_t cout, int32_t g, float alpha, int32_t dtype,
+                     void* out, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

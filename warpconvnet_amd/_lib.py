@@ -274,6 +274,14 @@ SIGNATURES = {
         [c_void_p] * 6 + [c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32] + [c_void_p] * 5 +
         [c_int64, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_ln_act_supported": (c_int, [c_int32, c_int32]),
+    "wcn_ln_act_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "wcn_ln_act_fwd": (c_int, [c_void_p] * 3 + [c_int64, c_int32, ctypes.c_float, c_int32, c_int32, c_void_p, c_void_p,
+                                                 c_void_p]),
+    "wcn_ln_act_bwd": (c_int, [c_void_p] * 5 + [c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "wcn_channel_spread": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p,
+                                   c_void_p]),
+    "wcn_channel_fold": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p]),
     "wcn_resample_pack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_void_p, c_void_p]),
     "wcn_resample_unpack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

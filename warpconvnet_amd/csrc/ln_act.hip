@@ -1,0 +1,496 @@
+// ln_act.hip - the per-voxel glue of the sparse U-Net residual blocks (reference: nn/modules/sparse_unet.py runs, between
+// two convolutions, x.float() -> layer_norm -> .to(dtype) -> silu as five or six [N, C] passes, and closes with
+// h + repeat_interleave(x) or h + reshape(...).mean(-1)).  One row-streaming pass per site and direction:
+//   LN (+ affine) (+ SiLU)   y = act(LN(x) * weight + bias), biased variance, fp32, rounded once; the launch shape and the
+//                            two-pass variance of adaln.hip (ada_row.h: G lanes hold a row in registers, <= 4 pieces each).
+//     forward   the lane groups stride over the rows; writes stats [rows, 2] = (mean, rstd).
+//     backward  z = xhat * weight + bias is formed again in fp32 from x and stats, never read back from the rounded y.
+//               Lane group u owns the kAdaChunk rows of chunk u, keeps the column sums of dweight / dbias in registers and
+//               writes them once to the partial slot u; ln_act_final_kernel adds the slots in a fixed order.  No float
+//               atomics, no zero-filled workspace: two runs are bit-identical.
+//   spread   out[n, c * r + j] = alpha * x[n, c] (+ h[n, c * r + j])        the decoder's skip, and the fold's gradient
+//   fold     out[n, c] = alpha * sum_{j < g} x[n, c * g + j] (+ h[n, c])    the encoder's skip, and the spread's gradient
+//     One lane per 8-element piece of an output row, 16-B accesses, where the narrow side's channel count is a multiple of
+//     8 and r / g is 1, 2, 4 or 8 (what halving / doubling widths around a factor-2 resample give; every index into the
+//     lane's registers is then a compile-time constant, so nothing goes to scratch); one lane per output element otherwise.
+#include <limits.h>
+
+#include <cmath>
+
+#include "ada_row.h"
+
+namespace wcn {
+
+struct LnGeom {
+  int64_t rows;
+  int64_t units;  // lane groups of the launch: the forward's stride over the rows, the backward's chunks
+  int channels, glog;
+  float eps;
+};
+
+// hardware exp2 and reciprocal (1 ulp each): z -> -inf gives 1 / inf = 0, never a NaN
+__device__ __forceinline__ float ln_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
+
+template <typename T, int NCH, bool AFFINE, bool SILU>
+__global__ __launch_bounds__(kAdaThreads) void ln_act_fwd_kernel(const T* __restrict__ x, const float* __restrict__ weight,
+                                                                 const float* __restrict__ bias, T* __restrict__ y,
+                                                                 float* __restrict__ stats, const LnGeom g) {
+  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
+  const int64_t unit = v >> g.glog;
+  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
+  const int C = g.channels, nvec = C >> 3;
+  const float fc = (float)C;
+
+  // every lane of a wave walks the same number of trips: the butterfly needs its partners
+  for (int64_t t0 = 0; t0 < g.rows; t0 += g.units) {
+    const int64_t t = t0 + unit;
+    const bool act = t < g.rows;
+    float f[NCH][8];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (act && c < nvec) {
+        ada_ld8(x + t * C + c * 8, f[k]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += f[k][e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[k][e] = 0.f;
+      }
+    }
+    float mean = ada_group_sum(s, g.glog) / fc;  // a division: a constant row's mean is the constant, exactly
+    float sd = 0.f, ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const bool m = act && gl + k * G < nvec;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = m ? f[k][e] - mean : 0.f;
+        f[k][e] = d;
+        sd += d;
+        ss += d * d;
+      }
+    }
+    const float delta = ada_group_sum(sd, g.glog) / fc;  // what the rounded mean missed
+    ss = ada_group_sum(ss, g.glog) / fc;
+    const float var = fmaxf(ss - delta * delta, 0.f);
+    const float rstd = 1.0f / sqrtf(var + g.eps);
+    mean += delta;
+    if (act && gl == 0) *reinterpret_cast<float2*>(stats + 2 * t) = make_float2(mean, rstd);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (act && c < nvec) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - delta) * rstd;
+        if constexpr (AFFINE) {
+          float w[8], b[8];
+          ada_ld8(weight + c * 8, w);
+          ada_ld8(bias + c * 8, b);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = o[e] * w[e] + b[e];
+        }
+        if constexpr (SILU) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] *= ln_sigmoid(o[e]);
+        }
+        ada_st8(y + t * C + c * 8, o);
+      }
+    }
+  }
+}
+
+// partial [units][2][C]: 0 = dweight, 1 = dbias
+template <typename T, int NCH, bool AFFINE, bool SILU>
+__global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                 const float* __restrict__ weight,
+                                                                 const float* __restrict__ bias,
+                                                                 const float* __restrict__ stats, T* __restrict__ dx,
+                                                                 float* __restrict__ partial, const LnGeom g) {
+  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
+  const int64_t unit = v >> g.glog;
+  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
+  const int C = g.channels, nvec = C >> 3;
+  const float inv_c = 1.0f / (float)C;
+  const bool live = unit < g.units;
+
+  float a_w[AFFINE ? NCH : 1][8], a_b[AFFINE ? NCH : 1][8];
+  if constexpr (AFFINE) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { a_w[k][e] = 0.f; a_b[k][e] = 0.f; }
+  }
+
+#pragma unroll 1
+  for (int i = 0; i < kAdaChunk; ++i) {
+    const int64_t t = unit * kAdaChunk + i;
+    const bool act = live && t < g.rows;
+    float gd[NCH][8], xh[NCH][8];  // g * weight; xhat
+    float mean = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
+    if (act) {
+      const float2 st = *reinterpret_cast<const float2*>(stats + 2 * t);
+      mean = st.x;
+      rstd = st.y;
+    }
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (act && c < nvec) {
+        const int64_t at = t * C + c * 8;
+        float xv[8], w[8], b[8];
+        ada_ld8(dy + at, gd[k]);
+        ada_ld8(x + at, xv);
+        if constexpr (AFFINE) {
+          ada_ld8(weight + c * 8, w);
+          ada_ld8(bias + c * 8, b);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float d = gd[k][e];
+          xh[k][e] = (xv[e] - mean) * rstd;
+          if constexpr (SILU) {
+            float z = xh[k][e];
+            if constexpr (AFFINE) z = z * w[e] + b[e];
+            const float sg = ln_sigmoid(z);
+            d *= sg * (1.0f + z * (1.0f - sg));
+          }
+          if constexpr (AFFINE) {
+            a_b[k][e] += d;
+            a_w[k][e] += d * xh[k][e];
+            d *= w[e];
+          }
+          gd[k][e] = d;
+          s1 += d;
+          s2 += d * xh[k][e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { gd[k][e] = 0.f; xh[k][e] = 0.f; }
+      }
+    }
+    s1 = ada_group_sum(s1, g.glog) * inv_c;
+    s2 = ada_group_sum(s2, g.glog) * inv_c;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = gl + k * G;
+      if (act && c < nvec) {
+        float r[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = rstd * (gd[k][e] - s1 - xh[k][e] * s2);
+        ada_st8(dx + t * C + c * 8, r);
+      }
+    }
+  }
+  if constexpr (AFFINE) {
+    if (live) {  // every chunk has a row, and every column of its slot a lane
+      float* p = partial + unit * 2 * (int64_t)C;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        const int c = gl + k * G;
+        if (c < nvec) {
+          ada_st8(p + c * 8, a_w[k]);
+          ada_st8(p + C + c * 8, a_b[k]);
+        }
+      }
+    }
+  }
+}
+
+// second level of the column sums: 32 columns x 32 slot slices per workgroup, one of the two sums each; both levels in a
+// fixed order
+constexpr int kLnFinalSlices = 32;
+
+__global__ __launch_bounds__(32 * kLnFinalSlices) void ln_act_final_kernel(const float* __restrict__ partial, int64_t slots,
+                                                                           int C, float* __restrict__ dweight,
+                                                                           float* __restrict__ dbias) {
+  __shared__ float s[kLnFinalSlices][33];
+  const int which = blockIdx.y;
+  float* out = which == 0 ? dweight : dbias;
+  const int cl = threadIdx.x & 31, q = threadIdx.x >> 5;
+  const int col = blockIdx.x * 32 + cl;
+  float sum = 0.f;
+  if (col < C)
+    for (int64_t sl = q; sl < slots; sl += kLnFinalSlices) sum += partial[(sl * 2 + which) * C + col];
+  s[q][cl] = sum;
+  __syncthreads();
+  if (q == 0 && col < C) {
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < kLnFinalSlices; ++i) tot += s[i][cl];
+    out[col] = tot;
+  }
+}
+
+// ---- channel spread / fold -------------------------------------------------------------------------------------------------
+struct SkipGeom {
+  int64_t rows;
+  int64_t units;  // lane groups of the launch: the stride over the rows
+  int cout;       // channels of an output row
+  int ratio;      // r or g (the element kernels; the piece kernels have it as R)
+  int glog;
+  float alpha;
+};
+
+template <typename T> __device__ __forceinline__ float skip_ld(const T* p) { return (float)*p; }
+
+// One lane per 8-element piece of an output row; G = 1 << glog lanes side by side on a row, striding over its pieces.
+// FOLD = false: the piece [8p, 8p + 8) of out reads the 8 / R elements of x from 8p / R on.
+// FOLD = true:  it reads the R pieces of x from piece p * R on; output e is the sum of the R elements from e * R on.
+template <typename T, int R, bool FOLD>
+__global__ __launch_bounds__(kAdaThreads) void channel_pieces_kernel(const T* __restrict__ x, const T* __restrict__ h,
+                                                                     T* __restrict__ out, const SkipGeom g) {
+  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
+  const int64_t unit = v >> g.glog;
+  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
+  const int npiece = g.cout >> 3;
+  const int64_t cx = FOLD ? (int64_t)g.cout * R : g.cout / R;  // channels of a row of x
+  for (int64_t t = unit; t < g.rows; t += g.units) {
+    for (int p = gl; p < npiece; p += G) {
+      float o[8];
+      if constexpr (FOLD) {
+        float f[R][8];
+#pragma unroll
+        for (int k = 0; k < R; ++k) ada_ld8(x + t * cx + ((int64_t)p * R + k) * 8, f[k]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float s = 0.f;
+#pragma unroll
+          for (int j = 0; j < R; ++j) s += f[(e * R + j) >> 3][(e * R + j) & 7];
+          o[e] = g.alpha * s;
+        }
+      } else if constexpr (R == 1) {
+        ada_ld8(x + t * cx + p * 8, o);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] *= g.alpha;
+      } else {
+        float f[8 / R];
+        const T* src = x + t * cx + p * (8 / R);
+#pragma unroll
+        for (int k = 0; k < 8 / R; ++k) f[k] = g.alpha * skip_ld(src + k);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = f[e / R];
+      }
+      const int64_t at = t * g.cout + p * 8;
+      if (h != nullptr) {  // the same in every lane
+        float hv[8];
+        ada_ld8(h + at, hv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] += hv[e];
+      }
+      ada_st8(out + at, o);
+    }
+  }
+}
+
+// One lane per output element: any channel count, any ratio, any alignment.
+template <typename T, bool FOLD>
+__global__ __launch_bounds__(kAdaThreads) void channel_elements_kernel(const T* __restrict__ x, const T* __restrict__ h,
+                                                                       T* __restrict__ out, const SkipGeom g) {
+  const int64_t total = g.rows * g.cout;
+  const int64_t stride = (int64_t)gridDim.x * kAdaThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x; i < total; i += stride) {
+    const int64_t t = i / g.cout;
+    const int c = (int)(i - t * g.cout);
+    float o;
+    if constexpr (FOLD) {
+      const T* src = x + (t * g.cout + c) * g.ratio;  // a row of x has cout * g channels
+      float s = 0.f;
+      for (int j = 0; j < g.ratio; ++j) s += skip_ld(src + j);
+      o = g.alpha * s;
+    } else {
+      o = g.alpha * skip_ld(x + t * (g.cout / g.ratio) + c / g.ratio);
+    }
+    if (h != nullptr) o += skip_ld(h + i);
+    out[i] = (T)o;
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+static bool ln_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+static LnGeom ln_geom(int64_t rows, int channels, float eps) {
+  LnGeom g;
+  const int nvec = channels / 8;
+  g.glog = 0;
+  while ((1 << g.glog) < nvec && g.glog < 6) ++g.glog;
+  g.rows = rows;
+  g.units = 0;
+  g.channels = channels;
+  g.eps = eps;
+  return g;
+}
+static int ln_nch(const LnGeom& g) { return (int)ceil_div(g.channels / 8, 1 << g.glog); }
+
+// Shared argument checks.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing to launch.
+static int ln_check(int64_t rows, int32_t channels, int32_t dtype, int32_t act, const float* weight, const float* bias) {
+  if (rows < 0) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!wcn_ln_act_supported(channels, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (rows > INT32_MAX || (act != 0 && act != 1)) return WCN_ERROR_INVALID_PARAMETERS;
+  if ((weight != nullptr) != (bias != nullptr)) return WCN_ERROR_INVALID_PARAMETERS;
+  return rows == 0 ? 1 : WCN_SUCCESS;
+}
+
+template <typename T, bool AFFINE, bool SILU>
+static int ln_fwd_t(const void* x, const float* weight, const float* bias, void* y, float* stats, LnGeom g, hipStream_t s) {
+  const int64_t per_block = kAdaThreads >> g.glog;
+  int64_t blocks = ceil_div(g.rows, per_block);
+  if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
+  g.units = blocks * per_block;
+#define WCN_LN_FWD(NCH)                                                                                                   \
+  hipLaunchKernelGGL((ln_act_fwd_kernel<T, NCH, AFFINE, SILU>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)x, \
+                     weight, bias, (T*)y, stats, g)
+  switch (ln_nch(g)) {
+    case 1: WCN_LN_FWD(1); break;
+    case 2: WCN_LN_FWD(2); break;
+    case 3: WCN_LN_FWD(3); break;
+    default: WCN_LN_FWD(4); break;
+  }
+#undef WCN_LN_FWD
+  return launch_status();
+}
+
+template <typename T, bool AFFINE, bool SILU>
+static int ln_bwd_t(const void* dy, const void* x, const float* weight, const float* bias, const float* stats, void* dx,
+                    float* partial, LnGeom g, hipStream_t s) {
+  g.units = ceil_div(g.rows, kAdaChunk);
+  const int64_t blocks = ceil_div(g.units, kAdaThreads >> g.glog);
+#define WCN_LN_BWD(NCH)                                                                                                    \
+  hipLaunchKernelGGL((ln_act_bwd_kernel<T, NCH, AFFINE, SILU>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)dy, \
+                     (const T*)x, weight, bias, stats, (T*)dx, partial, g)
+  switch (ln_nch(g)) {
+    case 1: WCN_LN_BWD(1); break;
+    case 2: WCN_LN_BWD(2); break;
+    case 3: WCN_LN_BWD(3); break;
+    default: WCN_LN_BWD(4); break;
+  }
+#undef WCN_LN_BWD
+  return launch_status();
+}
+
+// the four uses of one dtype
+#define WCN_LN_USES(FN, T, ...)                                                                \
+  (affine ? (act ? FN<T, true, true>(__VA_ARGS__) : FN<T, true, false>(__VA_ARGS__))           \
+          : (act ? FN<T, false, true>(__VA_ARGS__) : FN<T, false, false>(__VA_ARGS__)))
+#define WCN_LN_DTYPES(FN, ...)                                                          \
+  (dtype == WCN_F32 ? WCN_LN_USES(FN, float, __VA_ARGS__)                               \
+                    : dtype == WCN_F16 ? WCN_LN_USES(FN, _Float16, __VA_ARGS__) : WCN_LN_USES(FN, __bf16, __VA_ARGS__))
+
+template <typename T, bool FOLD>
+static int skip_t(const void* x, const void* h, void* out, SkipGeom g, bool pieces, hipStream_t s) {
+  const T *xp = (const T*)x, *hp = (const T*)h;
+  T* op = (T*)out;
+  if (!pieces) {
+    int64_t blocks = ceil_div(g.rows * g.cout, kAdaThreads);
+    if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
+    hipLaunchKernelGGL((channel_elements_kernel<T, FOLD>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, xp, hp, op, g);
+    return launch_status();
+  }
+  const int npiece = g.cout / 8;
+  g.glog = 0;
+  while ((1 << g.glog) < npiece && g.glog < 6) ++g.glog;
+  const int64_t per_block = kAdaThreads >> g.glog;
+  int64_t blocks = ceil_div(g.rows, per_block);
+  if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
+  g.units = blocks * per_block;
+#define WCN_SKIP(R) \
+  hipLaunchKernelGGL((channel_pieces_kernel<T, R, FOLD>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, xp, hp, op, g)
+  switch (g.ratio) {
+    case 1: WCN_SKIP(1); break;
+    case 2: WCN_SKIP(2); break;
+    case 4: WCN_SKIP(4); break;
+    default: WCN_SKIP(8); break;
+  }
+#undef WCN_SKIP
+  return launch_status();
+}
+
+// narrow = the channel count of the narrow side (x of a spread, out of a fold); the output row has `cout` channels
+static int skip_run(bool fold, const void* x, const void* h, int64_t rows, int64_t narrow, int64_t ratio, float alpha,
+                    int32_t dtype, void* out, hipStream_t s) {
+  if (rows < 0 || narrow < 1 || ratio < 1) return WCN_ERROR_INVALID_PARAMETERS;
+  if (dtype != WCN_F32 && dtype != WCN_F16 && dtype != WCN_BF16) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (narrow * ratio > INT32_MAX) return WCN_ERROR_UNSUPPORTED_CONFIG;  // a row's channels are counted in int32
+  if (rows > INT32_MAX || !std::isfinite(alpha)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (rows == 0) return WCN_SUCCESS;
+  if (!x || !out) return WCN_ERROR_INVALID_PARAMETERS;
+  const size_t el = dtype == WCN_F32 ? 4 : 2;
+  if (!ln_aligned(x, el) || !ln_aligned(h, el) || !ln_aligned(out, el)) return WCN_ERROR_INVALID_PARAMETERS;
+  SkipGeom g;
+  g.rows = rows;
+  g.units = 0;
+  g.cout = (int)(fold ? narrow : narrow * ratio);
+  g.ratio = (int)ratio;
+  g.glog = 0;
+  g.alpha = alpha;
+  // 16-B pieces: every row of both sides starts on the 16-B grid, and a piece's indices are compile-time constants
+  const bool pieces = narrow % 8 == 0 && (ratio == 1 || ratio == 2 || ratio == 4 || ratio == 8) && ln_aligned(x, 16) &&
+                      ln_aligned(h, 16) && ln_aligned(out, 16);
+#define WCN_SKIP_DTYPE(T) (fold ? skip_t<T, true>(x, h, out, g, pieces, s) : skip_t<T, false>(x, h, out, g, pieces, s))
+  return dtype == WCN_F32 ? WCN_SKIP_DTYPE(float) : dtype == WCN_F16 ? WCN_SKIP_DTYPE(_Float16) : WCN_SKIP_DTYPE(__bf16);
+#undef WCN_SKIP_DTYPE
+}
+
+}  // namespace wcn
+
+using namespace wcn;
+
+int wcn_ln_act_supported(int32_t channels, int32_t dtype) { return wcn_adaln_supported(channels, dtype); }
+
+size_t wcn_ln_act_workspace_bytes(int64_t rows, int32_t channels) {
+  if (rows <= 0 || channels < 1) return 0;
+  return (size_t)ceil_div(rows, kAdaChunk) * 2 * (size_t)channels * sizeof(float);
+}
+
+int wcn_ln_act_fwd(const void* x, const float* weight, const float* bias, int64_t rows, int32_t channels, float eps,
+                   int32_t act, int32_t dtype, void* y, float* stats, wcn_stream_t stream) {
+  int st = ln_check(rows, channels, dtype, act, weight, bias);
+  if ((st == WCN_SUCCESS || st == 1) && !(eps >= 0.f && std::isfinite(eps))) st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!x || !y || !stats) st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!ln_aligned(x, 16) || !ln_aligned(weight, 16) || !ln_aligned(bias, 16) || !ln_aligned(y, 16) ||
+             !ln_aligned(stats, 8))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
+  const bool affine = weight != nullptr;
+  const LnGeom g = ln_geom(rows, channels, eps);
+  return WCN_LN_DTYPES(ln_fwd_t, x, weight, bias, y, stats, g, (hipStream_t)stream);
+}
+
+int wcn_ln_act_bwd(const void* dy, const void* x, const float* weight, const float* bias, const float* stats, int64_t rows,
+                   int32_t channels, int32_t act, int32_t dtype, void* dx, float* dweight, float* dbias, void* workspace,
+                   size_t workspace_bytes, wcn_stream_t stream) {
+  const bool affine = weight != nullptr;
+  int st = ln_check(rows, channels, dtype, act, weight, bias);
+  if ((st == WCN_SUCCESS || st == 1) && affine && workspace_bytes < wcn_ln_act_workspace_bytes(rows, channels))
+    st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!dy || !x || !stats || !dx || (affine && (!dweight || !dbias || !workspace))) st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!ln_aligned(dy, 16) || !ln_aligned(x, 16) || !ln_aligned(weight, 16) || !ln_aligned(bias, 16) ||
+             !ln_aligned(stats, 8) || !ln_aligned(dx, 16) || !ln_aligned(dweight, 4) || !ln_aligned(dbias, 4) ||
+             (affine && !ln_aligned(workspace, 16)))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
+  hipStream_t s = (hipStream_t)stream;
+  const LnGeom g = ln_geom(rows, channels, 0.f);
+  float* partial = affine ? (float*)workspace : nullptr;
+  st = WCN_LN_DTYPES(ln_bwd_t, dy, x, weight, bias, stats, dx, partial, g, s);
+  if (st != WCN_SUCCESS || !affine) return st;
+  hipLaunchKernelGGL(ln_act_final_kernel, dim3((unsigned)ceil_div(channels, 32), 2), dim3(32 * kLnFinalSlices), 0, s,
+                     (const float*)partial, ceil_div(rows, kAdaChunk), channels, dweight, dbias);
+  return launch_status();
+}
+
+int wcn_channel_spread(const void* x, const void* h, int64_t rows, int32_t cx, int32_t r, float alpha, int32_t dtype,
+                       void* out, wcn_stream_t stream) {
+  return skip_run(false, x, h, rows, cx, r, alpha, dtype, out, (hipStream_t)stream);
+}
+
+int wcn_channel_fold(const void* x, const void* h, int64_t rows, int32_t cout, int32_t g, float alpha, int32_t dtype,
+                     void* out, wcn_stream_t stream) {
+  return skip_run(true, x, h, rows, cout, g, alpha, dtype, out, (hipStream_t)stream);
+}

@@ -9,6 +9,9 @@ from .rope import VoxelRotaryPositionalEmbeddings, suggest_voxel_rope_base
 from .sequential import Sequential
 from .sparse_attention import SparseMultiHeadAttention, SparseRotaryPositionEmbedder
 from .sparse_dit import ModulatedSparseTransformerBlock, SparseFeedForwardNet
+from .sparse_convnext import SparseConvNeXtBlock3d
+from .sparse_unet import (SparseChannelToSpatialResBlock3d, SparseSpatialToChannelResBlock3d, SparseUNetDecoderStages,
+                          SparseUNetEncoderStages)
 from .sparse_conv import SparseConv2d, SparseConv3d, SpatiallySparseConv
 from .sparse_pool import GlobalPool, SparseMaxPool, SparseMinPool, SparsePool, SparseUnpool
 from .sparse_resample import SparseChannel2Spatial, SparseDownsample, SparseSpatial2Channel, SparseSubdivide, SparseUpsample
@@ -20,4 +23,6 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "BatchedLinear", "FeedForward", "LayerNorm", "PatchAttention", "TransformerBlock",
            "SparseChannel2Spatial", "SparseDownsample", "SparsePrune", "SparseSpatial2Channel", "SparseSubdivide", "SparseUpsample",
            "MultiHeadRMSNorm", "SparseMultiHeadAttention", "SparseRotaryPositionEmbedder", "VoxelRotaryPositionalEmbeddings",
-           "suggest_voxel_rope_base", "LayerNorm32", "ModulatedSparseTransformerBlock", "SparseFeedForwardNet"]
+           "suggest_voxel_rope_base", "LayerNorm32", "ModulatedSparseTransformerBlock", "SparseFeedForwardNet",
+           "SparseConvNeXtBlock3d", "SparseChannelToSpatialResBlock3d", "SparseSpatialToChannelResBlock3d",
+           "SparseUNetDecoderStages", "SparseUNetEncoderStages"]
