@@ -626,6 +626,50 @@ int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, cons
                         float softmax_scale, int32_t dtype, void* dqkv, void* workspace, size_t workspace_bytes,
                         wcn_stream_t stream);
 
+/* ---- varlen attention with separate Q and K/V operands: cross-attention (ABI 10, additions only) ------------------------------
+ * The attention core of the reference's SparseMultiHeadAttention(type="cross") (nn/modules/sparse_dit_attention.py:265-315 calls
+ * flash_attn.flash_attn_varlen_func / flash_attn_varlen_kvpacked_func); same contract without dropout, causal mask or window,
+ * and the same kernels as the packed form above (which calls them with the three slots of its one tensor).
+ * `q` [total_q] rows of heads * head_dim elements, `q_stride` elements apart; `k`, `v` [total_k] rows with ONE common stride
+ * `kv_stride` (a kv-packed [total_k, 2, heads, head_dim] tensor: v = k + heads * head_dim, kv_stride = 2 * heads * head_dim).
+ * `cu_q`, `cu_k` int32 [num_seqs + 1], device: sequence s is the queries [cu_q[s], cu_q[s+1]) against the keys
+ * [cu_k[s], cu_k[s+1]).  `max_seqlen_q` / `max_seqlen_k` >= every length of their side (they size the grids; the host never
+ * reads cu_*).  `out`, `dout` [total_q, heads, head_dim] and `lse` [total_q, heads] fp32 are contiguous; `dq` has the row
+ * stride `dq_stride`, `dk` and `dv` ONE common stride `dkv_stride`.  Rows outside every sequence are not written; every row
+ * of every sequence is written exactly once in each of out, lse, dq, dk, dv.
+ * Empty sides: a query of a sequence with no key gets out = 0 and lse = -inf, and dq = 0 in the backward; the keys of a
+ * sequence with no query get dk = dv = 0 (exact zeros, never NaN).
+ * The dK/dV pass is one wave per (sequence, 32-key block, head) sweeping the sequence's query blocks.  `q_splits` > 1 cuts that
+ * sweep into q_splits contiguous shares, each wave writing fp32 partials [q_splits, total_k, 2, heads, head_dim] into the
+ * workspace; a second kernel adds the splits in the fixed order 0 .. q_splits - 1, scales, casts and stores.  q_splits = 1
+ * stores directly and touches no partials.  Any q_splits gives bit-identical results across calls; dq does not depend on it.
+ *   wcn_attn_varlen_kv_splits           host-only: the split count the library chooses for q_splits = 0, >= 1, from these
+ *                                       numbers alone: enough splits for about 4096 waves, at least 16 query blocks of
+ *                                       max_seqlen_q per split, at most 16 splits, and never more than fit a partial workspace
+ *                                       of 256 MiB at num_seqs * max_seqlen_k keys and head_dim 64.
+ *   wcn_attn_varlen_kv_workspace_bytes  host-only: delta fp32 [total_q, heads] = 4 * total_q * heads bytes, plus, when
+ *                                       q_splits > 1, the partials 4 * q_splits * total_k * 2 * heads * head_dim bytes.
+ *   wcn_attn_varlen_kv_fwd              out, lse.
+ *   wcn_attn_varlen_kv_bwd              dq, dk, dv from dout / out and the forward's lse.  q_splits = 0: choose as
+ *                                       wcn_attn_varlen_kv_splits does; the workspace must hold what
+ *                                       wcn_attn_varlen_kv_workspace_bytes reports for the count in use.
+ * Arguments are checked before any launch: unsupported head_dim / dtype -> WCN_ERROR_UNSUPPORTED_CONFIG; heads < 1, negative
+ * sizes or max_seqlen_*, total_q or total_k > INT32_MAX, a stride that is not a multiple of 8 elements or shorter than a row,
+ * a base pointer (q, k, v, out, dout, dq, dk, dv, workspace) that is not 16-byte aligned, null pointers with rows to process,
+ * q_splits < 0, a short workspace -> WCN_ERROR_INVALID_PARAMETERS. */
+int32_t wcn_attn_varlen_kv_splits(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads);
+size_t wcn_attn_varlen_kv_workspace_bytes(int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t q_splits);
+int wcn_attn_varlen_kv_fwd(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                           const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                           int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                           int32_t dtype, void* out, float* lse, wcn_stream_t stream);
+int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                           const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                           int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                           int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                           void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
+                           wcn_stream_t stream);
+
 /* ---- sparse resampling over a CHILD TABLE (ABI 6, additions only) -----------------------------------------------------------
  * Space-to-channel / channel-to-space / subdivide / up- and down-sampling / prune of sparse VAEs and generative decoders
  * (reference, pure torch: nn/modules/sparse_resample.py:44-287, nn/modules/prune.py, nn/functional/sparse_ops.py:33-65).

@@ -249,6 +249,19 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_float,
          c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_attn_varlen_kv_splits": (c_int32, [c_int64, c_int32, c_int32, c_int32]),
+    "wcn_attn_varlen_kv_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    "wcn_attn_varlen_kv_fwd": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
+         c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p, c_void_p],
+    ),
+    "wcn_attn_varlen_kv_bwd": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+         c_int64, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+         c_int32, c_void_p, c_size_t, c_void_p],
+    ),
     "wcn_rope_table": (c_int, [c_void_p, c_int32, c_int64, c_void_p, ctypes.c_float, c_void_p, c_int32, c_void_p, c_void_p]),
     "wcn_qk_prologue_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_qk_prologue_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),

@@ -19,6 +19,16 @@
 //   dQ           one wave per (sequence, 32-query block, head) sweeps the key blocks: S^T, dP^T as in the forward,
 //                dQ^T += K^T dS^T (K^T from an LDS image).
 //   delta        rowsum(dO * O) per (token, head) into the caller's fp32 workspace, before the two sweeps.
+// Operands.  The kernels take Q, K and V as separate row pointers: q rows with stride q_stride, k and v rows with one
+// common stride kv_stride (elements), and two boundary arrays: sequence s is queries [cu_q[s], cu_q[s+1]) against keys
+// [cu_k[s], cu_k[s+1]) (cross-attention: voxel queries against a context).  The packed entry points pass the three slots
+// of one [T, 3, H, D] tensor with q_stride = kv_stride = 3 H D and cu_q = cu_k.  out / dout / lse / delta are contiguous
+// [Tq, H, D] / [Tq, H].  An empty side is defined, not NaN: a query with no key gets out = 0, lse = -inf, dq = 0; the
+// keys of a sequence with no query get dk = dv = 0.
+// Split dK/dV sweep.  With few long query sequences (tens of thousands of voxels against ~1000 context tokens) the dK/dV
+// pass has only nblk_k * H waves per sequence, each sweeping every query block.  With q_splits > 1 an item is (sequence,
+// key block, split, head): split j sweeps its contiguous share of the query blocks and writes unscaled fp32 partials to
+// part [q_splits, total_k, 2, H, D]; attn_dkdv_reduce_kernel sums them in the order 0 .. q_splits - 1, scales, casts.
 // D in {16, 32, 64}: D / 16 k-steps per score product, one (D <= 32) or two 32-row halves of d per output product
 // (D = 16 computes 16 rows it drops; the bound at that size is the exp and the softmax VALU work, not the MFMA).
 #include "wcn_common.h"
@@ -56,19 +66,21 @@ constexpr float kLn2 = 0.6931471805599453f;
 // Row (within its 32-row half) of accumulator register i of lane half h: (i & 3) + 8 (i >> 2) + 4 h.
 __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
-// The work item of a flat id: (sequence, block, head); false when the block starts past the sequence's end.
+// The work item of a flat id: (sequence, block, head).  The caller skips a block that starts past its side's end.
 struct AttnItem {
-  int64_t beg;
-  int len, b0, hd;
+  int64_t beg_q, beg_k;
+  int len_q, len_k, b0, hd;
 };
-__device__ __forceinline__ bool attn_item(int64_t id, int nblk, int heads, const int32_t* __restrict__ cu, AttnItem& it) {
+__device__ __forceinline__ void attn_item(int64_t id, int nblk, int heads, const int32_t* __restrict__ cu_q,
+                                          const int32_t* __restrict__ cu_k, AttnItem& it) {
   it.hd = (int)(id % heads);
   const int64_t t = id / heads;
   const int64_t seq = t / nblk;
   it.b0 = (int)(t % nblk) * kAttnBlock;
-  it.beg = cu[seq];
-  it.len = cu[seq + 1] - (int)it.beg;
-  return it.b0 < it.len;
+  it.beg_q = cu_q[seq];
+  it.len_q = cu_q[seq + 1] - (int)it.beg_q;
+  it.beg_k = cu_k[seq];
+  it.len_k = cu_k[seq + 1] - (int)it.beg_k;
 }
 
 // 8 consecutive elements d0 .. d0+7 of one head's slice of a row, or zeros when the row is outside the sequence.
@@ -150,48 +162,72 @@ __device__ __forceinline__ void store_dcol(T* __restrict__ dst, const a_f32x16* 
     }
 }
 
+// Q, K, V of a call as the kernels read them: separate row pointers, two strides (elements), two boundary arrays.
+template <typename T>
+struct AttnOperands {
+  const T *q, *k, *v;
+  int64_t q_stride, kv_stride;
+  const int32_t *cu_q, *cu_k;
+  int heads;
+};
+
+// Stores rows of d of this lane's column as fp32 (the partials of a split dK/dV sweep): runs of 4 consecutive d.
+template <int D>
+__device__ __forceinline__ void store_dcol_f32(float* __restrict__ dst, const a_f32x16* acc, int h) {
+#pragma unroll
+  for (int mb = 0; mb < (D + 31) / 32; ++mb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = 32 * mb + 8 * g + 4 * h;
+      if (d < D)
+        *reinterpret_cast<float4*>(dst + d) =
+            make_float4(acc[mb][4 * g], acc[mb][4 * g + 1], acc[mb][4 * g + 2], acc[mb][4 * g + 3]);
+    }
+}
+
 // ---- forward --------------------------------------------------------------------------------------------------------
 template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_fwd_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ cu,
-                                                      int64_t items, int nblk, int heads, float c2, T* __restrict__ out,
-                                                      float* __restrict__ lse) {
+__global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnOperands<T> a, int64_t items, int nblk, float c2,
+                                                      T* __restrict__ out, float* __restrict__ lse) {
   typedef typename AFrag<T>::type frag;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
   __shared__ __attribute__((aligned(16))) T vt[NMB * 32 * kAttnPitch];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int64_t pitch = 3LL * heads * D;
+  const int heads = a.heads;
+  const int64_t qp = a.q_stride, kp = a.kv_stride;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    if (!attn_item(id, nblk, heads, cu, w)) continue;
-    const T* q = qkv + w.beg * pitch + (int64_t)w.hd * D;
-    const T* k = q + (int64_t)heads * D;
-    const T* v = k + (int64_t)heads * D;
+    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    if (w.b0 >= w.len_q) continue;
+    const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
+    const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
     frag qf[NS];
 #pragma unroll
-    for (int s = 0; s < NS; ++s) qf[s] = load8<T>(q, pitch, w.b0 + r, w.len, 16 * s + 8 * h);
+    for (int s = 0; s < NS; ++s) qf[s] = load8<T>(q, qp, w.b0 + r, w.len_q, 16 * s + 8 * h);
     a_f32x16 acc[NMB];
 #pragma unroll
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[mb][i] = 0.f;
     float m = -INFINITY, l = 0.f;
-    for (int k0 = 0; k0 < w.len; k0 += kAttnBlock) {
+    for (int k0 = 0; k0 < w.len_k; k0 += kAttnBlock) {
       a_f32x16 st;
 #pragma unroll
       for (int i = 0; i < 16; ++i) st[i] = 0.f;
 #pragma unroll
-      for (int s = 0; s < NS; ++s) st = AFrag<T>::mfma(load8<T>(k, pitch, k0 + r, w.len, 16 * s + 8 * h), qf[s], st);
+      for (int s = 0; s < NS; ++s) st = AFrag<T>::mfma(load8<T>(k, kp, k0 + r, w.len_k, 16 * s + 8 * h), qf[s], st);
       __syncthreads();  // the previous tile's reads of vt are done
-      stage_transposed<T, D>(vt, v, pitch, k0, w.len);
+      stage_transposed<T, D>(vt, v, kp, k0, w.len_k);
       float x[16];
       float mx = -INFINITY;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        x[i] = k0 + acc_row(i, h) < w.len ? st[i] * c2 : -INFINITY;
+        x[i] = k0 + acc_row(i, h) < w.len_k ? st[i] * c2 : -INFINITY;
         mx = fmaxf(mx, x[i]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mn = fmaxf(m, mx);  // finite: key k0 is inside the sequence
+      const float mn = fmaxf(m, mx);  // finite: key k0 is inside the sequence's keys
       const float alpha = __builtin_amdgcn_exp2f(m - mn);
       float ls = 0.f;
 #pragma unroll
@@ -215,10 +251,13 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const T* __restrict__ qkv,
       }
     }
     const int row = w.b0 + r;
-    if (row < w.len) {
-      const int64_t t = w.beg + row;
-      store_dcol<T, D>(out + (t * heads + w.hd) * D, acc, 1.f / l, h);
-      if (h == 0) lse[t * heads + w.hd] = (m + __log2f(l)) * kLn2;
+    if (row < w.len_q) {
+      // l > 0 whenever the sequence has a key (the row maximum contributes exp2(0) = 1).  No key: the accumulator is
+      // still zero and is stored as exact zeros, lse = -inf.
+      const bool any = w.len_k > 0;
+      const int64_t t = w.beg_q + row;
+      store_dcol<T, D>(out + (t * heads + w.hd) * D, acc, any ? 1.f / l : 0.f, h);
+      if (h == 0) lse[t * heads + w.hd] = any ? (m + __log2f(l)) * kLn2 : -INFINITY;
     }
   }
 }
@@ -242,12 +281,14 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ d
   delta[i] = acc;
 }
 
-// dK, dV of one (sequence, 32-key block, head).
-template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_bwd_dkdv_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+// dK, dV of one (sequence, 32-key block, head) - or, with SPLIT, of one share of that item's query blocks: item ids then
+// are (sequence, key block, split, head) and the unscaled sums go to part [q_splits, total_k, 2, H, D] in fp32.
+template <typename T, int D, bool SPLIT>
+__global__ __launch_bounds__(64) void attn_bwd_dkdv_kernel(const AttnOperands<T> a, const T* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
-                                                           const int32_t* __restrict__ cu, int64_t items, int nblk, int heads,
-                                                           float c2, float scale, T* __restrict__ dqkv) {
+                                                           int64_t items, int nblk, float c2, float scale,
+                                                           T* __restrict__ dk_out, T* __restrict__ dv_out, int64_t dkv_stride,
+                                                           int q_splits, int64_t total_k, float* __restrict__ part) {
   typedef typename AFrag<T>::type frag;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
   __shared__ __attribute__((aligned(16))) T qt[NMB * 32 * kAttnPitch];
@@ -255,35 +296,52 @@ __global__ __launch_bounds__(64) void attn_bwd_dkdv_kernel(const T* __restrict__
   __shared__ __attribute__((aligned(16))) float s_lse[kAttnBlock];
   __shared__ __attribute__((aligned(16))) float s_del[kAttnBlock];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int64_t pitch = 3LL * heads * D, opitch = (int64_t)heads * D;
+  const int heads = a.heads;
+  const int64_t qp = a.q_stride, kp = a.kv_stride, opitch = (int64_t)heads * D;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    if (!attn_item(id, nblk, heads, cu, w)) continue;
-    const T* q = qkv + w.beg * pitch + (int64_t)w.hd * D;
-    const T* k = q + (int64_t)heads * D;
-    const T* v = k + (int64_t)heads * D;
-    const T* dO = dout + w.beg * opitch + (int64_t)w.hd * D;
+    int split = 0;
+    if (SPLIT) {
+      const int64_t t = id / heads;
+      split = (int)(t % q_splits);
+      attn_item((t / q_splits) * heads + id % heads, nblk, heads, a.cu_q, a.cu_k, w);
+    } else {
+      attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    }
+    if (w.b0 >= w.len_k) continue;
+    // the query rows this wave sweeps: all of them, or split's share of the 32-row blocks (an empty share stores zeros)
+    int q_beg = 0, q_end = w.len_q;
+    if (SPLIT) {
+      const int64_t nq = (w.len_q + kAttnBlock - 1) / kAttnBlock, per = (nq + q_splits - 1) / q_splits;
+      const int64_t lo = split * per * kAttnBlock, hi = (split + 1) * per * kAttnBlock;
+      q_beg = (int)(lo < w.len_q ? lo : w.len_q);
+      q_end = (int)(hi < w.len_q ? hi : w.len_q);
+    }
+    const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
+    const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* dO = dout + w.beg_q * opitch + (int64_t)w.hd * D;
     const int key = w.b0 + r;
     frag kf[NS], vf[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      kf[s] = load8<T>(k, pitch, key, w.len, 16 * s + 8 * h);
-      vf[s] = load8<T>(v, pitch, key, w.len, 16 * s + 8 * h);
+      kf[s] = load8<T>(k, kp, key, w.len_k, 16 * s + 8 * h);
+      vf[s] = load8<T>(v, kp, key, w.len_k, 16 * s + 8 * h);
     }
     a_f32x16 dk[NMB], dv[NMB];
 #pragma unroll
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) dk[mb][i] = dv[mb][i] = 0.f;
-    for (int q0 = 0; q0 < w.len; q0 += kAttnBlock) {
+    for (int q0 = q_beg; q0 < q_end; q0 += kAttnBlock) {
       a_f32x16 sc, dp;
       frag qf[NS], df[NS];
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[i] = dp[i] = 0.f;
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        qf[s] = load8<T>(q, pitch, q0 + r, w.len, 16 * s + 8 * h);
-        df[s] = load8<T>(dO, opitch, q0 + r, w.len, 16 * s + 8 * h);
+        qf[s] = load8<T>(q, qp, q0 + r, w.len_q, 16 * s + 8 * h);
+        df[s] = load8<T>(dO, opitch, q0 + r, w.len_q, 16 * s + 8 * h);
         sc = AFrag<T>::mfma(qf[s], kf[s], sc);
         dp = AFrag<T>::mfma(df[s], vf[s], dp);
       }
@@ -291,15 +349,21 @@ __global__ __launch_bounds__(64) void attn_bwd_dkdv_kernel(const T* __restrict__
       stage_frags<T, D>(qt, qf, r, h);
       stage_frags<T, D>(dot, df, r, h);
       {
+        // this sequence has a key (b0 < len_k), so the forward's lse of its queries is finite; the test keeps an lse of
+        // -inf (a caller's own buffer) out of the subtraction below all the same
         const int qr = q0 + r;
-        const bool ok = qr < w.len;
-        const int64_t t = w.beg + qr;
-        if (h == 0) s_lse[r] = ok ? lse[t * heads + w.hd] * kLog2e : 0.f;
-        else s_del[r] = ok ? delta[t * heads + w.hd] : 0.f;
+        const bool ok = qr < w.len_q;
+        const int64_t t = w.beg_q + qr;
+        if (h == 0) {
+          const float L = ok ? lse[t * heads + w.hd] : 0.f;
+          s_lse[r] = L > -INFINITY ? L * kLog2e : INFINITY;  // +inf: p = exp2(-inf) = 0
+        } else {
+          s_del[r] = ok ? delta[t * heads + w.hd] : 0.f;
+        }
       }
       __syncthreads();
-      // Rows of sc / dp are queries, the lane's column is its key.  Query rows past the end carry Q = dO = 0, lse =
-      // delta = 0: p = 1, dS = 0, and their dO^T / Q^T columns are zero, so they add nothing.
+      // Rows of sc / dp are queries, the lane's column is its key.  Query rows past len_q carry Q = dO = 0, lse =
+      // delta = 0: p = 1, dS = 0, and their dO^T / Q^T columns are zero, so they add nothing.  Keys past len_k: p = 0.
       float p[16], ds[16];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -309,7 +373,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkdv_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = 4 * g + e;
-          p[i] = key < w.len ? __builtin_amdgcn_exp2f(sc[i] * c2 - Lv[e]) : 0.f;
+          p[i] = key < w.len_k ? __builtin_amdgcn_exp2f(sc[i] * c2 - Lv[e]) : 0.f;
           ds[i] = p[i] * (dp[i] - Ev[e]);
         }
       }
@@ -323,65 +387,106 @@ __global__ __launch_bounds__(64) void attn_bwd_dkdv_kernel(const T* __restrict__
         }
       }
     }
-    if (key < w.len) {
-      T* dst = dqkv + (w.beg + key) * pitch + (int64_t)w.hd * D;
-      store_dcol<T, D>(dst + (int64_t)heads * D, dk, scale, h);
-      store_dcol<T, D>(dst + 2LL * heads * D, dv, 1.f, h);
+    if (key < w.len_k) {
+      if (SPLIT) {
+        float* dst = part + (((int64_t)split * total_k + w.beg_k + key) * 2 * heads + w.hd) * D;
+        store_dcol_f32<D>(dst, dk, h);
+        store_dcol_f32<D>(dst + (int64_t)heads * D, dv, h);
+      } else {
+        const int64_t off = (w.beg_k + key) * dkv_stride + (int64_t)w.hd * D;
+        store_dcol<T, D>(dk_out + off, dk, scale, h);
+        store_dcol<T, D>(dv_out + off, dv, 1.f, h);
+      }
     }
+  }
+}
+
+// dk / dv rows from the partials of a split sweep: splits summed in the order 0 .. q_splits - 1, one thread per 4
+// consecutive d of a (key row, slot, head).  Rows outside [cu_k[0], cu_k[num_seqs]) belong to no sequence: not written.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_dkdv_reduce_kernel(const float* __restrict__ part, const int32_t* __restrict__ cu_k,
+                                                               int64_t num_seqs, int64_t total_k, int heads, int q_splits,
+                                                               float scale, T* __restrict__ dk_out, T* __restrict__ dv_out,
+                                                               int64_t dkv_stride) {
+  typedef typename AFrag<T>::half_type half;
+  const int64_t n = total_k * 2 * heads * (D / 4), slab = total_k * 2 * heads * D;
+  const int64_t first = cu_k[0], last = cu_k[num_seqs];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % (D / 4));
+    int64_t t = i / (D / 4);
+    const int hd = (int)(t % heads);
+    t /= heads;
+    const int slot = (int)(t & 1);
+    const int64_t row = t >> 1;
+    if (row < first || row >= last) continue;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < q_splits; ++j) {
+      const float4 x = *reinterpret_cast<const float4*>(part + j * slab + 4 * i);
+      acc.x += x.x, acc.y += x.y, acc.z += x.z, acc.w += x.w;
+    }
+    const float mul = slot ? 1.f : scale;
+    half o;
+    o[0] = (T)(acc.x * mul), o[1] = (T)(acc.y * mul), o[2] = (T)(acc.z * mul), o[3] = (T)(acc.w * mul);
+    *reinterpret_cast<half*>((slot ? dv_out : dk_out) + row * dkv_stride + (int64_t)hd * D + 4 * c) = o;
   }
 }
 
 // dQ of one (sequence, 32-query block, head).
 template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+__global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const AttnOperands<T> a, const T* __restrict__ dout,
                                                          const float* __restrict__ lse, const float* __restrict__ delta,
-                                                         const int32_t* __restrict__ cu, int64_t items, int nblk, int heads,
-                                                         float c2, float scale, T* __restrict__ dqkv) {
+                                                         int64_t items, int nblk, float c2, float scale, T* __restrict__ dq_out,
+                                                         int64_t dq_stride) {
   typedef typename AFrag<T>::type frag;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
   __shared__ __attribute__((aligned(16))) T kt[NMB * 32 * kAttnPitch];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int64_t pitch = 3LL * heads * D, opitch = (int64_t)heads * D;
+  const int heads = a.heads;
+  const int64_t qp = a.q_stride, kp = a.kv_stride, opitch = (int64_t)heads * D;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    if (!attn_item(id, nblk, heads, cu, w)) continue;
-    const T* q = qkv + w.beg * pitch + (int64_t)w.hd * D;
-    const T* k = q + (int64_t)heads * D;
-    const T* v = k + (int64_t)heads * D;
-    const T* dO = dout + w.beg * opitch + (int64_t)w.hd * D;
+    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    if (w.b0 >= w.len_q) continue;
+    const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
+    const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* dO = dout + w.beg_q * opitch + (int64_t)w.hd * D;
     const int row = w.b0 + r;
-    const bool ok = row < w.len;
+    const bool ok = row < w.len_q;
     frag qf[NS], df[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      qf[s] = load8<T>(q, pitch, row, w.len, 16 * s + 8 * h);
-      df[s] = load8<T>(dO, opitch, row, w.len, 16 * s + 8 * h);
+      qf[s] = load8<T>(q, qp, row, w.len_q, 16 * s + 8 * h);
+      df[s] = load8<T>(dO, opitch, row, w.len_q, 16 * s + 8 * h);
     }
-    const float L = ok ? lse[(w.beg + row) * heads + w.hd] * kLog2e : 0.f;
-    const float E = ok ? delta[(w.beg + row) * heads + w.hd] : 0.f;
+    // lse = -inf marks a query with no key: its sweep below is empty and dq stays zero; +inf here (p = exp2(-inf) = 0)
+    // keeps such a value out of the subtraction whatever the caller's buffer holds
+    float L = ok ? lse[(w.beg_q + row) * heads + w.hd] : 0.f;
+    L = L > -INFINITY ? L * kLog2e : INFINITY;
+    const float E = ok ? delta[(w.beg_q + row) * heads + w.hd] : 0.f;
     a_f32x16 dq[NMB];
 #pragma unroll
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) dq[mb][i] = 0.f;
-    for (int k0 = 0; k0 < w.len; k0 += kAttnBlock) {
+    for (int k0 = 0; k0 < w.len_k; k0 += kAttnBlock) {
       a_f32x16 st, dpt;
       frag kf[NS];
 #pragma unroll
       for (int i = 0; i < 16; ++i) st[i] = dpt[i] = 0.f;
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        kf[s] = load8<T>(k, pitch, k0 + r, w.len, 16 * s + 8 * h);
+        kf[s] = load8<T>(k, kp, k0 + r, w.len_k, 16 * s + 8 * h);
         st = AFrag<T>::mfma(kf[s], qf[s], st);
-        dpt = AFrag<T>::mfma(load8<T>(v, pitch, k0 + r, w.len, 16 * s + 8 * h), df[s], dpt);
+        dpt = AFrag<T>::mfma(load8<T>(v, kp, k0 + r, w.len_k, 16 * s + 8 * h), df[s], dpt);
       }
       __syncthreads();
       stage_frags<T, D>(kt, kf, r, h);
-      // rows are keys, the lane's column its query; keys past the end get p = 0 (their K, V rows were read as zeros)
+      // rows are keys, the lane's column its query; keys past len_k get p = 0 (their K, V rows were read as zeros)
       float ds[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float p = k0 + acc_row(i, h) < w.len ? __builtin_amdgcn_exp2f(st[i] * c2 - L) : 0.f;
+        const float p = k0 + acc_row(i, h) < w.len_k ? __builtin_amdgcn_exp2f(st[i] * c2 - L) : 0.f;
         ds[i] = p * (dpt[i] - E);
       }
       __syncthreads();
@@ -392,34 +497,99 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const T* __restrict__ q
         for (int mb = 0; mb < NMB; ++mb) dq[mb] = AFrag<T>::mfma(read_tr<T>(kt, mb, s, r, h), dsf, dq[mb]);
       }
     }
-    if (ok) store_dcol<T, D>(dqkv + (w.beg + row) * pitch + (int64_t)w.hd * D, dq, scale, h);
+    if (ok) store_dcol<T, D>(dq_out + (w.beg_q + row) * dq_stride + (int64_t)w.hd * D, dq, scale, h);
   }
 }
 
+// ---- host -----------------------------------------------------------------------------------------------------------
+// One call's operands and sizes, already checked.
+struct AttnCall {
+  const void *q, *k, *v;
+  int64_t q_stride, kv_stride;
+  const int32_t *cu_q, *cu_k;
+  int64_t num_seqs, total_q, total_k;
+  int heads, max_q, max_k;
+  float scale;
+};
+
+static inline int attn_blocks(int max_seqlen) { return (max_seqlen + kAttnBlock - 1) / kAttnBlock; }
+static inline unsigned attn_grid(int64_t items) { return (unsigned)(items < kAttnMaxGrid ? items : kAttnMaxGrid); }
+
+template <typename T>
+static AttnOperands<T> attn_operands(const AttnCall& c) {
+  return AttnOperands<T>{(const T*)c.q, (const T*)c.k, (const T*)c.v, c.q_stride, c.kv_stride, c.cu_q, c.cu_k, c.heads};
+}
+
 template <typename T, int D>
-static int attn_fwd_t(const void* qkv, const int32_t* cu, int64_t items, int nblk, int heads, float scale, void* out, float* lse,
-                      hipStream_t s) {
-  const int64_t grid = items < kAttnMaxGrid ? items : kAttnMaxGrid;
-  hipLaunchKernelGGL((attn_fwd_kernel<T, D>), dim3((unsigned)grid), dim3(64), 0, s, (const T*)qkv, cu, items, nblk, heads,
-                     scale * kLog2e, (T*)out, lse);
+static int attn_fwd_t(const AttnCall& c, void* out, float* lse, hipStream_t s) {
+  const int nblk = attn_blocks(c.max_q);
+  const int64_t items = c.num_seqs * nblk * c.heads;
+  if (items > 0)
+    hipLaunchKernelGGL((attn_fwd_kernel<T, D>), dim3(attn_grid(items)), dim3(64), 0, s, attn_operands<T>(c), items, nblk,
+                       c.scale * kLog2e, (T*)out, lse);
   return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
 }
 
 template <typename T, int D>
-static int attn_bwd_t(const void* dout, const void* qkv, const void* out, const float* lse, const int32_t* cu, int64_t items,
-                      int nblk, int64_t total, int heads, float scale, void* dqkv, float* delta, hipStream_t s) {
-  const int64_t rows = total * heads;
-  hipLaunchKernelGGL((attn_delta_kernel<T, D>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (const T*)dout,
-                     (const T*)out, rows, delta);
-  const int64_t grid = items < kAttnMaxGrid ? items : kAttnMaxGrid;
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D>), dim3((unsigned)grid), dim3(64), 0, s, (const T*)qkv, (const T*)dout, lse,
-                     (const float*)delta, cu, items, nblk, heads, scale * kLog2e, scale, (T*)dqkv);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), dim3((unsigned)grid), dim3(64), 0, s, (const T*)qkv, (const T*)dout, lse,
-                     (const float*)delta, cu, items, nblk, heads, scale * kLog2e, scale, (T*)dqkv);
+static int attn_bwd_t(const AttnCall& c, const void* dout, const void* out, const float* lse, void* dq, int64_t dq_stride,
+                      void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part, float* delta, hipStream_t s) {
+  const AttnOperands<T> a = attn_operands<T>(c);
+  const float c2 = c.scale * kLog2e;
+  const int64_t rows = c.total_q * c.heads;
+  const int nblk_q = attn_blocks(c.max_q), nblk_k = attn_blocks(c.max_k);
+  const int64_t items_q = c.num_seqs * nblk_q * c.heads, items_k = c.num_seqs * nblk_k * c.heads;
+  if (rows > 0)
+    hipLaunchKernelGGL((attn_delta_kernel<T, D>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (const T*)dout,
+                       (const T*)out, rows, delta);
+  if (items_k > 0 && c.total_k > 0) {
+    if (q_splits > 1) {
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, true>), dim3(attn_grid(items_k * q_splits)), dim3(64), 0, s, a,
+                         (const T*)dout, lse, (const float*)delta, items_k * q_splits, nblk_k, c2, c.scale, (T*)dk, (T*)dv,
+                         dkv_stride, q_splits, c.total_k, part);
+      const int64_t n = c.total_k * 2 * c.heads * (D / 4);
+      hipLaunchKernelGGL((attn_dkdv_reduce_kernel<T, D>), dim3(attn_grid((n + 255) / 256)), dim3(256), 0, s,
+                         (const float*)part, c.cu_k, c.num_seqs, c.total_k, c.heads, q_splits, c.scale, (T*)dk, (T*)dv,
+                         dkv_stride);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, false>), dim3(attn_grid(items_k)), dim3(64), 0, s, a, (const T*)dout, lse,
+                         (const float*)delta, items_k, nblk_k, c2, c.scale, (T*)dk, (T*)dv, dkv_stride, 1, c.total_k,
+                         (float*)nullptr);
+    }
+  }
+  if (items_q > 0 && c.total_q > 0)
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), dim3(attn_grid(items_q)), dim3(64), 0, s, a, (const T*)dout, lse,
+                       (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride);
   return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
 }
 
-// Shared argument checks of both directions.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing to launch.
+static int attn_fwd_dispatch(const AttnCall& c, int head_dim, int dtype, void* out, float* lse, hipStream_t s) {
+#define WCN_ATTN_FWD(DD) \
+  return dtype == WCN_BF16 ? attn_fwd_t<__bf16, DD>(c, out, lse, s) : attn_fwd_t<_Float16, DD>(c, out, lse, s);
+  switch (head_dim) {
+    case 16: WCN_ATTN_FWD(16);
+    case 32: WCN_ATTN_FWD(32);
+    default: WCN_ATTN_FWD(64);
+  }
+#undef WCN_ATTN_FWD
+}
+
+static int attn_bwd_dispatch(const AttnCall& c, int head_dim, int dtype, const void* dout, const void* out, const float* lse,
+                             void* dq, int64_t dq_stride, void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part,
+                             float* delta, hipStream_t s) {
+#define WCN_ATTN_BWD(DD)                                                                                                      \
+  return dtype == WCN_BF16                                                                                                    \
+             ? attn_bwd_t<__bf16, DD>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s)         \
+             : attn_bwd_t<_Float16, DD>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
+  switch (head_dim) {
+    case 16: WCN_ATTN_BWD(16);
+    case 32: WCN_ATTN_BWD(32);
+    default: WCN_ATTN_BWD(64);
+  }
+#undef WCN_ATTN_BWD
+}
+
+// Shared argument checks of both directions of the packed form.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing
+// to launch.
 static int attn_check(const void* qkv, const int32_t* cu, int64_t num_seqs, int64_t total, int32_t heads, int32_t head_dim,
                       int32_t max_seqlen, float scale, int32_t dtype) {
   if (num_seqs < 0 || total < 0 || heads < 1 || head_dim < 1 || max_seqlen < 0 || !(scale == scale)) return WCN_ERROR_INVALID_PARAMETERS;
@@ -431,12 +601,39 @@ static int attn_check(const void* qkv, const int32_t* cu, int64_t num_seqs, int6
   return WCN_SUCCESS;
 }
 
-#define WCN_ATTN_DISPATCH(CALL)                              \
-  switch (head_dim) {                                        \
-    case 16: CALL(16);                                       \
-    case 32: CALL(32);                                       \
-    default: CALL(64);                                       \
-  }
+// The packed tensor as three operands: slots of one [T, 3, H, D], one boundary array for both sides.
+static AttnCall attn_packed_call(const void* qkv, const int32_t* cu, int64_t num_seqs, int64_t total, int32_t heads,
+                                 int32_t head_dim, int32_t max_seqlen, float scale, int32_t esize) {
+  const int64_t hd = (int64_t)heads * head_dim;
+  const char* base = (const char*)qkv;
+  return AttnCall{base, base + hd * esize, base + 2 * hd * esize, 3 * hd, 3 * hd, cu, cu, num_seqs, total, total, heads,
+                  max_seqlen, max_seqlen, scale};
+}
+
+static inline bool attn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Checks of the separate-operand form (both directions).  Same return convention as attn_check; "nothing to launch" is
+// left to the caller, which knows what each direction writes.
+static int attn_kv_check(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* cu_q,
+                         const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k, int32_t heads,
+                         int32_t head_dim, int32_t max_q, int32_t max_k, float scale, int32_t dtype) {
+  if (num_seqs < 0 || total_q < 0 || total_k < 0 || heads < 1 || head_dim < 1 || max_q < 0 || max_k < 0 || !(scale == scale))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (num_seqs > 0 && (!cu_q || !cu_k)) return WCN_ERROR_INVALID_PARAMETERS;
+  if ((total_q > 0 && !q) || (total_k > 0 && (!k || !v))) return WCN_ERROR_INVALID_PARAMETERS;
+  if (total_q > INT32_MAX || total_k > INT32_MAX) return WCN_ERROR_INVALID_PARAMETERS;  // cu_* are int32
+  if (!wcn_attn_varlen_supported(head_dim, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  const int64_t hd = (int64_t)heads * head_dim;
+  if (q_stride < hd || kv_stride < hd || (q_stride & 7) || (kv_stride & 7)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!attn_aligned16(q) || !attn_aligned16(k) || !attn_aligned16(v)) return WCN_ERROR_INVALID_PARAMETERS;
+  return WCN_SUCCESS;
+}
+
+// The split rule of the dK/dV sweep (see wcn.h).  Measured on an MI355X: docs/OPTIMISATION_LOG.md.
+constexpr int64_t kAttnSplitTargetWaves = 4096;          // (sequence, key block, split, head) waves worth launching
+constexpr int kAttnSplitMinBlocks = 16;                  // query blocks a split sweeps at the least
+constexpr int kAttnSplitMax = 16;
+constexpr int64_t kAttnSplitPartCap = 256LL << 20;       // bytes of partials the rule may ask for (at head_dim 64)
 
 }  // namespace wcn
 
@@ -457,14 +654,8 @@ int wcn_attn_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, int64_t num_
   int st = attn_check(qkv, cu_seqlens, num_seqs, total, heads, head_dim, max_seqlen, softmax_scale, dtype);
   if (st == WCN_SUCCESS && (!out || !lse)) st = WCN_ERROR_INVALID_PARAMETERS;
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
-  const int nblk = (max_seqlen + kAttnBlock - 1) / kAttnBlock;
-  const int64_t items = num_seqs * nblk * heads;
-  hipStream_t s = (hipStream_t)stream;
-#define WCN_ATTN_FWD(DD)                                                                                              \
-  return dtype == WCN_BF16 ? attn_fwd_t<__bf16, DD>(qkv, cu_seqlens, items, nblk, heads, softmax_scale, out, lse, s)  \
-                           : attn_fwd_t<_Float16, DD>(qkv, cu_seqlens, items, nblk, heads, softmax_scale, out, lse, s);
-  WCN_ATTN_DISPATCH(WCN_ATTN_FWD)
-#undef WCN_ATTN_FWD
+  const AttnCall c = attn_packed_call(qkv, cu_seqlens, num_seqs, total, heads, head_dim, max_seqlen, softmax_scale, 2);
+  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, (hipStream_t)stream);
 }
 
 int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, const float* lse, const int32_t* cu_seqlens,
@@ -476,16 +667,71 @@ int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, cons
                             workspace_bytes < wcn_attn_varlen_workspace_bytes(total, heads)))
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
-  const int nblk = (max_seqlen + kAttnBlock - 1) / kAttnBlock;
-  const int64_t items = num_seqs * nblk * heads;
-  hipStream_t s = (hipStream_t)stream;
-  float* delta = (float*)workspace;
-#define WCN_ATTN_BWD(DD)                                                                                                 \
-  return dtype == WCN_BF16                                                                                               \
-             ? attn_bwd_t<__bf16, DD>(dout, qkv, out, lse, cu_seqlens, items, nblk, total, heads, softmax_scale, dqkv,    \
-                                      delta, s)                                                                         \
-             : attn_bwd_t<_Float16, DD>(dout, qkv, out, lse, cu_seqlens, items, nblk, total, heads, softmax_scale, dqkv, \
-                                        delta, s);
-  WCN_ATTN_DISPATCH(WCN_ATTN_BWD)
-#undef WCN_ATTN_BWD
+  const AttnCall c = attn_packed_call(qkv, cu_seqlens, num_seqs, total, heads, head_dim, max_seqlen, softmax_scale, 2);
+  const int64_t hd = (int64_t)heads * head_dim;
+  char* d = (char*)dqkv;
+  return attn_bwd_dispatch(c, head_dim, dtype, dout, out, lse, d, 3 * hd, d + 2 * hd, d + 4 * hd, 3 * hd, 1, nullptr,
+                           (float*)workspace, (hipStream_t)stream);
+}
+
+int32_t wcn_attn_varlen_kv_splits(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads) {
+  if (num_seqs < 1 || max_seqlen_q < 1 || max_seqlen_k < 1 || heads < 1) return 1;
+  const int64_t base = num_seqs * attn_blocks(max_seqlen_k) * heads;
+  int64_t s = (kAttnSplitTargetWaves + base - 1) / base;
+  const int64_t by_blocks = attn_blocks(max_seqlen_q) / kAttnSplitMinBlocks;
+  const int64_t by_bytes = kAttnSplitPartCap / (num_seqs * max_seqlen_k * 2 * heads * 64 * (int64_t)sizeof(float));
+  if (s > by_blocks) s = by_blocks;
+  if (s > by_bytes) s = by_bytes;
+  if (s > kAttnSplitMax) s = kAttnSplitMax;
+  return s < 1 ? 1 : (int32_t)s;
+}
+
+size_t wcn_attn_varlen_kv_workspace_bytes(int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t q_splits) {
+  if (total_q < 0 || total_k < 0 || heads < 0 || head_dim < 0) return 0;
+  size_t bytes = (size_t)total_q * (size_t)heads * sizeof(float);
+  if (q_splits > 1) bytes += (size_t)q_splits * (size_t)total_k * 2 * (size_t)heads * (size_t)head_dim * sizeof(float);
+  return bytes;
+}
+
+int wcn_attn_varlen_kv_fwd(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                           const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                           int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                           int32_t dtype, void* out, float* lse, wcn_stream_t stream) {
+  const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
+                               max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
+  if (st != WCN_SUCCESS) return st;
+  if (total_q > 0 && (!out || !lse || !attn_aligned16(out))) return WCN_ERROR_INVALID_PARAMETERS;
+  if (num_seqs == 0 || total_q == 0 || max_seqlen_q == 0) return WCN_SUCCESS;
+  const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
+                   softmax_scale};
+  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, (hipStream_t)stream);
+}
+
+int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                           const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                           int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                           int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                           void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
+                           wcn_stream_t stream) {
+  const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
+                               max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
+  if (st != WCN_SUCCESS) return st;
+  const int64_t hd = (int64_t)heads * head_dim;
+  if (q_splits < 0 || dq_stride < hd || dkv_stride < hd || (dq_stride & 7) || (dkv_stride & 7)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (total_q > 0 && (!dout || !out || !lse || !dq)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (total_k > 0 && (!dk || !dv)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!attn_aligned16(dout) || !attn_aligned16(out) || !attn_aligned16(dq) || !attn_aligned16(dk) || !attn_aligned16(dv) ||
+      !attn_aligned16(workspace))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (q_splits == 0) q_splits = wcn_attn_varlen_kv_splits(num_seqs, max_seqlen_q, max_seqlen_k, heads);
+  const size_t need = wcn_attn_varlen_kv_workspace_bytes(total_q, total_k, heads, head_dim, q_splits);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (num_seqs == 0 || (total_q == 0 && total_k == 0)) return WCN_SUCCESS;
+  // the partials come first (their size is a multiple of 16 bytes), delta [total_q, heads] after them
+  float* part = (float*)workspace;
+  float* delta = (float*)((char*)workspace + (need - (size_t)total_q * (size_t)heads * sizeof(float)));
+  const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
+                   softmax_scale};
+  return attn_bwd_dispatch(c, head_dim, dtype, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta,
+                           (hipStream_t)stream);
 }

@@ -240,16 +240,54 @@ def fused_rope_qkv(qkv: Tensor, coords: Tensor, theta: Tensor, num_heads: int, r
 
 
 # ---- attention over the voxels of each batch element ----------------------------------------------------------------------
-def sparse_scaled_dot_product_attention(qkv: Tensor, voxels) -> Tensor:
-    """Full self-attention of every voxel over the voxels of its own batch element (the two-argument form of the
-    reference's function of this name): ``qkv`` [T, 3, H, D] -> [T, H, D].  A batch element is one sequence:
-    ``cu_seqlens`` and ``max_seqlen`` both come from the host ``offsets``, nothing is read back from the device."""
-    from warpconvnet_amd.nn.functional.attention import flash_attn_varlen_qkvpacked, varlen_attention_reference
-
+def _voxel_cu_seqlens(voxels) -> Tuple[Tensor, int]:
+    """(host int64 boundaries, longest element) of a ``Voxels``: both from the host ``offsets``, nothing is read back."""
     offsets = voxels.offsets.to(device="cpu", dtype=torch.int64)
     lens = offsets[1:] - offsets[:-1]
-    max_seqlen = int(lens.max()) if lens.numel() else 0
-    if not qkv.is_cuda:
-        out, _ = varlen_attention_reference(qkv, offsets)
-        return out.to(qkv.dtype)
-    return flash_attn_varlen_qkvpacked(qkv, offsets.to(torch.int32), max_seqlen)
+    return offsets, (int(lens.max()) if lens.numel() else 0)
+
+
+def sparse_scaled_dot_product_attention(*args) -> Tensor:
+    """Full attention of every voxel within its batch element; the reference function's three call shapes:
+
+    - ``(qkv, voxels)``: self-attention, ``qkv`` [T, 3, H, D] -> [T, H, D]; a batch element is one sequence.
+    - ``(q, voxels, kv_dense)``: voxel queries ``q`` [T, H, D] over a dense context ``kv_dense`` [B, L, 2, H, D].
+    - ``(q, voxels, k_dense, v_dense)``: the same with keys and values apart, [B, L, H, D] each.
+
+    The key boundaries of the dense forms are ``arange(B + 1) * L``.  CPU tensors take the per-sequence references."""
+    from warpconvnet_amd.nn.functional.attention import (cross_attention_reference, flash_attn_varlen_func,
+                                                         flash_attn_varlen_kvpacked_func, flash_attn_varlen_qkvpacked,
+                                                         varlen_attention_reference)
+
+    if len(args) not in (2, 3, 4):
+        raise ValueError(f"sparse_scaled_dot_product_attention: bad arity {len(args)}")
+    offsets, max_seqlen = _voxel_cu_seqlens(args[1])
+    if len(args) == 2:
+        qkv = args[0]
+        if not qkv.is_cuda:
+            out, _ = varlen_attention_reference(qkv, offsets)
+            return out.to(qkv.dtype)
+        return flash_attn_varlen_qkvpacked(qkv, offsets.to(torch.int32), max_seqlen)
+    q = args[0]
+    if len(args) == 3:
+        kv = args[2]
+        if kv.ndim != 5 or kv.shape[2] != 2:
+            raise ValueError(f"kv_dense must be [B, L, 2, H, D], got {tuple(kv.shape)}")
+        b, l = kv.shape[0], kv.shape[1]
+        kv = kv.reshape(b * l, 2, *kv.shape[3:])
+        k, v = kv[:, 0], kv[:, 1]
+    else:
+        k, v = args[2], args[3]
+        if k.ndim != 4 or v.ndim != 4:
+            raise ValueError(f"k_dense and v_dense must be [B, L, H, D], got {tuple(k.shape)} and {tuple(v.shape)}")
+        b, l = k.shape[0], k.shape[1]
+        kv, k, v = None, k.reshape(b * l, *k.shape[2:]), v.reshape(b * l, *v.shape[2:])
+    if b != offsets.numel() - 1:
+        raise ValueError(f"the dense context has {b} batch elements, the voxels {offsets.numel() - 1}")
+    cu_k = torch.arange(b + 1, dtype=torch.int64) * l
+    if not q.is_cuda:
+        out, _ = cross_attention_reference(q, k, v, offsets, cu_k)
+        return out.to(q.dtype)
+    if kv is not None:
+        return flash_attn_varlen_kvpacked_func(q, kv, offsets.to(torch.int32), cu_k.to(torch.int32), max_seqlen, l)
+    return flash_attn_varlen_func(q, k, v, offsets.to(torch.int32), cu_k.to(torch.int32), max_seqlen, l)

@@ -7,8 +7,8 @@ from .point_conv import PointConv
 from .prune import SparsePrune
 from .rope import VoxelRotaryPositionalEmbeddings, suggest_voxel_rope_base
 from .sequential import Sequential
-from .sparse_attention import SparseMultiHeadAttention, SparseRotaryPositionEmbedder
-from .sparse_dit import ModulatedSparseTransformerBlock, SparseFeedForwardNet
+from .sparse_attention import SparseMultiHeadAttention, SparseMultiHeadCrossAttention, SparseRotaryPositionEmbedder
+from .sparse_dit import ModulatedSparseTransformerBlock, ModulatedSparseTransformerCrossBlock, SparseFeedForwardNet
 from .sparse_convnext import SparseConvNeXtBlock3d
 from .sparse_unet import (SparseChannelToSpatialResBlock3d, SparseSpatialToChannelResBlock3d, SparseUNetDecoderStages,
                           SparseUNetEncoderStages)
@@ -24,5 +24,6 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "SparseChannel2Spatial", "SparseDownsample", "SparsePrune", "SparseSpatial2Channel", "SparseSubdivide", "SparseUpsample",
            "MultiHeadRMSNorm", "SparseMultiHeadAttention", "SparseRotaryPositionEmbedder", "VoxelRotaryPositionalEmbeddings",
            "suggest_voxel_rope_base", "LayerNorm32", "ModulatedSparseTransformerBlock", "SparseFeedForwardNet",
+           "SparseMultiHeadCrossAttention", "ModulatedSparseTransformerCrossBlock",
            "SparseConvNeXtBlock3d", "SparseChannelToSpatialResBlock3d", "SparseSpatialToChannelResBlock3d",
            "SparseUNetDecoderStages", "SparseUNetEncoderStages"]

@@ -1,9 +1,11 @@
-"""Multi-head self-attention over the voxels of each batch element, with rotary position embeddings from the voxel
-coordinates and a per-head RMS norm on Q and K (reference `nn/modules/sparse_dit_attention.py`).
+"""Multi-head attention over the voxels of each batch element (reference `nn/modules/sparse_dit_attention.py`):
+self-attention with rotary position embeddings from the voxel coordinates and a per-head RMS norm on Q and K, and
+cross-attention of the voxels to a dense context or to a second ``Voxels``.
 
-The forward is ``to_qkv`` -> ONE ``qk_prologue`` call (norm, rotation, cast: `csrc/qk_prologue.hip`) ->
-``flash_attn_varlen_qkvpacked`` (`csrc/attn_varlen.hip`, a batch element is one sequence) -> ``to_out``.  Cross-attention,
-windowed attention and dropout are not implemented.
+The self forward is ``to_qkv`` -> ONE ``qk_prologue`` call (norm, rotation, cast: `csrc/qk_prologue.hip`) ->
+``flash_attn_varlen_qkvpacked`` (`csrc/attn_varlen.hip`, a batch element is one sequence) -> ``to_out``.  The cross forward
+is ``to_q`` / ``to_kv`` -> ``flash_attn_varlen_kvpacked_func`` or ``flash_attn_varlen_func`` (the same kernels with separate
+K/V operands and lengths) -> ``to_out``.  Windowed attention and dropout are not implemented.
 """
 from typing import Optional, Tuple
 
@@ -12,11 +14,14 @@ import torch.nn as nn
 from torch import Tensor
 
 from warpconvnet_amd.geometry.types.voxels import Voxels
+from warpconvnet_amd.nn.functional.attention import (cross_attention_reference, flash_attn_varlen_func,
+                                                     flash_attn_varlen_kvpacked_func)
 from warpconvnet_amd.nn.functional.qk_prologue import (qk_prologue, qk_prologue_reference, rope_table,
                                                        sparse_scaled_dot_product_attention)
 from warpconvnet_amd.nn.modules.normalizations import MultiHeadRMSNorm
 
-__all__ = ["SparseMultiHeadAttention", "SparseRotaryPositionEmbedder", "sparse_scaled_dot_product_attention"]
+__all__ = ["SparseMultiHeadAttention", "SparseMultiHeadCrossAttention", "SparseRotaryPositionEmbedder",
+           "sparse_scaled_dot_product_attention"]
 
 
 class SparseRotaryPositionEmbedder(nn.Module):
@@ -75,8 +80,8 @@ class SparseMultiHeadAttention(nn.Module):
         if type == "cross" and use_rope:
             raise ValueError("Rotary position embeddings only supported for self-attn")
         if type == "cross":
-            raise NotImplementedError("SparseMultiHeadAttention: type='cross' needs a varlen attention kernel with separate "
-                                      "K/V sequence lengths, which is not implemented (only type='self')")
+            raise NotImplementedError("SparseMultiHeadAttention: type='cross' (attention with separate K/V sequence lengths) "
+                                      "is a class of its own here: use SparseMultiHeadCrossAttention")
         self.channels = channels
         self.head_dim = channels // num_heads
         self.ctx_channels = ctx_channels if ctx_channels is not None else channels
@@ -107,5 +112,72 @@ class SparseMultiHeadAttention(nn.Module):
             else:
                 qkv = qk_prologue_reference(qkv, table, gq, gk, out_dtype=qkv.dtype)
         h = sparse_scaled_dot_product_attention(qkv, x)  # [T, H, D]
+        out = self.to_out(h.reshape(t, -1).to(feats.dtype))
+        return x.replace(batched_features=out.to(feats.dtype))
+
+
+class SparseMultiHeadCrossAttention(nn.Module):
+    """Cross-attention of a ``Voxels`` token sequence to a context: the reference's
+    ``SparseMultiHeadAttention(type="cross")`` with its attribute names and state dict (``to_q``, ``to_kv``, ``to_out``,
+    ``q_rms_norm.gamma``, ``k_rms_norm.gamma``).  It is a class of its own because ``SparseMultiHeadAttention`` keeps
+    refusing ``type="cross"`` (its constructor's contract is pinned by the existing tests); a checkpoint of the reference's
+    cross module loads into this one unchanged.
+
+    ``context`` is a dense [B, L, ctx_channels] tensor (every batch element attends to its own L tokens) or a ``Voxels``
+    (element b attends to the context's element b).  Key boundaries and ``max_seqlen_k`` come from the host offsets.  With
+    ``qk_rms_norm`` Q and K pass through ``MultiHeadRMSNorm`` in plain torch.  fp32 features are cast to fp16 in front of
+    the attention kernel and back after ``to_out``; CPU tensors take ``cross_attention_reference``."""
+
+    def __init__(self, channels: int, num_heads: int, ctx_channels: Optional[int] = None, qkv_bias: bool = True,
+                 qk_rms_norm: bool = False):
+        super().__init__()
+        assert channels % num_heads == 0
+        self.channels = channels
+        self.head_dim = channels // num_heads
+        self.ctx_channels = ctx_channels if ctx_channels is not None else channels
+        self.num_heads = num_heads
+        self.qk_rms_norm = qk_rms_norm
+        self.to_q = nn.Linear(channels, channels, bias=qkv_bias)
+        self.to_kv = nn.Linear(self.ctx_channels, channels * 2, bias=qkv_bias)
+        if qk_rms_norm:
+            self.q_rms_norm = MultiHeadRMSNorm(self.head_dim, num_heads)
+            self.k_rms_norm = MultiHeadRMSNorm(self.head_dim, num_heads)
+        self.to_out = nn.Linear(channels, channels)
+
+    def forward(self, x: Voxels, context) -> Voxels:
+        feats = x.feature_tensor
+        t, nh, hd = feats.shape[0], self.num_heads, self.head_dim
+        if isinstance(context, Voxels):
+            ctx = context.feature_tensor
+            cu_k = context.offsets.to(device="cpu", dtype=torch.int64)
+        else:
+            if not isinstance(context, Tensor) or context.ndim != 3:
+                raise ValueError("context must be a Voxels or a dense [B, L, ctx_channels] tensor")
+            b, l = context.shape[0], context.shape[1]
+            ctx = context.reshape(b * l, context.shape[2])
+            cu_k = torch.arange(b + 1, dtype=torch.int64) * l
+        cu_q = x.offsets.to(device="cpu", dtype=torch.int64)
+        if cu_k.numel() != cu_q.numel():
+            raise ValueError(f"the context has {cu_k.numel() - 1} batch elements, x has {x.batch_size}")
+        lens_q, lens_k = cu_q[1:] - cu_q[:-1], cu_k[1:] - cu_k[:-1]
+        max_q = int(lens_q.max()) if lens_q.numel() else 0
+        max_k = int(lens_k.max()) if lens_k.numel() else 0
+        q = self.to_q(feats).reshape(t, nh, hd)
+        kv = self.to_kv(ctx).reshape(ctx.shape[0], 2, nh, hd)
+        k = None
+        if self.qk_rms_norm:
+            q = self.q_rms_norm(q)
+            k, v = self.k_rms_norm(kv[:, 0]), kv[:, 1]
+        if not q.is_cuda:
+            if k is None:
+                k, v = kv[:, 0], kv[:, 1]
+            h, _ = cross_attention_reference(q, k, v, cu_q, cu_k)
+        else:
+            kdt = q.dtype if q.dtype in (torch.float16, torch.bfloat16) else torch.float16
+            cq, ck = cu_q.to(torch.int32), cu_k.to(torch.int32)
+            if k is None:
+                h = flash_attn_varlen_kvpacked_func(q.to(kdt), kv.to(kdt), cq, ck, max_q, max_k)
+            else:
+                h = flash_attn_varlen_func(q.to(kdt), k.to(kdt), v.to(kdt), cq, ck, max_q, max_k)
         out = self.to_out(h.reshape(t, -1).to(feats.dtype))
         return x.replace(batched_features=out.to(feats.dtype))
