@@ -842,6 +842,44 @@ int wcn_channel_spread(const void* x, const void* h, int64_t rows, int32_t cx, i
 int wcn_channel_fold(const void* x, const void* h, int64_t rows, int32_t cout, int32_t g, float alpha, int32_t dtype,
                      void* out, wcn_stream_t stream);
 
+/* ---- window grouping of voxels: a deterministic counting sort by 3-D window (ABI 11, additions only) ------------------------
+ * The step that turns coordinates into the attention sequences of SpaceAttention (reference: voxel_encode(...,
+ * encoding_method="counting_sort"), nn/functional/voxel_encode.py:237-316, on the two kernels of
+ * csrc/window_grouping_kernels.cu: window_group_histogram_kernel :35-75 with find_batch_idx :14-25, and
+ * window_group_scatter_kernel :82-99).
+ * `coords` int32 [n, 3], `batch_offsets` int32 [num_batches + 1] (device; empty elements are legal).  `window`, `shift`
+ * (= round(offset_fraction * window), voxel_encode.py:166-172), `min_coord` (column minimum over all rows) and `grid_shape`
+ * (= ceil((max - min + shift + 1) / window), voxel_encode.py:249-255) are host values.  With W = prod(grid_shape) the
+ * window code of voxel i of element b is
+ *     w = (coords[i] + shift - min_coord) / window        per axis (operands non-negative: truncation = floor)
+ *     code = b * W + (w.x * grid_shape.y + w.y) * grid_shape.z + w.z        int64
+ * Outputs (device): `codes` int64 [n]; `perm` int64 [n] = the STABLE sort of the rows by code (inside a window rows appear
+ * in ascending original index), `inverse_perm` int64 [n] with inverse_perm[perm[j]] = j; `cu_seqlens` int32 [S + 1] the
+ * boundaries of the S non-empty windows in code order (cu_seqlens[S] = n) and `counts` int64 [S] their lengths, both
+ * allocated by the caller for the worst case S = min(n, num_batches * W); `summary` int32 [2] = (S, max_count), the only
+ * words the caller needs on the host.  S = -1: a voxel fell outside the announced box (min_coord / grid_shape do not fit the
+ * coordinates, or batch_offsets does not cover n); nothing else is then meaningful.
+ * The reference's scatter takes its slot with a racy atomic, so its row order inside a window changes from run to run.  Here
+ * the slots are taken the same way (integer atomics only) and every window's segment is then sorted ascending - one wave
+ * per segment of <= 64 rows, one workgroup per longer segment, in LDS - so two calls give bit-identical outputs.  Segments
+ * longer than wcn_window_group_max_segment() = 8192 rows (32 KiB of LDS) are NOT sorted and their parts of perm /
+ * inverse_perm are not written: the caller reads max_count from the summary and takes another path.  The prefix sum over the
+ * dense histogram and the compaction of the non-empty bins are tile sums -> one-workgroup scan of the sums -> apply; no
+ * kernel waits on another workgroup, every grid is capped at 4096 workgroups and strides.  The host is not read or waited
+ * for by the call.
+ *   wcn_window_group_max_segment     host-only: rows of the longest segment the call sorts (8192).
+ *   wcn_window_group_workspace_bytes host-only: histogram (num_bins rounded up to 2048 int32), tile sums, n slot words.
+ *   wcn_window_group                 the whole encode, seven launches on `stream`.
+ * Arguments are checked before any launch: n < 0 or > INT32_MAX, num_batches < 1, a window or grid_shape entry < 1,
+ * num_batches * W >= INT32_MAX - 2048, null pointers with n > 0 (summary and cu_seqlens always), a workspace that is short or
+ * not 16-B aligned -> WCN_ERROR_INVALID_PARAMETERS.  n == 0 -> summary = (0, 0), cu_seqlens[0] = 0, no kernel launch. */
+int32_t wcn_window_group_max_segment(void);
+size_t wcn_window_group_workspace_bytes(int64_t n, int64_t num_bins);
+int wcn_window_group(const int32_t* coords, int64_t n, const int32_t* batch_offsets, int32_t num_batches,
+                     const int32_t window[3], const int32_t shift[3], const int32_t min_coord[3], const int32_t grid_shape[3],
+                     int64_t* codes, int64_t* perm, int64_t* inverse_perm, int32_t* cu_seqlens, int64_t* counts,
+                     int32_t* summary, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

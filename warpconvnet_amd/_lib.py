@@ -295,6 +295,10 @@ SIGNATURES = {
     "wcn_channel_spread": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p,
                                    c_void_p]),
     "wcn_channel_fold": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p]),
+    "wcn_window_group_max_segment": (c_int32, []),
+    "wcn_window_group_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "wcn_window_group": (c_int, [c_void_p, c_int64, c_void_p, c_int32, _3I, _3I, _3I, _3I] + [c_void_p] * 7 +
+                         [c_size_t, c_void_p]),
     "wcn_resample_pack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_void_p, c_void_p]),
     "wcn_resample_unpack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

@@ -261,7 +261,8 @@ extern "C" {
 // 5 (signatures changed): COMPACT neighbour rows - `compact` argument of wcn_kmap_build_binned / wcn_kmap_tally_sort /
 //    wcn_kmap_scatter, wcn_kmap_compact_supported, wcn_kmap_densify, WCN_FLAG_ROW_OVERFLOW; mask = NULL in the gather GEMMs now means
 //    a compact table (wcn_conv_compact_table_supported replaces wcn_conv_mask_in_table_supported; dense rows no longer carry a mask)
-int wcn_abi_version(void) { return 10; }
+// 11 (additions only): wcn_window_group (window grouping of voxels by a deterministic counting sort, csrc/window_group.hip)
+int wcn_abi_version(void) { return 11; }
 
 const char* wcn_status_string(int status) {
   switch (status) {

@@ -1,7 +1,8 @@
 from .attention import BatchedLinear, FeedForward, LayerNorm, PatchAttention, TransformerBlock
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
-from .mlp import MLPBlock
+from .activations import DropPath
+from .mlp import Linear, MLPBlock
 from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
 from .point_conv import PointConv
 from .prune import SparsePrune
@@ -16,6 +17,8 @@ from .sparse_conv import SparseConv2d, SparseConv3d, SpatiallySparseConv
 from .sparse_pool import GlobalPool, SparseMaxPool, SparseMinPool, SparsePool, SparseUnpool
 from .sparse_resample import SparseChannel2Spatial, SparseDownsample, SparseSpatial2Channel, SparseSubdivide, SparseUpsample
 from .sparse_conv_depth import SparseDepthwiseConv2d, SparseDepthwiseConv3d, SpatiallySparseDepthwiseConv
+from .space_attention import (BLOCK_REGISTRY, STR2ATTN, AllAttention, PostNormBlock, PreNormBlock, SpaceAttention,
+                              SpaCeFormerBlockBase, StreamNormBlock, block_factory)
 
 __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Sequential", "SparseConv2d", "SparseConv3d", "SpatiallySparseConv",
            "SparseDepthwiseConv2d", "SparseDepthwiseConv3d", "SpatiallySparseDepthwiseConv",
@@ -26,4 +29,6 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "suggest_voxel_rope_base", "LayerNorm32", "ModulatedSparseTransformerBlock", "SparseFeedForwardNet",
            "SparseMultiHeadCrossAttention", "ModulatedSparseTransformerCrossBlock",
            "SparseConvNeXtBlock3d", "SparseChannelToSpatialResBlock3d", "SparseSpatialToChannelResBlock3d",
-           "SparseUNetDecoderStages", "SparseUNetEncoderStages"]
+           "SparseUNetDecoderStages", "SparseUNetEncoderStages",
+           "DropPath", "Linear", "SpaceAttention", "AllAttention", "STR2ATTN", "SpaCeFormerBlockBase", "PreNormBlock",
+           "PostNormBlock", "StreamNormBlock", "BLOCK_REGISTRY", "block_factory"]

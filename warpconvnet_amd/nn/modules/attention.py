@@ -16,7 +16,8 @@ from torch import Tensor
 
 from warpconvnet_amd.geometry.base.geometry import Geometry
 from warpconvnet_amd.geometry.coords.ops.serialization import POINT_ORDERING, encode, to_point_ordering
-from warpconvnet_amd.nn.functional.attention import flash_attn_varlen_qkvpacked, patch_cu_seqlens
+from warpconvnet_amd.nn.functional.attention import (flash_attn_varlen_qkvpacked, patch_cu_seqlens,
+                                                     varlen_attention_reference)
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 from warpconvnet_amd.nn.modules.normalizations import NormalizationBase
 
@@ -63,7 +64,8 @@ class LayerNorm(NormalizationBase):
 class PatchAttention(BaseSpatialModule):
     """Multi-head attention inside patches of ``patch_size`` consecutive rows of the ``order``-serialized batch elements.
     Features in fp32 run the attention core in fp16 (as the reference does); the output has the input's dtype and row
-    order.  ``use_rope`` and attention dropout are not implemented."""
+    order.  CPU tensors take ``varlen_attention_reference`` as the core.  ``use_rope`` and attention dropout are not
+    implemented."""
 
     def __init__(self, dim: int, patch_size: int, num_heads: int = 8, qkv_bias: bool = False, qk_scale: Optional[float] = None,
                  attn_drop: float = 0.0, proj_drop: float = 0.0, order: POINT_ORDERING = POINT_ORDERING.MORTON_XYZ,
@@ -99,9 +101,16 @@ class PatchAttention(BaseSpatialModule):
             feats = feats[res.perm]
             inverse_perm = res.inverse_perm
         qkv = self.qkv(feats).reshape(m, 3, self.num_heads, c // self.num_heads)
+        cu = patch_cu_seqlens(x.offsets, self.patch_size).to(torch.int32)
+        if not qkv.is_cuda:  # CPU tensors: the per-sequence torch reference in the features' precision (no fp16 cast)
+            out, _ = varlen_attention_reference(qkv, cu, self.scale,
+                                                dtype=torch.float64 if qkv.dtype == torch.float64 else torch.float32)
+            out = self.proj_drop(self.proj(out.reshape(m, c).to(feats.dtype)))
+            if inverse_perm is not None:
+                out = out[inverse_perm]
+            return x.replace(batched_features=out.to(feats.dtype))
         if qkv.dtype not in (torch.float16, torch.bfloat16):
             qkv = qkv.to(torch.float16)
-        cu = patch_cu_seqlens(x.offsets, self.patch_size).to(torch.int32)
         out = flash_attn_varlen_qkvpacked(qkv, cu, max_seqlen=self.patch_size, dropout_p=0.0, softmax_scale=self.scale)
         out = self.proj(out.reshape(m, c).to(feats.dtype))
         out = self.proj_drop(out)

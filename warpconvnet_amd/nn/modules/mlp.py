@@ -1,7 +1,7 @@
 """``MLPBlock``: Linear - LayerNorm - activation - Linear - LayerNorm plus a (projected) shortcut
 (reference `warpconvnet/nn/modules/mlp.py:124-177`).  On fp32 CUDA features whose widths fit (in <= 64, hidden <= 128, out <= 64)
 the whole block runs as one HIP kernel per direction (the PointConv edge kernel with one row per "edge"); otherwise the
-linears are library GEMMs."""
+linears are library GEMMs.  ``Linear`` is the geometry-aware ``nn.Linear`` of the same reference file."""
 from typing import Union
 
 import torch.nn as nn
@@ -10,6 +10,17 @@ from torch import Tensor
 from warpconvnet_amd.geometry.base.geometry import Geometry
 from warpconvnet_amd.nn.functional.point_conv import fused_mlp_block, fused_mlp_block_supported
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
+
+
+class Linear(BaseSpatialModule):
+    """``nn.Linear`` (as ``block``) over ``Geometry`` features (reference `warpconvnet/nn/modules/mlp.py:16-34`)."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True):
+        super().__init__()
+        self.block = nn.Linear(in_features, out_features, bias=bias)
+
+    def forward(self, x: Geometry):
+        return x.replace(batched_features=self.block(x.feature_tensor))
 
 
 class MLPBlock(BaseSpatialModule):

@@ -5,7 +5,8 @@ cross-attention of the voxels to a dense context or to a second ``Voxels``.
 The self forward is ``to_qkv`` -> ONE ``qk_prologue`` call (norm, rotation, cast: `csrc/qk_prologue.hip`) ->
 ``flash_attn_varlen_qkvpacked`` (`csrc/attn_varlen.hip`, a batch element is one sequence) -> ``to_out``.  The cross forward
 is ``to_q`` / ``to_kv`` -> ``flash_attn_varlen_kvpacked_func`` or ``flash_attn_varlen_func`` (the same kernels with separate
-K/V operands and lengths) -> ``to_out``.  Windowed attention and dropout are not implemented.
+K/V operands and lengths) -> ``to_out``.  Dropout is not implemented; ``attn_mode`` other than ``"full"`` raises here -
+attention inside 3-D windows (with an optional shift of the window grid) is ``SpaceAttention`` (`nn/modules/space_attention.py`).
 """
 from typing import Optional, Tuple
 
