@@ -880,6 +880,61 @@ int wcn_window_group(const int32_t* coords, int64_t n, const int32_t* batch_offs
                      int64_t* codes, int64_t* perm, int64_t* inverse_perm, int32_t* cu_seqlens, int64_t* counts,
                      int32_t* summary, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
 
+/* ---- points <-> voxels: the voxel map of a point cloud and the two feature kernels over it (ABI 12, additions only) ---------
+ * Reference: point_pool / point_unpool (nn/functional/point_pool.py, point_unpool.py) on ToUnique (utils/unique.py:146-240):
+ * torch.unique over rows, an argsort, a materialised features[perm] and torch_scatter.segment_csr.
+ *   wcn_voxel_keys   `points` fp32 [n, 3], `batch_offsets` int32 [num_batches + 1] (device; empty elements are legal) ->
+ *                    `keys` int64 [n] = b << 54 | (x + 2^17) << 36 | (y + 2^17) << 18 | (z + 2^17) with the cell
+ *                    x = floor(p.x * inv_voxel_size) in fp32; the caller passes fp32(1.0 / voxel_size) with the quotient taken
+ *                    in double, which is how the framework evaluates `points / voxel_size` for a host scalar on the device
+ *                    (a true division puts points on a cell face elsewhere).  Biased 18-bit fields, so int64 order is the
+ *                    lexicographic order of the signed (b, x, y, z) rows.  `status` int32 [1] is cleared by the call and receives bit 0:
+ *                    a cell outside [-2^17, 2^17) (the key of that point is -1), bit 1: a row that belongs to no batch
+ *                    element.  `points` == NULL: the keys are the caller's own codes, only the status is cleared.
+ *   wcn_voxel_map    `sorted_keys` int64 [n] (ascending) and `perm` int64 [n] of a STABLE sort -> `unique_keys` int64 [M],
+ *                    `unique_coords` int32 [M, 3] decoded from the keys (may be NULL), `csr_offsets` int64 [M + 1],
+ *                    `to_orig` int64 [n] (voxel of every point), `to_unique` int64 [M] (first point of every voxel = its
+ *                    smallest row), `batch_voxel_offsets` int32 [num_batches + 1] (voxels of the batch elements, from the
+ *                    key's batch field; may be NULL), `summary` int32 [2] = (M, longest segment).  Every array is the
+ *                    caller's, sized for M = n (csr_offsets n + 1); `perm` itself is the CSR's index list.  Tile sums ->
+ *                    one-workgroup scan -> apply: no kernel waits on another workgroup.  The host is not read or waited for.
+ *   wcn_csr_gather_reduce  out[s, :] = op over j in [offsets[s], offsets[s + 1]) of in[indices[j], :c], op 0 sum, 1 mean,
+ *                    2 max, 3 min; `in` has `n_in` rows of stride `ld_in` >= c elements, `indices` int64 [nnz] (NULL = the
+ *                    identity), `offsets` int64 [m + 1], `out` [m, c] and `in` of `dtype` (fp32 / fp16 / bf16), fp32
+ *                    accumulation, one rounding.  Rows of a segment are added in ascending j; a segment longer than
+ *                    wcn_csr_chunk_rows() = 256 rows is cut into chunks of that many rows, each added in ascending j into an
+ *                    fp32 partial, and the partials are added in chunk order: a row's bits depend on its segment alone.  No
+ *                    float atomics, no copy of in[indices].  max / min return the input element; `arg` int64 [m, c] (may
+ *                    be NULL, max / min only) receives the FIRST extremum's row indices[j], -1 for an empty segment, whose
+ *                    value is 0 (the wcn_segment_reduce convention).  `max_segment`: the longest segment if the caller
+ *                    knows it (the chunk passes and the workspace are skipped when it is <= 256), -1 if not.  16-B or 8-B
+ *                    pieces per lane when c, ld_in and both pointers allow, single elements otherwise; indices outside
+ *                    [0, n_in) and offsets outside [0, nnz] contribute nothing.
+ *   wcn_row_spread   out[i, :c] = scale(i) * src[to_orig[i], :], out[i, c:c + cs] = skip[i, :] (cs = 0: no second operand);
+ *                    `out` has row stride `ld_out` >= c + cs, src is [m, c], skip [n, cs].  mode 0: scale = 1; 1: scale =
+ *                    1 / (offsets[v + 1] - offsets[v]) for v = to_orig[i] (gradient of the mean); 2: out[i, ch] = src[v, ch]
+ *                    if arg[v, ch] == i, else 0 (gradient of max / min).  Every element is written exactly once.
+ * Arguments are checked before any launch: negative sizes, n / m / nnz > INT32_MAX, num_batches outside [1, 512] (0 allowed
+ * for wcn_voxel_map without batch_voxel_offsets), an inv_voxel_size that is not positive and finite, an op / mode outside the lists,
+ * ld_in < c, ld_out < c + cs, `arg` with sum / mean, a required pointer missing, sorted_keys or a workspace not 16-B aligned, a
+ * short workspace -> WCN_ERROR_INVALID_PARAMETERS; an unknown dtype -> WCN_ERROR_UNSUPPORTED_CONFIG.  A call with no row
+ * (n == 0, m == 0, c == 0) -> WCN_SUCCESS without a kernel launch (wcn_voxel_map still clears summary and the offsets). */
+int32_t wcn_csr_chunk_rows(void);
+int wcn_voxel_keys(const float* points, int64_t n, const int32_t* batch_offsets, int32_t num_batches, float inv_voxel_size,
+                   int64_t* keys, int32_t* status, wcn_stream_t stream);
+size_t wcn_voxel_map_workspace_bytes(int64_t n);
+int wcn_voxel_map(const int64_t* sorted_keys, const int64_t* perm, int64_t n, int32_t num_batches, int64_t* unique_keys,
+                  int32_t* unique_coords, int64_t* csr_offsets, int64_t* to_orig, int64_t* to_unique,
+                  int32_t* batch_voxel_offsets, int32_t* summary, void* workspace, size_t workspace_bytes,
+                  wcn_stream_t stream);
+size_t wcn_csr_gather_reduce_workspace_bytes(int64_t nnz, int32_t c, int32_t op);
+int wcn_csr_gather_reduce(const void* in, int64_t ld_in, int64_t n_in, const int64_t* indices, const int64_t* offsets,
+                          int64_t m, int64_t nnz, int32_t c, int32_t dtype, int32_t op, int64_t max_segment, void* out,
+                          int64_t* arg, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_row_spread(const void* src, const int64_t* to_orig, int64_t n, int64_t m, int32_t c, const void* skip, int32_t cs,
+                   int64_t ld_out, int32_t mode, const int64_t* offsets, const int64_t* arg, int32_t dtype, void* out,
+                   wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,6 +299,18 @@ SIGNATURES = {
     "wcn_window_group_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "wcn_window_group": (c_int, [c_void_p, c_int64, c_void_p, c_int32, _3I, _3I, _3I, _3I] + [c_void_p] * 7 +
                          [c_size_t, c_void_p]),
+    "wcn_csr_chunk_rows": (c_int32, []),
+    "wcn_voxel_keys": (c_int, [c_void_p, c_int64, c_void_p, c_int32, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "wcn_voxel_map_workspace_bytes": (c_size_t, [c_int64]),
+    "wcn_voxel_map": (c_int, [c_void_p, c_void_p, c_int64, c_int32] + [c_void_p] * 7 + [c_void_p, c_size_t, c_void_p]),
+    "wcn_csr_gather_reduce_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "wcn_csr_gather_reduce": (
+        c_int,
+        [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "wcn_row_spread": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p,
+                               c_void_p, c_int32, c_void_p, c_void_p]),
     "wcn_resample_pack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_void_p, c_void_p]),
     "wcn_resample_unpack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

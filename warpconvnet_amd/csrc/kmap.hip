@@ -262,7 +262,7 @@ extern "C" {
 //    wcn_kmap_scatter, wcn_kmap_compact_supported, wcn_kmap_densify, WCN_FLAG_ROW_OVERFLOW; mask = NULL in the gather GEMMs now means
 //    a compact table (wcn_conv_compact_table_supported replaces wcn_conv_mask_in_table_supported; dense rows no longer carry a mask)
 // 11 (additions only): wcn_window_group (window grouping of voxels by a deterministic counting sort, csrc/window_group.hip)
-int wcn_abi_version(void) { return 11; }
+int wcn_abi_version(void) { return 12; }
 
 const char* wcn_status_string(int status) {
   switch (status) {
