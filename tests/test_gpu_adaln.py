@@ -151,13 +151,14 @@ def _check_all(use, case, got, dtype, tag):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
-@pytest.mark.parametrize("c", [8, 72, 512, 2048])
+@pytest.mark.parametrize("c", [8, 72, 512, 520, 1032, 2048])
 @pytest.mark.parametrize("lens", [MIXED, SINGLE], ids=["mixed", "single"])
 @pytest.mark.parametrize("use", ["A", "B", "C"])
 def test_forward_backward_vs_fp64(use, lens, c, dtype):
     """Every segment's modulation vectors sit a large constant apart (8 in shift, 1.5 in scale and gate per segment): a row
     that took a neighbour's index - the rows next to the empty segments are the candidates - misses the bound by orders
-    of magnitude."""
+    of magnitude.  The widths hold one, two (520), three (1032) and four (2048) pieces a lane; 520 and 1032 are the
+    smallest of their kind: one lane of 64 holds the last piece, 63 a masked one."""
     case = _case(lens, c, dtype)
     got = _run(use, case, _dev())
     _check_all(use, case, got, dtype, f"C={c} {dtype}")

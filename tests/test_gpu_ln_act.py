@@ -123,9 +123,10 @@ def _check_all(case, got, dtype, tag):
 @pytest.mark.parametrize("act", ["none", "silu"])
 @pytest.mark.parametrize("affine", [True, False], ids=["affine", "plain"])
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
-@pytest.mark.parametrize("c", [8, 24, 64, 520, 2048])
+@pytest.mark.parametrize("c", [8, 24, 64, 520, 1032, 2048])
 def test_forward_backward_vs_fp64(c, dtype, affine, act):
-    """C = 24 leaves a lane of its group of 4 idle, 520 half-fills the second piece of every lane; every row count of ROWS."""
+    """C = 24 leaves a lane of its group of 4 idle, 520 half-fills the second piece of every lane, 1032 is the smallest
+    width with three pieces a lane (129 over 64 lanes: one lane holds a third, 63 a masked one); every row count of ROWS."""
     dev = _dev()
     for rows in ROWS:
         case = _case(rows, c, dtype, affine, act)

@@ -8,11 +8,10 @@
 // segment of the row: cu[b] <= t < cu[b+1], cu int32 [B + 1] on the device, empty segments allowed, never read on the host.
 // shift / scale / gate are fp32 [B, C] views with one row pitch (chunks of one [B, 6C] tensor).
 //
-// Launch shape.  A row is C / 8 pieces of 8 elements (one 16-B load of f16 / bf16, two of f32).  G = the power of two >=
-// min(C / 8, 64) lanes stand side by side on a row and hold it in registers, NCH = ceil(C / 8 / G) <= 4 pieces each; 64 / G
-// rows share a wave.  Sums over a row go across its G lanes with an xor butterfly (every lane ends with the same bits).
-// The variance is two-pass: the mean, then the sums of the deviations and of their squares - the first corrects the mean's
-// own rounding, which at |mean| >> sigma is what limits xhat.
+// Launch shape and row arithmetic are ada_row.h's, shared with ln_act.hip: G lanes stand side by side on a row and hold
+// it in registers, NCH <= 4 pieces of 8 elements each; row sums cross the G lanes with an xor butterfly; the variance is
+// two-pass.  Here is what is adaLN's own: the gated residual in front of the statistics, 1 + scale and shift behind them,
+// the segment of a row and the per-segment column sums.
 //   forward   the lane groups stride over the rows; writes stats [T, 2] = (mean, rstd) for the backward.
 //   backward  reads x, not the rounded x1 the forward wrote: x1 = x + h * gate[b] is formed again in fp32, so xhat is the
 //             forward's at the same bytes per element.  Lane group u owns the chunk of kAdaChunk consecutive rows u and
@@ -24,7 +23,6 @@
 #include <limits.h>
 
 #include "ada_row.h"
-#include "wcn_common.h"
 
 namespace wcn {
 
@@ -42,23 +40,21 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_fwd_kernel(const T* __restr
                                                                 const float* __restrict__ scale, const int32_t* __restrict__ cu,
                                                                 T* __restrict__ x1, T* __restrict__ y,
                                                                 float* __restrict__ stats, const AdaGeom g) {
-  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
-  const int64_t unit = v >> g.glog;
-  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
-  const int C = g.channels, nvec = C >> 3;
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
   const float fc = (float)C;
 
   // every lane of a wave walks the same number of trips: the butterfly needs its partners
   for (int64_t t0 = 0; t0 < g.rows; t0 += g.units) {
-    const int64_t t = t0 + unit;
+    const int64_t t = t0 + l.unit;
     const bool act = t < g.rows;
     const int b = act ? last_offset_not_above(cu, g.num_segs, t) : 0;
     float f[NCH][8];
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (act && c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
         const int64_t at = t * C + c * 8;
         ada_ld8(x + at, f[k]);
         if constexpr (RES) {
@@ -77,34 +73,25 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_fwd_kernel(const T* __restr
       }
     }
     if constexpr (NORM) {
-      float mean = ada_group_sum(s, g.glog) / fc;  // a division: a constant row's mean is the constant, exactly
+      const float mean = row_mean(s, g.glog, fc);
       float sd = 0.f, ss = 0.f;
 #pragma unroll
       for (int k = 0; k < NCH; ++k) {
-        const bool m = act && gl + k * G < nvec;
+        const bool m = act && l.gl + k * l.G < l.nvec;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = m ? f[k][e] - mean : 0.f;
-          f[k][e] = d;
-          sd += d;
-          ss += d * d;
-        }
+        for (int e = 0; e < 8; ++e) row_dev(&f[k][e], m, mean, sd, ss);
       }
-      const float delta = ada_group_sum(sd, g.glog) / fc;  // what the rounded mean missed
-      ss = ada_group_sum(ss, g.glog) / fc;
-      const float var = fmaxf(ss - delta * delta, 0.f);
-      const float rstd = 1.0f / sqrtf(var + g.eps);
-      mean += delta;
-      if (act && gl == 0) *reinterpret_cast<float2*>(stats + 2 * t) = make_float2(mean, rstd);
+      const RowStats st = row_stats(mean, sd, ss, g.glog, fc, g.eps);
+      if (act && l.gl == 0) row_stats_st(stats, t, st);
 #pragma unroll
       for (int k = 0; k < NCH; ++k) {
-        const int c = gl + k * G;
-        if (act && c < nvec) {
+        const int c = l.gl + k * l.G;
+        if (act && c < l.nvec) {
           float sc[8], sh[8], o[8];
           ada_ld8(scale + b * g.mod_ld + c * 8, sc);
           ada_ld8(shift + b * g.mod_ld + c * 8, sh);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - delta) * rstd * (1.0f + sc[e]) + sh[e];
+          for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - st.delta) * st.rstd * (1.0f + sc[e]) + sh[e];
           ada_st8(y + t * C + c * 8, o);
         }
       }
@@ -120,12 +107,10 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
                                                                 const float* __restrict__ stats, const int32_t* __restrict__ cu,
                                                                 T* __restrict__ dx, T* __restrict__ dh,
                                                                 float* __restrict__ partial, const AdaGeom g) {
-  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
-  const int64_t unit = v >> g.glog;
-  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
-  const int C = g.channels, nvec = C >> 3;
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
   const float inv_c = 1.0f / (float)C;
-  const bool live = unit < g.units;
+  const bool live = l.unit < g.units;
   const bool has_dx1 = dx1 != nullptr;  // the same in every lane
 
   float a_gate[RES ? NCH : 1][8], a_shift[NORM ? NCH : 1][8], a_scale[NORM ? NCH : 1][8];
@@ -139,11 +124,11 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
 
   // the lane's sums -> slot unit + seg, then zero
   auto flush = [&](int seg) {
-    float* p = partial + (unit + seg) * 3 * (int64_t)C;
+    float* p = partial + (l.unit + seg) * 3 * (int64_t)C;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (c < l.nvec) {
         if constexpr (RES) ada_st8(p + c * 8, a_gate[k]);
         if constexpr (NORM) { ada_st8(p + C + c * 8, a_shift[k]); ada_st8(p + 2 * C + c * 8, a_scale[k]); }
       }
@@ -159,7 +144,7 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
   int64_t next = 0;        // cu[b + 1], or never
 #pragma unroll 1
   for (int i = 0; i < kAdaChunk; ++i) {
-    const int64_t t = unit * kAdaChunk + i;
+    const int64_t t = l.unit * kAdaChunk + i;
     const bool act = live && t < g.rows;
     if (act) {
       int nb = b;
@@ -182,15 +167,11 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
     float hk[NORM && RES ? NCH : 1][8];
     float mean = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
     if constexpr (NORM) {
-      if (act) {
-        const float2 st = *reinterpret_cast<const float2*>(stats + 2 * t);
-        mean = st.x;
-        rstd = st.y;
-      }
+      if (act) row_stats_ld(stats, t, mean, rstd);
 #pragma unroll
       for (int k = 0; k < NCH; ++k) {
-        const int c = gl + k * G;
-        if (act && c < nvec) {
+        const int c = l.gl + k * l.G;
+        if (act && c < l.nvec) {
           const int64_t at = t * C + c * 8;
           float xv[8], sc[8];
           ada_ld8(dy + at, gd[k]);
@@ -206,7 +187,7 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float d = gd[k][e];
-            xh[k][e] = (xv[e] - mean) * rstd;
+            xh[k][e] = row_xhat(xv[e], mean, rstd);
             a_shift[k][e] += d;
             a_scale[k][e] += d * xh[k][e];
             gd[k][e] = d * (1.0f + sc[e]);
@@ -218,13 +199,13 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
           for (int e = 0; e < 8; ++e) { gd[k][e] = 0.f; xh[k][e] = 0.f; }
         }
       }
-      s1 = ada_group_sum(s1, g.glog) * inv_c;
-      s2 = ada_group_sum(s2, g.glog) * inv_c;
+      s1 = row_mean_rcp(s1, g.glog, inv_c);
+      s2 = row_mean_rcp(s2, g.glog, inv_c);
     }
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (act && c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
         const int64_t at = t * C + c * 8;
         float r[8];
         if (has_dx1) {
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
         }
         if constexpr (NORM) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) r[e] += rstd * (gd[k][e] - s1 - xh[k][e] * s2);
+          for (int e = 0; e < 8; ++e) r[e] += row_dx(rstd, gd[k][e], xh[k][e], s1, s2);
         }
         if (NORM || dx != nullptr) ada_st8(dx + at, r);
         if constexpr (RES) {
@@ -292,22 +273,17 @@ __global__ __launch_bounds__(256) void adaln_final_kernel(const float* __restric
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static bool ada_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 static AdaGeom ada_geom(int64_t rows, int64_t num_segs, int channels, int64_t mod_ld, float eps) {
   AdaGeom g;
-  const int nvec = channels / 8;
-  g.glog = 0;
-  while ((1 << g.glog) < nvec && g.glog < 6) ++g.glog;
   g.rows = rows;
   g.units = 0;
   g.mod_ld = mod_ld;
   g.channels = channels;
   g.num_segs = (int)num_segs;
+  g.glog = row_glog(channels / 8);
   g.eps = eps;
   return g;
 }
-static int ada_nch(const AdaGeom& g) { return (int)ceil_div(g.channels / 8, 1 << g.glog); }
 
 // Shared argument checks.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing to launch.
 static int ada_check(int64_t rows, int64_t num_segs, int32_t channels, int32_t dtype, bool norm, bool res, bool paired,
@@ -323,38 +299,22 @@ static int ada_check(int64_t rows, int64_t num_segs, int32_t channels, int32_t d
 template <typename T, bool NORM, bool RES>
 static int ada_fwd_t(const void* x, const void* h, const float* gate, const float* shift, const float* scale,
                      const int32_t* cu, void* x1, void* y, float* stats, AdaGeom g, hipStream_t s) {
-  const int64_t per_block = kAdaThreads >> g.glog;
-  int64_t blocks = ceil_div(g.rows, per_block);
-  if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
-  g.units = blocks * per_block;
-#define WCN_ADA_FWD(NCH)                                                                                               \
-  hipLaunchKernelGGL((adaln_fwd_kernel<T, NCH, NORM, RES>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)x, \
-                     (const T*)h, gate, shift, scale, cu, (T*)x1, (T*)y, stats, g)
-  switch (ada_nch(g)) {
-    case 1: WCN_ADA_FWD(1); break;
-    case 2: WCN_ADA_FWD(2); break;
-    case 3: WCN_ADA_FWD(3); break;
-    default: WCN_ADA_FWD(4); break;
-  }
-#undef WCN_ADA_FWD
+  const unsigned blocks = row_fwd_grid(g.rows, g.glog, &g.units);
+  row_with_nch(g.channels, g.glog, [&](auto nch) {
+    hipLaunchKernelGGL((adaln_fwd_kernel<T, nch(), NORM, RES>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)x,
+                       (const T*)h, gate, shift, scale, cu, (T*)x1, (T*)y, stats, g);
+  });
   return launch_status();
 }
 
 template <typename T, bool NORM, bool RES>
 static int ada_bwd_t(const void* dx1, const void* dy, const void* x, const void* h, const float* gate, const float* scale,
                      const float* stats, const int32_t* cu, void* dx, void* dh, float* partial, AdaGeom g, hipStream_t s) {
-  g.units = ceil_div(g.rows, kAdaChunk);
-  const int64_t blocks = ceil_div(g.units, kAdaThreads >> g.glog);
-#define WCN_ADA_BWD(NCH)                                                                                                  \
-  hipLaunchKernelGGL((adaln_bwd_kernel<T, NCH, NORM, RES>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)dx1, \
-                     (const T*)dy, (const T*)x, (const T*)h, gate, scale, stats, cu, (T*)dx, (T*)dh, partial, g)
-  switch (ada_nch(g)) {
-    case 1: WCN_ADA_BWD(1); break;
-    case 2: WCN_ADA_BWD(2); break;
-    case 3: WCN_ADA_BWD(3); break;
-    default: WCN_ADA_BWD(4); break;
-  }
-#undef WCN_ADA_BWD
+  const unsigned blocks = row_bwd_grid(g.rows, g.glog, &g.units);
+  row_with_nch(g.channels, g.glog, [&](auto nch) {
+    hipLaunchKernelGGL((adaln_bwd_kernel<T, nch(), NORM, RES>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)dx1,
+                       (const T*)dy, (const T*)x, (const T*)h, gate, scale, stats, cu, (T*)dx, (T*)dh, partial, g);
+  });
   return launch_status();
 }
 
@@ -362,19 +322,15 @@ static int ada_bwd_t(const void* dx1, const void* dy, const void* x, const void*
 #define WCN_ADA_USES(FN, T, ...)                                      \
   (norm && res ? FN<T, true, true>(__VA_ARGS__)                       \
                : norm ? FN<T, true, false>(__VA_ARGS__) : FN<T, false, true>(__VA_ARGS__))
-#define WCN_ADA_DTYPES(FN, ...)                                                           \
-  (dtype == WCN_F32 ? WCN_ADA_USES(FN, float, __VA_ARGS__)                                \
-                    : dtype == WCN_F16 ? WCN_ADA_USES(FN, _Float16, __VA_ARGS__) : WCN_ADA_USES(FN, __bf16, __VA_ARGS__))
+#define WCN_ADA_DTYPES(FN, ...) \
+  row_with_dtype(dtype, [&](auto el) { return WCN_ADA_USES(FN, decltype(el), __VA_ARGS__); })
 
 }  // namespace wcn
 
 using namespace wcn;
 
 int wcn_adaln_supported(int32_t channels, int32_t dtype) {
-  return channels >= 8 && channels % 8 == 0 && channels <= kAdaMaxChannels &&
-                 (dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16)
-             ? 1
-             : 0;
+  return channels >= 8 && channels % 8 == 0 && channels <= kAdaMaxChannels && dtype_ok(dtype) ? 1 : 0;
 }
 
 size_t wcn_adaln_workspace_bytes(int64_t rows, int64_t num_segs, int32_t channels) {
@@ -391,9 +347,9 @@ int wcn_adaln_fwd(const void* x, const void* h, const float* gate, const float* 
   if ((st == WCN_SUCCESS || st == 1) && !(eps >= 0.f)) st = WCN_ERROR_INVALID_PARAMETERS;
   if (st == WCN_SUCCESS) {
     if (!x || !cu || (res && !x1) || (norm && (!y || !stats))) st = WCN_ERROR_INVALID_PARAMETERS;
-    else if (!ada_aligned(x, 16) || !ada_aligned(h, 16) || !ada_aligned(gate, 16) || !ada_aligned(shift, 16) ||
-             !ada_aligned(scale, 16) || !ada_aligned(x1, 16) || !ada_aligned(y, 16) || !ada_aligned(stats, 8) ||
-             !ada_aligned(cu, 4))
+    else if (!aligned_to(x, 16) || !aligned_to(h, 16) || !aligned_to(gate, 16) || !aligned_to(shift, 16) ||
+             !aligned_to(scale, 16) || !aligned_to(x1, 16) || !aligned_to(y, 16) || !aligned_to(stats, 8) ||
+             !aligned_to(cu, 4))
       st = WCN_ERROR_INVALID_PARAMETERS;
   }
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
@@ -415,10 +371,10 @@ int wcn_adaln_bwd(const void* dx1, const void* dy, const void* x, const void* h,
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st == WCN_SUCCESS) {
     if (!cu || !workspace || (!norm && !dx1) || (norm && (!x || !stats || !dx)) || (res && !dh)) st = WCN_ERROR_INVALID_PARAMETERS;
-    else if (!ada_aligned(dx1, 16) || !ada_aligned(dy, 16) || !ada_aligned(x, 16) || !ada_aligned(h, 16) ||
-             !ada_aligned(gate, 16) || !ada_aligned(scale, 16) || !ada_aligned(stats, 8) || !ada_aligned(cu, 4) ||
-             !ada_aligned(dx, 16) || !ada_aligned(dh, 16) || !ada_aligned(dgate, 4) || !ada_aligned(dshift, 4) ||
-             !ada_aligned(dscale, 4) || !ada_aligned(workspace, 16))
+    else if (!aligned_to(dx1, 16) || !aligned_to(dy, 16) || !aligned_to(x, 16) || !aligned_to(h, 16) ||
+             !aligned_to(gate, 16) || !aligned_to(scale, 16) || !aligned_to(stats, 8) || !aligned_to(cu, 4) ||
+             !aligned_to(dx, 16) || !aligned_to(dh, 16) || !aligned_to(dgate, 4) || !aligned_to(dshift, 4) ||
+             !aligned_to(dscale, 4) || !aligned_to(workspace, 16))
       st = WCN_ERROR_INVALID_PARAMETERS;
   }
   hipStream_t s = (hipStream_t)stream;

@@ -610,7 +610,6 @@ static AttnCall attn_packed_call(const void* qkv, const int32_t* cu, int64_t num
                   max_seqlen, max_seqlen, scale};
 }
 
-static inline bool attn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Checks of the separate-operand form (both directions).  Same return convention as attn_check; "nothing to launch" is
 // left to the caller, which knows what each direction writes.
@@ -625,7 +624,7 @@ static int attn_kv_check(const void* q, int64_t q_stride, const void* k, const v
   if (!wcn_attn_varlen_supported(head_dim, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   const int64_t hd = (int64_t)heads * head_dim;
   if (q_stride < hd || kv_stride < hd || (q_stride & 7) || (kv_stride & 7)) return WCN_ERROR_INVALID_PARAMETERS;
-  if (!attn_aligned16(q) || !attn_aligned16(k) || !attn_aligned16(v)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16)) return WCN_ERROR_INVALID_PARAMETERS;
   return WCN_SUCCESS;
 }
 
@@ -700,7 +699,7 @@ int wcn_attn_varlen_kv_fwd(const void* q, int64_t q_stride, const void* k, const
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
   if (st != WCN_SUCCESS) return st;
-  if (total_q > 0 && (!out || !lse || !attn_aligned16(out))) return WCN_ERROR_INVALID_PARAMETERS;
+  if (total_q > 0 && (!out || !lse || !aligned_to(out, 16))) return WCN_ERROR_INVALID_PARAMETERS;
   if (num_seqs == 0 || total_q == 0 || max_seqlen_q == 0) return WCN_SUCCESS;
   const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
                    softmax_scale};
@@ -720,8 +719,8 @@ int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, co
   if (q_splits < 0 || dq_stride < hd || dkv_stride < hd || (dq_stride & 7) || (dkv_stride & 7)) return WCN_ERROR_INVALID_PARAMETERS;
   if (total_q > 0 && (!dout || !out || !lse || !dq)) return WCN_ERROR_INVALID_PARAMETERS;
   if (total_k > 0 && (!dk || !dv)) return WCN_ERROR_INVALID_PARAMETERS;
-  if (!attn_aligned16(dout) || !attn_aligned16(out) || !attn_aligned16(dq) || !attn_aligned16(dk) || !attn_aligned16(dv) ||
-      !attn_aligned16(workspace))
+  if (!aligned_to(dout, 16) || !aligned_to(out, 16) || !aligned_to(dq, 16) || !aligned_to(dk, 16) || !aligned_to(dv, 16) ||
+      !aligned_to(workspace, 16))
     return WCN_ERROR_INVALID_PARAMETERS;
   if (q_splits == 0) q_splits = wcn_attn_varlen_kv_splits(num_seqs, max_seqlen_q, max_seqlen_k, heads);
   const size_t need = wcn_attn_varlen_kv_workspace_bytes(total_q, total_k, heads, head_dim, q_splits);

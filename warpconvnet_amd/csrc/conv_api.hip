@@ -37,7 +37,6 @@ int segment_reduce(const void* in, const int64_t* splits, int64_t m, int c, int 
 using namespace wcn;
 
 static inline size_t dtype_size(int dtype) { return dtype == WCN_F32 ? 4 : 2; }
-static inline bool dtype_ok(int dtype) { return dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16; }
 
 extern "C" {
 

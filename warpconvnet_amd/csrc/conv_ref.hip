@@ -10,20 +10,6 @@
 
 namespace wcn {
 
-template <typename T> struct Cvt;
-template <> struct Cvt<float> {
-  static __device__ __forceinline__ float ld(const float* p) { return *p; }
-  static __device__ __forceinline__ void st(float* p, float v) { *p = v; }
-};
-template <> struct Cvt<__half> {
-  static __device__ __forceinline__ float ld(const __half* p) { return __half2float(*p); }
-  static __device__ __forceinline__ void st(__half* p, float v) { *p = __float2half(v); }
-};
-template <> struct Cvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(const __hip_bfloat16* p) { return __bfloat162float(*p); }
-  static __device__ __forceinline__ void st(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
-};
-
 // out[r][co] = sum_k sum_ci in[tbl[r][kt]][ci] * W(kw, ci, co); one thread per (row, co).
 template <typename T>
 __global__ __launch_bounds__(256) void gather_gemm_ref_kernel(const T* __restrict__ in, const T* __restrict__ w,
@@ -43,14 +29,15 @@ __global__ __launch_bounds__(256) void gather_gemm_ref_kernel(const T* __restric
     const T* xin = in + (int64_t)idx * cin;
     if (!w_transposed) {
       const T* wk = w + (int64_t)kw * cin * cout + co;  // w[kw][ci][co]
-      for (int ci = 0; ci < cin; ++ci) acc += Cvt<T>::ld(xin + ci) * Cvt<T>::ld(wk + (int64_t)ci * cout);
+      for (int ci = 0; ci < cin; ++ci) acc += Cvt<T>::ld(xin[ci]) * Cvt<T>::ld(wk[(int64_t)ci * cout]);
     } else {
       const T* wk = w + ((int64_t)kw * cout + co) * cin;  // w_fwd[kw][co][ci]
-      for (int ci = 0; ci < cin; ++ci) acc += Cvt<T>::ld(xin + ci) * Cvt<T>::ld(wk + ci);
+      for (int ci = 0; ci < cin; ++ci) acc += Cvt<T>::ld(xin[ci]) * Cvt<T>::ld(wk[ci]);
     }
   }
   if (bias) acc += bias[co];
-  Cvt<T>::st(out + e, acc);
+  T* dst = out + e;
+  *dst = Cvt<T>::st(acc);
 }
 
 // colsum[c] = sum_r in[r][c] (fp32): bias gradient.  Two deterministic passes: per-workgroup partial sums over a
@@ -80,9 +67,9 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict
           T tmp[VEC];
           *reinterpret_cast<uint4*>(tmp) = *reinterpret_cast<const uint4*>(p);  // VEC * sizeof(T) == 16
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(tmp + v);
+          for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(tmp[v]);
         } else {
-          acc[0] += Cvt<T>::ld(p);
+          acc[0] += Cvt<T>::ld(*p);
         }
       }
     }
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(256) void wgrad_ref_kernel(const T* __restrict__ x,
   const int p0 = offsets[k], p1 = offsets[k + 1];
   float acc = 0.f;
   for (int p = p0; p < p1; ++p)
-    acc += Cvt<T>::ld(x + (int64_t)in_maps[p] * cin + ci) * Cvt<T>::ld(dy + (int64_t)out_maps[p] * cout + co);
+    acc += Cvt<T>::ld(x[(int64_t)in_maps[p] * cin + ci]) * Cvt<T>::ld(dy[(int64_t)out_maps[p] * cout + co]);
   dw[e] = acc;
 }
 
@@ -158,7 +145,7 @@ size_t colsum_workspace(int c) { return (size_t)kColsumBlocks * c * sizeof(float
 template <typename T>
 static int launch_colsum(const void* in, int64_t n, int c, float* out, float* partial, hipStream_t s) {
   constexpr int kVec = 16 / sizeof(T);
-  if (sizeof(T) == 2 && c % kVec == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0)
+  if (sizeof(T) == 2 && c % kVec == 0 && aligned_to(in, 16))
     hipLaunchKernelGGL((colsum_partial_kernel<T, (sizeof(T) == 2 ? 8 : 1)>), dim3(kColsumBlocks), dim3(256), 0, s,
                        (const T*)in, n, c, partial);
   else

@@ -20,20 +20,6 @@
 
 namespace wcn {
 
-template <typename T> struct DwCvt;
-template <> struct DwCvt<float> {
-  static __device__ __forceinline__ float ld(float v) { return v; }
-  static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct DwCvt<__half> {
-  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
-};
-template <> struct DwCvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
-};
-
 constexpr int kDwThreads = 256;
 constexpr int kDwMaxLdsWeights = 12 * 1024;  // elements of w kept in LDS by the fast kernels
 
@@ -72,13 +58,13 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_gather_kernel(const T* __re
         *reinterpret_cast<uint4*>(xv) = *reinterpret_cast<const uint4*>(in + (int64_t)idx * C + piece * VEC);
         *reinterpret_cast<uint4*>(wv) = *reinterpret_cast<const uint4*>(s_w + kw * C + piece * VEC);
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] += DwCvt<T>::ld(xv[v]) * DwCvt<T>::ld(wv[v]);
+        for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(xv[v]) * Cvt<T>::ld(wv[v]);
       }
     }
     if (live) {
       T ov[VEC];
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) ov[v] = DwCvt<T>::st(acc[v] + (bias ? bias[piece * VEC + v] : 0.f));
+      for (int v = 0; v < VEC; ++v) ov[v] = Cvt<T>::st(acc[v] + (bias ? bias[piece * VEC + v] : 0.f));
       *reinterpret_cast<uint4*>(out + r * C + piece * VEC) = *reinterpret_cast<const uint4*>(ov);
     }
   }
@@ -100,9 +86,9 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_gather_generic_kernel(const
     const int32_t idx = tbl[r * kp + kt];
     if (idx < 0) continue;
     const int kw = k_flip ? (K - 1 - kt) : kt;
-    acc += DwCvt<T>::ld(in[(int64_t)idx * C + c]) * DwCvt<T>::ld(w[(int64_t)kw * C + c]);
+    acc += Cvt<T>::ld(in[(int64_t)idx * C + c]) * Cvt<T>::ld(w[(int64_t)kw * C + c]);
   }
-  out[e] = DwCvt<T>::st(acc + (bias ? bias[c] : 0.f));
+  out[e] = Cvt<T>::st(acc + (bias ? bias[c] : 0.f));
 }
 
 // ---- wgrad ---------------------------------------------------------------------------------------------------------------
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_wgrad_kernel(const T* __res
     *reinterpret_cast<uint4*>(xv) = *reinterpret_cast<const uint4*>(x + (int64_t)i * C + piece * VEC);
     *reinterpret_cast<uint4*>(gv) = *reinterpret_cast<const uint4*>(dy + (int64_t)o * C + piece * VEC);
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] += DwCvt<T>::ld(xv[v]) * DwCvt<T>::ld(gv[v]);
+    for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(xv[v]) * Cvt<T>::ld(gv[v]);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) s_acc[grp * C + piece * VEC + v] = acc[v];
@@ -162,7 +148,7 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_wgrad_generic_kernel(const 
   for (int c = threadIdx.x; c < C; c += kDwThreads) {
     float t = 0.f;
     for (int64_t p = p0; p < p1; ++p)
-      t += DwCvt<T>::ld(x[(int64_t)in_maps[p] * C + c]) * DwCvt<T>::ld(dy[(int64_t)out_maps[p] * C + c]);
+      t += Cvt<T>::ld(x[(int64_t)in_maps[p] * C + c]) * Cvt<T>::ld(dy[(int64_t)out_maps[p] * C + c]);
     partial[((int64_t)k * kDwSplits + s) * C + c] = t;
   }
 }

@@ -1,8 +1,9 @@
 // ln_act.hip - the per-voxel glue of the sparse U-Net residual blocks (reference: nn/modules/sparse_unet.py runs, between
 // two convolutions, x.float() -> layer_norm -> .to(dtype) -> silu as five or six [N, C] passes, and closes with
 // h + repeat_interleave(x) or h + reshape(...).mean(-1)).  One row-streaming pass per site and direction:
-//   LN (+ affine) (+ SiLU)   y = act(LN(x) * weight + bias), biased variance, fp32, rounded once; the launch shape and the
-//                            two-pass variance of adaln.hip (ada_row.h: G lanes hold a row in registers, <= 4 pieces each).
+//   LN (+ affine) (+ SiLU)   y = act(LN(x) * weight + bias), biased variance, fp32, rounded once; launch shape, two-pass
+//                            statistics and backward row step are ada_row.h's (G lanes hold a row in registers, <= 4
+//                            pieces each), as in adaln.hip; here are the affine pair, SiLU and their column sums.
 //     forward   the lane groups stride over the rows; writes stats [rows, 2] = (mean, rstd).
 //     backward  z = xhat * weight + bias is formed again in fp32 from x and stats, never read back from the rounded y.
 //               Lane group u owns the kAdaChunk rows of chunk u, keeps the column sums of dweight / dbias in registers and
@@ -35,22 +36,20 @@ template <typename T, int NCH, bool AFFINE, bool SILU>
 __global__ __launch_bounds__(kAdaThreads) void ln_act_fwd_kernel(const T* __restrict__ x, const float* __restrict__ weight,
                                                                  const float* __restrict__ bias, T* __restrict__ y,
                                                                  float* __restrict__ stats, const LnGeom g) {
-  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
-  const int64_t unit = v >> g.glog;
-  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
-  const int C = g.channels, nvec = C >> 3;
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
   const float fc = (float)C;
 
   // every lane of a wave walks the same number of trips: the butterfly needs its partners
   for (int64_t t0 = 0; t0 < g.rows; t0 += g.units) {
-    const int64_t t = t0 + unit;
+    const int64_t t = t0 + l.unit;
     const bool act = t < g.rows;
     float f[NCH][8];
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (act && c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
         ada_ld8(x + t * C + c * 8, f[k]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += f[k][e];
@@ -59,32 +58,23 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_fwd_kernel(const T* __rest
         for (int e = 0; e < 8; ++e) f[k][e] = 0.f;
       }
     }
-    float mean = ada_group_sum(s, g.glog) / fc;  // a division: a constant row's mean is the constant, exactly
+    const float mean = row_mean(s, g.glog, fc);
     float sd = 0.f, ss = 0.f;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const bool m = act && gl + k * G < nvec;
+      const bool m = act && l.gl + k * l.G < l.nvec;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float d = m ? f[k][e] - mean : 0.f;
-        f[k][e] = d;
-        sd += d;
-        ss += d * d;
-      }
+      for (int e = 0; e < 8; ++e) row_dev(&f[k][e], m, mean, sd, ss);
     }
-    const float delta = ada_group_sum(sd, g.glog) / fc;  // what the rounded mean missed
-    ss = ada_group_sum(ss, g.glog) / fc;
-    const float var = fmaxf(ss - delta * delta, 0.f);
-    const float rstd = 1.0f / sqrtf(var + g.eps);
-    mean += delta;
-    if (act && gl == 0) *reinterpret_cast<float2*>(stats + 2 * t) = make_float2(mean, rstd);
+    const RowStats st = row_stats(mean, sd, ss, g.glog, fc, g.eps);
+    if (act && l.gl == 0) row_stats_st(stats, t, st);
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (act && c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
         float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - delta) * rstd;
+        for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - st.delta) * st.rstd;
         if constexpr (AFFINE) {
           float w[8], b[8];
           ada_ld8(weight + c * 8, w);
@@ -109,12 +99,10 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
                                                                  const float* __restrict__ bias,
                                                                  const float* __restrict__ stats, T* __restrict__ dx,
                                                                  float* __restrict__ partial, const LnGeom g) {
-  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
-  const int64_t unit = v >> g.glog;
-  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
-  const int C = g.channels, nvec = C >> 3;
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
   const float inv_c = 1.0f / (float)C;
-  const bool live = unit < g.units;
+  const bool live = l.unit < g.units;
 
   float a_w[AFFINE ? NCH : 1][8], a_b[AFFINE ? NCH : 1][8];
   if constexpr (AFFINE) {
@@ -126,19 +114,15 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
 
 #pragma unroll 1
   for (int i = 0; i < kAdaChunk; ++i) {
-    const int64_t t = unit * kAdaChunk + i;
+    const int64_t t = l.unit * kAdaChunk + i;
     const bool act = live && t < g.rows;
     float gd[NCH][8], xh[NCH][8];  // g * weight; xhat
     float mean = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
-    if (act) {
-      const float2 st = *reinterpret_cast<const float2*>(stats + 2 * t);
-      mean = st.x;
-      rstd = st.y;
-    }
+    if (act) row_stats_ld(stats, t, mean, rstd);
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (act && c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
         const int64_t at = t * C + c * 8;
         float xv[8], w[8], b[8];
         ada_ld8(dy + at, gd[k]);
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float d = gd[k][e];
-          xh[k][e] = (xv[e] - mean) * rstd;
+          xh[k][e] = row_xhat(xv[e], mean, rstd);
           if constexpr (SILU) {
             float z = xh[k][e];
             if constexpr (AFFINE) z = z * w[e] + b[e];
@@ -171,26 +155,26 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
         for (int e = 0; e < 8; ++e) { gd[k][e] = 0.f; xh[k][e] = 0.f; }
       }
     }
-    s1 = ada_group_sum(s1, g.glog) * inv_c;
-    s2 = ada_group_sum(s2, g.glog) * inv_c;
+    s1 = row_mean_rcp(s1, g.glog, inv_c);
+    s2 = row_mean_rcp(s2, g.glog, inv_c);
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-      const int c = gl + k * G;
-      if (act && c < nvec) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
         float r[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] = rstd * (gd[k][e] - s1 - xh[k][e] * s2);
+        for (int e = 0; e < 8; ++e) r[e] = row_dx(rstd, gd[k][e], xh[k][e], s1, s2);
         ada_st8(dx + t * C + c * 8, r);
       }
     }
   }
   if constexpr (AFFINE) {
     if (live) {  // every chunk has a row, and every column of its slot a lane
-      float* p = partial + unit * 2 * (int64_t)C;
+      float* p = partial + l.unit * 2 * (int64_t)C;
 #pragma unroll
       for (int k = 0; k < NCH; ++k) {
-        const int c = gl + k * G;
-        if (c < nvec) {
+        const int c = l.gl + k * l.G;
+        if (c < l.nvec) {
           ada_st8(p + c * 8, a_w[k]);
           ada_st8(p + C + c * 8, a_b[k]);
         }
@@ -242,13 +226,10 @@ template <typename T> __device__ __forceinline__ float skip_ld(const T* p) { ret
 template <typename T, int R, bool FOLD>
 __global__ __launch_bounds__(kAdaThreads) void channel_pieces_kernel(const T* __restrict__ x, const T* __restrict__ h,
                                                                      T* __restrict__ out, const SkipGeom g) {
-  const int64_t v = (int64_t)blockIdx.x * kAdaThreads + threadIdx.x;
-  const int64_t unit = v >> g.glog;
-  const int gl = (int)(v & ((1 << g.glog) - 1)), G = 1 << g.glog;
-  const int npiece = g.cout >> 3;
+  const RowLane l = row_lane(g.glog, g.cout);
   const int64_t cx = FOLD ? (int64_t)g.cout * R : g.cout / R;  // channels of a row of x
-  for (int64_t t = unit; t < g.rows; t += g.units) {
-    for (int p = gl; p < npiece; p += G) {
+  for (int64_t t = l.unit; t < g.rows; t += g.units) {
+    for (int p = l.gl; p < l.nvec; p += l.G) {
       float o[8];
       if constexpr (FOLD) {
         float f[R][8];
@@ -309,20 +290,15 @@ __global__ __launch_bounds__(kAdaThreads) void channel_elements_kernel(const T* 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static bool ln_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 static LnGeom ln_geom(int64_t rows, int channels, float eps) {
   LnGeom g;
-  const int nvec = channels / 8;
-  g.glog = 0;
-  while ((1 << g.glog) < nvec && g.glog < 6) ++g.glog;
   g.rows = rows;
   g.units = 0;
   g.channels = channels;
+  g.glog = row_glog(channels / 8);
   g.eps = eps;
   return g;
 }
-static int ln_nch(const LnGeom& g) { return (int)ceil_div(g.channels / 8, 1 << g.glog); }
 
 // Shared argument checks.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing to launch.
 static int ln_check(int64_t rows, int32_t channels, int32_t dtype, int32_t act, const float* weight, const float* bias) {
@@ -335,38 +311,22 @@ static int ln_check(int64_t rows, int32_t channels, int32_t dtype, int32_t act, 
 
 template <typename T, bool AFFINE, bool SILU>
 static int ln_fwd_t(const void* x, const float* weight, const float* bias, void* y, float* stats, LnGeom g, hipStream_t s) {
-  const int64_t per_block = kAdaThreads >> g.glog;
-  int64_t blocks = ceil_div(g.rows, per_block);
-  if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
-  g.units = blocks * per_block;
-#define WCN_LN_FWD(NCH)                                                                                                   \
-  hipLaunchKernelGGL((ln_act_fwd_kernel<T, NCH, AFFINE, SILU>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)x, \
-                     weight, bias, (T*)y, stats, g)
-  switch (ln_nch(g)) {
-    case 1: WCN_LN_FWD(1); break;
-    case 2: WCN_LN_FWD(2); break;
-    case 3: WCN_LN_FWD(3); break;
-    default: WCN_LN_FWD(4); break;
-  }
-#undef WCN_LN_FWD
+  const unsigned blocks = row_fwd_grid(g.rows, g.glog, &g.units);
+  row_with_nch(g.channels, g.glog, [&](auto nch) {
+    hipLaunchKernelGGL((ln_act_fwd_kernel<T, nch(), AFFINE, SILU>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)x,
+                       weight, bias, (T*)y, stats, g);
+  });
   return launch_status();
 }
 
 template <typename T, bool AFFINE, bool SILU>
 static int ln_bwd_t(const void* dy, const void* x, const float* weight, const float* bias, const float* stats, void* dx,
                     float* partial, LnGeom g, hipStream_t s) {
-  g.units = ceil_div(g.rows, kAdaChunk);
-  const int64_t blocks = ceil_div(g.units, kAdaThreads >> g.glog);
-#define WCN_LN_BWD(NCH)                                                                                                    \
-  hipLaunchKernelGGL((ln_act_bwd_kernel<T, NCH, AFFINE, SILU>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, (const T*)dy, \
-                     (const T*)x, weight, bias, stats, (T*)dx, partial, g)
-  switch (ln_nch(g)) {
-    case 1: WCN_LN_BWD(1); break;
-    case 2: WCN_LN_BWD(2); break;
-    case 3: WCN_LN_BWD(3); break;
-    default: WCN_LN_BWD(4); break;
-  }
-#undef WCN_LN_BWD
+  const unsigned blocks = row_bwd_grid(g.rows, g.glog, &g.units);
+  row_with_nch(g.channels, g.glog, [&](auto nch) {
+    hipLaunchKernelGGL((ln_act_bwd_kernel<T, nch(), AFFINE, SILU>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)dy,
+                       (const T*)x, weight, bias, stats, (T*)dx, partial, g);
+  });
   return launch_status();
 }
 
@@ -374,9 +334,8 @@ static int ln_bwd_t(const void* dy, const void* x, const float* weight, const fl
 #define WCN_LN_USES(FN, T, ...)                                                                \
   (affine ? (act ? FN<T, true, true>(__VA_ARGS__) : FN<T, true, false>(__VA_ARGS__))           \
           : (act ? FN<T, false, true>(__VA_ARGS__) : FN<T, false, false>(__VA_ARGS__)))
-#define WCN_LN_DTYPES(FN, ...)                                                          \
-  (dtype == WCN_F32 ? WCN_LN_USES(FN, float, __VA_ARGS__)                               \
-                    : dtype == WCN_F16 ? WCN_LN_USES(FN, _Float16, __VA_ARGS__) : WCN_LN_USES(FN, __bf16, __VA_ARGS__))
+#define WCN_LN_DTYPES(FN, ...) \
+  row_with_dtype(dtype, [&](auto el) { return WCN_LN_USES(FN, decltype(el), __VA_ARGS__); })
 
 template <typename T, bool FOLD>
 static int skip_t(const void* x, const void* h, void* out, SkipGeom g, bool pieces, hipStream_t s) {
@@ -388,15 +347,10 @@ static int skip_t(const void* x, const void* h, void* out, SkipGeom g, bool piec
     hipLaunchKernelGGL((channel_elements_kernel<T, FOLD>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, xp, hp, op, g);
     return launch_status();
   }
-  const int npiece = g.cout / 8;
-  g.glog = 0;
-  while ((1 << g.glog) < npiece && g.glog < 6) ++g.glog;
-  const int64_t per_block = kAdaThreads >> g.glog;
-  int64_t blocks = ceil_div(g.rows, per_block);
-  if (blocks > kAdaFwdBlocks) blocks = kAdaFwdBlocks;
-  g.units = blocks * per_block;
+  g.glog = row_glog(g.cout / 8);
+  const unsigned blocks = row_fwd_grid(g.rows, g.glog, &g.units);
 #define WCN_SKIP(R) \
-  hipLaunchKernelGGL((channel_pieces_kernel<T, R, FOLD>), dim3((unsigned)blocks), dim3(kAdaThreads), 0, s, xp, hp, op, g)
+  hipLaunchKernelGGL((channel_pieces_kernel<T, R, FOLD>), dim3(blocks), dim3(kAdaThreads), 0, s, xp, hp, op, g)
   switch (g.ratio) {
     case 1: WCN_SKIP(1); break;
     case 2: WCN_SKIP(2); break;
@@ -411,13 +365,13 @@ static int skip_t(const void* x, const void* h, void* out, SkipGeom g, bool piec
 static int skip_run(bool fold, const void* x, const void* h, int64_t rows, int64_t narrow, int64_t ratio, float alpha,
                     int32_t dtype, void* out, hipStream_t s) {
   if (rows < 0 || narrow < 1 || ratio < 1) return WCN_ERROR_INVALID_PARAMETERS;
-  if (dtype != WCN_F32 && dtype != WCN_F16 && dtype != WCN_BF16) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (narrow * ratio > INT32_MAX) return WCN_ERROR_UNSUPPORTED_CONFIG;  // a row's channels are counted in int32
   if (rows > INT32_MAX || !std::isfinite(alpha)) return WCN_ERROR_INVALID_PARAMETERS;
   if (rows == 0) return WCN_SUCCESS;
   if (!x || !out) return WCN_ERROR_INVALID_PARAMETERS;
   const size_t el = dtype == WCN_F32 ? 4 : 2;
-  if (!ln_aligned(x, el) || !ln_aligned(h, el) || !ln_aligned(out, el)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!aligned_to(x, el) || !aligned_to(h, el) || !aligned_to(out, el)) return WCN_ERROR_INVALID_PARAMETERS;
   SkipGeom g;
   g.rows = rows;
   g.units = 0;
@@ -426,11 +380,12 @@ static int skip_run(bool fold, const void* x, const void* h, int64_t rows, int64
   g.glog = 0;
   g.alpha = alpha;
   // 16-B pieces: every row of both sides starts on the 16-B grid, and a piece's indices are compile-time constants
-  const bool pieces = narrow % 8 == 0 && (ratio == 1 || ratio == 2 || ratio == 4 || ratio == 8) && ln_aligned(x, 16) &&
-                      ln_aligned(h, 16) && ln_aligned(out, 16);
-#define WCN_SKIP_DTYPE(T) (fold ? skip_t<T, true>(x, h, out, g, pieces, s) : skip_t<T, false>(x, h, out, g, pieces, s))
-  return dtype == WCN_F32 ? WCN_SKIP_DTYPE(float) : dtype == WCN_F16 ? WCN_SKIP_DTYPE(_Float16) : WCN_SKIP_DTYPE(__bf16);
-#undef WCN_SKIP_DTYPE
+  const bool pieces = narrow % 8 == 0 && (ratio == 1 || ratio == 2 || ratio == 4 || ratio == 8) && aligned_to(x, 16) &&
+                      aligned_to(h, 16) && aligned_to(out, 16);
+  return row_with_dtype(dtype, [&](auto el) {
+    using T = decltype(el);
+    return fold ? skip_t<T, true>(x, h, out, g, pieces, s) : skip_t<T, false>(x, h, out, g, pieces, s);
+  });
 }
 
 }  // namespace wcn
@@ -450,8 +405,8 @@ int wcn_ln_act_fwd(const void* x, const float* weight, const float* bias, int64_
   if ((st == WCN_SUCCESS || st == 1) && !(eps >= 0.f && std::isfinite(eps))) st = WCN_ERROR_INVALID_PARAMETERS;
   if (st == WCN_SUCCESS) {
     if (!x || !y || !stats) st = WCN_ERROR_INVALID_PARAMETERS;
-    else if (!ln_aligned(x, 16) || !ln_aligned(weight, 16) || !ln_aligned(bias, 16) || !ln_aligned(y, 16) ||
-             !ln_aligned(stats, 8))
+    else if (!aligned_to(x, 16) || !aligned_to(weight, 16) || !aligned_to(bias, 16) || !aligned_to(y, 16) ||
+             !aligned_to(stats, 8))
       st = WCN_ERROR_INVALID_PARAMETERS;
   }
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
@@ -469,9 +424,9 @@ int wcn_ln_act_bwd(const void* dy, const void* x, const float* weight, const flo
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st == WCN_SUCCESS) {
     if (!dy || !x || !stats || !dx || (affine && (!dweight || !dbias || !workspace))) st = WCN_ERROR_INVALID_PARAMETERS;
-    else if (!ln_aligned(dy, 16) || !ln_aligned(x, 16) || !ln_aligned(weight, 16) || !ln_aligned(bias, 16) ||
-             !ln_aligned(stats, 8) || !ln_aligned(dx, 16) || !ln_aligned(dweight, 4) || !ln_aligned(dbias, 4) ||
-             (affine && !ln_aligned(workspace, 16)))
+    else if (!aligned_to(dy, 16) || !aligned_to(x, 16) || !aligned_to(weight, 16) || !aligned_to(bias, 16) ||
+             !aligned_to(stats, 8) || !aligned_to(dx, 16) || !aligned_to(dweight, 4) || !aligned_to(dbias, 4) ||
+             (affine && !aligned_to(workspace, 16)))
       st = WCN_ERROR_INVALID_PARAMETERS;
   }
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;

@@ -35,22 +35,6 @@ namespace wcn {
 constexpr int kNormBlocks = WCN_NORM_BLOCKS;
 constexpr int kNormRowsInFlight = WCN_NORM_ROWS;
 
-template <typename T> struct NCvt;
-template <> struct NCvt<float> {
-  static __device__ __forceinline__ float ld(float v) { return v; }
-  static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct NCvt<__half> {
-  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
-};
-template <> struct NCvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
-};
-
-template <typename T, int VEC> struct alignas(sizeof(T) * VEC) NVec { T v[VEC]; };
-
 // y = x * scale + shift as ONE fused multiply-add, in the forward pass and wherever the backward passes need to know whether
 // the ReLU behind it let a value through: the mask (stored y > 0) is recomputed from x with the very same operation instead
 // of reading the forward output again (a third of the backward passes' traffic).
@@ -66,7 +50,7 @@ __device__ __forceinline__ float bn_affine(float xf, float sc, float sh) {
 }
 template <typename T>
 __device__ __forceinline__ bool bn_relu_passes(float xf, float sc, float sh) {
-  return NCvt<T>::ld(NCvt<T>::st(fmaxf(bn_affine(xf, sc, sh), 0.f))) > 0.f;  // what the forward stored, compared with zero
+  return Cvt<T>::ld(Cvt<T>::st(fmaxf(bn_affine(xf, sc, sh), 0.f))) > 0.f;  // what the forward stored, compared with zero
 }
 
 // Thread layout of the column reductions: lanes_c threads side by side cover one row (VEC channels each), the
@@ -101,7 +85,7 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const T* __restrict__ 
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         if (ch0 + v < c) {
-          if (MODE == 0) a[v] = NCvt<T>::ld(x[ch0 + v]);  // pivot: row 0
+          if (MODE == 0) a[v] = Cvt<T>::ld(x[ch0 + v]);  // pivot: row 0
           else {
             a[v] = mean[ch0 + v]; b[v] = rstd[ch0 + v];
             if (rscale) { sc[v] = rscale[ch0 + v]; sh[v] = rshift[ch0 + v]; }
@@ -109,7 +93,7 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const T* __restrict__ 
         }
       }
       for (int64_t r = r0 + rr; r < r1; r += (int64_t)rsteps * kNormRowsInFlight) {
-        NVec<T, VEC> xv[kNormRowsInFlight], gv[kNormRowsInFlight], zv[kNormRowsInFlight];
+        Vec<T, VEC> xv[kNormRowsInFlight], gv[kNormRowsInFlight], zv[kNormRowsInFlight];
         // clamped addresses: the loads of all rows in flight are issued before the first one is used
 #pragma unroll
         for (int q = 0; q < kNormRowsInFlight; ++q) {
@@ -117,9 +101,9 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const T* __restrict__ 
           const int64_t rc = rq < r1 ? rq : r1 - 1;
           const int64_t at = rc * c + ch0;
           if (VEC > 1) {
-            xv[q] = *reinterpret_cast<const NVec<T, VEC>*>(x + at);
-            if (MODE == 1) gv[q] = *reinterpret_cast<const NVec<T, VEC>*>(dy + rc * dy_ld + ch0);
-            if (MODE == 1 && zmask) zv[q] = *reinterpret_cast<const NVec<T, VEC>*>(zmask + at);
+            xv[q] = *reinterpret_cast<const Vec<T, VEC>*>(x + at);
+            if (MODE == 1) gv[q] = *reinterpret_cast<const Vec<T, VEC>*>(dy + rc * dy_ld + ch0);
+            if (MODE == 1 && zmask) zv[q] = *reinterpret_cast<const Vec<T, VEC>*>(zmask + at);
           } else {
             xv[q].v[0] = x[at];
             if (MODE == 1) gv[q].v[0] = dy[rc * dy_ld + ch0];
@@ -131,14 +115,14 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const T* __restrict__ 
           if (r + (int64_t)q * rsteps >= r1) continue;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) {
-            const float xf = NCvt<T>::ld(xv[q].v[v]);
+            const float xf = Cvt<T>::ld(xv[q].v[v]);
             if (MODE == 0) {
               const float d = xf - a[v];
               s0[v] += d;
               s1[v] += d * d;
             } else {
-              float g = NCvt<T>::ld(gv[q].v[v]);
-              if (zmask) { if (!(NCvt<T>::ld(zv[q].v[v]) > 0.f)) g = 0.f; }
+              float g = Cvt<T>::ld(gv[q].v[v]);
+              if (zmask) { if (!(Cvt<T>::ld(zv[q].v[v]) > 0.f)) g = 0.f; }
               else if (rscale && !bn_relu_passes<T>(xf, sc[v], sh[v])) g = 0.f;
               s0[v] += g;
               s1[v] += g * ((xf - a[v]) * b[v]);
@@ -211,7 +195,7 @@ __global__ __launch_bounds__(64) void norm_final_kernel(const float* __restrict_
       const float inv = 1.0f / (float)n;
       const float md = t0 * inv;                       // mean of (x - pivot)
       const float var = fmaxf(t1 * inv - md * md, 0.f);
-      const float mean = NCvt<T>::ld(x[ch]) + md;
+      const float mean = Cvt<T>::ld(x[ch]) + md;
       out0[ch] = mean;
       out1[ch] = var;
       if (f.rstd) {
@@ -266,19 +250,19 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const T* __restrict__ x
   const int64_t total = n * cv;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int ch0 = (int)(e % cv) * VEC;
-    const NVec<T, VEC> xv = *reinterpret_cast<const NVec<T, VEC>*>(x + e * VEC);
-    NVec<T, VEC> yv, rv;
-    if (res) rv = *reinterpret_cast<const NVec<T, VEC>*>(res + e * VEC);
+    const Vec<T, VEC> xv = *reinterpret_cast<const Vec<T, VEC>*>(x + e * VEC);
+    Vec<T, VEC> yv, rv;
+    if (res) rv = *reinterpret_cast<const Vec<T, VEC>*>(res + e * VEC);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-      float f = bn_affine(NCvt<T>::ld(xv.v[v]), s_coef[ch0 + v], s_coef[c + ch0 + v]);
+      float f = bn_affine(Cvt<T>::ld(xv.v[v]), s_coef[ch0 + v], s_coef[c + ch0 + v]);
       // round, then add in fp32 and round again: what the framework's elementwise add of two 16-bit tensors does (for fp16 the
       // fp32 sum is exact enough that this equals one rounding of the exact sum - checked on 84 M pairs)
-      if (res) f = NCvt<T>::ld(NCvt<T>::st(NCvt<T>::ld(NCvt<T>::st(f)) + NCvt<T>::ld(rv.v[v])));
+      if (res) f = Cvt<T>::ld(Cvt<T>::st(Cvt<T>::ld(Cvt<T>::st(f)) + Cvt<T>::ld(rv.v[v])));
       if (relu) f = fmaxf(f, 0.f);
-      yv.v[v] = NCvt<T>::st(f);
+      yv.v[v] = Cvt<T>::st(f);
     }
-    *reinterpret_cast<NVec<T, VEC>*>(y + e * VEC) = yv;
+    *reinterpret_cast<Vec<T, VEC>*>(y + e * VEC) = yv;
   }
 }
 
@@ -310,22 +294,22 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const T* __restrict
   const int64_t total = n * cv;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int ch0 = (int)(e % cv) * VEC;
-    const NVec<T, VEC> gv = *reinterpret_cast<const NVec<T, VEC>*>(dy + (dy_ld == c ? e * VEC : (e / cv) * dy_ld + ch0));
-    const NVec<T, VEC> xv = *reinterpret_cast<const NVec<T, VEC>*>(x + e * VEC);
-    NVec<T, VEC> ov, zv, mv;
-    if (zmask) zv = *reinterpret_cast<const NVec<T, VEC>*>(zmask + e * VEC);
+    const Vec<T, VEC> gv = *reinterpret_cast<const Vec<T, VEC>*>(dy + (dy_ld == c ? e * VEC : (e / cv) * dy_ld + ch0));
+    const Vec<T, VEC> xv = *reinterpret_cast<const Vec<T, VEC>*>(x + e * VEC);
+    Vec<T, VEC> ov, zv, mv;
+    if (zmask) zv = *reinterpret_cast<const Vec<T, VEC>*>(zmask + e * VEC);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       const int ch = ch0 + v;
-      const float xf = NCvt<T>::ld(xv.v[v]);
-      float g = NCvt<T>::ld(gv.v[v]);
-      if (zmask) { if (!(NCvt<T>::ld(zv.v[v]) > 0.f)) g = 0.f; }
+      const float xf = Cvt<T>::ld(xv.v[v]);
+      float g = Cvt<T>::ld(gv.v[v]);
+      if (zmask) { if (!(Cvt<T>::ld(zv.v[v]) > 0.f)) g = 0.f; }
       else if (rscale && !bn_relu_passes<T>(xf, s_coef[3 * c + ch], s_coef[4 * c + ch])) g = 0.f;
-      mv.v[v] = NCvt<T>::st(g);
-      ov.v[v] = NCvt<T>::st(s_coef[ch] * g + s_coef[c + ch] * xf + s_coef[2 * c + ch]);
+      mv.v[v] = Cvt<T>::st(g);
+      ov.v[v] = Cvt<T>::st(s_coef[ch] * g + s_coef[c + ch] * xf + s_coef[2 * c + ch]);
     }
-    *reinterpret_cast<NVec<T, VEC>*>(dx + e * VEC) = ov;
-    if (dres) *reinterpret_cast<NVec<T, VEC>*>(dres + e * VEC) = mv;
+    *reinterpret_cast<Vec<T, VEC>*>(dx + e * VEC) = ov;
+    if (dres) *reinterpret_cast<Vec<T, VEC>*>(dres + e * VEC) = mv;
   }
 }
 
@@ -403,11 +387,10 @@ extern "C" {
 
 size_t wcn_bn_workspace(int32_t channels) { return channels > 0 ? (size_t)kNormBlocks * 2 * channels * sizeof(float) : 0; }
 
-static bool bn_dtype_ok(int dtype) { return dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16; }
 
 int wcn_bn_stats(const void* x, int64_t n, int32_t channels, int32_t dtype, float* mean, float* var, void* workspace,
                  size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !bn_dtype_ok(dtype) || !x || !mean || !var || !workspace ||
+  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !x || !mean || !var || !workspace ||
       workspace_bytes < wcn_bn_workspace(channels))
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
@@ -423,7 +406,7 @@ int wcn_bn_stats_fold(const void* x, int64_t n, int32_t channels, int32_t dtype,
                       float* running_mean, float* running_var, float momentum, float eps, float* mean, float* var,
                       float* rstd, float* scale, float* shift, int64_t* num_batches_tracked, void* workspace,
                       size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !bn_dtype_ok(dtype) || !x || !mean || !var || !rstd || !scale || !shift || !workspace ||
+  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !x || !mean || !var || !rstd || !scale || !shift || !workspace ||
       workspace_bytes < wcn_bn_workspace(channels) || ((running_mean == nullptr) != (running_var == nullptr)))
     return WCN_ERROR_INVALID_PARAMETERS;
   BnFold f;
@@ -451,7 +434,7 @@ int wcn_bn_fold(const float* running_mean, const float* running_var, const float
 
 int wcn_bn_apply(const void* x, int64_t n, int32_t channels, int32_t dtype, const float* scale, const float* shift,
                  int32_t relu, void* y, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !bn_dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (n < 0 || channels < 1 || !dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
   if (n == 0) return WCN_SUCCESS;
   if (!x || !y || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
@@ -465,7 +448,7 @@ int wcn_bn_apply(const void* x, int64_t n, int32_t channels, int32_t dtype, cons
 static int bn_backward_reduce_ld(const void* dy, int64_t dy_ld, const void* x, const float* relu_scale, const float* relu_shift,
                                 int64_t n, int32_t channels, int32_t dtype, const float* mean, const float* rstd, float* sum_dy,
                                 float* sum_dy_xhat, void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !bn_dtype_ok(dtype) || !dy || !x || !mean || !rstd || !sum_dy || !sum_dy_xhat ||
+  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !dy || !x || !mean || !rstd || !sum_dy || !sum_dy_xhat ||
       !workspace || workspace_bytes < wcn_bn_workspace(channels) || ((relu_scale == nullptr) != (relu_shift == nullptr)))
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
@@ -490,7 +473,7 @@ int wcn_bn_backward_reduce(const void* dy, const void* x, const float* relu_scal
 static int bn_backward_apply_ld(const void* dy, int64_t dy_ld, const void* x, const float* relu_scale, const float* relu_shift,
                                int64_t n, int32_t channels, int32_t dtype, const float* mean, const float* rstd, const float* gamma,
                                const float* sum_dy, const float* sum_dy_xhat, void* dx, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !bn_dtype_ok(dtype) || ((relu_scale == nullptr) != (relu_shift == nullptr)))
+  if (n < 0 || channels < 1 || !dtype_ok(dtype) || ((relu_scale == nullptr) != (relu_shift == nullptr)))
     return WCN_ERROR_INVALID_PARAMETERS;
   if (n == 0) return WCN_SUCCESS;
   if (!dy || !x || !dx || !mean || !rstd || !sum_dy || !sum_dy_xhat) return WCN_ERROR_INVALID_PARAMETERS;
@@ -517,7 +500,7 @@ int wcn_bn_backward_apply(const void* dy, const void* x, const float* relu_scale
 
 int wcn_bn_apply_residual(const void* x, const void* residual, int64_t n, int32_t channels, int32_t dtype, const float* scale,
                           const float* shift, int32_t relu, void* y, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !bn_dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (n < 0 || channels < 1 || !dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
   if (n == 0) return WCN_SUCCESS;
   if (!x || !residual || !y || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
@@ -531,7 +514,7 @@ int wcn_bn_apply_residual(const void* x, const void* residual, int64_t n, int32_
 static int bn_backward_reduce_masked_ld(const void* dy, int64_t dy_ld, const void* x, const void* z, int64_t n, int32_t channels,
                                        int32_t dtype, const float* mean, const float* rstd, float* sum_dy, float* sum_dy_xhat,
                                        void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !bn_dtype_ok(dtype) || !dy || !x || !z || !mean || !rstd || !sum_dy || !sum_dy_xhat ||
+  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !dy || !x || !z || !mean || !rstd || !sum_dy || !sum_dy_xhat ||
       !workspace || workspace_bytes < wcn_bn_workspace(channels))
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
@@ -553,7 +536,7 @@ int wcn_bn_backward_reduce_masked(const void* dy, const void* x, const void* z, 
 static int bn_backward_apply_masked_ld(const void* dy, int64_t dy_ld, const void* x, const void* z, int64_t n, int32_t channels,
                                       int32_t dtype, const float* mean, const float* rstd, const float* gamma, const float* sum_dy,
                                       const float* sum_dy_xhat, void* dx, void* dres, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !bn_dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (n < 0 || channels < 1 || !dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
   if (n == 0) return WCN_SUCCESS;
   if (!dy || !x || !z || !dx || !mean || !rstd || !sum_dy || !sum_dy_xhat) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;

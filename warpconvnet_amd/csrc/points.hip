@@ -187,20 +187,6 @@ int radius_grid_write(const float* ref, const int32_t* ref_id, const int32_t* ce
 // ---- segment reduce ---------------------------------------------------------------------------------------------------
 enum { kRedSum = 0, kRedMean = 1, kRedMax = 2, kRedMin = 3 };
 
-template <typename T> struct PtCvt;
-template <> struct PtCvt<float> {
-  static __device__ __forceinline__ float ld(float v) { return v; }
-  static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct PtCvt<__half> {
-  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
-};
-template <> struct PtCvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
-};
-
 // one thread per (segment, channel); adjacent threads = adjacent channels => every step of the loop reads one row
 // contiguously.  fp32 accumulation in ascending row order => deterministic.
 template <typename T>
@@ -215,14 +201,14 @@ __global__ __launch_bounds__(256) void segment_reduce_kernel(const T* __restrict
   float acc = (op == kRedMax) ? -FLT_MAX : (op == kRedMin ? FLT_MAX : 0.f);
   int64_t best = -1;
   for (int64_t r = r0; r < r1; ++r) {
-    const float v = PtCvt<T>::ld(in[r * c + ch]);
+    const float v = Cvt<T>::ld(in[r * c + ch]);
     if (op == kRedMax) { if (v > acc || best < 0) { acc = v; best = r; } }
     else if (op == kRedMin) { if (v < acc || best < 0) { acc = v; best = r; } }
     else acc += v;
   }
   if (op == kRedMean && r1 > r0) acc /= (float)(r1 - r0);
   if ((op == kRedMax || op == kRedMin) && r1 == r0) acc = 0.f;  // empty segment: zero (torch_scatter convention)
-  out[e] = PtCvt<T>::st(acc);
+  out[e] = Cvt<T>::st(acc);
   if (arg) arg[e] = best;
 }
 

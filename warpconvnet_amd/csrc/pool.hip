@@ -21,22 +21,6 @@ namespace wcn {
 
 enum { kPoolSum = 0, kPoolMean = 1, kPoolMax = 2, kPoolMin = 3 };
 
-template <typename T> struct PoolCvt;
-template <> struct PoolCvt<float> {
-  static __device__ __forceinline__ float ld(float v) { return v; }
-  static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct PoolCvt<__half> {
-  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
-};
-template <> struct PoolCvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
-};
-
-template <typename T, int VEC> struct alignas(sizeof(T) * VEC) PoolVec { T v[VEC]; };
-
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void pool_gather_kernel(const T* __restrict__ in, const int32_t* __restrict__ tbl,
                                                           int64_t m, int c, int K, int kp, int op, T* __restrict__ out,
@@ -55,21 +39,21 @@ __global__ __launch_bounds__(256) void pool_gather_kernel(const T* __restrict__ 
   for (int k = 0; k < K; ++k) {
     const int32_t r = trow[k];
     if (r < 0) continue;
-    const PoolVec<T, VEC> x = *reinterpret_cast<const PoolVec<T, VEC>*>(in + (int64_t)r * c + (int64_t)v * VEC);
+    const Vec<T, VEC> x = *reinterpret_cast<const Vec<T, VEC>*>(in + (int64_t)r * c + (int64_t)v * VEC);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const float f = PoolCvt<T>::ld(x.v[j]);
+      const float f = Cvt<T>::ld(x.v[j]);
       if (op == kPoolMax) { if (n == 0 || f > acc[j]) { acc[j] = f; best[j] = r; } }
       else if (op == kPoolMin) { if (n == 0 || f < acc[j]) { acc[j] = f; best[j] = r; } }
       else acc[j] += f;
     }
     ++n;
   }
-  PoolVec<T, VEC> y;
+  Vec<T, VEC> y;
   const float scale = (op == kPoolMean && n > 0) ? 1.0f / (float)n : 1.0f;
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) y.v[j] = PoolCvt<T>::st(acc[j] * scale);
-  *reinterpret_cast<PoolVec<T, VEC>*>(out + row * c + (int64_t)v * VEC) = y;
+  for (int j = 0; j < VEC; ++j) y.v[j] = Cvt<T>::st(acc[j] * scale);
+  *reinterpret_cast<Vec<T, VEC>*>(out + row * c + (int64_t)v * VEC) = y;
   if (arg) {
 #pragma unroll
     for (int j = 0; j < VEC; ++j) arg[row * c + (int64_t)v * VEC + j] = best[j];
@@ -94,15 +78,15 @@ __global__ __launch_bounds__(256) void pool_select_kernel(const T* __restrict__ 
     const int32_t r = trow[k];
     if (r < 0) continue;
     const int64_t at = (int64_t)r * c + (int64_t)v * VEC;
-    const PoolVec<T, VEC> g = *reinterpret_cast<const PoolVec<T, VEC>*>(dy + at);
+    const Vec<T, VEC> g = *reinterpret_cast<const Vec<T, VEC>*>(dy + at);
 #pragma unroll
     for (int j = 0; j < VEC; ++j)
-      if (arg[at + j] == (int32_t)row) acc[j] += PoolCvt<T>::ld(g.v[j]);
+      if (arg[at + j] == (int32_t)row) acc[j] += Cvt<T>::ld(g.v[j]);
   }
-  PoolVec<T, VEC> y;
+  Vec<T, VEC> y;
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) y.v[j] = PoolCvt<T>::st(acc[j]);
-  *reinterpret_cast<PoolVec<T, VEC>*>(dx + row * c + (int64_t)v * VEC) = y;
+  for (int j = 0; j < VEC; ++j) y.v[j] = Cvt<T>::st(acc[j]);
+  *reinterpret_cast<Vec<T, VEC>*>(dx + row * c + (int64_t)v * VEC) = y;
 }
 
 template <typename T>

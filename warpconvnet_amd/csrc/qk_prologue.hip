@@ -35,7 +35,6 @@ constexpr float kQkNormEps = 1e-12f;
 constexpr int kQkThreads = 256;
 constexpr int kQkLaneBudget = 1 << 19;  // lanes in flight the row groups are sized for (2048 workgroups of 256)
 
-template <typename T, int N> struct alignas(sizeof(T) * N) QkVec { T v[N]; };
 
 struct QkGeom {
   int64_t total;           // T
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(kQkThreads) void qk_fwd_kernel(const TI* __restrict
     for (int k = 0; k < NCH; ++k) {
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
-        const QkVec<TI, EPL> v = *reinterpret_cast<const QkVec<TI, EPL>*>(x + t * row_elems + col0 + c * EPL);
+        const Vec<TI, EPL> v = *reinterpret_cast<const Vec<TI, EPL>*>(x + t * row_elems + col0 + c * EPL);
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
           f[k][e] = (float)v.v[e];
@@ -161,10 +160,10 @@ __global__ __launch_bounds__(kQkThreads) void qk_fwd_kernel(const TI* __restrict
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
         if (qk && g.rot_pairs > 0) qk_rotate<EPL>(f[k], table + t * (2 * (int64_t)g.rot_pairs), c * (EPL / 2), g.rot_pairs, sgn);
-        QkVec<TO, EPL> o;
+        Vec<TO, EPL> o;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) o.v[e] = (TO)f[k][e];
-        *reinterpret_cast<QkVec<TO, EPL>*>(out + t * row_elems + col0 + c * EPL) = o;
+        *reinterpret_cast<Vec<TO, EPL>*>(out + t * row_elems + col0 + c * EPL) = o;
       }
     }
   }
@@ -214,11 +213,11 @@ __global__ __launch_bounds__(kQkThreads) void qk_bwd_kernel(const TG* __restrict
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
         const int64_t at = t * row_elems + col0 + c * EPL;
-        const QkVec<TG, EPL> gv = *reinterpret_cast<const QkVec<TG, EPL>*>(dout + at);
+        const Vec<TG, EPL> gv = *reinterpret_cast<const Vec<TG, EPL>*>(dout + at);
 #pragma unroll
         for (int e = 0; e < EPL; ++e) dy[k][e] = (float)gv.v[e];
         if (qk) {
-          const QkVec<TX, EPL> xv = *reinterpret_cast<const QkVec<TX, EPL>*>(x + at);
+          const Vec<TX, EPL> xv = *reinterpret_cast<const Vec<TX, EPL>*>(x + at);
           if (g.rot_pairs > 0) qk_rotate<EPL>(dy[k], table + t * (2 * (int64_t)g.rot_pairs), c * (EPL / 2), g.rot_pairs, -1.f);
 #pragma unroll
           for (int e = 0; e < EPL; ++e) {
@@ -242,10 +241,10 @@ __global__ __launch_bounds__(kQkThreads) void qk_bwd_kernel(const TG* __restrict
     for (int k = 0; k < NCH; ++k) {
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
-        QkVec<TX, EPL> o;
+        Vec<TX, EPL> o;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) o.v[e] = (TX)(qk ? (dy[k][e] - xh[k][e] * dot) * inv : dy[k][e]);
-        *reinterpret_cast<QkVec<TX, EPL>*>(dx + t * row_elems + col0 + c * EPL) = o;
+        *reinterpret_cast<Vec<TX, EPL>*>(dx + t * row_elems + col0 + c * EPL) = o;
       }
     }
   }
@@ -301,8 +300,6 @@ __global__ __launch_bounds__(256) void rope_table_kernel(const TC* __restrict__ 
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 static int qk_elem_size(int dtype) { return dtype == WCN_F32 ? 4 : 2; }
-static bool qk_dtype_ok(int dtype) { return dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16; }
-static bool qk_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 static int qk_pow2_ceil(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -331,7 +328,7 @@ static QkPath qk_path(int64_t total, int heads, int head_dim, int rot_pairs, int
 }
 // a lane's piece of the narrower buffer is 8 B, of the wider 16 B: every buffer 16-B aligned covers both
 static bool qk_all_aligned16(const void* a, const void* b, const void* c = nullptr) {
-  return qk_aligned(a, 16) && qk_aligned(b, 16) && qk_aligned(c, 16);
+  return aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(c, 16);
 }
 static unsigned qk_grid(const QkGeom& g) { return (unsigned)ceil_div((int64_t)g.rows * g.lanes_per_row, kQkThreads); }
 
@@ -384,7 +381,7 @@ static int qk_fwd_any(const void* x, int in_dtype, void* out, int out_dtype, con
 static int qk_check(const void* a, int a_dtype, const void* b, int b_dtype, bool b_half_only, int64_t total, int32_t heads,
                     int32_t head_dim, const float* table, int32_t rot_pairs, const float* gq, const float* gk) {
   if (total < 0 || heads < 1 || head_dim < 1 || rot_pairs < 0) return WCN_ERROR_INVALID_PARAMETERS;
-  if (!qk_dtype_ok(a_dtype) || !qk_dtype_ok(b_dtype) || (b_half_only && b_dtype == WCN_F32) || head_dim % 2 != 0 ||
+  if (!dtype_ok(a_dtype) || !dtype_ok(b_dtype) || (b_half_only && b_dtype == WCN_F32) || head_dim % 2 != 0 ||
       head_dim > kQkMaxHeadDim)
     return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (2 * rot_pairs > head_dim || (gq == nullptr) != (gk == nullptr)) return WCN_ERROR_INVALID_PARAMETERS;
@@ -392,8 +389,8 @@ static int qk_check(const void* a, int a_dtype, const void* b, int b_dtype, bool
   if (total == 0) return 1;
   if (!a || !b || (rot_pairs > 0 && !table)) return WCN_ERROR_INVALID_PARAMETERS;
   // whole pairs are the smallest access; 8-B table entries
-  if (!qk_aligned(a, 2 * (size_t)qk_elem_size(a_dtype)) || !qk_aligned(b, 2 * (size_t)qk_elem_size(b_dtype)) ||
-      (table && !qk_aligned(table, 8)))
+  if (!aligned_to(a, 2 * (size_t)qk_elem_size(a_dtype)) || !aligned_to(b, 2 * (size_t)qk_elem_size(b_dtype)) ||
+      (table && !aligned_to(table, 8)))
     return WCN_ERROR_INVALID_PARAMETERS;
   return WCN_SUCCESS;
 }
@@ -403,7 +400,7 @@ static int qk_check(const void* a, int a_dtype, const void* b, int b_dtype, bool
 using namespace wcn;
 
 int wcn_qk_prologue_supported(int32_t head_dim, int32_t in_dtype, int32_t out_dtype) {
-  return head_dim >= 2 && head_dim % 2 == 0 && head_dim <= kQkMaxHeadDim && qk_dtype_ok(in_dtype) &&
+  return head_dim >= 2 && head_dim % 2 == 0 && head_dim <= kQkMaxHeadDim && dtype_ok(in_dtype) &&
                  (out_dtype == WCN_F16 || out_dtype == WCN_BF16)
              ? 1
              : 0;
@@ -421,7 +418,7 @@ int wcn_rope_table(const void* coords, int32_t coords_float, int64_t total, cons
   if (6 * (int64_t)num_freqs > kQkMaxHeadDim) return WCN_ERROR_UNSUPPORTED_CONFIG;
   const int64_t entries = total * 3 * num_freqs;
   if (entries == 0) return WCN_SUCCESS;
-  if (!coords || !freqs || !table || !qk_aligned(table, 8)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!coords || !freqs || !table || !aligned_to(table, 8)) return WCN_ERROR_INVALID_PARAMETERS;
   const int64_t blocks = ceil_div(entries, 256);
   if (blocks > INT32_MAX) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
@@ -454,7 +451,7 @@ int wcn_qk_prologue_bwd(const void* dout, int32_t dout_dtype, const void* qkv, i
   if ((st == WCN_SUCCESS || st == 1) && norm && workspace_bytes < wcn_qk_prologue_workspace_bytes(total, heads, head_dim))
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st == WCN_SUCCESS && norm &&
-      (!qkv || !inv_norm || !dgamma_q || !dgamma_k || !workspace || !qk_aligned(qkv, 2 * (size_t)qk_elem_size(in_dtype))))
+      (!qkv || !inv_norm || !dgamma_q || !dgamma_k || !workspace || !aligned_to(qkv, 2 * (size_t)qk_elem_size(in_dtype))))
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
   hipStream_t s = (hipStream_t)stream;

@@ -102,7 +102,6 @@ static int unpack_u(const void* src, const int32_t* tbl, int64_t P, int64_t n_ds
 }
 
 static inline int elem_bytes(int dtype) { return dtype == WCN_F32 ? 4 : (dtype == WCN_F16 || dtype == WCN_BF16) ? 2 : 0; }
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // ---- expand --------------------------------------------------------------------------------------------------------------
 struct ExpandWs {
@@ -219,7 +218,7 @@ int wcn_resample_pack(const void* src, const int32_t* tbl, int64_t n_src, int64_
   if (!tbl || !dst || (n_src > 0 && !src)) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
   const int row_bytes = channels * eb;
-  if (row_bytes % 16 == 0 && aligned16(src) && aligned16(dst))
+  if (row_bytes % 16 == 0 && aligned_to(src, 16) && aligned_to(dst, 16))
     return pack_u<uint4>(src, tbl, n_src, n_parent, n_per, pitch, sc, row_bytes / 16, dst, s);
   if (eb == 4) return pack_u<uint32_t>(src, tbl, n_src, n_parent, n_per, pitch, sc, channels, dst, s);
   return pack_u<uint16_t>(src, tbl, n_src, n_parent, n_per, pitch, sc, channels, dst, s);
@@ -238,7 +237,7 @@ int wcn_resample_unpack(const void* src, const int32_t* tbl, int64_t n_parent, i
   hipStream_t s = (hipStream_t)stream;
   const int row_bytes = channels * eb;
   const int bc = broadcast ? 1 : 0;
-  if (row_bytes % 16 == 0 && aligned16(src) && aligned16(dst))
+  if (row_bytes % 16 == 0 && aligned_to(src, 16) && aligned_to(dst, 16))
     return unpack_u<uint4>(src, tbl, n_parent, n_dst, n_per, pitch, sc, row_bytes / 16, bc, dst, s);
   if (eb == 4) return unpack_u<uint32_t>(src, tbl, n_parent, n_dst, n_per, pitch, sc, channels, bc, dst, s);
   return unpack_u<uint16_t>(src, tbl, n_parent, n_dst, n_per, pitch, sc, channels, bc, dst, s);

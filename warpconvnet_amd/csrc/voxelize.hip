@@ -465,7 +465,6 @@ static int pow2_lanes(int64_t pieces) {
   return L;
 }
 
-static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 template <int D, int V>
 static void cg_launch(const void* in, int64_t ld_in, int64_t n_in, const int64_t* indices, const int64_t* offsets, int64_t m,
@@ -623,7 +622,7 @@ int wcn_voxel_map(const int64_t* sorted_keys, const int64_t* perm, int64_t n, in
 static int cg_args_ok(int64_t m, int64_t nnz, int64_t n_in, int32_t c, int64_t ld, int32_t dtype, int32_t op) {
   if (m < 0 || m > INT32_MAX || nnz < 0 || nnz > INT32_MAX || n_in < 0 || c < 0 || ld < c || op < kOpSum || op > kOpMin)
     return WCN_ERROR_INVALID_PARAMETERS;
-  if (dtype != WCN_F32 && dtype != WCN_F16 && dtype != WCN_BF16) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   return WCN_SUCCESS;
 }
 
@@ -659,7 +658,7 @@ int wcn_row_spread(const void* src, const int64_t* to_orig, int64_t n, int64_t m
   if (n < 0 || n > INT32_MAX || m < 0 || m > INT32_MAX || c < 0 || cs < 0 || ld_out < (int64_t)c + cs ||
       mode < kSpreadPlain || mode > kSpreadArgMatch)
     return WCN_ERROR_INVALID_PARAMETERS;
-  if (dtype != WCN_F32 && dtype != WCN_F16 && dtype != WCN_BF16) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (n == 0 || c + cs == 0) return WCN_SUCCESS;
   if (!out || (c > 0 && (!to_orig || (!src && m > 0))) || (cs > 0 && !skip) || (mode == kSpreadInvCount && !offsets) ||
       (mode == kSpreadArgMatch && !arg))

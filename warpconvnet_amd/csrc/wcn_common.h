@@ -4,6 +4,8 @@
 // wrap-around behaviour are identical (reference: warpconvnet/csrc/include/cuhash/hash_functions.cuh:29-84).
 #pragma once
 
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -95,6 +97,32 @@ inline int launch_status() {
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool valid_k(int64_t num_offsets) { return num_offsets >= 1 && num_offsets <= 4096; }  // kernel volumes the library takes
+
+// ---- element types --------------------------------------------------------------------------------------------------------
+// The storage dtypes (WCN_F32 / WCN_F16 / WCN_BF16) as HIP's own types, converted with HIP's intrinsics.  Two other
+// conventions exist and are not this one: ada_row.h and qk_prologue.hip take _Float16 / __bf16 and convert with C casts,
+// voxelize.hip's El<D> works on raw 16-bit patterns keyed by the dtype code.
+template <typename T> struct Cvt;
+template <> struct Cvt<float> {
+  static __device__ __forceinline__ float ld(float v) { return v; }
+  static __device__ __forceinline__ float st(float v) { return v; }
+};
+template <> struct Cvt<__half> {
+  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
+  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
+};
+template <> struct Cvt<__hip_bfloat16> {
+  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
+  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
+};
+
+// N elements moved as one access
+template <typename T, int N> struct alignas(sizeof(T) * N) Vec { T v[N]; };
+
+// a = a power of two; true for null (an absent optional buffer)
+inline bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+inline bool dtype_ok(int dtype) { return dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16; }
 
 // ---- prefix sums (wave64) -------------------------------------------------------------------------------------------------
 // inclusive scan over the first WIDTH (64 or 32) lanes of a wave; with 32 the upper half's results are unspecified

@@ -347,7 +347,7 @@ int wcn_window_group(const int32_t* coords, int64_t n, const int32_t* batch_offs
     return WCN_SUCCESS;
   }
   if (!coords || !batch_offsets || !codes || !perm || !inverse_perm || !counts || !workspace ||
-      ((uintptr_t)workspace & 15) != 0)
+      !aligned_to(workspace, 16))
     return WCN_ERROR_INVALID_PARAMETERS;
   const WgCarve c = wg_carve(workspace, n, num_bins);
   if (workspace_bytes < c.bytes) return WCN_ERROR_INVALID_PARAMETERS;
