@@ -26,9 +26,11 @@ def _ref(bn: nn.BatchNorm1d, x: torch.Tensor, g: torch.Tensor, relu: bool):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("n,c", [(5000, 96), (20000, 13), (257, 256), (7, 32), (1, 8)])
+@pytest.mark.parametrize("n,c", [(5000, 96), (20000, 13), (257, 256), (7, 32), (1, 8), (65665, 24)])
 @pytest.mark.parametrize("relu", [False, True])
 def test_training_forward_backward(n, c, dtype, relu):
+    """65665 rows: above 128 x WCN_NORM_BLOCKS = 65536, where the first reduction level stops adding workgroups and every
+    workgroup takes more than its 128 rows (pinned by tests/test_grid_cap_constants.py)."""
     from warpconvnet_amd.nn.functional.normalizations import batch_norm_module_forward
 
     torch.manual_seed(n + c)
