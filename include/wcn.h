@@ -935,6 +935,68 @@ int wcn_row_spread(const void* src, const int64_t* to_orig, int64_t n, int64_t m
                    int64_t ld_out, int32_t mode, const int64_t* offsets, const int64_t* arg, int32_t dtype, void* out,
                    wcn_stream_t stream);
 
+/* ---- lattice filters: permutohedral lattice and bilateral grid (ABI 13, additions only) -------------------------------------
+ * Reference: nn/functional/permutohedral.py, nn/functional/bilateral_grid.py, geometry/coords/search/packed128_hashmap.py.
+ * Keys are rows of key_dim <= 7 int32 coordinates, each in [-65536, 65535] (17-bit fields biased by 2^16, axis 0 in the most
+ * significant field of a 128-bit number that travels as two 64-bit words hi, lo).
+ *   wcn_hash128_insert  `table_keys` int64 [capacity, 2] (16-B aligned), `table_values` int32 [capacity], capacity a power of
+ *                    two.  The call clears the values to -1 and inserts `coords` int32 [n, key_dim]: a slot is claimed under
+ *                    linear probing by a 32-bit compare-and-swap on its value word (-1 -> row), the key words follow as one
+ *                    plain 16-B store.  The caller guarantees DISTINCT keys; an inserting thread never compares keys.  `status`
+ *                    int32 [1] is OR-ed with WCN_FLAG_COORD_RANGE (a coordinate outside the range, that row is not inserted)
+ *                    and WCN_FLAG_TABLE_FULL; the caller clears it.  Searches belong in a later launch.
+ *   wcn_hash128_search  out[j, i] = row of queries[i] + offsets[j] or -1 (absent, or outside the coordinate range); `queries`
+ *                    int32 [m, key_dim], `offsets` int32 [k, key_dim] with 1 <= k <= 32 (NULL: k = 1, a zero offset), `out`
+ *                    int32 [k, m].
+ *   wcn_permuto_simplex `positions` fp32 [n, d], d <= 6, `scale` d HOST floats (the embedding's per-axis factors, formed by
+ *                    the caller with the framework's own expression) -> per point the d + 1 vertices of the enclosing simplex:
+ *                    entry e = i * (d + 1) + v gets `key_hi` / `key_lo` int64 (either may be NULL; the top bit of lo is flipped
+ *                    so that a SIGNED 64-bit sort of lo, then of hi, orders the rows lexicographically), `keys` int32
+ *                    [n (d + 1), d + 1] (may be NULL) and `bary` fp32 [n, d + 1].  fp32 arithmetic in the framework's order of
+ *                    operations, never contracted into FMAs; rank ties go to the lower axis.
+ *   wcn_grid_corners    the same for the 2^d corners of the enclosing grid cell: `floors` int64 [n, d] (may be NULL), keys as
+ *                    above with entry e = i * 2^d + c, bit (d - 1 - j) of c stepping axis j, `weights` fp32 [n, 2^d] the
+ *                    d-linear weights (product over the axes in ascending order).
+ *                    Both OR WCN_FLAG_COORD_RANGE into `status` for a point with a key outside the range (NaN included).
+ *   wcn_lattice_map     `sorted_hi` (NULL when key_dim * 17 <= 64), `sorted_lo` int64 [nnz] and `perm` int64 [nnz] of a STABLE
+ *                    sort -> `unique_keys` int32 [V, key_dim] in lexicographic order, `inverse` int64 [nnz] (vertex of every
+ *                    entry), `row_offsets` int64 [V + 1] (CSR by vertex over `perm`: inside a vertex the entries ascend),
+ *                    `summary` int32 [2] = (V, longest row).  Arrays are the caller's, sized for V = nnz.
+ *   wcn_lattice_plan    the rows of a CSR longer than wcn_lattice_chunk_rows() = 256 entries and their chunks, into `plan`
+ *                    (wcn_lattice_plan_ints(nnz) int32 words); wcn_lattice_plan_items(nnz) = the partial rows a splat needs.
+ *   Feature kernels, fp32, rows of `pitch` floats with pitch % 4 == 0 and 16-B aligned buffers (16-B pieces throughout):
+ *   wcn_lattice_splat   out[r, :] = alpha * sum over j in [row_offsets[r], row_offsets[r + 1]) of w[e] * f[e / k, :] with
+ *                    e = row_entries[j], ascending j, fp32 FMAs.  `plan` NULL: every row by one lane group.  Otherwise rows
+ *                    longer than the chunk are cut into chunks, each summed the same way into `partials`
+ *                    [wcn_lattice_plan_items(nnz), pitch], and added in chunk order.  No float atomics.
+ *   wcn_lattice_blur    y[r] = s0 x[r] + s1 x[n1[r]] + s2 x[n2[r]]; n1, n2 int32 [v], -1 reads as zero, n2 may be NULL; x != y.
+ *   wcn_lattice_slice   out[i] = alpha * sum over j < k of w[i, j] * x[idx[i, j]], ascending j; idx int64, -1 reads as zero.
+ * Arguments are checked before any launch (WCN_ERROR_INVALID_PARAMETERS); an empty call returns WCN_SUCCESS without a launch.
+ * Every grid is capped at 4096 workgroups and strides. */
+int32_t wcn_lattice_chunk_rows(void);
+int wcn_hash128_insert(int64_t* table_keys, int32_t* table_values, int64_t capacity, const int32_t* coords, int64_t n,
+                       int32_t key_dim, int32_t* status, wcn_stream_t stream);
+int wcn_hash128_search(const int64_t* table_keys, const int32_t* table_values, int64_t capacity, const int32_t* queries,
+                       const int32_t* offsets, int64_t m, int32_t k, int32_t key_dim, int32_t* out, wcn_stream_t stream);
+int wcn_permuto_simplex(const float* positions, int64_t n, int32_t d, const float* scale, int64_t* key_hi, int64_t* key_lo,
+                        int32_t* keys, float* bary, int32_t* status, wcn_stream_t stream);
+int wcn_grid_corners(const float* positions, int64_t n, int32_t d, int64_t* floors, int64_t* key_hi, int64_t* key_lo,
+                     int32_t* keys, float* weights, int32_t* status, wcn_stream_t stream);
+size_t wcn_lattice_map_workspace_bytes(int64_t nnz);
+int wcn_lattice_map(const int64_t* sorted_hi, const int64_t* sorted_lo, const int64_t* perm, int64_t nnz, int32_t key_dim,
+                    int32_t* unique_keys, int64_t* inverse, int64_t* row_offsets, int32_t* summary, void* workspace,
+                    size_t workspace_bytes, wcn_stream_t stream);
+int64_t wcn_lattice_plan_items(int64_t nnz);
+int64_t wcn_lattice_plan_ints(int64_t nnz);
+int wcn_lattice_plan(const int64_t* row_offsets, int64_t v, int64_t nnz, int32_t* plan, wcn_stream_t stream);
+int wcn_lattice_splat(const float* f, const float* w, const int64_t* row_offsets, const int64_t* row_entries, int64_t v,
+                      int64_t nnz, int32_t k, int32_t pitch, float alpha, const int32_t* plan, float* partials, float* out,
+                      wcn_stream_t stream);
+int wcn_lattice_blur(const float* x, const int32_t* n1, const int32_t* n2, float s0, float s1, float s2, int64_t v,
+                     int32_t pitch, float* y, wcn_stream_t stream);
+int wcn_lattice_slice(const float* x, const int64_t* idx, const float* w, int64_t n, int32_t k, int64_t v, int32_t pitch,
+                      float alpha, float* out, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -324,6 +324,20 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
          c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_lattice_chunk_rows": (c_int32, []),
+    "wcn_hash128_insert": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "wcn_hash128_search": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                   c_void_p]),
+    "wcn_permuto_simplex": (c_int, [c_void_p, c_int64, c_int32, ctypes.c_float * 6] + [c_void_p] * 6),
+    "wcn_grid_corners": (c_int, [c_void_p, c_int64, c_int32] + [c_void_p] * 7),
+    "wcn_lattice_map_workspace_bytes": (c_size_t, [c_int64]),
+    "wcn_lattice_map": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "wcn_lattice_plan_items": (c_int64, [c_int64]),
+    "wcn_lattice_plan_ints": (c_int64, [c_int64]),
+    "wcn_lattice_plan": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "wcn_lattice_splat": (c_int, [c_void_p] * 4 + [c_int64, c_int64, c_int32, c_int32, ctypes.c_float] + [c_void_p] * 4),
+    "wcn_lattice_blur": (c_int, [c_void_p] * 3 + [ctypes.c_float] * 3 + [c_int64, c_int32, c_void_p, c_void_p]),
+    "wcn_lattice_slice": (c_int, [c_void_p] * 3 + [c_int64, c_int32, c_int64, c_int32, ctypes.c_float, c_void_p, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

@@ -262,7 +262,9 @@ extern "C" {
 //    wcn_kmap_scatter, wcn_kmap_compact_supported, wcn_kmap_densify, WCN_FLAG_ROW_OVERFLOW; mask = NULL in the gather GEMMs now means
 //    a compact table (wcn_conv_compact_table_supported replaces wcn_conv_mask_in_table_supported; dense rows no longer carry a mask)
 // 11 (additions only): wcn_window_group (window grouping of voxels by a deterministic counting sort, csrc/window_group.hip)
-int wcn_abi_version(void) { return 12; }
+// 12 (additions only): wcn_voxel_keys / wcn_voxel_map / wcn_csr_gather_reduce / wcn_row_spread (points <-> voxels, csrc/voxelize.hip)
+// 13 (additions only): lattice filters - wcn_hash128_*, wcn_permuto_simplex, wcn_grid_corners, wcn_lattice_* (csrc/lattice.hip)
+int wcn_abi_version(void) { return 13; }
 
 const char* wcn_status_string(int status) {
   switch (status) {

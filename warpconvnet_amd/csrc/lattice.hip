@@ -1,0 +1,789 @@
+// lattice.hip - high-dimensional filtering on sparse lattices: the permutohedral lattice and the bilateral grid (reference:
+// nn/functional/permutohedral.py, nn/functional/bilateral_grid.py and geometry/coords/search/packed128_hashmap.py, where a
+// filter call is about 40 framework launches with float-atomic index_add_ and a neighbour search per call).
+//
+//   a. hash128       a table for keys of up to 7 axes of 17 bits.  A slot is claimed under linear probing by a 32-bit CAS on
+//                    its VALUE word (-1 -> row); the two key words follow as one plain 16-B store.  Keys are distinct by
+//                    contract, so an inserting thread never compares keys: a claimed slot is skipped.  Searches run in a later
+//                    launch and read value first, key second.
+//   b. geometry      one thread per point, everything in registers: the d + 1 simplex vertices and barycentric weights of the
+//                    permutohedral lattice, or the 2^d corners and d-linear weights of the grid.  Every vertex key goes out as
+//                    a (hi, lo) pair of 64-bit words, axis 0 in the most significant field, fields biased by 2^16, so that the
+//                    unsigned order of the pair is the lexicographic order of the signed rows.  The top bit of `lo` is flipped:
+//                    the framework's sort compares int64 as signed.
+//   c. vertex map    sorted pairs + permutation -> unique keys (decoded), the vertex of every entry, CSR offsets by vertex and
+//                    the longest row.  Tile sums -> one-workgroup scan -> apply, no kernel waits on another workgroup.
+//   d. features      fp32 rows of `pitch` floats, pitch a multiple of 4: every row access is 16-B pieces.
+//                    splat  out[v] = alpha * sum over e in row v of w[e] * f[e / K], ascending; rows longer than kLtChunk are
+//                           cut into chunks summed by their own lane groups into partials that are added in chunk order
+//                    blur   y[v] = s0 x[v] + s1 x[n1[v]] + s2 x[n2[v]], -1 reads as zero
+//                    slice  out[i] = alpha * sum over k of w[i, k] * x[idx[i, k]], -1 reads as zero
+// No float atomics anywhere: the bits of a result depend on the lattice alone.  The integer atomics (status word, longest row,
+// the list of long rows) give the same result in any order.  Every grid is capped at kLtMaxGrid workgroups and strides.
+#include <limits.h>
+
+#include "wcn_common.h"
+
+namespace wcn {
+
+constexpr int kLtThreads = 256;
+constexpr int kLtPer = 8;
+constexpr int kLtTile = kLtThreads * kLtPer;  // sorted entries of one scan tile
+constexpr int kLtMaxGrid = 4096;
+constexpr int kLtChunk = 256;                 // entries of one chunk of a long vertex row (the chunk rule)
+constexpr int kLtCounterInts = 64;            // plan header: [0] chunk items, [1] long rows; padded to 256 B
+constexpr int kLtAxes = 7;                    // key fields
+constexpr int kLtBits = 17;                   // bits of a field
+constexpr int kLtSearchMax = 32;              // offsets of one batched search
+constexpr int kLtCoordMin = -(1 << (kLtBits - 1));
+constexpr int kLtCoordMax = (1 << (kLtBits - 1)) - 1;
+constexpr uint64_t kLtField = (1ull << kLtBits) - 1;
+constexpr uint64_t kLtSign = 1ull << 63;
+
+static unsigned lt_grid(int64_t items) {
+  const int64_t g = items < 1 ? 1 : items;
+  return (unsigned)(g < kLtMaxGrid ? g : kLtMaxGrid);
+}
+
+struct Key128 {
+  uint64_t hi, lo;
+};
+
+// append one field below the ones already there (the caller has checked the range)
+__device__ __forceinline__ void key_push(Key128& k, int c) {
+  k.hi = (k.hi << kLtBits) | (k.lo >> (64 - kLtBits));
+  k.lo = (k.lo << kLtBits) | (uint64_t)(uint32_t)(c - kLtCoordMin);
+}
+
+__device__ __forceinline__ bool lt_in_range(int64_t c) { return c >= kLtCoordMin && c <= kLtCoordMax; }
+
+// field j of a key of key_dim fields
+__device__ __forceinline__ int key_field(const Key128& k, int key_dim, int j) {
+  const int sh = kLtBits * (key_dim - 1 - j);
+  uint64_t f;
+  if (sh >= 64) f = k.hi >> (sh - 64);
+  else if (sh == 0) f = k.lo;
+  else f = (k.lo >> sh) | (k.hi << (64 - sh));
+  return (int)(f & kLtField) + kLtCoordMin;
+}
+
+// ---- a. hash128 -------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t h128_slot(const Key128& k, uint32_t mask) {
+  return hash_slot(k.lo ^ (k.hi * 0x9E3779B97F4A7C15ull), mask);
+}
+
+__global__ __launch_bounds__(kLtThreads) void h128_insert_kernel(ulonglong2* __restrict__ tkeys, int32_t* __restrict__ tvals,
+                                                                 uint32_t mask, const int32_t* __restrict__ coords, int64_t n,
+                                                                 int key_dim, int32_t* __restrict__ status) {
+  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLtThreads) {
+    Key128 k{0, 0};
+    bool ok = true;
+    for (int j = 0; j < key_dim; ++j) {
+      const int c = coords[i * key_dim + j];
+      ok = ok && lt_in_range(c);
+      key_push(k, ok ? c : 0);
+    }
+    if (!ok) {
+      atomicOr(status, WCN_FLAG_COORD_RANGE);
+      continue;
+    }
+    uint32_t s = h128_slot(k, mask);
+    bool placed = false;
+    for (uint32_t attempts = 0; attempts <= mask; ++attempts) {
+      if (atomicCAS(tvals + s, -1, (int32_t)i) == -1) {
+        tkeys[s] = make_ulonglong2(k.hi, k.lo);
+        placed = true;
+        break;
+      }
+      s = (s + 1) & mask;
+    }
+    // n <= capacity distinct keys always find a slot, and the Python class refuses n > capacity before any launch (a thread of a
+    // full table probes every slot): the flag is for direct callers of the C ABI
+    if (!placed) atomicOr(status, WCN_FLAG_TABLE_FULL);
+  }
+}
+
+__device__ __forceinline__ int h128_lookup(const ulonglong2* __restrict__ tkeys, const int32_t* __restrict__ tvals,
+                                           uint32_t mask, const Key128& k) {
+  uint32_t s = h128_slot(k, mask);
+  for (uint32_t attempts = 0; attempts <= mask; ++attempts) {
+    const int32_t v = tvals[s];
+    if (v == -1) return -1;
+    const ulonglong2 q = tkeys[s];
+    if (q.x == k.hi && q.y == k.lo) return v;
+    s = (s + 1) & mask;
+  }
+  return -1;
+}
+
+// out[k, i] = row of queries[i] + offsets[k], -1 when absent or outside the key range; offsets == null: one zero offset
+__global__ __launch_bounds__(kLtThreads) void h128_search_kernel(const ulonglong2* __restrict__ tkeys,
+                                                                 const int32_t* __restrict__ tvals, uint32_t mask,
+                                                                 const int32_t* __restrict__ queries,
+                                                                 const int32_t* __restrict__ offsets, int64_t m, int K,
+                                                                 int key_dim, int32_t* __restrict__ out) {
+  __shared__ int s_off[kLtSearchMax * kLtAxes];
+  for (int t = threadIdx.x; t < K * key_dim; t += kLtThreads) s_off[t] = offsets ? offsets[t] : 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kLtThreads) {
+    int c[kLtAxes];
+#pragma unroll
+    for (int j = 0; j < kLtAxes; ++j) c[j] = j < key_dim ? queries[i * key_dim + j] : 0;
+    for (int k = 0; k < K; ++k) {
+      Key128 key{0, 0};
+      bool ok = true;
+#pragma unroll
+      for (int j = 0; j < kLtAxes; ++j) {
+        if (j < key_dim) {
+          const int64_t v = (int64_t)c[j] + s_off[k * key_dim + j];
+          ok = ok && lt_in_range(v);
+          key_push(key, ok ? (int)v : 0);
+        }
+      }
+      out[(int64_t)k * m + i] = ok ? h128_lookup(tkeys, tvals, mask, key) : -1;
+    }
+  }
+}
+
+// ---- b. geometry ------------------------------------------------------------------------------------------------------------
+struct LtScale {
+  float v[kLtAxes - 1];
+};
+
+__device__ __forceinline__ void lt_emit(const Key128& k, bool ok, int64_t e, int64_t* __restrict__ key_hi,
+                                        int64_t* __restrict__ key_lo) {
+  if (key_hi) key_hi[e] = ok ? (int64_t)k.hi : 0;
+  if (key_lo) key_lo[e] = ok ? (int64_t)(k.lo ^ kLtSign) : (int64_t)kLtSign;
+}
+
+// The arithmetic is the framework's, operation by operation and without contraction into FMAs (embed: product with the scale
+// table, suffix sums; round to the nearest multiple of d + 1; rank the residuals, ties to the lower axis; correct the vertex to
+// coordinate sum 0; weights as differences of neighbouring residuals), so an fp32 build on the host gives the same bits.
+__global__ __launch_bounds__(kLtThreads) void permuto_simplex_kernel(const float* __restrict__ pos, int64_t n, int d, LtScale sc,
+                                                                     int64_t* __restrict__ key_hi, int64_t* __restrict__ key_lo,
+                                                                     int32_t* __restrict__ keys, float* __restrict__ bary,
+                                                                     int32_t* __restrict__ status) {
+#pragma clang fp contract(off)
+  const int dp1 = d + 1;
+  const float fdp1 = (float)dp1;
+  const float inv = (float)(1.0 / (double)dp1);
+  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLtThreads) {
+    float cf[kLtAxes - 1], el[kLtAxes];
+#pragma unroll
+    for (int j = 0; j < kLtAxes - 1; ++j) cf[j] = j < d ? pos[i * d + j] * sc.v[j] : 0.f;
+    float sm = 0.f;
+#pragma unroll
+    for (int t = kLtAxes - 1; t >= 1; --t) {
+      if (t <= d) {
+        el[t] = sm - (float)t * cf[t - 1];
+        sm = sm + cf[t - 1];
+      } else {
+        el[t] = 0.f;
+      }
+    }
+    el[0] = sm;
+    int g[kLtAxes], rank[kLtAxes];
+    float diff[kLtAxes];
+    bool ok = true;
+    int sum = 0;
+#pragma unroll
+    for (int j = 0; j < kLtAxes; ++j) {
+      g[j] = 0;
+      diff[j] = 0.f;
+      if (j < dp1) {
+        const float v = el[j] * inv;
+        const float up = ceilf(v) * fdp1, down = floorf(v) * fdp1;
+        const float gr = (up - el[j]) < (el[j] - down) ? up : down;
+        ok = ok && fabsf(gr) <= 1048576.f;  // NaN and anything the 17-bit fields cannot hold by far
+        g[j] = ok ? (int)gr : 0;
+        diff[j] = el[j] - gr;
+        sum += g[j];
+      }
+    }
+    if (!ok) {
+      atomicOr(status, WCN_FLAG_COORD_RANGE);
+      for (int k = 0; k < dp1; ++k) {
+        lt_emit(Key128{0, 0}, false, i * dp1 + k, key_hi, key_lo);
+        bary[i * dp1 + k] = 0.f;
+        if (keys)
+          for (int j = 0; j < dp1; ++j) keys[(i * dp1 + k) * dp1 + j] = 0;
+      }
+      continue;
+    }
+    const int sum_g = sum >= 0 ? sum / dp1 : -((-sum + dp1 - 1) / dp1);  // floor division
+#pragma unroll
+    for (int j = 0; j < kLtAxes; ++j) {
+      int r = 0;
+#pragma unroll
+      for (int q = 0; q < kLtAxes; ++q)
+        if (q < dp1 && j < dp1 && (diff[q] > diff[j] || (diff[q] == diff[j] && q < j))) ++r;
+      rank[j] = r;
+    }
+    const int up_n = sum_g > 0 ? sum_g : 0, dn_n = sum_g < 0 ? -sum_g : 0;
+    float delta[kLtAxes];
+#pragma unroll
+    for (int j = 0; j < kLtAxes; ++j) {
+      delta[j] = 0.f;
+      if (j < dp1) {
+        const int shift = ((rank[j] < dn_n) ? dp1 : 0) - ((rank[j] >= dp1 - up_n) ? dp1 : 0);
+        g[j] += shift;
+        rank[j] += sum_g + shift;
+        delta[j] = (el[j] - (float)g[j]) * inv;
+      }
+    }
+    // weight t = residual of the axis with rank d - t, minus the residual of the axis with rank d + 1 - t
+    float b[kLtAxes];
+    float wrap = 0.f;
+#pragma unroll
+    for (int t = 0; t < kLtAxes; ++t) {
+      float plus = 0.f, minus = 0.f;
+#pragma unroll
+      for (int j = 0; j < kLtAxes; ++j) {
+        if (j < dp1) {
+          plus = rank[j] == d - t ? delta[j] : plus;
+          minus = rank[j] == d + 1 - t ? delta[j] : minus;
+        }
+      }
+      b[t] = plus - minus;
+    }
+#pragma unroll
+    for (int j = 0; j < kLtAxes; ++j)
+      if (j < dp1 && rank[j] == 0) wrap = -delta[j];
+    b[0] = (b[0] + 1.0f) + wrap;
+    bool all_ok = true;
+#pragma unroll
+    for (int k = 0; k < kLtAxes; ++k) {
+      if (k < dp1) {
+        Key128 key{0, 0};
+        bool kok = true;
+        const int64_t e = i * dp1 + k;
+#pragma unroll
+        for (int j = 0; j < kLtAxes; ++j) {
+          if (j < dp1) {
+            const int c = g[j] + (rank[j] <= d - k ? k : k - dp1);
+            kok = kok && lt_in_range(c);
+            key_push(key, kok ? c : 0);
+            if (keys) keys[e * dp1 + j] = c;
+          }
+        }
+        lt_emit(key, kok, e, key_hi, key_lo);
+        bary[e] = b[k];
+        all_ok = all_ok && kok;
+      }
+    }
+    if (!all_ok) atomicOr(status, WCN_FLAG_COORD_RANGE);
+  }
+}
+
+// corner c of a point: bit (d - 1 - j) of c steps axis j, the order of itertools.product([0, 1], repeat=d)
+__global__ __launch_bounds__(kLtThreads) void grid_corners_kernel(const float* __restrict__ pos, int64_t n, int d,
+                                                                  int64_t* __restrict__ floors, int64_t* __restrict__ key_hi,
+                                                                  int64_t* __restrict__ key_lo, int32_t* __restrict__ keys,
+                                                                  float* __restrict__ weights, int32_t* __restrict__ status) {
+#pragma clang fp contract(off)
+  const int K = 1 << d;
+  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLtThreads) {
+    int fl[kLtAxes - 1];
+    float fr[kLtAxes - 1];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < kLtAxes - 1; ++j) {
+      fl[j] = 0;
+      fr[j] = 0.f;
+      if (j < d) {
+        const float p = pos[i * d + j], f = floorf(p);
+        ok = ok && f >= (float)kLtCoordMin && f <= (float)kLtCoordMax;  // the floor itself; its upper corner is judged per corner
+        fl[j] = ok ? (int)f : 0;
+        fr[j] = p - f;
+        if (floors) floors[i * d + j] = fl[j];
+      }
+    }
+    bool all_ok = ok;
+    for (int c = 0; c < K; ++c) {
+      Key128 key{0, 0};
+      bool kok = ok;
+      float w = 1.f;
+      const int64_t e = i * K + c;
+#pragma unroll
+      for (int j = 0; j < kLtAxes - 1; ++j) {
+        if (j < d) {
+          const int bit = (c >> (d - 1 - j)) & 1;
+          w = w * (bit ? fr[j] : 1.f - fr[j]);
+          kok = kok && lt_in_range(fl[j] + bit);
+          key_push(key, kok ? fl[j] + bit : 0);
+          if (keys) keys[e * d + j] = fl[j] + bit;  // a corner one past the range: the search reports it absent
+        }
+      }
+      lt_emit(key, kok, e, key_hi, key_lo);
+      weights[e] = ok ? w : 0.f;  // a point whose floor is outside the range (NaN included) weighs nothing
+      all_ok = all_ok && kok;
+    }
+    if (!all_ok) atomicOr(status, WCN_FLAG_COORD_RANGE);
+  }
+}
+
+// ---- c. runs -> vertex map --------------------------------------------------------------------------------------------------
+// thread t of a tile owns the sorted positions tile * kLtTile + t * kLtPer .. + kLtPer - 1; head = first position of a run
+__device__ __forceinline__ int lt_load_heads(const int64_t* __restrict__ hi, const int64_t* __restrict__ lo, int64_t n, int64_t i0,
+                                             int64_t (&kh)[kLtPer], int64_t (&kl)[kLtPer], bool (&head)[kLtPer]) {
+#pragma unroll
+  for (int j = 0; j < kLtPer; ++j) {
+    kh[j] = (hi && i0 + j < n) ? hi[i0 + j] : 0;
+    kl[j] = i0 + j < n ? lo[i0 + j] : 0;
+  }
+  int64_t ph = (hi && i0 > 0 && i0 < n) ? hi[i0 - 1] : 0;
+  int64_t pl = (i0 > 0 && i0 < n) ? lo[i0 - 1] : 0;
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < kLtPer; ++j) {
+    head[j] = i0 + j < n && (i0 + j == 0 || kh[j] != ph || kl[j] != pl);
+    ph = kh[j];
+    pl = kl[j];
+    cnt += head[j] ? 1 : 0;
+  }
+  return cnt;
+}
+
+__global__ __launch_bounds__(kLtThreads) void lt_tile_count_kernel(const int64_t* __restrict__ hi, const int64_t* __restrict__ lo,
+                                                                   int64_t n, int64_t ntiles, int32_t* __restrict__ tile_sum) {
+  __shared__ int s_wave[kLtThreads / 64];
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t kh[kLtPer], kl[kLtPer];
+    bool head[kLtPer];
+    const int cnt = lt_load_heads(hi, lo, n, tile * kLtTile + (int64_t)threadIdx.x * kLtPer, kh, kl, head);
+    int tot;
+    block_excl_scan<kLtThreads>(cnt, s_wave, &tot);
+    if (threadIdx.x == 0) tile_sum[tile] = tot;
+    __syncthreads();  // s_wave is rewritten by the next trip
+  }
+}
+
+// ONE workgroup: exclusive scan of the tile sums in place; summary[0] = V and the closing boundary row_offsets[V] = n
+__global__ __launch_bounds__(kLtThreads) void lt_tile_scan_kernel(int32_t* __restrict__ tile_sum, int64_t ntiles, int64_t n,
+                                                                  int32_t* __restrict__ summary,
+                                                                  int64_t* __restrict__ row_offsets) {
+  __shared__ int s_wave[kLtThreads / 64];
+  int carry = 0;
+  for (int64_t base = 0; base < ntiles; base += kLtThreads) {
+    const int64_t i = base + threadIdx.x;
+    const int v = i < ntiles ? tile_sum[i] : 0;
+    int tot;
+    const int e = block_excl_scan<kLtThreads>(v, s_wave, &tot);
+    if (i < ntiles) tile_sum[i] = carry + e;
+    carry += tot;
+    __syncthreads();  // s_wave is rewritten by the next trip
+  }
+  if (threadIdx.x == 0) {
+    summary[0] = carry;
+    row_offsets[carry] = n;  // carry <= n: the caller's buffer holds n + 1 words
+  }
+}
+
+__global__ __launch_bounds__(kLtThreads) void lt_apply_kernel(const int64_t* __restrict__ hi, const int64_t* __restrict__ lo,
+                                                              const int64_t* __restrict__ perm, int64_t n, int64_t ntiles,
+                                                              const int32_t* __restrict__ tile_sum, int key_dim,
+                                                              int32_t* __restrict__ unique_keys, int64_t* __restrict__ inverse,
+                                                              int64_t* __restrict__ row_offsets) {
+  __shared__ int s_wave[kLtThreads / 64];
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t i0 = tile * kLtTile + (int64_t)threadIdx.x * kLtPer;
+    int64_t kh[kLtPer], kl[kLtPer];
+    bool head[kLtPer];
+    const int cnt = lt_load_heads(hi, lo, n, i0, kh, kl, head);
+    int tot;
+    int64_t vid = (int64_t)tile_sum[tile] + block_excl_scan<kLtThreads>(cnt, s_wave, &tot) - 1;  // vertex of position i0 - 1
+#pragma unroll
+    for (int j = 0; j < kLtPer; ++j) {
+      const int64_t i = i0 + j;
+      if (i >= n) break;
+      if (head[j]) {
+        ++vid;
+        if (vid >= 0 && vid < n) {
+          row_offsets[vid] = i;
+          const Key128 k{(uint64_t)kh[j], (uint64_t)kl[j] ^ kLtSign};
+          for (int a = 0; a < key_dim; ++a) unique_keys[vid * key_dim + a] = key_field(k, key_dim, a);
+        }
+      }
+      const int64_t e = perm[i];
+      if (e >= 0 && e < n) inverse[e] = vid;
+    }
+    __syncthreads();  // s_wave is rewritten by the next trip
+  }
+}
+
+__global__ __launch_bounds__(kLtThreads) void lt_longest_kernel(const int64_t* __restrict__ row_offsets, int64_t n,
+                                                                int32_t* __restrict__ summary) {
+  int64_t V = summary[0];
+  if (V > n) V = n;
+  int longest = 0;
+  for (int64_t v = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kLtThreads) {
+    const int64_t len = row_offsets[v + 1] - row_offsets[v];
+    longest = max(longest, (int)(len < INT_MAX ? len : INT_MAX));
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d));
+  if ((threadIdx.x & 63) == 0 && longest > 0) atomicMax(summary + 1, longest);
+}
+
+// ---- long rows: the chunk plan of a CSR -------------------------------------------------------------------------------------
+struct LtPlan {  // int32 words of the caller's plan buffer
+  int32_t* counters;   // [0] chunk items, [1] long rows
+  int32_t* item_row;   // [item_cap]
+  int32_t* item_k;     // [item_cap] chunk number inside the row
+  int32_t* long_row;   // [long_cap]
+  int32_t* long_base;  // [long_cap] first item of the row
+  int64_t item_cap, long_cap, ints;
+};
+
+static LtPlan lt_carve(int32_t* base, int64_t nnz) {
+  LtPlan p;
+  p.long_cap = nnz / kLtChunk + 1;  // a long row holds more than kLtChunk entries
+  p.item_cap = 2 * p.long_cap;      // ceil(len / chunk) <= len / chunk + 1 per long row
+  int64_t at = 0;
+  p.counters = base + at;
+  at += kLtCounterInts;
+  p.item_row = base + at;
+  at += p.item_cap;
+  p.item_k = base + at;
+  at += p.item_cap;
+  p.long_row = base + at;
+  at += p.long_cap;
+  p.long_base = base + at;
+  at += p.long_cap;
+  p.ints = at;
+  return p;
+}
+
+// one wave looks at 64 rows; every long one takes its run of items with one integer atomic and the wave writes the run
+__global__ __launch_bounds__(kLtThreads) void lt_plan_kernel(const int64_t* __restrict__ offsets, int64_t m, int64_t nnz,
+                                                             LtPlan w) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (kLtThreads / 64) + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (kLtThreads / 64);
+  for (int64_t base = wave * 64; base < m; base += nwaves * 64) {
+    const int64_t row = base + lane;
+    int nch = 0;
+    if (row < m) {
+      const int64_t j0 = offsets[row], j1 = offsets[row + 1];
+      if (j0 >= 0 && j1 <= nnz && j1 - j0 > kLtChunk) nch = (int)((j1 - j0 + kLtChunk - 1) / kLtChunk);
+    }
+    unsigned long long todo = __ballot(nch > 0);
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int s_row = (int)__shfl((int)row, src), s_n = __shfl(nch, src);
+      int first = 0, slot = 0;
+      if (lane == 0) {
+        first = atomicAdd(w.counters, s_n);
+        slot = atomicAdd(w.counters + 1, 1);
+        if (slot < w.long_cap) {
+          w.long_row[slot] = s_row;
+          w.long_base[slot] = first;
+        }
+      }
+      first = __shfl(first, 0);
+      for (int k = lane; k < s_n; k += 64) {
+        if ((int64_t)first + k < w.item_cap) {
+          w.item_row[first + k] = s_row;
+          w.item_k[first + k] = k;
+        }
+      }
+    }
+  }
+}
+
+// ---- d. feature kernels -----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 f4_fma(float a, const float4& x, const float4& acc) {
+  return make_float4(fmaf(a, x.x, acc.x), fmaf(a, x.y, acc.y), fmaf(a, x.z, acc.z), fmaf(a, x.w, acc.w));
+}
+__device__ __forceinline__ float4 f4_scale(float a, const float4& x) { return make_float4(a * x.x, a * x.y, a * x.z, a * x.w); }
+
+// entries [j0, j1) of one row, ascending, four loads in flight: acc += w[e] * f[e / K]
+__device__ __forceinline__ float4 lt_row_sum(const float4* __restrict__ f, const float* __restrict__ w,
+                                             const int64_t* __restrict__ entries, int64_t j0, int64_t j1, int64_t nnz,
+                                             uint32_t K, int P4, int p) {
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  int64_t j = j0;
+  for (; j + 4 <= j1; j += 4) {
+    float wt[4];
+    float4 x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t e = entries[j + u];
+      const bool ok = e >= 0 && e < nnz;
+      wt[u] = ok ? w[e] : 0.f;
+      x[u] = ok ? f[(int64_t)((uint32_t)e / K) * P4 + p] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc = f4_fma(wt[u], x[u], acc);
+  }
+  for (; j < j1; ++j) {
+    const int64_t e = entries[j];
+    if (e >= 0 && e < nnz) acc = f4_fma(w[e], f[(int64_t)((uint32_t)e / K) * P4 + p], acc);
+  }
+  return acc;
+}
+
+// L lanes (a power of two <= 64) own one list: ITEMS = false, a whole row (longer ones are skipped when `split`); ITEMS = true,
+// one chunk of a long row into the partials.  Rows wider than L pieces take several trips.
+template <bool ITEMS>
+__global__ __launch_bounds__(kLtThreads) void lt_splat_kernel(const float4* __restrict__ f, const float* __restrict__ w,
+                                                              const int64_t* __restrict__ offsets,
+                                                              const int64_t* __restrict__ entries, int64_t m, int64_t nnz,
+                                                              uint32_t K, int P4, int L, float alpha, int split,
+                                                              float4* __restrict__ out, LtPlan plan, float4* __restrict__ part) {
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  int64_t total = m;
+  if (ITEMS) {
+    total = plan.counters[0];
+    if (total > plan.item_cap) total = plan.item_cap;
+  }
+  for (int64_t t = (int64_t)blockIdx.x * groups + g; t < total; t += (int64_t)gridDim.x * groups) {
+    const int64_t row = ITEMS ? plan.item_row[t] : t;
+    if (row < 0 || row >= m) continue;
+    int64_t j0 = offsets[row], j1 = offsets[row + 1];
+    if (j0 < 0 || j1 > nnz || j1 < j0) j1 = j0 = 0;  // offsets that do not describe the list: an empty row
+    if (ITEMS) {
+      j0 += (int64_t)plan.item_k[t] * kLtChunk;
+      if (j0 > j1) j0 = j1;
+      if (j1 - j0 > kLtChunk) j1 = j0 + kLtChunk;
+    } else if (split && j1 - j0 > kLtChunk) {
+      continue;
+    }
+    for (int p = sub; p < P4; p += L) {
+      const float4 acc = lt_row_sum(f, w, entries, j0, j1, nnz, K, P4, p);
+      if (ITEMS) part[t * P4 + p] = acc;
+      else out[row * P4 + p] = f4_scale(alpha, acc);
+    }
+  }
+}
+
+// L lanes per long row: its partials in chunk order
+__global__ __launch_bounds__(kLtThreads) void lt_combine_kernel(const int64_t* __restrict__ offsets, int64_t m, int P4, int L,
+                                                                float alpha, float4* __restrict__ out, LtPlan plan,
+                                                                const float4* __restrict__ part) {
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  int64_t total = plan.counters[1];
+  if (total > plan.long_cap) total = plan.long_cap;
+  for (int64_t t = (int64_t)blockIdx.x * groups + g; t < total; t += (int64_t)gridDim.x * groups) {
+    const int64_t row = plan.long_row[t], first = plan.long_base[t];
+    if (row < 0 || row >= m) continue;
+    const int64_t len = offsets[row + 1] - offsets[row];
+    const int64_t nch = (len + kLtChunk - 1) / kLtChunk;
+    if (first < 0 || nch < 1 || first + nch > plan.item_cap) continue;
+    for (int p = sub; p < P4; p += L) {
+      float4 acc = part[first * P4 + p];
+      for (int64_t k = 1; k < nch; ++k) {
+        const float4 q = part[(first + k) * P4 + p];
+        acc = make_float4(acc.x + q.x, acc.y + q.y, acc.z + q.z, acc.w + q.w);
+      }
+      out[row * P4 + p] = f4_scale(alpha, acc);
+    }
+  }
+}
+
+__device__ __forceinline__ float4 lt_row_or_zero(const float4* __restrict__ x, int64_t r, int64_t m, int P4, int p) {
+  return (r >= 0 && r < m) ? x[r * P4 + p] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__global__ __launch_bounds__(kLtThreads) void lt_blur_kernel(const float4* __restrict__ x, const int32_t* __restrict__ n1,
+                                                             const int32_t* __restrict__ n2, float s0, float s1, float s2,
+                                                             int64_t m, int P4, int L, float4* __restrict__ y) {
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
+    const int64_t a = n1[v], b = n2 ? n2[v] : -1;
+    for (int p = sub; p < P4; p += L) {
+      const float4 xa = lt_row_or_zero(x, a, m, P4, p), xb = lt_row_or_zero(x, b, m, P4, p);
+      float4 acc = f4_scale(s0, x[v * P4 + p]);
+      acc = f4_fma(s1, xa, acc);
+      if (n2) acc = f4_fma(s2, xb, acc);
+      y[v * P4 + p] = acc;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kLtThreads) void lt_slice_kernel(const float4* __restrict__ x, const int64_t* __restrict__ idx,
+                                                              const float* __restrict__ w, int64_t n, int K, int64_t m, int P4,
+                                                              int L, float alpha, float4* __restrict__ out) {
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  for (int64_t i = (int64_t)blockIdx.x * groups + g; i < n; i += (int64_t)gridDim.x * groups) {
+    for (int p = sub; p < P4; p += L) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k = 0; k < K; ++k) {
+        const int64_t r = idx[i * K + k];
+        if (r >= 0 && r < m) acc = f4_fma(w[i * K + k], x[r * P4 + p], acc);
+      }
+      out[i * P4 + p] = f4_scale(alpha, acc);
+    }
+  }
+}
+
+static int lt_lanes(int64_t pieces) {
+  int L = 1;
+  while (L < pieces && L < 64) L <<= 1;
+  return L;
+}
+
+static bool lt_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
+
+}  // namespace wcn
+
+using namespace wcn;
+
+extern "C" {
+
+int32_t wcn_lattice_chunk_rows(void) { return kLtChunk; }
+
+int wcn_hash128_insert(int64_t* table_keys, int32_t* table_values, int64_t capacity, const int32_t* coords, int64_t n,
+                       int32_t key_dim, int32_t* status, wcn_stream_t stream) {
+  if (!lt_pow2(capacity) || capacity > (1ll << 31) || n < 0 || n > INT32_MAX || key_dim < 1 || key_dim > kLtAxes ||
+      !table_keys || !table_values || !status || !aligned_to(table_keys, 16) || (n > 0 && !coords))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(table_values, 0xFF, (size_t)capacity * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
+  if (n == 0) return WCN_SUCCESS;
+  hipLaunchKernelGGL(h128_insert_kernel, dim3(lt_grid(ceil_div(n, kLtThreads))), dim3(kLtThreads), 0, s,
+                     (ulonglong2*)table_keys, table_values, (uint32_t)(capacity - 1), coords, n, (int)key_dim, status);
+  return launch_status();
+}
+
+int wcn_hash128_search(const int64_t* table_keys, const int32_t* table_values, int64_t capacity, const int32_t* queries,
+                       const int32_t* offsets, int64_t m, int32_t k, int32_t key_dim, int32_t* out, wcn_stream_t stream) {
+  if (!lt_pow2(capacity) || capacity > (1ll << 31) || m < 0 || m > INT32_MAX || k < 1 || k > kLtSearchMax || key_dim < 1 ||
+      key_dim > kLtAxes || !table_keys || !table_values || !aligned_to(table_keys, 16))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (m == 0) return WCN_SUCCESS;
+  if (!queries || !out) return WCN_ERROR_INVALID_PARAMETERS;
+  hipLaunchKernelGGL(h128_search_kernel, dim3(lt_grid(ceil_div(m, kLtThreads))), dim3(kLtThreads), 0, (hipStream_t)stream,
+                     (const ulonglong2*)table_keys, table_values, (uint32_t)(capacity - 1), queries, offsets, m, (int)k,
+                     (int)key_dim, out);
+  return launch_status();
+}
+
+static int geometry_args_ok(const float* positions, int64_t n, int32_t d, int64_t entries_per_point, const float* weights,
+                            const int32_t* status) {
+  if (n < 0 || d < 1 || d > kLtAxes - 1 || !status || n * entries_per_point > INT32_MAX) return WCN_ERROR_INVALID_PARAMETERS;
+  if (n > 0 && (!positions || !weights)) return WCN_ERROR_INVALID_PARAMETERS;
+  return WCN_SUCCESS;
+}
+
+int wcn_permuto_simplex(const float* positions, int64_t n, int32_t d, const float* scale, int64_t* key_hi, int64_t* key_lo,
+                        int32_t* keys, float* bary, int32_t* status, wcn_stream_t stream) {
+  const int st = geometry_args_ok(positions, n, d, (int64_t)d + 1, bary, status);
+  if (st != WCN_SUCCESS) return st;
+  if (!scale) return WCN_ERROR_INVALID_PARAMETERS;
+  if (n == 0) return WCN_SUCCESS;
+  LtScale sc{};
+  for (int j = 0; j < d; ++j) sc.v[j] = scale[j];
+  hipLaunchKernelGGL(permuto_simplex_kernel, dim3(lt_grid(ceil_div(n, kLtThreads))), dim3(kLtThreads), 0, (hipStream_t)stream,
+                     positions, n, (int)d, sc, key_hi, key_lo, keys, bary, status);
+  return launch_status();
+}
+
+int wcn_grid_corners(const float* positions, int64_t n, int32_t d, int64_t* floors, int64_t* key_hi, int64_t* key_lo,
+                     int32_t* keys, float* weights, int32_t* status, wcn_stream_t stream) {
+  const int st = geometry_args_ok(positions, n, d, d >= 1 && d < kLtAxes ? (int64_t)1 << d : 1, weights, status);
+  if (st != WCN_SUCCESS) return st;
+  if (n == 0) return WCN_SUCCESS;
+  hipLaunchKernelGGL(grid_corners_kernel, dim3(lt_grid(ceil_div(n, kLtThreads))), dim3(kLtThreads), 0, (hipStream_t)stream,
+                     positions, n, (int)d, floors, key_hi, key_lo, keys, weights, status);
+  return launch_status();
+}
+
+size_t wcn_lattice_map_workspace_bytes(int64_t nnz) {
+  if (nnz < 0) return 0;
+  return align256((size_t)ceil_div(nnz > 0 ? nnz : 1, kLtTile) * 4);
+}
+
+int wcn_lattice_map(const int64_t* sorted_hi, const int64_t* sorted_lo, const int64_t* perm, int64_t nnz, int32_t key_dim,
+                    int32_t* unique_keys, int64_t* inverse, int64_t* row_offsets, int32_t* summary, void* workspace,
+                    size_t workspace_bytes, wcn_stream_t stream) {
+  if (nnz < 0 || nnz > INT32_MAX || key_dim < 1 || key_dim > kLtAxes || !summary || !row_offsets)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (nnz > 0 && (!sorted_lo || !perm || !unique_keys || !inverse || !workspace ||
+                  workspace_bytes < wcn_lattice_map_workspace_bytes(nnz) || (!sorted_hi && key_dim * kLtBits > 64)))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(summary, 0, 8, s) != hipSuccess || hipMemsetAsync(row_offsets, 0, 8, s) != hipSuccess)
+    return WCN_ERROR_KERNEL_EXECUTION;
+  if (nnz == 0) return WCN_SUCCESS;
+  const int64_t ntiles = ceil_div(nnz, kLtTile);
+  int32_t* tile_sum = (int32_t*)workspace;
+  const dim3 block(kLtThreads), tiles(lt_grid(ntiles));
+  hipLaunchKernelGGL(lt_tile_count_kernel, tiles, block, 0, s, sorted_hi, sorted_lo, nnz, ntiles, tile_sum);
+  hipLaunchKernelGGL(lt_tile_scan_kernel, dim3(1), block, 0, s, tile_sum, ntiles, nnz, summary, row_offsets);
+  hipLaunchKernelGGL(lt_apply_kernel, tiles, block, 0, s, sorted_hi, sorted_lo, perm, nnz, ntiles, tile_sum, (int)key_dim,
+                     unique_keys, inverse, row_offsets);
+  hipLaunchKernelGGL(lt_longest_kernel, dim3(lt_grid(ceil_div(nnz, kLtThreads))), block, 0, s, row_offsets, nnz, summary);
+  return launch_status();
+}
+
+int64_t wcn_lattice_plan_items(int64_t nnz) { return nnz < 0 ? 0 : lt_carve(nullptr, nnz).item_cap; }
+int64_t wcn_lattice_plan_ints(int64_t nnz) { return nnz < 0 ? 0 : lt_carve(nullptr, nnz).ints; }
+
+int wcn_lattice_plan(const int64_t* row_offsets, int64_t v, int64_t nnz, int32_t* plan, wcn_stream_t stream) {
+  if (v < 0 || v > INT32_MAX || nnz < 0 || nnz > INT32_MAX || !plan || (v > 0 && !row_offsets))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(plan, 0, kLtCounterInts * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
+  if (v == 0) return WCN_SUCCESS;
+  hipLaunchKernelGGL(lt_plan_kernel, dim3(lt_grid(ceil_div(v, kLtThreads))), dim3(kLtThreads), 0, s, row_offsets, v, nnz,
+                     lt_carve(plan, nnz));
+  return launch_status();
+}
+
+static bool feature_args_ok(int64_t rows, int32_t pitch, const void* a, const void* b) {
+  return rows >= 0 && rows <= INT32_MAX && pitch >= 4 && pitch % 4 == 0 && aligned_to(a, 16) && aligned_to(b, 16);
+}
+
+int wcn_lattice_splat(const float* f, const float* w, const int64_t* row_offsets, const int64_t* row_entries, int64_t v,
+                      int64_t nnz, int32_t k, int32_t pitch, float alpha, const int32_t* plan, float* partials, float* out,
+                      wcn_stream_t stream) {
+  if (!feature_args_ok(v, pitch, f, out) || nnz < 0 || nnz > INT32_MAX || k < 1 || !aligned_to(partials, 16) ||
+      (plan && !partials))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (v == 0) return WCN_SUCCESS;
+  if (!out || !row_offsets || (nnz > 0 && (!f || !w || !row_entries))) return WCN_ERROR_INVALID_PARAMETERS;
+  hipStream_t s = (hipStream_t)stream;
+  const int P4 = pitch / 4, L = lt_lanes(P4), groups = kLtThreads / L;
+  const LtPlan p = plan ? lt_carve(const_cast<int32_t*>(plan), nnz) : LtPlan{};
+  hipLaunchKernelGGL(lt_splat_kernel<false>, dim3(lt_grid(ceil_div(v, groups))), dim3(kLtThreads), 0, s, (const float4*)f, w,
+                     row_offsets, row_entries, v, nnz, (uint32_t)k, P4, L, alpha, plan ? 1 : 0, (float4*)out, p,
+                     (float4*)partials);
+  if (!plan) return launch_status();
+  hipLaunchKernelGGL(lt_splat_kernel<true>, dim3(lt_grid(ceil_div(p.item_cap, groups))), dim3(kLtThreads), 0, s,
+                     (const float4*)f, w, row_offsets, row_entries, v, nnz, (uint32_t)k, P4, L, alpha, 1, (float4*)out, p,
+                     (float4*)partials);
+  hipLaunchKernelGGL(lt_combine_kernel, dim3(lt_grid(ceil_div(p.long_cap, groups))), dim3(kLtThreads), 0, s, row_offsets, v, P4,
+                     L, alpha, (float4*)out, p, (const float4*)partials);
+  return launch_status();
+}
+
+int wcn_lattice_blur(const float* x, const int32_t* n1, const int32_t* n2, float s0, float s1, float s2, int64_t v,
+                     int32_t pitch, float* y, wcn_stream_t stream) {
+  if (!feature_args_ok(v, pitch, x, y) || x == y) return WCN_ERROR_INVALID_PARAMETERS;
+  if (v == 0) return WCN_SUCCESS;
+  if (!x || !y || !n1) return WCN_ERROR_INVALID_PARAMETERS;
+  const int P4 = pitch / 4, L = lt_lanes(P4);
+  hipLaunchKernelGGL(lt_blur_kernel, dim3(lt_grid(ceil_div(v, kLtThreads / L))), dim3(kLtThreads), 0, (hipStream_t)stream,
+                     (const float4*)x, n1, n2, s0, s1, s2, v, P4, L, (float4*)y);
+  return launch_status();
+}
+
+int wcn_lattice_slice(const float* x, const int64_t* idx, const float* w, int64_t n, int32_t k, int64_t v, int32_t pitch,
+                      float alpha, float* out, wcn_stream_t stream) {
+  if (!feature_args_ok(n, pitch, x, out) || v < 0 || v > INT32_MAX || k < 1 || n * (int64_t)k > INT32_MAX)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (n == 0) return WCN_SUCCESS;
+  if (!out || !idx || !w || (v > 0 && !x)) return WCN_ERROR_INVALID_PARAMETERS;
+  const int P4 = pitch / 4, L = lt_lanes(P4);
+  hipLaunchKernelGGL(lt_slice_kernel, dim3(lt_grid(ceil_div(n, kLtThreads / L))), dim3(kLtThreads), 0, (hipStream_t)stream,
+                     (const float4*)x, idx, w, n, (int)k, v, P4, L, alpha, (float4*)out);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -4,6 +4,9 @@ from .fused_block import FusedSparseConvBlock
 from .activations import DropPath
 from .mlp import Linear, MLPBlock
 from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
+from .bilateral import BilateralFilterGrid, BilateralFilterGridCached
+from .permutohedral import (BilateralPermutohedralFilter, BilateralPermutohedralFilterCached, PermutohedralFilter,
+                            PermutohedralFilterCached)
 from .point_conv import PointConv
 from .prune import SparsePrune
 from .rope import VoxelRotaryPositionalEmbeddings, suggest_voxel_rope_base
@@ -31,4 +34,6 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "SparseConvNeXtBlock3d", "SparseChannelToSpatialResBlock3d", "SparseSpatialToChannelResBlock3d",
            "SparseUNetDecoderStages", "SparseUNetEncoderStages",
            "DropPath", "Linear", "SpaceAttention", "AllAttention", "STR2ATTN", "SpaCeFormerBlockBase", "PreNormBlock",
-           "PostNormBlock", "StreamNormBlock", "BLOCK_REGISTRY", "block_factory"]
+           "PostNormBlock", "StreamNormBlock", "BLOCK_REGISTRY", "block_factory",
+           "PermutohedralFilter", "PermutohedralFilterCached", "BilateralPermutohedralFilter",
+           "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached"]
