@@ -997,6 +997,36 @@ int wcn_lattice_blur(const float* x, const int32_t* n1, const int32_t* n2, float
 int wcn_lattice_slice(const float* x, const int64_t* idx, const float* w, int64_t n, int32_t k, int64_t v, int32_t pitch,
                       float alpha, float* out, wcn_stream_t stream);
 
+/* ---- the fast bilateral solver and the kNN bilateral filter (ABI 14, additions only) -----------------------------------------
+ * Reference: bilateral_solver of nn/functional/bilateral_grid.py and nn/functional/bilateral.py.  fp32 rows of `pitch` floats
+ * as above; `neighbours` int32 [2 d, v] is the grid's table (rows 2a / 2a + 1 = one step forward / backward along axis a, -1
+ * absent); the blur is the grid's: per axis y = b x + (c b) x[fwd], then y + a y[bwd], with the taps (a, b, c).
+ *   wcn_lattice_max_grid  the cap of every grid of these kernels (4096) = the slots of one scalar's partials.
+ *   wcn_lattice_row_grid  workgroups of a row kernel over `rows` rows of `pitch` floats = the partials it writes.
+ *   wcn_bilateral_matvec  ap = (dc p) - lam n blur(n p) with per-vertex `nvec`, `dc` fp32 [v]; partials[g] = workgroup g's share
+ *                    of sum p . ap in fp64.  `spare`: [2, v, pitch] floats.  2 d launches.
+ *   wcn_bilateral_pcg     the preconditioned conjugate-gradient loop of the solver on the device.  In: `tbar` [v, pitch], `y` =
+ *                    the start t / C, `minv` = 1 / diag(A).  `work` [6, v, pitch] floats (r, p, z, A p, two blur buffers),
+ *                    `partials` fp64 [3, wcn_lattice_max_grid()], `state` fp64 [8] = (rz_old by iteration parity [2], |r0|,
+ *                    done by parity [2], iterations carried out, a residual norm was not finite, 0).  max_iters iterations of
+ *                    2 d + 2 launches each are enqueued; once |r| / |r0| < tol holds after the update of y and r, every later
+ *                    launch that could write y, r, p or z returns at once, so y is the y of a loop that broke there.  Scalars:
+ *                    fp64 products and sums, one partial per workgroup, partials added in index order; no float atomics.
+ *   wcn_bilateral_knn_weights  weights[i, s] = w / max(sum over s of w, 1e-20), w = exp(-|src_xyz[nbr[i, s]] - query_xyz[i]|^2
+ *                    / (2 sigma_xyz^2) - |src_feat[..] - query_feat[i]|^2 / (2 sigma_feat^2)); fp32 [*, dx] / [*, df] rows,
+ *                    `nbr` int64 [m, k], the row sum in slot order; an index outside [0, n) weighs nothing. */
+int32_t wcn_lattice_max_grid(void);
+int32_t wcn_lattice_row_grid(int64_t rows, int32_t pitch);
+int wcn_bilateral_matvec(const int32_t* neighbours, int32_t d, int64_t v, int32_t pitch, float tap_a, float tap_b, float tap_c,
+                         const float* nvec, const float* dc, float lam, const float* p, float* spare, float* ap,
+                         double* partials, wcn_stream_t stream);
+int wcn_bilateral_pcg(const int32_t* neighbours, int32_t d, int64_t v, int32_t pitch, float tap_a, float tap_b, float tap_c,
+                      const float* nvec, const float* dc, const float* minv, float lam, const float* tbar, float* y, float* work,
+                      double* partials, double* state, int32_t max_iters, double tol, wcn_stream_t stream);
+int wcn_bilateral_knn_weights(const float* src_xyz, const float* src_feat, const float* query_xyz, const float* query_feat,
+                              const int64_t* nbr, int64_t n, int64_t m, int32_t k, int32_t dx, int32_t df, float sigma_xyz,
+                              float sigma_feat, float* weights, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,6 +338,14 @@ SIGNATURES = {
     "wcn_lattice_splat": (c_int, [c_void_p] * 4 + [c_int64, c_int64, c_int32, c_int32, ctypes.c_float] + [c_void_p] * 4),
     "wcn_lattice_blur": (c_int, [c_void_p] * 3 + [ctypes.c_float] * 3 + [c_int64, c_int32, c_void_p, c_void_p]),
     "wcn_lattice_slice": (c_int, [c_void_p] * 3 + [c_int64, c_int32, c_int64, c_int32, ctypes.c_float, c_void_p, c_void_p]),
+    "wcn_lattice_max_grid": (c_int32, []),
+    "wcn_lattice_row_grid": (c_int32, [c_int64, c_int32]),
+    "wcn_bilateral_matvec": (c_int, [c_void_p, c_int32, c_int64, c_int32] + [ctypes.c_float] * 3 + [c_void_p, c_void_p,
+                                                                                                   ctypes.c_float] + [c_void_p] * 5),
+    "wcn_bilateral_pcg": (c_int, [c_void_p, c_int32, c_int64, c_int32] + [ctypes.c_float] * 3 + [c_void_p] * 3 + [ctypes.c_float] +
+                          [c_void_p] * 5 + [c_int32, ctypes.c_double, c_void_p]),
+    "wcn_bilateral_knn_weights": (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_float,
+                                                           ctypes.c_float, c_void_p, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

@@ -1,5 +1,5 @@
 // lattice.hip - high-dimensional filtering on sparse lattices: the permutohedral lattice and the bilateral grid (reference:
-// nn/functional/permutohedral.py, nn/functional/bilateral_grid.py and geometry/coords/search/packed128_hashmap.py, where a
+// nn/functional/permutohedral.py, bilateral_grid.py, bilateral.py and geometry/coords/search/packed128_hashmap.py, where a
 // filter call is about 40 framework launches with float-atomic index_add_ and a neighbour search per call).
 //
 //   a. hash128       a table for keys of up to 7 axes of 17 bits.  A slot is claimed under linear probing by a 32-bit CAS on
@@ -18,6 +18,9 @@
 //                           cut into chunks summed by their own lane groups into partials that are added in chunk order
 //                    blur   y[v] = s0 x[v] + s1 x[n1[v]] + s2 x[n2[v]], -1 reads as zero
 //                    slice  out[i] = alpha * sum over k of w[i, k] * x[idx[i, k]], -1 reads as zero
+//   e. solver        the conjugate-gradient loop of the fast bilateral solver on the grid: 2 d + 2 launches an iteration, every
+//                    scalar from per-workgroup fp64 partials added in index order, a state block instead of a host read
+//   f. knn weights   the normalised weights of the kNN bilateral filter, one thread per query; the aggregation is the slice
 // No float atomics anywhere: the bits of a result depend on the lattice alone.  The integer atomics (status word, longest row,
 // the list of long rows) give the same result in any order.  Every grid is capped at kLtMaxGrid workgroups and strides.
 #include <limits.h>
@@ -622,6 +625,221 @@ __global__ __launch_bounds__(kLtThreads) void lt_slice_kernel(const float4* __re
   }
 }
 
+// ---- e. the bilateral solver's conjugate-gradient loop (reference: bilateral_solver of nn/functional/bilateral_grid.py) -------
+// A p = (lam D + C) p - lam n blur(n p) over fp32 rows; 2 d blur passes of which the first folds the n p scaling into its gather
+// and the last forms A p and one partial of sum p . A p per workgroup.  Every scalar of the loop is the sum of per-workgroup
+// partials: products and sums in fp64, xor butterflies inside a wave, the waves in order, the partials in index order by every
+// workgroup that needs the scalar.  The state block (doubles) carries rz_old and the done flag twice, by iteration parity: the
+// direction kernel of iteration `it` reads slot it & 1 and its workgroup 0 writes slot (it + 1) & 1, which only later launches
+// read, so no launch reads a word that the same launch writes.
+constexpr int kPcgRz = 0;         // [2] sum r . z the iteration starts from
+constexpr int kPcgNorm0 = 2;      // max(|r0|, 1e-20)
+constexpr int kPcgDone = 3;       // [2] non-zero: the stop test has held, every launch returns without writing
+constexpr int kPcgIters = 5;      // updates of y carried out
+constexpr int kPcgNonFinite = 6;  // a residual norm was not finite
+constexpr int kPcgWords = 8;
+
+// the workgroup's sum of one double per thread, the same bits in every thread; `s_red`: kLtThreads / 64 doubles
+__device__ __forceinline__ double lt_block_sum(double v, double* s_red) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+  __syncthreads();  // s_red may still be read by the call before
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int w = 0; w < kLtThreads / 64; ++w) t += s_red[w];
+  return t;
+}
+
+__device__ __forceinline__ double lt_sum_partials(const double* __restrict__ part, int n, double* s_red) {
+  double acc = 0.0;
+  for (int j = threadIdx.x; j < n; j += kLtThreads) acc += part[j];
+  return lt_block_sum(acc, s_red);
+}
+
+__device__ __forceinline__ double f4_dot(const float4& a, const float4& b) {
+  return (double)a.x * (double)b.x + (double)a.y * (double)b.y + (double)a.z * (double)b.z + (double)a.w * (double)b.w;
+}
+
+__device__ __forceinline__ double clamp_min_keep_nan(double v, double lo) { return v < lo ? lo : v; }
+
+// the first pass of the matvec: a blur pass over scale[.] * x[.]
+__global__ __launch_bounds__(kLtThreads) void lt_blur_scaled_kernel(const float4* __restrict__ x, const float* __restrict__ scale,
+                                                                    const int32_t* __restrict__ n1, float s0, float s1, int64_t m,
+                                                                    int P4, int L, const double* __restrict__ skip,
+                                                                    float4* __restrict__ y) {
+  if (skip && *skip != 0.0) return;
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
+    const int64_t a = n1[v];
+    const float sv = scale[v], sa = (a >= 0 && a < m) ? scale[a] : 0.f;
+    for (int p = sub; p < P4; p += L) {
+      const float4 xa = f4_scale(sa, lt_row_or_zero(x, a, m, P4, p));
+      y[v * P4 + p] = f4_fma(s1, xa, f4_scale(s0, f4_scale(sv, x[v * P4 + p])));
+    }
+  }
+}
+
+// the last pass: t = s0 x[v] + s1 x[n1[v]], Ap[v] = dc[v] p[v] - lam n[v] t, partial[workgroup] = sum p . Ap
+__global__ __launch_bounds__(kLtThreads) void lt_matvec_last_kernel(const float4* __restrict__ x, const int32_t* __restrict__ n1,
+                                                                    float s0, float s1, const float4* __restrict__ pv,
+                                                                    const float* __restrict__ nvec, const float* __restrict__ dc,
+                                                                    float lam, int64_t m, int P4, int L,
+                                                                    const double* __restrict__ skip, float4* __restrict__ Ap,
+                                                                    double* __restrict__ partial) {
+  __shared__ double s_red[kLtThreads / 64];
+  if (skip && *skip != 0.0) return;
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  double sum = 0.0;
+  for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
+    const int64_t a = n1[v];
+    const float dv = dc[v], ln = lam * nvec[v];
+    for (int p = sub; p < P4; p += L) {
+      const float4 t = f4_fma(s1, lt_row_or_zero(x, a, m, P4, p), f4_scale(s0, x[v * P4 + p]));
+      const float4 q = pv[v * P4 + p];
+      const float4 ap = make_float4(fmaf(dv, q.x, -(ln * t.x)), fmaf(dv, q.y, -(ln * t.y)), fmaf(dv, q.z, -(ln * t.z)),
+                                    fmaf(dv, q.w, -(ln * t.w)));
+      Ap[v * P4 + p] = ap;
+      sum += f4_dot(q, ap);
+    }
+  }
+  sum = lt_block_sum(sum, s_red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+// INIT: r = tbar - Ap (Ap = A y0), z = minv r, p = z.  Otherwise alpha = rz_old / max(sum of the p . Ap partials, 1e-20),
+// y += alpha p, r -= alpha Ap, z = minv r.  Both leave the partials of sum r . r and sum r . z.
+template <bool INIT>
+__global__ __launch_bounds__(kLtThreads) void lt_pcg_update_kernel(const double* __restrict__ st, int it,
+                                                                   const double* __restrict__ pap_part, int nparts,
+                                                                   float4* __restrict__ p, const float4* __restrict__ Ap,
+                                                                   const float* __restrict__ minv, const float4* __restrict__ tbar,
+                                                                   float4* __restrict__ y, float4* __restrict__ r,
+                                                                   float4* __restrict__ z, int64_t m, int P4, int L,
+                                                                   double* __restrict__ rr_part, double* __restrict__ rz_part) {
+  __shared__ double s_red[kLtThreads / 64];
+  float alpha = 0.f;
+  if (!INIT) {
+    if (st[kPcgDone + (it & 1)] != 0.0) return;
+    const double pap = lt_sum_partials(pap_part, nparts, s_red);
+    alpha = (float)(st[kPcgRz + (it & 1)] / clamp_min_keep_nan(pap, 1e-20));
+  }
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  double rr = 0.0, rz = 0.0;
+  for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
+    const float mi = minv[v];
+    for (int q = sub; q < P4; q += L) {
+      const int64_t at = v * P4 + q;
+      const float4 ap = Ap[at];
+      float4 rv;
+      if (INIT) {
+        const float4 t = tbar[at];
+        rv = make_float4(t.x - ap.x, t.y - ap.y, t.z - ap.z, t.w - ap.w);
+      } else {
+        y[at] = f4_fma(alpha, p[at], y[at]);
+        rv = f4_fma(-alpha, ap, r[at]);
+      }
+      const float4 zv = f4_scale(mi, rv);
+      r[at] = rv;
+      z[at] = zv;
+      if (INIT) p[at] = zv;
+      rr += f4_dot(rv, rv);
+      rz += f4_dot(rv, zv);
+    }
+  }
+  rr = lt_block_sum(rr, s_red);
+  rz = lt_block_sum(rz, s_red);
+  if (threadIdx.x == 0) {
+    rr_part[blockIdx.x] = rr;
+    rz_part[blockIdx.x] = rz;
+  }
+}
+
+// ONE workgroup: the state block from the partials of the first residual
+__global__ __launch_bounds__(kLtThreads) void lt_pcg_start_kernel(double* __restrict__ st, const double* __restrict__ rr_part,
+                                                                  const double* __restrict__ rz_part, int nparts) {
+  __shared__ double s_red[kLtThreads / 64];
+  const double rr = lt_sum_partials(rr_part, nparts, s_red), rz = lt_sum_partials(rz_part, nparts, s_red);
+  if (threadIdx.x == 0) {
+    const double norm = sqrt(rr);
+    st[kPcgRz] = rz;
+    st[kPcgRz + 1] = 0.0;
+    st[kPcgNorm0] = clamp_min_keep_nan(norm, 1e-20);
+    st[kPcgDone] = st[kPcgDone + 1] = 0.0;
+    st[kPcgIters] = 0.0;
+    st[kPcgNonFinite] = isfinite(norm) ? 0.0 : 1.0;
+    st[kPcgWords - 1] = 0.0;
+  }
+}
+
+// the stop test |r| / |r0| < tol on the reduced norm, then beta = rz_new / max(rz_old, 1e-20), p = z + beta p
+__global__ __launch_bounds__(kLtThreads) void lt_pcg_direction_kernel(double* __restrict__ st, int it, double tol,
+                                                                      const double* __restrict__ rr_part,
+                                                                      const double* __restrict__ rz_part, int nparts,
+                                                                      const float4* __restrict__ z, float4* __restrict__ p,
+                                                                      int64_t m, int P4, int L) {
+  __shared__ double s_red[kLtThreads / 64];
+  const int cur = it & 1, nxt = cur ^ 1;
+  if (st[kPcgDone + cur] != 0.0) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) st[kPcgDone + nxt] = 1.0;
+    return;
+  }
+  const double rr = lt_sum_partials(rr_part, nparts, s_red), rz_new = lt_sum_partials(rz_part, nparts, s_red);
+  const double norm = sqrt(rr);
+  const bool stop = norm / st[kPcgNorm0] < tol;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st[kPcgIters] = (double)(it + 1);
+    st[kPcgDone + nxt] = stop ? 1.0 : 0.0;
+    st[kPcgRz + nxt] = rz_new;
+    if (!isfinite(norm)) st[kPcgNonFinite] = 1.0;
+  }
+  if (stop) return;
+  const float beta = (float)(rz_new / clamp_min_keep_nan(st[kPcgRz + cur], 1e-20));
+  const int groups = kLtThreads / L;
+  const int g = threadIdx.x / L, sub = threadIdx.x % L;
+  for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups)
+    for (int q = sub; q < P4; q += L) p[v * P4 + q] = f4_fma(beta, p[v * P4 + q], z[v * P4 + q]);
+}
+
+// ---- f. weights of the kNN bilateral filter (reference: nn/functional/bilateral.py) ---------------------------------------------
+// one thread per query: w[s] = exp(-|dxyz|^2 ix - |dfeat|^2 if) over its k neighbours, the row sum in slot order, then
+// w / max(sum, 1e-20).  A neighbour index outside [0, n) weighs nothing.
+__global__ __launch_bounds__(kLtThreads) void bilateral_knn_weights_kernel(const float* __restrict__ src_xyz,
+                                                                           const float* __restrict__ src_feat,
+                                                                           const float* __restrict__ q_xyz,
+                                                                           const float* __restrict__ q_feat,
+                                                                           const int64_t* __restrict__ nbr, int64_t n, int64_t m,
+                                                                           int K, int dx, int df, float inv_xyz, float inv_feat,
+                                                                           float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kLtThreads) {
+    float sum = 0.f;
+    for (int s = 0; s < K; ++s) {
+      const int64_t r = nbr[i * K + s];
+      float w = 0.f;
+      if (r >= 0 && r < n) {
+        float a = 0.f, b = 0.f;
+        for (int j = 0; j < dx; ++j) {
+          const float t = src_xyz[r * dx + j] - q_xyz[i * dx + j];
+          a = fmaf(t, t, a);
+        }
+        for (int j = 0; j < df; ++j) {
+          const float t = src_feat[r * df + j] - q_feat[i * df + j];
+          b = fmaf(t, t, b);
+        }
+        w = expf(-a * inv_xyz - b * inv_feat);
+      }
+      out[i * K + s] = w;
+      sum += w;
+    }
+    const float den = sum < 1e-20f ? 1e-20f : sum;
+    for (int s = 0; s < K; ++s) out[i * K + s] = out[i * K + s] / den;
+  }
+}
+
 static int lt_lanes(int64_t pieces) {
   int L = 1;
   while (L < pieces && L < 64) L <<= 1;
@@ -783,6 +1001,103 @@ int wcn_lattice_slice(const float* x, const int64_t* idx, const float* w, int64_
   const int P4 = pitch / 4, L = lt_lanes(P4);
   hipLaunchKernelGGL(lt_slice_kernel, dim3(lt_grid(ceil_div(n, kLtThreads / L))), dim3(kLtThreads), 0, (hipStream_t)stream,
                      (const float4*)x, idx, w, n, (int)k, v, P4, L, alpha, (float4*)out);
+  return launch_status();
+}
+
+// ---- the bilateral solver -------------------------------------------------------------------------------------------------------
+static bool pcg_args_ok(const int32_t* neighbours, int32_t d, int64_t v, int32_t pitch, const void* a, const void* b) {
+  return neighbours && d >= 1 && d <= kLtAxes - 1 && v >= 1 && feature_args_ok(v, pitch, a, b) && a && b;
+}
+
+struct PcgPasses {  // the grid's default blur: per axis y = b x + (c b) x[fwd], then y + a y[bwd]
+  float s0[2], s1[2];
+};
+
+// A p into `Ap`, the partials of sum p . A p into `partial`; `spare`: two [v, pitch] buffers.  Returns the number of partials.
+static int pcg_matvec(const int32_t* nb, int d, int64_t v, int P4, const PcgPasses& ps, const float* nvec, const float* dc,
+                      float lam, const float* p, float* spare, const double* skip, float* Ap, double* partial, hipStream_t s) {
+  const int L = lt_lanes(P4);
+  const dim3 grid(lt_grid(ceil_div(v, kLtThreads / L))), block(kLtThreads);
+  float4* buf[2] = {(float4*)spare, (float4*)spare + v * P4};
+  hipLaunchKernelGGL(lt_blur_scaled_kernel, grid, block, 0, s, (const float4*)p, nvec, nb, ps.s0[0], ps.s1[0], v, P4, L, skip,
+                     buf[0]);
+  for (int i = 1; i < 2 * d - 1; ++i)
+    hipLaunchKernelGGL(lt_blur_kernel, grid, block, 0, s, (const float4*)buf[(i - 1) & 1], nb + (int64_t)i * v,
+                       (const int32_t*)nullptr, ps.s0[i & 1], ps.s1[i & 1], 0.f, v, P4, L, buf[i & 1]);
+  const int last = 2 * d - 1;
+  hipLaunchKernelGGL(lt_matvec_last_kernel, grid, block, 0, s, (const float4*)buf[(last - 1) & 1], nb + (int64_t)last * v,
+                     ps.s0[1], ps.s1[1], (const float4*)p, nvec, dc, lam, v, P4, L, skip, (float4*)Ap, partial);
+  return (int)grid.x;
+}
+
+static PcgPasses pcg_passes(float tap_a, float tap_b, float tap_c) {
+  return PcgPasses{{tap_b, 1.f}, {(float)((double)tap_c * (double)tap_b), tap_a}};
+}
+
+int32_t wcn_lattice_max_grid(void) { return kLtMaxGrid; }
+
+int32_t wcn_lattice_row_grid(int64_t rows, int32_t pitch) {
+  if (rows < 0 || pitch < 4 || pitch % 4 != 0) return 0;
+  return (int32_t)lt_grid(ceil_div(rows, kLtThreads / lt_lanes(pitch / 4)));
+}
+
+int wcn_bilateral_matvec(const int32_t* neighbours, int32_t d, int64_t v, int32_t pitch, float tap_a, float tap_b, float tap_c,
+                         const float* nvec, const float* dc, float lam, const float* p, float* spare, float* ap,
+                         double* partials, wcn_stream_t stream) {
+  if (v == 0) return WCN_SUCCESS;
+  if (!pcg_args_ok(neighbours, d, v, pitch, p, ap) || !nvec || !dc || !spare || !partials || !aligned_to(spare, 16) || p == ap)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  pcg_matvec(neighbours, d, v, pitch / 4, pcg_passes(tap_a, tap_b, tap_c), nvec, dc, lam, p, spare, nullptr, ap, partials,
+             (hipStream_t)stream);
+  return launch_status();
+}
+
+int wcn_bilateral_pcg(const int32_t* neighbours, int32_t d, int64_t v, int32_t pitch, float tap_a, float tap_b, float tap_c,
+                      const float* nvec, const float* dc, const float* minv, float lam, const float* tbar, float* y, float* work,
+                      double* partials, double* state, int32_t max_iters, double tol, wcn_stream_t stream) {
+  if (max_iters < 0 || !state) return WCN_ERROR_INVALID_PARAMETERS;
+  if (v == 0) return WCN_SUCCESS;
+  if (!pcg_args_ok(neighbours, d, v, pitch, tbar, y) || !nvec || !dc || !minv || !work || !partials || !aligned_to(work, 16) ||
+      tbar == y)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  hipStream_t s = (hipStream_t)stream;
+  const int P4 = pitch / 4, L = lt_lanes(P4);
+  const int64_t rows = v * pitch;  // floats of one buffer
+  float *r = work, *p = work + rows, *z = work + 2 * rows, *ap = work + 3 * rows, *spare = work + 4 * rows;
+  double *pap_part = partials, *rr_part = partials + kLtMaxGrid, *rz_part = partials + 2 * kLtMaxGrid;
+  const PcgPasses ps = pcg_passes(tap_a, tap_b, tap_c);
+  const dim3 block(kLtThreads);
+  // the first residual: A y0 through the same matvec, then r, z, p and the state block
+  const int parts = pcg_matvec(neighbours, d, v, P4, ps, nvec, dc, lam, y, spare, nullptr, ap, pap_part, s);
+  const dim3 grid(parts);
+  hipLaunchKernelGGL(lt_pcg_update_kernel<true>, grid, block, 0, s, (const double*)state, 0, (const double*)pap_part, parts,
+                     (float4*)p, (const float4*)ap, minv, (const float4*)tbar, (float4*)y, (float4*)r, (float4*)z, v, P4, L,
+                     rr_part, rz_part);
+  hipLaunchKernelGGL(lt_pcg_start_kernel, dim3(1), block, 0, s, state, (const double*)rr_part, (const double*)rz_part, parts);
+  for (int it = 0; it < max_iters; ++it) {  // 2 d + 2 launches, no host read
+    pcg_matvec(neighbours, d, v, P4, ps, nvec, dc, lam, p, spare, state + kPcgDone + (it & 1), ap, pap_part, s);
+    hipLaunchKernelGGL(lt_pcg_update_kernel<false>, grid, block, 0, s, (const double*)state, it, (const double*)pap_part, parts,
+                       (float4*)p, (const float4*)ap, minv, (const float4*)tbar, (float4*)y, (float4*)r, (float4*)z, v, P4, L,
+                       rr_part, rz_part);
+    hipLaunchKernelGGL(lt_pcg_direction_kernel, grid, block, 0, s, state, it, tol, (const double*)rr_part,
+                       (const double*)rz_part, parts, (const float4*)z, (float4*)p, v, P4, L);
+  }
+  return launch_status();
+}
+
+int wcn_bilateral_knn_weights(const float* src_xyz, const float* src_feat, const float* query_xyz, const float* query_feat,
+                              const int64_t* nbr, int64_t n, int64_t m, int32_t k, int32_t dx, int32_t df, float sigma_xyz,
+                              float sigma_feat, float* weights, wcn_stream_t stream) {
+  if (n < 0 || m < 0 || k < 1 || dx < 1 || df < 1 || n > INT32_MAX || m * (int64_t)k > INT32_MAX || !(sigma_xyz > 0.f) ||
+      !(sigma_feat > 0.f))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (m == 0) return WCN_SUCCESS;
+  if (!query_xyz || !query_feat || !nbr || !weights || (n > 0 && (!src_xyz || !src_feat))) return WCN_ERROR_INVALID_PARAMETERS;
+  const float inv_xyz = (float)(1.0 / (2.0 * (double)sigma_xyz * (double)sigma_xyz));
+  const float inv_feat = (float)(1.0 / (2.0 * (double)sigma_feat * (double)sigma_feat));
+  hipLaunchKernelGGL(bilateral_knn_weights_kernel, dim3(lt_grid(ceil_div(m, kLtThreads))), dim3(kLtThreads), 0,
+                     (hipStream_t)stream, src_xyz, src_feat, query_xyz, query_feat, nbr, n, m, (int)k, (int)dx, (int)df,
+                     inv_xyz, inv_feat, weights);
   return launch_status();
 }
 

@@ -4,7 +4,7 @@ from .fused_block import FusedSparseConvBlock
 from .activations import DropPath
 from .mlp import Linear, MLPBlock
 from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
-from .bilateral import BilateralFilterGrid, BilateralFilterGridCached
+from .bilateral import BilateralFilter, BilateralFilterGrid, BilateralFilterGridCached, FastBilateralSolver
 from .permutohedral import (BilateralPermutohedralFilter, BilateralPermutohedralFilterCached, PermutohedralFilter,
                             PermutohedralFilterCached)
 from .point_conv import PointConv
@@ -36,4 +36,5 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "DropPath", "Linear", "SpaceAttention", "AllAttention", "STR2ATTN", "SpaCeFormerBlockBase", "PreNormBlock",
            "PostNormBlock", "StreamNormBlock", "BLOCK_REGISTRY", "block_factory",
            "PermutohedralFilter", "PermutohedralFilterCached", "BilateralPermutohedralFilter",
-           "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached"]
+           "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",
+           "FastBilateralSolver"]

@@ -1,13 +1,45 @@
-"""Bilateral-grid filters as modules (reference `warpconvnet/nn/modules/bilateral.py`; the KNN / radius ``BilateralFilter`` and
-``FastBilateralSolver`` of that file are not part of this package)."""
+"""The bilateral filters and the fast bilateral solver as modules (reference `warpconvnet/nn/modules/bilateral.py`).  Stateless
+but for the cached grid; ``backend`` is passed on to the functional forms."""
 from typing import Optional
 
 from torch import Tensor, nn
 
-from warpconvnet_amd.nn.functional.bilateral_grid import BilateralGrid, bilateral_filter_grid
+from warpconvnet_amd.nn.functional.bilateral import bilateral_filter
+from warpconvnet_amd.nn.functional.bilateral_grid import BilateralGrid, bilateral_filter_grid, fast_bilateral_solver
 from warpconvnet_amd.nn.functional.permutohedral import bilateral_positions
 
-__all__ = ["BilateralFilterGrid", "BilateralFilterGridCached"]
+__all__ = ["BilateralFilter", "BilateralFilterGrid", "BilateralFilterGridCached", "FastBilateralSolver"]
+
+
+class BilateralFilter(nn.Module):
+    """kNN / radius bilateral filter (a Gaussian on xyz and on the range features); see ``bilateral_filter``."""
+
+    def __init__(self, sigma_xyz: float = 0.05, sigma_feat: float = 20.0, k: int = 16, mode: str = "knn",
+                 radius_mult: float = 3.0, chunk_size: int = 32768, backend: str = "auto"):
+        super().__init__()
+        self.sigma_xyz, self.sigma_feat, self.k, self.mode = sigma_xyz, sigma_feat, k, mode
+        self.radius_mult, self.chunk_size, self.backend = radius_mult, chunk_size, backend
+
+    def forward(self, src_xyz: Tensor, src_feat: Tensor, src_value: Tensor, query_xyz: Optional[Tensor] = None,
+                query_feat: Optional[Tensor] = None) -> Tensor:
+        return bilateral_filter(src_xyz, src_feat, src_value, query_xyz, query_feat, sigma_xyz=self.sigma_xyz,
+                                sigma_feat=self.sigma_feat, k=self.k, mode=self.mode, radius_mult=self.radius_mult,
+                                chunk_size=self.chunk_size, backend=self.backend)
+
+
+class FastBilateralSolver(nn.Module):
+    """Confidence-weighted bilateral smoothing by conjugate gradients on the grid; see ``fast_bilateral_solver``."""
+
+    def __init__(self, sigma_xyz: float = 0.05, sigma_feat: float = 20.0, lam: float = 128.0, max_iters: int = 25,
+                 tol: float = 1e-5, backend: str = "auto"):
+        super().__init__()
+        self.sigma_xyz, self.sigma_feat, self.lam, self.max_iters, self.tol = sigma_xyz, sigma_feat, lam, max_iters, tol
+        self.backend = backend
+
+    def forward(self, src_xyz: Tensor, src_feat: Tensor, target: Tensor, confidence: Tensor) -> Tensor:
+        return fast_bilateral_solver(src_xyz, src_feat, target, confidence, sigma_xyz=self.sigma_xyz,
+                                     sigma_feat=self.sigma_feat, lam=self.lam, max_iters=self.max_iters, tol=self.tol,
+                                     backend=self.backend)
 
 
 class BilateralFilterGrid(nn.Module):
