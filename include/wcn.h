@@ -1027,6 +1027,43 @@ int wcn_bilateral_knn_weights(const float* src_xyz, const float* src_feat, const
                               const int64_t* nbr, int64_t n, int64_t m, int32_t k, int32_t dx, int32_t df, float sigma_xyz,
                               float sigma_feat, float* weights, wcn_stream_t stream);
 
+/* ---- dense grids and point clouds: Grid / FactorGrid geometry (ABI 15, additions only) -------------------------------------
+ * Reference: geometry/types/conversion/to_grid.py (points -> grid) and the F.grid_sample composition of
+ * nn/modules/factor_grid.py / nn/functional/factor_grid.py (grid -> points, align_corners, border padding).
+ *   wcn_grid_max_grid      the cap of every grid of these kernels (4096); they stride beyond it.
+ *   wcn_grid_chunk_points  points of one chunk of a crowded cell in the backward (256).
+ *   wcn_grid_point_keys    `points` fp32 [n, 3], `point_offsets` int64 [num_batches + 1] on the device, `dims` = vertices per
+ *                    axis, `lo` / `scale` fp32 [3] on the host.  u_a = (p_a - lo_a) * scale_a clamped to [0, dims_a - 1] in
+ *                    float (NaN -> 0).  WCN_GRID_KEY_CELL: keys[i] = b * cells + flat cell (int) u over `dims` (scale =
+ *                    dims / (hi - lo)).  WCN_GRID_KEY_CORNER: i0_a = min(floor(u_a), max(dims_a - 2, 0)), fractions[i, a] =
+ *                    u_a - i0_a, keys[i] = b * cells + flat base cell over max(dims_a - 1, 1) (scale = (dims - 1) / (hi - lo)).
+ *   wcn_grid_sample        out[p, col0 + c] = sum over the 8 corners (dx, dy, dz; dz fastest) of w * grid[b, x, y, z, c], w =
+ *                    wx * wy * wz in fp32, fp32 FMA accumulation, one rounding to `dtype`.  `strides` int64 [5] on the host:
+ *                    the element strides of (b, x, y, z, c); `sorted_keys` / `perm`: the stable sort of the corner keys;
+ *                    `fractions` in the points' own order; `out` rows of `out_pitch` elements.
+ *   wcn_grid_sample_backward  d_grid through the same strides, every element written exactly once (0 where no point reaches
+ *                    a vertex).  `cell_offsets` int64 [num_batches * cells + 1]: the rows of `sorted_keys` of every base cell.
+ *                    `max_cell_points`: the longest cell if known, -1 if not; above wcn_grid_chunk_points() (or unknown) the
+ *                    workspace of wcn_grid_sample_backward_workspace_bytes(n, channels) is needed.  No float atomics.
+ * WCN_ERROR_INVALID_PARAMETERS: negative sizes, n or the vertex count above INT32_MAX, a missing pointer, a dims entry below
+ * 1, col0 + channels beyond the pitch, a short workspace.  WCN_ERROR_UNSUPPORTED_CONFIG: an unknown dtype.  An empty call
+ * returns success without a launch. */
+enum wcn_grid_key_mode { WCN_GRID_KEY_CELL = 0, WCN_GRID_KEY_CORNER = 1 };
+int32_t wcn_grid_max_grid(void);
+int32_t wcn_grid_chunk_points(void);
+int wcn_grid_point_keys(const float* points, int64_t n, const int64_t* point_offsets, int32_t num_batches, const int32_t* dims,
+                        const float* lo, const float* scale, int32_t mode, int64_t* keys, float* fractions,
+                        wcn_stream_t stream);
+int wcn_grid_sample(const void* grid, const int64_t* strides, const int32_t* dims, int32_t channels, int32_t dtype,
+                    int64_t num_batches, const int64_t* sorted_keys, const int64_t* perm, const float* fractions, int64_t n,
+                    void* out, int64_t out_pitch, int64_t col0, wcn_stream_t stream);
+size_t wcn_grid_sample_backward_workspace_bytes(int64_t n, int32_t channels);
+int wcn_grid_sample_backward(const void* dy, int64_t dy_pitch, int64_t col0, const int64_t* strides, const int32_t* dims,
+                             int32_t channels, int32_t dtype, int64_t num_batches, const int64_t* sorted_keys,
+                             const int64_t* perm, const int64_t* cell_offsets, const float* fractions, int64_t n,
+                             int64_t max_cell_points, void* d_grid, void* workspace, size_t workspace_bytes,
+                             wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ WCN_FLAG_NEED_STRICT = 16
 WCN_FLAG_ROW_OVERFLOW = 32
 WCN_SLOT_X_FASTEST, WCN_SLOT_Z_FASTEST = 0, 1  # column order of a child table (csrc/resample.hip)
 WCN_MASK_U8 = 3  # mask_dtype of wcn_resample_expand: a bool / uint8 mask
+WCN_GRID_KEY_CELL, WCN_GRID_KEY_CORNER = 0, 1  # mode of wcn_grid_point_keys (csrc/grid.hip)
 
 _I32P = c_void_p  # all pointers travel as void*
 _3I = c_int32 * 3
@@ -346,6 +347,16 @@ SIGNATURES = {
                           [c_void_p] * 5 + [c_int32, ctypes.c_double, c_void_p]),
     "wcn_bilateral_knn_weights": (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int32, c_int32, c_int32, ctypes.c_float,
                                                            ctypes.c_float, c_void_p, c_void_p]),
+    "wcn_grid_max_grid": (c_int32, []),
+    "wcn_grid_chunk_points": (c_int32, []),
+    "wcn_grid_point_keys": (c_int, [c_void_p, c_int64, c_void_p, c_int32, _3I, ctypes.c_float * 3, ctypes.c_float * 3, c_int32,
+                                    c_void_p, c_void_p, c_void_p]),
+    "wcn_grid_sample": (c_int, [c_void_p, c_int64 * 5, _3I, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                c_void_p, c_int64, c_int64, c_void_p]),
+    "wcn_grid_sample_backward_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "wcn_grid_sample_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64 * 5, _3I, c_int32, c_int32, c_int64, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

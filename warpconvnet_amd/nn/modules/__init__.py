@@ -2,6 +2,8 @@ from .attention import BatchedLinear, FeedForward, LayerNorm, PatchAttention, Tr
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
 from .activations import DropPath
+from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool, FactorGridToPoint,
+                          FactorGridTransform, PointToFactorGrid)
 from .mlp import Linear, MLPBlock
 from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
 from .bilateral import BilateralFilter, BilateralFilterGrid, BilateralFilterGridCached, FastBilateralSolver
@@ -37,4 +39,6 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "PostNormBlock", "StreamNormBlock", "BLOCK_REGISTRY", "block_factory",
            "PermutohedralFilter", "PermutohedralFilterCached", "BilateralPermutohedralFilter",
            "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",
-           "FastBilateralSolver"]
+           "FastBilateralSolver",
+           "FactorGridCat", "FactorGridIntraCommunication", "FactorGridPadToMatch", "FactorGridPool", "FactorGridToPoint",
+           "FactorGridTransform", "PointToFactorGrid"]
