@@ -2,8 +2,9 @@ from .attention import BatchedLinear, FeedForward, LayerNorm, PatchAttention, Tr
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
 from .activations import DropPath
-from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool, FactorGridToPoint,
-                          FactorGridTransform, PointToFactorGrid)
+from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool,
+                          FactorGridProjection, FactorGridToPoint, FactorGridTransform, PointToFactorGrid)
+from .grid_conv import GridConv
 from .mlp import Linear, MLPBlock
 from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
 from .bilateral import BilateralFilter, BilateralFilterGrid, BilateralFilterGridCached, FastBilateralSolver
@@ -41,4 +42,4 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",
            "FastBilateralSolver",
            "FactorGridCat", "FactorGridIntraCommunication", "FactorGridPadToMatch", "FactorGridPool", "FactorGridToPoint",
-           "FactorGridTransform", "PointToFactorGrid"]
+           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "GridConv"]

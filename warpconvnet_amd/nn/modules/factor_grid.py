@@ -5,9 +5,15 @@ constructor arguments and parameter names, so ``state_dict``s interchange).
 (`grid_sample_points`: on the GPU one strided launch per grid writing side by side into one tensor, ragged batches allowed),
 joined with the point features and the position relative to the box centre (raw or sinusoidally embedded) and passed through
 ``combine_mlp``.  ``PointToFactorGrid`` is ``points_to_factor_grid`` with the box and search settings held by the module.
-The convolution blocks of FIGConvNet (``FactorGridProjection``, ``FactorGridGlobalConv``) are not part of this module yet.
+
+``FactorGridProjection`` is the first of FIGConvNet's convolution blocks: one ``Conv2d`` - ``norm`` - ``activation`` per grid
+over the folded 2-D image, channel dim ``C * compressed_dim`` (the framework's convolution).  Two defects of the reference
+are not copied: its ``forward`` hands a ``Grid`` to an ``nn.Sequential`` of tensor ops and raises - here the block runs on the
+feature tensor and the grid is rebuilt; and with image sizes that ``stride`` does not divide it would build a ``Grid`` whose
+shape disagrees with its features - here that raises a ``ValueError`` naming the shapes.  ``FactorGridGlobalConv`` and the
+model are not part of this module.
 """
-from typing import List, Literal, Optional, Tuple
+from typing import List, Literal, Optional, Tuple, Type
 
 import torch
 import torch.nn as nn
@@ -24,7 +30,7 @@ from warpconvnet_amd.nn.functional.grid_sample import grid_sample_points
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 
 __all__ = ["FactorGridTransform", "FactorGridCat", "FactorGridPool", "FactorGridIntraCommunication", "FactorGridPadToMatch",
-           "FactorGridToPoint", "PointToFactorGrid"]
+           "FactorGridToPoint", "PointToFactorGrid", "FactorGridProjection"]
 
 
 class FactorGridTransform(BaseSpatialModule):
@@ -185,3 +191,46 @@ class PointToFactorGrid(BaseSpatialModule):
                                      bounds=(torch.tensor(self.aabb_min), torch.tensor(self.aabb_max)),
                                      search_radius=self.search_radius, k=self.k, search_type=self.search_type,
                                      reduction=self.reduction)
+
+
+def _image_axes(memory_format: GridMemoryFormat) -> List[int]:
+    return [a for a in range(3) if a != FORMAT_TO_AXIS[memory_format]]
+
+
+def _rebuilt(grid, features: Tensor, grid_shape: Tuple[int, int, int]):
+    """``grid`` with new features over ``grid_shape`` (same box, batch size and memory format)."""
+    from warpconvnet_amd.geometry.coords.grid import GridCoords
+    from warpconvnet_amd.geometry.types.grid import Grid
+
+    if tuple(grid_shape) == tuple(grid.grid_shape):
+        return grid.replace(batched_features=features)
+    coords = GridCoords.from_shape(tuple(grid_shape), bounds=grid.bounds, batch_size=grid.batch_size, device=features.device)
+    return Grid(coords, features, memory_format=grid.memory_format, grid_shape=tuple(grid_shape))
+
+
+class FactorGridProjection(BaseSpatialModule):
+    """One ``Conv2d - norm - activation`` per grid over the folded channels (``convs``)."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int, compressed_spatial_dims: Tuple[int, ...],
+                 compressed_memory_formats: Tuple[GridMemoryFormat, ...], stride: int = 1,
+                 norm: Type[nn.Module] = nn.BatchNorm2d, activation: Type[nn.Module] = nn.GELU):
+        super().__init__()
+        self.stride = stride
+        self.convs = nn.ModuleList()
+        for dim, _ in zip(compressed_spatial_dims, compressed_memory_formats):
+            self.convs.append(nn.Sequential(
+                nn.Conv2d(in_channels * dim, out_channels * dim, kernel_size, stride, (kernel_size - 1) // 2, bias=True),
+                norm(out_channels * dim), activation()))
+
+    def forward(self, grid: FactorGrid) -> FactorGrid:
+        assert len(grid) == len(self.convs), f"Expected {len(self.convs)} grids, got {len(grid)}"
+        out = []
+        for g, conv in zip(grid, self.convs):
+            feats = conv(g.grid_features.batched_tensor)
+            axes, shape = _image_axes(g.memory_format), list(g.grid_shape)
+            shape[axes[0]], shape[axes[1]] = int(feats.shape[2]), int(feats.shape[3])
+            if self.stride != 1 and any(g.grid_shape[a] % self.stride for a in axes):
+                raise ValueError(f"stride {self.stride} does not divide the image axes of grid shape {tuple(g.grid_shape)} "
+                                 f"({g.memory_format.name}); the convolution gives features of shape {tuple(feats.shape)}")
+            out.append(_rebuilt(g, feats, tuple(shape)))
+        return FactorGrid(out)
