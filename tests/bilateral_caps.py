@@ -1,7 +1,7 @@
 """Shapes at which the solver's and the kNN filter's capped, striding kernels of csrc/lattice.hip take a second trip, derived
 from its constants (tests/test_bilateral_cap_constants.py fails when a constant changes without these being re-derived)."""
-LT_THREADS = 256    # kLtThreads
-LT_MAX_GRID = 4096  # kLtMaxGrid: also the slots of one scalar's partials
+LT_THREADS = 256    # kRowThreads
+LT_MAX_GRID = 4096  # kRowMaxGrid: also the slots of one scalar's partials
 
 # matvec, update and direction kernels: min(64, pow2(pitch / 4)) lanes per row; 253 channels -> pitch 256 -> 64 lanes -> four
 # rows per workgroup.  More vertices than this: every workgroup strides and every scalar has LT_MAX_GRID partials.

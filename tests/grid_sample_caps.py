@@ -1,8 +1,8 @@
 """Shapes at which the capped, striding kernels of csrc/grid.hip take a second trip, derived from its constants
 (tests/test_grid_sample_cap_constants.py fails when a constant changes without these being re-derived)."""
-GS_THREADS = 256    # kGsThreads
-GS_MAX_GRID = 4096  # kGsMaxGrid
-GS_CHUNK = 256      # kGsChunk: points of one chunk of a crowded cell = sorted positions of one tile of the chunk kernel
+GS_THREADS = 256    # kRowThreads
+GS_MAX_GRID = 4096  # kRowMaxGrid
+GS_CHUNK = 256      # kRowChunk: points of one chunk of a crowded cell = sorted positions of one tile of the chunk kernel
 GS_PLANAR_CH = 8    # kGsPlanarCh: channels of one thread of the planar forward kernel
 
 # keys: one thread per point

@@ -1,9 +1,9 @@
 """Shapes at which the capped, striding kernels of csrc/lattice.hip take a second trip, derived from its constants
 (tests/test_lattice_cap_constants.py fails when a constant changes without these being re-derived)."""
-LT_THREADS = 256    # kLtThreads
-LT_PER = 8          # kLtPer: sorted entries per thread of a scan tile
-LT_MAX_GRID = 4096  # kLtMaxGrid
-LT_CHUNK = 256      # kLtChunk
+LT_THREADS = 256    # kRowThreads
+LT_PER = 8          # kRunPer: sorted entries per thread of a scan tile
+LT_MAX_GRID = 4096  # kRowMaxGrid
+LT_CHUNK = 256      # kRowChunk
 
 # geometry, hash insert and hash search: one thread per point / key
 POINTS_SECOND_TRIP = LT_MAX_GRID * LT_THREADS + 1

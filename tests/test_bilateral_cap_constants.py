@@ -1,5 +1,5 @@
-"""The constants of csrc/lattice.hip that the second-trip shapes of tests/test_gpu_bilateral_solver.py are derived from, read
-from the source and from the library.  A constant changed later would silently turn those into single-trip tests, so a change
+"""The constants of csrc/row_lists.h and csrc/lattice.hip that the second-trip shapes of tests/test_gpu_bilateral_solver.py are derived from, read
+from the sources and from the library.  A constant changed later would silently turn those into single-trip tests, so a change
 here must come with new shapes there."""
 import os
 
@@ -8,21 +8,23 @@ import pytest
 from tests.test_grid_cap_constants import CSRC, _value
 
 WHY = "tests/bilateral_caps.py derives the second-trip shapes from this value: re-derive them there (and here) with the new one"
-CONSTANTS = [("kLtThreads", 256), ("kLtMaxGrid", 4096), ("kPcgWords", 8)]
+CONSTANTS = [("kRowThreads", 256), ("kRowMaxGrid", 4096), ("kPcgWords", 8)]
+SOURCE = {"kPcgWords": "lattice.hip"}  # the rest: row_lists.h
 
 
 @pytest.mark.parametrize("name,want", CONSTANTS, ids=[c[0] for c in CONSTANTS])
 def test_constant_is_what_the_second_trip_shapes_assume(name, want):
-    with open(os.path.join(CSRC, "lattice.hip")) as f:
+    source = SOURCE.get(name, "row_lists.h")
+    with open(os.path.join(CSRC, source)) as f:
         got = _value(f.read(), name)
-    assert got == want, f"lattice.hip: {name} = {got}, the tests assume {want}. {WHY}"
+    assert got == want, f"{source}: {name} = {got}, the tests assume {want}. {WHY}"
 
 
 def test_the_tests_use_the_same_values():
     from tests import bilateral_caps as caps
 
     want = dict(CONSTANTS)
-    assert (caps.LT_THREADS, caps.LT_MAX_GRID) == (want["kLtThreads"], want["kLtMaxGrid"]), WHY
+    assert (caps.LT_THREADS, caps.LT_MAX_GRID) == (want["kRowThreads"], want["kRowMaxGrid"]), WHY
     assert caps.WIDE_CHANNELS == 253 and caps.WIDE_PITCH == 256 and caps.ROWS_PER_WORKGROUP == 4
     assert caps.VERTICES_SECOND_TRIP == 4096 * 4 + 1
     assert caps.LATTICE_VERTICES == 131 * 131 and caps.LATTICE_VERTICES >= caps.VERTICES_SECOND_TRIP

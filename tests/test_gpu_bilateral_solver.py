@@ -180,8 +180,8 @@ def test_two_knn_filter_runs_give_equal_bits():
 
 # ---- 5. second trips ----------------------------------------------------------------------------------------------------------------
 def test_second_trip_of_the_solver_kernels():
-    """253 channels -> pitch 256 -> four rows per workgroup, and more than kLtMaxGrid * 4 vertices: the matvec, update and
-    direction kernels stride and every scalar is the sum of kLtMaxGrid partials."""
+    """253 channels -> pitch 256 -> four rows per workgroup, and more than kRowMaxGrid * 4 vertices: the matvec, update and
+    direction kernels stride and every scalar is the sum of kRowMaxGrid partials."""
     from warpconvnet_amd import _lib
 
     side = torch.arange(LATTICE_SIDE, dtype=torch.float32)
@@ -203,7 +203,7 @@ def test_second_trip_of_the_solver_kernels():
 
 
 def test_second_trip_of_the_weights_kernel():
-    """One thread per query: more than kLtMaxGrid * kLtThreads queries, k = 1, arbitrary neighbour indices.  The weight of a
+    """One thread per query: more than kRowMaxGrid * kRowThreads queries, k = 1, arbitrary neighbour indices.  The weight of a
     single neighbour is w / max(w, 1e-20): one, unless w itself is below the clamp, where it is w * 1e20 and carries the
     rounding of the exponent x: (dx + df + 3) * 2^-24 * |x| relative."""
     from warpconvnet_amd.nn.functional.bilateral import hip_knn_weights

@@ -29,9 +29,9 @@ F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
 
 # the constants of the sources (tests/test_grid_cap_constants.py reads them there)
 ADA_THREADS, ADA_FWD_BLOCKS = 256, 4096            # ada_row.h: kAdaThreads, kAdaFwdBlocks
-VX_THREADS, VX_PER, VX_MAX_GRID = 256, 8, 4096     # voxelize.hip: kVxThreads, kVxPer, kVxMaxGrid
+VX_THREADS, VX_PER, VX_MAX_GRID = 256, 8, 4096     # row_lists.h: kRowThreads, kRunPer, kRowMaxGrid
 VX_TILE = VX_THREADS * VX_PER                      # sorted keys of one scan tile
-CG_CHUNK = 256                                     # voxelize.hip: kCgChunk
+CG_CHUNK = 256                                     # row_lists.h: kRowChunk
 ATTN_MAX_GRID, ATTN_BLOCK = 1 << 22, 32            # attn_varlen.hip: kAttnMaxGrid, kAttnBlock
 
 
@@ -223,10 +223,10 @@ def test_adaln_rows_past_the_cap(c, rows, dtype, use):
 
 # ---- voxel map ---------------------------------------------------------------------------------------------------------------
 def test_voxel_map_points_past_the_cap(monkeypatch):
-    """1.4 M points on a 300^3 grid, three batch elements, the middle one empty.  n > kVxMaxGrid * kVxThreads = 1048576
+    """1.4 M points on a 300^3 grid, three batch elements, the middle one empty.  n > kRowMaxGrid * kRowThreads = 1048576
     points (vx_keys_kernel); M > 1048576 voxels (vx_finish_kernel), and the first element alone holds more than that, so the
     batch step - whose voxel offsets only the thread that sees it writes - lies in the finish kernel's second trip; 684 tiles
-    of kVxThreads * kVxPer = 2048 keys > kVxThreads (the carry of vx_tile_scan_kernel, from 524288 keys on)."""
+    of kRowThreads * kRunPer = 2048 keys > kRowThreads (the carry of run_scan_kernel, from 524288 keys on)."""
     n, a = 1_400_000, 1_150_000
     assert n > VX_MAX_GRID * VX_THREADS and -(-n // VX_TILE) > 2 * VX_THREADS
     uc, uoff, tu = vox._check(monkeypatch, vox._cloud(n, 5), [0, a, a, n], 0.02)
@@ -259,7 +259,7 @@ def _run_lengths(n):
 
 def test_voxel_map_codes_past_the_cap():
     """8388608 + 3 * 2048 + 5 int64 codes through ``ToUnique`` (the route of ``point_pool_by_code``).  ceil(n / 2048) = 4100
-    tiles > kVxMaxGrid = 4096: vx_tile_count_kernel and vx_apply_kernel take a second trip for the last four.  Long runs and
+    tiles > kRowMaxGrid = 4096: run_count_kernel and run_apply_kernel take a second trip for the last four.  Long runs and
     single codes, run boundaries on tile edges; every field exactly equal to the ``torch.unique`` construction."""
     from warpconvnet_amd.utils.unique import ToUnique
 
@@ -358,7 +358,7 @@ def _check_gather_reduce(x, indices, offsets, max_segment, sel, what):
 
 
 def test_csr_gather_reduce_unsplit_64_lanes():
-    """c = 33 fp32: one element a lane (V = 1), L = 64 lanes, kVxThreads / L = 4 segments a workgroup.  m > kVxMaxGrid * 4 =
+    """c = 33 fp32: one element a lane (V = 1), L = 64 lanes, kRowThreads / L = 4 segments a workgroup.  m > kRowMaxGrid * 4 =
     16384 segments a trip: 2 * 16384 + 3 segments of 0 to 5 rows are three trips, the last with three segments."""
     dev, g = _dev(), _gen(33)
     m, trip = 2 * 16384 + 3, VX_MAX_GRID * (VX_THREADS // 64)
@@ -372,9 +372,9 @@ def test_csr_gather_reduce_unsplit_64_lanes():
 
 
 def test_csr_gather_reduce_unsplit_one_lane():
-    """c = 8 bf16: one 16-B piece (V = 8), L = 1, 256 segments a workgroup.  m > kVxMaxGrid * 256 = 1048576 segments a trip:
+    """c = 8 bf16: one 16-B piece (V = 8), L = 1, 256 segments a workgroup.  m > kRowMaxGrid * 256 = 1048576 segments a trip:
     1048576 + 300 segments of 0 to 2 rows.  A second map, with the longest segment not known (max_segment = -1) and five
-    segments above kCgChunk = 256 rows at segment numbers beyond 1048576: cg_collect_kernel (64 segments a wave, four waves
+    segments above kRowChunk = 256 rows at segment numbers beyond 1048576: row_list_collect_kernel (64 segments a wave, four waves
     a workgroup, 1048576 a trip) finds them in its second trip."""
     dev, g = _dev(), _gen(8)
     trip = VX_MAX_GRID * VX_THREADS
@@ -393,8 +393,8 @@ def test_csr_gather_reduce_unsplit_one_lane():
 
 
 def test_csr_gather_reduce_split():
-    """c = 33 fp32, 16384 + 16 segments of 257 to 300 rows (all above kCgChunk = 256: two chunks each) over a small x of
-    4096 rows, about 4.6 M indices.  The chunk-item form of cg_reduce_kernel has about 32800 items against kVxMaxGrid * 4 =
+    """c = 33 fp32, 16384 + 16 segments of 257 to 300 rows (all above kRowChunk = 256: two chunks each) over a small x of
+    4096 rows, about 4.6 M indices.  The chunk-item form of cg_reduce_kernel has about 32800 items against kRowMaxGrid * 4 =
     16384 a trip (L = 64), cg_combine_kernel 16400 long segments against 16384 a trip.  The items are numbered by an integer
     atomic, in any order: which segments fall into the second trip differs from run to run, so the sample is drawn over all
     of them, with the last sixteen."""
@@ -413,7 +413,7 @@ def test_csr_gather_reduce_split():
 # ---- row_spread --------------------------------------------------------------------------------------------------------------
 def test_row_spread_past_the_cap():
     """300000 output rows of c = 32 bf16 plus a skip of 8 channels: (32 + 8) / 8 = 5 pieces of 8 a row, 1.5 M pieces >
-    kVxMaxGrid * kVxThreads = 1048576.  Plain mode is a copy; the inverse-count and arg-match modes against the CPU branch
+    kRowMaxGrid * kRowThreads = 1048576.  Plain mode is a copy; the inverse-count and arg-match modes against the CPU branch
     of ``_CsrPool.backward`` in fp64 (the mean gradient under the bound of tests/test_gpu_point_pool.py: one division, one
     rounding).  Some ``to_orig`` entries are out of range: rows of zeros."""
     from warpconvnet_amd.ops.csr_rows import SPREAD_ARG_MATCH, SPREAD_INV_COUNT, SPREAD_PLAIN, _CsrPool, row_spread

@@ -98,7 +98,7 @@ def test_batched_search_rejects_more_than_32_offsets():
 
 
 def test_second_trip_of_insert_and_search():
-    """More keys than kLtMaxGrid * kLtThreads: the striding threads insert and look up a second key each."""
+    """More keys than kRowMaxGrid * kRowThreads: the striding threads insert and look up a second key each."""
     T = _table()
     n = POINTS_SECOND_TRIP + 1000
     i = torch.arange(n, device=DEV)

@@ -226,7 +226,7 @@ def test_no_points(kind):
 # ---- second trips of the capped grids ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 def test_second_trip_of_geometry_and_vertex_map(kind):
-    """d = 1: two entries per point.  More than kLtMaxGrid scan tiles of entries, hence more than kLtMaxGrid * kLtThreads
+    """d = 1: two entries per point.  More than kRowMaxGrid scan tiles of entries, hence more than kRowMaxGrid * kRowThreads
     points: the geometry kernel and the three tile kernels stride.  Ties can occur among this many points, so the map is checked
     against the entry keys the geometry kernel itself reports, and the late points against a build of their own."""
     n = ENTRIES_SECOND_TRIP // 2 + 1000
@@ -247,7 +247,7 @@ def test_second_trip_of_geometry_and_vertex_map(kind):
 
 
 def test_second_trip_of_the_feature_kernels():
-    """253 channels -> pitch 256 -> 64 lanes per row and four rows per workgroup: more than kLtMaxGrid * 4 vertices and points."""
+    """253 channels -> pitch 256 -> 64 lanes per row and four rows per workgroup: more than kRowMaxGrid * 4 vertices and points."""
     gen = torch.Generator().manual_seed(5)
     pos = (torch.randn(WIDE_ROWS_SECOND_TRIP + 500, 2, generator=gen) * 40).to(DEV)
     lat = build("perm", pos, "hip")
@@ -261,7 +261,7 @@ def test_second_trip_of_the_feature_kernels():
 
 
 def test_second_trip_of_longest_row_and_plan():
-    """More than kLtMaxGrid * kLtThreads vertices, and the one long row among the last of them: the threads of the longest-row
+    """More than kRowMaxGrid * kRowThreads vertices, and the one long row among the last of them: the threads of the longest-row
     kernel and of the plan kernel (one per vertex row) stride, and only a second trip finds the long row."""
     gen = torch.Generator().manual_seed(11)
     n = VERTICES_SECOND_TRIP // 3 + 30_000  # three vertices a point, nearly all their own
@@ -278,7 +278,7 @@ def test_second_trip_of_longest_row_and_plan():
 
 
 def test_second_trip_of_chunk_partials_and_combine():
-    """A CSR of LONG_ROWS_SECOND_TRIP rows of kLtChunk + 1 entries at the wide pitch: more long rows than kLtMaxGrid * 4 lane
+    """A CSR of LONG_ROWS_SECOND_TRIP rows of kRowChunk + 1 entries at the wide pitch: more long rows than kRowMaxGrid * 4 lane
     groups (combine kernel) and twice as many chunk items (partials kernel)."""
     from warpconvnet_amd.nn.functional import _lattice as lt
 

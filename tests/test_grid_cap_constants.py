@@ -12,10 +12,10 @@ WHY = "tests/test_gpu_grid_caps.py derives its shapes from this value: re-derive
 CONSTANTS = [
     ("ada_row.h", "kAdaThreads", 256),
     ("ada_row.h", "kAdaFwdBlocks", 4096),
-    ("voxelize.hip", "kVxThreads", 256),
-    ("voxelize.hip", "kVxPer", 8),
-    ("voxelize.hip", "kVxMaxGrid", 4096),
-    ("voxelize.hip", "kCgChunk", 256),
+    ("row_lists.h", "kRowThreads", 256),
+    ("row_lists.h", "kRunPer", 8),
+    ("row_lists.h", "kRowMaxGrid", 4096),
+    ("row_lists.h", "kRowChunk", 256),
     ("attn_varlen.hip", "kAttnMaxGrid", 1 << 22),
     ("attn_varlen.hip", "kAttnBlock", 32),
     ("norm.hip", "WCN_NORM_BLOCKS", 512),
@@ -43,9 +43,9 @@ def test_the_tests_use_the_same_values():
 
     want = {name: value for _, name, value in CONSTANTS}
     assert (caps.ADA_THREADS, caps.ADA_FWD_BLOCKS) == (want["kAdaThreads"], want["kAdaFwdBlocks"]), WHY
-    assert (caps.VX_THREADS, caps.VX_PER, caps.VX_MAX_GRID) == (want["kVxThreads"], want["kVxPer"], want["kVxMaxGrid"]), WHY
-    assert caps.CG_CHUNK == want["kCgChunk"] and (caps.ATTN_MAX_GRID, caps.ATTN_BLOCK) == (want["kAttnMaxGrid"], want["kAttnBlock"]), WHY
+    assert (caps.VX_THREADS, caps.VX_PER, caps.VX_MAX_GRID) == (want["kRowThreads"], want["kRunPer"], want["kRowMaxGrid"]), WHY
+    assert caps.CG_CHUNK == want["kRowChunk"] and (caps.ATTN_MAX_GRID, caps.ATTN_BLOCK) == (want["kAttnMaxGrid"], want["kAttnBlock"]), WHY
 
 
 def test_chunk_rows_of_the_library(hip_lib):
-    assert hip_lib.wcn_csr_chunk_rows() == 256, f"wcn_csr_chunk_rows() (kCgChunk). {WHY}"
+    assert hip_lib.wcn_csr_chunk_rows() == 256, f"wcn_csr_chunk_rows() (kRowChunk). {WHY}"

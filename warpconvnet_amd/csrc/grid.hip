@@ -6,24 +6,15 @@
 //                strides (b, x, y, z, c), so every memory format and every permuted view is read in place
 //   c. backward  d_grid through the same strides, every element written exactly once: a vertex sums over its at most 8
 //                adjacent cells in a fixed order and inside a cell over the points in the map's (stable-sorted) order.  A
-//                cell of more than kGsChunk points is cut into chunks whose corner sums are formed by gs_bwd_chunk_kernel and
-//                added in chunk order.
-// No float atomics: the bits of a result depend on the map alone.  Every grid is capped at kGsMaxGrid workgroups and strides.
-#include <limits.h>
-
-#include "wcn_common.h"
+//                cell of more than kRowChunk points is cut into chunks whose corner sums are formed by gs_bwd_chunk_kernel and
+//                added in chunk order: the chunk rule of row_lists.h, with slots derived from the sorted position instead of
+//                a list.
+// No float atomics: the bits of a result depend on the map alone.  Every grid is capped at kRowMaxGrid workgroups and strides.
+#include "row_lists.h"
 
 namespace wcn {
 
-constexpr int kGsThreads = 256;
-constexpr int kGsMaxGrid = 4096;
-constexpr int kGsChunk = 256;   // points of one chunk of a crowded cell (the chunk rule)
 constexpr int kGsPlanarCh = 8;  // channels of one thread of the planar forward kernel
-
-static unsigned gs_grid(int64_t blocks) {
-  const int64_t g = blocks < 1 ? 1 : blocks;
-  return (unsigned)(g < kGsMaxGrid ? g : kGsMaxGrid);
-}
 
 struct GsShape {
   int32_t dims[3];   // vertices per axis
@@ -52,11 +43,11 @@ __device__ __forceinline__ int gs_batch_of(const int64_t* __restrict__ offsets, 
 __device__ __forceinline__ float gs_clamp(float v, float hi) { return fminf(fmaxf(v, 0.0f), hi); }
 
 template <bool CORNER>
-__global__ __launch_bounds__(kGsThreads) void gs_keys_kernel(const float* __restrict__ pos, int64_t n,
+__global__ __launch_bounds__(kRowThreads) void gs_keys_kernel(const float* __restrict__ pos, int64_t n,
                                                              const int64_t* __restrict__ offsets, int num_batches, GsShape sh,
                                                              GsBounds bd, int64_t* __restrict__ keys,
                                                              float* __restrict__ frac) {
-  for (int64_t i = (int64_t)blockIdx.x * kGsThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kGsThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowThreads) {
     const int b = gs_batch_of(offsets, num_batches, i);
     int64_t flat = b;
 #pragma unroll
@@ -117,12 +108,12 @@ __device__ __forceinline__ void gs_point(const GsShape& sh, int64_t key, const f
 
 // channel stride 1: `lanes` lanes (a power of two, <= 64) per point, VEC channels per access
 template <typename T, int VEC>
-__global__ __launch_bounds__(kGsThreads) void gs_fwd_rows_kernel(GsShape sh, const T* __restrict__ grid,
+__global__ __launch_bounds__(kRowThreads) void gs_fwd_rows_kernel(GsShape sh, const T* __restrict__ grid,
                                                                  const int64_t* __restrict__ keys,
                                                                  const int64_t* __restrict__ perm,
                                                                  const float* __restrict__ frac, int64_t n, T* __restrict__ out,
                                                                  int64_t pitch, int64_t col0, int lanes) {
-  const int per_block = kGsThreads / lanes, group = threadIdx.x / lanes, lane = threadIdx.x % lanes;
+  const int per_block = kRowThreads / lanes, group = threadIdx.x / lanes, lane = threadIdx.x % lanes;
   for (int64_t j = (int64_t)blockIdx.x * per_block + group; j < n; j += (int64_t)gridDim.x * per_block) {
     const int64_t p = perm[j];
     GsPoint pt;
@@ -149,13 +140,13 @@ __global__ __launch_bounds__(kGsThreads) void gs_fwd_rows_kernel(GsShape sh, con
 // planar channels: one thread per (point, kGsPlanarCh channels), points fastest, so that the lanes of a wave read
 // neighbouring cells of one channel plane
 template <typename T>
-__global__ __launch_bounds__(kGsThreads) void gs_fwd_planar_kernel(GsShape sh, const T* __restrict__ grid,
+__global__ __launch_bounds__(kRowThreads) void gs_fwd_planar_kernel(GsShape sh, const T* __restrict__ grid,
                                                                    const int64_t* __restrict__ keys,
                                                                    const int64_t* __restrict__ perm,
                                                                    const float* __restrict__ frac, int64_t n,
                                                                    T* __restrict__ out, int64_t pitch, int64_t col0) {
   const int64_t pieces = (sh.channels + kGsPlanarCh - 1) / kGsPlanarCh, items = pieces * n;
-  for (int64_t it = (int64_t)blockIdx.x * kGsThreads + threadIdx.x; it < items; it += (int64_t)gridDim.x * kGsThreads) {
+  for (int64_t it = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; it < items; it += (int64_t)gridDim.x * kRowThreads) {
     const int64_t j = it % n;
     const int cb = (int)(it / n) * kGsPlanarCh;
     const int64_t p = perm[j];
@@ -174,35 +165,37 @@ __global__ __launch_bounds__(kGsThreads) void gs_fwd_planar_kernel(GsShape sh, c
 }
 
 // ---- c. backward ------------------------------------------------------------------------------------------------------------
-// slot of the chunk of a crowded cell that starts at sorted position `start`: two slots per kGsChunk positions, the odd one
-// for a cell's first chunk.  Crowded cells are longer than kGsChunk, so no two first chunks and no two later chunks start
-// inside the same kGsChunk positions.
-__device__ __forceinline__ int64_t gs_chunk_slot(int64_t start, bool first) { return 2 * (start / kGsChunk) + (first ? 1 : 0); }
+// slot of the chunk of a crowded cell that starts at sorted position `start`: two slots per kRowChunk positions, the odd one
+// for a cell's first chunk.  Crowded cells are longer than kRowChunk, so no two first chunks and no two later chunks start
+// inside the same kRowChunk positions.
+__device__ __forceinline__ int64_t gs_chunk_slot(int64_t start, bool first) {
+  return 2 * (start / kRowChunk) + (first ? 1 : 0);
+}
 
-// one workgroup per kGsChunk sorted positions: the (at most two) chunk heads among them, then the 8 corner sums of each
+// one workgroup per kRowChunk sorted positions: the (at most two) chunk heads among them, then the 8 corner sums of each
 // chunk, one channel per thread, over the chunk's points in order
 template <typename T>
-__global__ __launch_bounds__(kGsThreads) void gs_bwd_chunk_kernel(int channels, const T* __restrict__ dy, int64_t pitch,
+__global__ __launch_bounds__(kRowThreads) void gs_bwd_chunk_kernel(int channels, const T* __restrict__ dy, int64_t pitch,
                                                                   int64_t col0, const int64_t* __restrict__ keys,
                                                                   const int64_t* __restrict__ perm,
                                                                   const int64_t* __restrict__ cell_offsets,
                                                                   const float* __restrict__ frac, int64_t n,
                                                                   float* __restrict__ partials) {
-  static_assert(kGsThreads == kGsChunk, "one thread per sorted position of a tile");
+  static_assert(kRowThreads == kRowChunk, "one thread per sorted position of a tile");
   __shared__ int64_t s_start[2];
   __shared__ int s_len[2], s_first[2], s_heads;
-  const int64_t tiles = (n + kGsChunk - 1) / kGsChunk;
+  const int64_t tiles = (n + kRowChunk - 1) / kRowChunk;
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     if (threadIdx.x == 0) s_heads = 0;
     __syncthreads();
-    const int64_t x = t * kGsChunk + threadIdx.x;
+    const int64_t x = t * kRowChunk + threadIdx.x;
     if (x < n) {
       const int64_t key = keys[x], o0 = cell_offsets[key], o1 = cell_offsets[key + 1];
-      if (o1 - o0 > kGsChunk && (x - o0) % kGsChunk == 0) {
+      if (o1 - o0 > kRowChunk && (x - o0) % kRowChunk == 0) {
         const int h = atomicAdd(&s_heads, 1);  // at most two heads: one first chunk, one later chunk
         if (h < 2) {
           s_start[h] = x;
-          s_len[h] = (int)(o1 - x < kGsChunk ? o1 - x : kGsChunk);
+          s_len[h] = (int)(o1 - x < kRowChunk ? o1 - x : kRowChunk);
           s_first[h] = x == o0;
         }
       }
@@ -213,7 +206,7 @@ __global__ __launch_bounds__(kGsThreads) void gs_bwd_chunk_kernel(int channels, 
       const int64_t start = s_start[h];
       const int len = s_len[h];
       float* __restrict__ dst = partials + gs_chunk_slot(start, s_first[h]) * 8 * channels;
-      for (int c = threadIdx.x; c < channels; c += kGsThreads) {
+      for (int c = threadIdx.x; c < channels; c += kRowThreads) {
         float acc[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
@@ -235,14 +228,14 @@ __global__ __launch_bounds__(kGsThreads) void gs_bwd_chunk_kernel(int channels, 
 
 // `lanes` lanes (a power of two, <= 64) per vertex, lanes over channels: the rows of dy are read 4 bytes a lane, coalesced
 template <typename T>
-__global__ __launch_bounds__(kGsThreads) void gs_bwd_vertex_kernel(GsShape sh, int64_t vertices, const T* __restrict__ dy,
+__global__ __launch_bounds__(kRowThreads) void gs_bwd_vertex_kernel(GsShape sh, int64_t vertices, const T* __restrict__ dy,
                                                                    int64_t pitch, int64_t col0,
                                                                    const int64_t* __restrict__ perm,
                                                                    const int64_t* __restrict__ cell_offsets,
                                                                    const float* __restrict__ frac,
                                                                    const float* __restrict__ partials, T* __restrict__ dgrid,
                                                                    int lanes) {
-  const int per_block = kGsThreads / lanes, group = threadIdx.x / lanes, lane = threadIdx.x % lanes;
+  const int per_block = kRowThreads / lanes, group = threadIdx.x / lanes, lane = threadIdx.x % lanes;
   const int C = sh.channels;
   for (int64_t v = (int64_t)blockIdx.x * per_block + group; v < vertices; v += (int64_t)gridDim.x * per_block) {
     int64_t r = v;
@@ -262,8 +255,8 @@ __global__ __launch_bounds__(kGsThreads) void gs_bwd_vertex_kernel(GsShape sh, i
         // an axis of one vertex has one cell whose two corners are both vertex 0: the upper one weighs exactly 0
         const int64_t cell = ((b * sh.cells[0] + cx) * sh.cells[1] + cy) * sh.cells[2] + cz;
         const int64_t o0 = cell_offsets[cell], o1 = cell_offsets[cell + 1];
-        if (partials && o1 - o0 > kGsChunk) {  // no partials: the caller vouched for short cells
-          for (int64_t s = o0; s < o1; s += kGsChunk)
+        if (partials && o1 - o0 > kRowChunk) {  // no partials: the caller vouched for short cells
+          for (int64_t s = o0; s < o1; s += kRowChunk)
             acc += partials[(gs_chunk_slot(s, s == o0) * 8 + corner) * C + c];
         } else {
           for (int64_t j = o0; j < o1; ++j) {
@@ -278,12 +271,6 @@ __global__ __launch_bounds__(kGsThreads) void gs_bwd_vertex_kernel(GsShape sh, i
       dst[c * sh.stride[4]] = Cvt<T>::st(acc);
     }
   }
-}
-
-static int gs_lanes(int64_t pieces) {
-  int l = 1;
-  while (l < 64 && l < pieces) l <<= 1;
-  return l;
 }
 
 // dims >= 1, their product and the batch count inside int32 where indices are 32-bit
@@ -319,13 +306,13 @@ static void gs_launch_forward(const GsShape& sh, const void* grid, const int64_t
   if (sh.stride[4] == 1) {
     const bool wide = sh.channels % V == 0 && pitch % V == 0 && col0 % V == 0 && aligned_to(g, 16) && aligned_to(o, 16) &&
                       sh.stride[0] % V == 0 && sh.stride[1] % V == 0 && sh.stride[2] % V == 0 && sh.stride[3] % V == 0;
-    const int lanes = gs_lanes(wide ? sh.channels / V : sh.channels);
-    const unsigned blocks = gs_grid(ceil_div(n, kGsThreads / lanes));
-    if (wide) gs_fwd_rows_kernel<T, V><<<blocks, kGsThreads, 0, s>>>(sh, g, keys, perm, frac, n, o, pitch, col0, lanes);
-    else gs_fwd_rows_kernel<T, 1><<<blocks, kGsThreads, 0, s>>>(sh, g, keys, perm, frac, n, o, pitch, col0, lanes);
+    const int lanes = row_lanes(wide ? sh.channels / V : sh.channels);
+    const unsigned blocks = capped_grid(ceil_div(n, kRowThreads / lanes));
+    if (wide) gs_fwd_rows_kernel<T, V><<<blocks, kRowThreads, 0, s>>>(sh, g, keys, perm, frac, n, o, pitch, col0, lanes);
+    else gs_fwd_rows_kernel<T, 1><<<blocks, kRowThreads, 0, s>>>(sh, g, keys, perm, frac, n, o, pitch, col0, lanes);
   } else {
     const int64_t items = ceil_div(sh.channels, kGsPlanarCh) * n;
-    gs_fwd_planar_kernel<T><<<gs_grid(ceil_div(items, kGsThreads)), kGsThreads, 0, s>>>(sh, g, keys, perm, frac, n, o, pitch, col0);
+    gs_fwd_planar_kernel<T><<<capped_grid(ceil_div(items, kRowThreads)), kRowThreads, 0, s>>>(sh, g, keys, perm, frac, n, o, pitch, col0);
   }
 }
 
@@ -334,15 +321,15 @@ static void gs_launch_backward(const GsShape& sh, int64_t vertices, const void* 
                                const int64_t* keys, const int64_t* perm, const int64_t* cell_offsets, const float* frac,
                                int64_t n, bool chunks, float* partials, void* dgrid, hipStream_t s) {
   if (chunks)
-    gs_bwd_chunk_kernel<T><<<gs_grid(ceil_div(n, kGsChunk)), kGsThreads, 0, s>>>(sh.channels, (const T*)dy, pitch, col0, keys,
-                                                                                perm, cell_offsets, frac, n, partials);
-  const int lanes = gs_lanes(sh.channels);
-  gs_bwd_vertex_kernel<T><<<gs_grid(ceil_div(vertices, kGsThreads / lanes)), kGsThreads, 0, s>>>(
+    gs_bwd_chunk_kernel<T><<<capped_grid(ceil_div(n, kRowChunk)), kRowThreads, 0, s>>>(
+        sh.channels, (const T*)dy, pitch, col0, keys, perm, cell_offsets, frac, n, partials);
+  const int lanes = row_lanes(sh.channels);
+  gs_bwd_vertex_kernel<T><<<capped_grid(ceil_div(vertices, kRowThreads / lanes)), kRowThreads, 0, s>>>(
       sh, vertices, (const T*)dy, pitch, col0, perm, cell_offsets, frac, partials, (T*)dgrid, lanes);
 }
 
 static size_t gs_partial_bytes(int64_t n, int32_t channels) {
-  return (size_t)(2 * ceil_div(n, kGsChunk) + 2) * 8 * (size_t)channels * sizeof(float);
+  return (size_t)(2 * ceil_div(n, kRowChunk) + 2) * 8 * (size_t)channels * sizeof(float);
 }
 
 }  // namespace wcn
@@ -351,8 +338,8 @@ using namespace wcn;
 
 extern "C" {
 
-int32_t wcn_grid_max_grid(void) { return kGsMaxGrid; }
-int32_t wcn_grid_chunk_points(void) { return kGsChunk; }
+int32_t wcn_grid_max_grid(void) { return kRowMaxGrid; }
+int32_t wcn_grid_chunk_points(void) { return kRowChunk; }
 
 int wcn_grid_point_keys(const float* points, int64_t n, const int64_t* point_offsets, int32_t num_batches, const int32_t* dims,
                         const float* lo, const float* scale, int32_t mode, int64_t* keys, float* fractions,
@@ -370,11 +357,11 @@ int wcn_grid_point_keys(const float* points, int64_t n, const int64_t* point_off
     bd.scale[a] = scale[a];
   }
   hipStream_t s = (hipStream_t)stream;
-  const unsigned g = gs_grid(ceil_div(n, kGsThreads));
+  const unsigned g = capped_grid(ceil_div(n, kRowThreads));
   if (mode == WCN_GRID_KEY_CORNER)
-    gs_keys_kernel<true><<<g, kGsThreads, 0, s>>>(points, n, point_offsets, num_batches, sh, bd, keys, fractions);
+    gs_keys_kernel<true><<<g, kRowThreads, 0, s>>>(points, n, point_offsets, num_batches, sh, bd, keys, fractions);
   else
-    gs_keys_kernel<false><<<g, kGsThreads, 0, s>>>(points, n, point_offsets, num_batches, sh, bd, keys, fractions);
+    gs_keys_kernel<false><<<g, kRowThreads, 0, s>>>(points, n, point_offsets, num_batches, sh, bd, keys, fractions);
   return launch_status();
 }
 
@@ -420,7 +407,7 @@ int wcn_grid_sample_backward(const void* dy, int64_t dy_pitch, int64_t col0, con
   if (st != WCN_SUCCESS) return st;
   if (vertices == 0 || channels == 0) return WCN_SUCCESS;
   if (!d_grid || !cell_offsets || (n > 0 && (!dy || !sorted_keys || !perm || !fractions))) return WCN_ERROR_INVALID_PARAMETERS;
-  const bool chunks = n > kGsChunk && (max_cell_points < 0 || max_cell_points > kGsChunk);
+  const bool chunks = n > kRowChunk && (max_cell_points < 0 || max_cell_points > kRowChunk);
   if (chunks && (!workspace || workspace_bytes < gs_partial_bytes(n, channels))) return WCN_ERROR_INVALID_PARAMETERS;
   const GsShape sh = gs_shape(dims, strides, channels);
   hipStream_t s = (hipStream_t)stream;

@@ -12,29 +12,21 @@
 //                    unsigned order of the pair is the lexicographic order of the signed rows.  The top bit of `lo` is flipped:
 //                    the framework's sort compares int64 as signed.
 //   c. vertex map    sorted pairs + permutation -> unique keys (decoded), the vertex of every entry, CSR offsets by vertex and
-//                    the longest row.  Tile sums -> one-workgroup scan -> apply, no kernel waits on another workgroup.
+//                    the longest row: the runs -> map kernels of row_lists.h on (hi, lo) pairs.
 //   d. features      fp32 rows of `pitch` floats, pitch a multiple of 4: every row access is 16-B pieces.
-//                    splat  out[v] = alpha * sum over e in row v of w[e] * f[e / K], ascending; rows longer than kLtChunk are
-//                           cut into chunks summed by their own lane groups into partials that are added in chunk order
+//                    splat  out[v] = alpha * sum over e in row v of w[e] * f[e / K], ascending; rows longer than kRowChunk go
+//                           by the chunk rule of row_lists.h, on a plan built once per CSR
 //                    blur   y[v] = s0 x[v] + s1 x[n1[v]] + s2 x[n2[v]], -1 reads as zero
 //                    slice  out[i] = alpha * sum over k of w[i, k] * x[idx[i, k]], -1 reads as zero
 //   e. solver        the conjugate-gradient loop of the fast bilateral solver on the grid: 2 d + 2 launches an iteration, every
 //                    scalar from per-workgroup fp64 partials added in index order, a state block instead of a host read
 //   f. knn weights   the normalised weights of the kNN bilateral filter, one thread per query; the aggregation is the slice
 // No float atomics anywhere: the bits of a result depend on the lattice alone.  The integer atomics (status word, longest row,
-// the list of long rows) give the same result in any order.  Every grid is capped at kLtMaxGrid workgroups and strides.
-#include <limits.h>
-
-#include "wcn_common.h"
+// the list of long rows) give the same result in any order.  Every grid is capped at kRowMaxGrid workgroups and strides.
+#include "row_lists.h"
 
 namespace wcn {
 
-constexpr int kLtThreads = 256;
-constexpr int kLtPer = 8;
-constexpr int kLtTile = kLtThreads * kLtPer;  // sorted entries of one scan tile
-constexpr int kLtMaxGrid = 4096;
-constexpr int kLtChunk = 256;                 // entries of one chunk of a long vertex row (the chunk rule)
-constexpr int kLtCounterInts = 64;            // plan header: [0] chunk items, [1] long rows; padded to 256 B
 constexpr int kLtAxes = 7;                    // key fields
 constexpr int kLtBits = 17;                   // bits of a field
 constexpr int kLtSearchMax = 32;              // offsets of one batched search
@@ -42,11 +34,6 @@ constexpr int kLtCoordMin = -(1 << (kLtBits - 1));
 constexpr int kLtCoordMax = (1 << (kLtBits - 1)) - 1;
 constexpr uint64_t kLtField = (1ull << kLtBits) - 1;
 constexpr uint64_t kLtSign = 1ull << 63;
-
-static unsigned lt_grid(int64_t items) {
-  const int64_t g = items < 1 ? 1 : items;
-  return (unsigned)(g < kLtMaxGrid ? g : kLtMaxGrid);
-}
 
 struct Key128 {
   uint64_t hi, lo;
@@ -75,10 +62,10 @@ __device__ __forceinline__ uint32_t h128_slot(const Key128& k, uint32_t mask) {
   return hash_slot(k.lo ^ (k.hi * 0x9E3779B97F4A7C15ull), mask);
 }
 
-__global__ __launch_bounds__(kLtThreads) void h128_insert_kernel(ulonglong2* __restrict__ tkeys, int32_t* __restrict__ tvals,
+__global__ __launch_bounds__(kRowThreads) void h128_insert_kernel(ulonglong2* __restrict__ tkeys, int32_t* __restrict__ tvals,
                                                                  uint32_t mask, const int32_t* __restrict__ coords, int64_t n,
                                                                  int key_dim, int32_t* __restrict__ status) {
-  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLtThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowThreads) {
     Key128 k{0, 0};
     bool ok = true;
     for (int j = 0; j < key_dim; ++j) {
@@ -120,15 +107,15 @@ __device__ __forceinline__ int h128_lookup(const ulonglong2* __restrict__ tkeys,
 }
 
 // out[k, i] = row of queries[i] + offsets[k], -1 when absent or outside the key range; offsets == null: one zero offset
-__global__ __launch_bounds__(kLtThreads) void h128_search_kernel(const ulonglong2* __restrict__ tkeys,
+__global__ __launch_bounds__(kRowThreads) void h128_search_kernel(const ulonglong2* __restrict__ tkeys,
                                                                  const int32_t* __restrict__ tvals, uint32_t mask,
                                                                  const int32_t* __restrict__ queries,
                                                                  const int32_t* __restrict__ offsets, int64_t m, int K,
                                                                  int key_dim, int32_t* __restrict__ out) {
   __shared__ int s_off[kLtSearchMax * kLtAxes];
-  for (int t = threadIdx.x; t < K * key_dim; t += kLtThreads) s_off[t] = offsets ? offsets[t] : 0;
+  for (int t = threadIdx.x; t < K * key_dim; t += kRowThreads) s_off[t] = offsets ? offsets[t] : 0;
   __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kLtThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kRowThreads) {
     int c[kLtAxes];
 #pragma unroll
     for (int j = 0; j < kLtAxes; ++j) c[j] = j < key_dim ? queries[i * key_dim + j] : 0;
@@ -162,7 +149,7 @@ __device__ __forceinline__ void lt_emit(const Key128& k, bool ok, int64_t e, int
 // The arithmetic is the framework's, operation by operation and without contraction into FMAs (embed: product with the scale
 // table, suffix sums; round to the nearest multiple of d + 1; rank the residuals, ties to the lower axis; correct the vertex to
 // coordinate sum 0; weights as differences of neighbouring residuals), so an fp32 build on the host gives the same bits.
-__global__ __launch_bounds__(kLtThreads) void permuto_simplex_kernel(const float* __restrict__ pos, int64_t n, int d, LtScale sc,
+__global__ __launch_bounds__(kRowThreads) void permuto_simplex_kernel(const float* __restrict__ pos, int64_t n, int d, LtScale sc,
                                                                      int64_t* __restrict__ key_hi, int64_t* __restrict__ key_lo,
                                                                      int32_t* __restrict__ keys, float* __restrict__ bary,
                                                                      int32_t* __restrict__ status) {
@@ -170,7 +157,7 @@ __global__ __launch_bounds__(kLtThreads) void permuto_simplex_kernel(const float
   const int dp1 = d + 1;
   const float fdp1 = (float)dp1;
   const float inv = (float)(1.0 / (double)dp1);
-  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLtThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowThreads) {
     float cf[kLtAxes - 1], el[kLtAxes];
 #pragma unroll
     for (int j = 0; j < kLtAxes - 1; ++j) cf[j] = j < d ? pos[i * d + j] * sc.v[j] : 0.f;
@@ -279,13 +266,13 @@ __global__ __launch_bounds__(kLtThreads) void permuto_simplex_kernel(const float
 }
 
 // corner c of a point: bit (d - 1 - j) of c steps axis j, the order of itertools.product([0, 1], repeat=d)
-__global__ __launch_bounds__(kLtThreads) void grid_corners_kernel(const float* __restrict__ pos, int64_t n, int d,
+__global__ __launch_bounds__(kRowThreads) void grid_corners_kernel(const float* __restrict__ pos, int64_t n, int d,
                                                                   int64_t* __restrict__ floors, int64_t* __restrict__ key_hi,
                                                                   int64_t* __restrict__ key_lo, int32_t* __restrict__ keys,
                                                                   float* __restrict__ weights, int32_t* __restrict__ status) {
 #pragma clang fp contract(off)
   const int K = 1 << d;
-  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLtThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowThreads) {
     int fl[kLtAxes - 1];
     float fr[kLtAxes - 1];
     bool ok = true;
@@ -326,125 +313,42 @@ __global__ __launch_bounds__(kLtThreads) void grid_corners_kernel(const float* _
 }
 
 // ---- c. runs -> vertex map --------------------------------------------------------------------------------------------------
-// thread t of a tile owns the sorted positions tile * kLtTile + t * kLtPer .. + kLtPer - 1; head = first position of a run
-__device__ __forceinline__ int lt_load_heads(const int64_t* __restrict__ hi, const int64_t* __restrict__ lo, int64_t n, int64_t i0,
-                                             int64_t (&kh)[kLtPer], int64_t (&kl)[kLtPer], bool (&head)[kLtPer]) {
+struct LtKeys {  // key policy of row_lists.h: a (hi, lo) pair per position, hi absent where the fields fit one word
+  struct Key {
+    int64_t hi, lo;
+  };
+  const int64_t* hi;
+  const int64_t* lo;
+  __device__ __forceinline__ void load(int64_t n, int64_t i0, Key (&k)[kRunPer]) const {
 #pragma unroll
-  for (int j = 0; j < kLtPer; ++j) {
-    kh[j] = (hi && i0 + j < n) ? hi[i0 + j] : 0;
-    kl[j] = i0 + j < n ? lo[i0 + j] : 0;
-  }
-  int64_t ph = (hi && i0 > 0 && i0 < n) ? hi[i0 - 1] : 0;
-  int64_t pl = (i0 > 0 && i0 < n) ? lo[i0 - 1] : 0;
-  int cnt = 0;
-#pragma unroll
-  for (int j = 0; j < kLtPer; ++j) {
-    head[j] = i0 + j < n && (i0 + j == 0 || kh[j] != ph || kl[j] != pl);
-    ph = kh[j];
-    pl = kl[j];
-    cnt += head[j] ? 1 : 0;
-  }
-  return cnt;
-}
-
-__global__ __launch_bounds__(kLtThreads) void lt_tile_count_kernel(const int64_t* __restrict__ hi, const int64_t* __restrict__ lo,
-                                                                   int64_t n, int64_t ntiles, int32_t* __restrict__ tile_sum) {
-  __shared__ int s_wave[kLtThreads / 64];
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int64_t kh[kLtPer], kl[kLtPer];
-    bool head[kLtPer];
-    const int cnt = lt_load_heads(hi, lo, n, tile * kLtTile + (int64_t)threadIdx.x * kLtPer, kh, kl, head);
-    int tot;
-    block_excl_scan<kLtThreads>(cnt, s_wave, &tot);
-    if (threadIdx.x == 0) tile_sum[tile] = tot;
-    __syncthreads();  // s_wave is rewritten by the next trip
-  }
-}
-
-// ONE workgroup: exclusive scan of the tile sums in place; summary[0] = V and the closing boundary row_offsets[V] = n
-__global__ __launch_bounds__(kLtThreads) void lt_tile_scan_kernel(int32_t* __restrict__ tile_sum, int64_t ntiles, int64_t n,
-                                                                  int32_t* __restrict__ summary,
-                                                                  int64_t* __restrict__ row_offsets) {
-  __shared__ int s_wave[kLtThreads / 64];
-  int carry = 0;
-  for (int64_t base = 0; base < ntiles; base += kLtThreads) {
-    const int64_t i = base + threadIdx.x;
-    const int v = i < ntiles ? tile_sum[i] : 0;
-    int tot;
-    const int e = block_excl_scan<kLtThreads>(v, s_wave, &tot);
-    if (i < ntiles) tile_sum[i] = carry + e;
-    carry += tot;
-    __syncthreads();  // s_wave is rewritten by the next trip
-  }
-  if (threadIdx.x == 0) {
-    summary[0] = carry;
-    row_offsets[carry] = n;  // carry <= n: the caller's buffer holds n + 1 words
-  }
-}
-
-__global__ __launch_bounds__(kLtThreads) void lt_apply_kernel(const int64_t* __restrict__ hi, const int64_t* __restrict__ lo,
-                                                              const int64_t* __restrict__ perm, int64_t n, int64_t ntiles,
-                                                              const int32_t* __restrict__ tile_sum, int key_dim,
-                                                              int32_t* __restrict__ unique_keys, int64_t* __restrict__ inverse,
-                                                              int64_t* __restrict__ row_offsets) {
-  __shared__ int s_wave[kLtThreads / 64];
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t i0 = tile * kLtTile + (int64_t)threadIdx.x * kLtPer;
-    int64_t kh[kLtPer], kl[kLtPer];
-    bool head[kLtPer];
-    const int cnt = lt_load_heads(hi, lo, n, i0, kh, kl, head);
-    int tot;
-    int64_t vid = (int64_t)tile_sum[tile] + block_excl_scan<kLtThreads>(cnt, s_wave, &tot) - 1;  // vertex of position i0 - 1
-#pragma unroll
-    for (int j = 0; j < kLtPer; ++j) {
-      const int64_t i = i0 + j;
-      if (i >= n) break;
-      if (head[j]) {
-        ++vid;
-        if (vid >= 0 && vid < n) {
-          row_offsets[vid] = i;
-          const Key128 k{(uint64_t)kh[j], (uint64_t)kl[j] ^ kLtSign};
-          for (int a = 0; a < key_dim; ++a) unique_keys[vid * key_dim + a] = key_field(k, key_dim, a);
-        }
-      }
-      const int64_t e = perm[i];
-      if (e >= 0 && e < n) inverse[e] = vid;
+    for (int j = 0; j < kRunPer; ++j) {
+      k[j].hi = (hi && i0 + j < n) ? hi[i0 + j] : 0;
+      k[j].lo = i0 + j < n ? lo[i0 + j] : 0;
     }
-    __syncthreads();  // s_wave is rewritten by the next trip
   }
-}
-
-__global__ __launch_bounds__(kLtThreads) void lt_longest_kernel(const int64_t* __restrict__ row_offsets, int64_t n,
-                                                                int32_t* __restrict__ summary) {
-  int64_t V = summary[0];
-  if (V > n) V = n;
-  int longest = 0;
-  for (int64_t v = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kLtThreads) {
-    const int64_t len = row_offsets[v + 1] - row_offsets[v];
-    longest = max(longest, (int)(len < INT_MAX ? len : INT_MAX));
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d));
-  if ((threadIdx.x & 63) == 0 && longest > 0) atomicMax(summary + 1, longest);
-}
-
-// ---- long rows: the chunk plan of a CSR -------------------------------------------------------------------------------------
-struct LtPlan {  // int32 words of the caller's plan buffer
-  int32_t* counters;   // [0] chunk items, [1] long rows
-  int32_t* item_row;   // [item_cap]
-  int32_t* item_k;     // [item_cap] chunk number inside the row
-  int32_t* long_row;   // [long_cap]
-  int32_t* long_base;  // [long_cap] first item of the row
-  int64_t item_cap, long_cap, ints;
+  __device__ __forceinline__ Key at(int64_t i) const { return Key{hi ? hi[i] : 0, lo[i]}; }
+  static __device__ __forceinline__ bool differ(const Key& a, const Key& b) { return a.hi != b.hi || a.lo != b.lo; }
 };
 
-static LtPlan lt_carve(int32_t* base, int64_t nnz) {
-  LtPlan p;
-  p.long_cap = nnz / kLtChunk + 1;  // a long row holds more than kLtChunk entries
-  p.item_cap = 2 * p.long_cap;      // ceil(len / chunk) <= len / chunk + 1 per long row
+struct LtWriter {  // what a vertex and an entry get
+  int key_dim;
+  int32_t* unique_keys;
+  int64_t* inverse;
+  __device__ __forceinline__ void head(int64_t vid, int64_t, const LtKeys::Key& key) const {
+    const Key128 k{(uint64_t)key.hi, (uint64_t)key.lo ^ kLtSign};
+    for (int a = 0; a < key_dim; ++a) unique_keys[vid * key_dim + a] = key_field(k, key_dim, a);
+  }
+  __device__ __forceinline__ void each(int64_t e, int64_t vid) const { inverse[e] = vid; }
+};
+
+// ---- long rows: the chunk plan of a CSR -------------------------------------------------------------------------------------
+// the list in the int32 words of the caller's plan buffer, packed; *ints = the words it takes
+static RowList lt_carve(int32_t* base, int64_t nnz, int64_t* ints = nullptr) {
+  RowList p;
+  row_list_caps(nnz, p);
   int64_t at = 0;
   p.counters = base + at;
-  at += kLtCounterInts;
+  at += kRowListCounterInts;
   p.item_row = base + at;
   at += p.item_cap;
   p.item_k = base + at;
@@ -453,46 +357,8 @@ static LtPlan lt_carve(int32_t* base, int64_t nnz) {
   at += p.long_cap;
   p.long_base = base + at;
   at += p.long_cap;
-  p.ints = at;
+  if (ints) *ints = at;
   return p;
-}
-
-// one wave looks at 64 rows; every long one takes its run of items with one integer atomic and the wave writes the run
-__global__ __launch_bounds__(kLtThreads) void lt_plan_kernel(const int64_t* __restrict__ offsets, int64_t m, int64_t nnz,
-                                                             LtPlan w) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (kLtThreads / 64) + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * (kLtThreads / 64);
-  for (int64_t base = wave * 64; base < m; base += nwaves * 64) {
-    const int64_t row = base + lane;
-    int nch = 0;
-    if (row < m) {
-      const int64_t j0 = offsets[row], j1 = offsets[row + 1];
-      if (j0 >= 0 && j1 <= nnz && j1 - j0 > kLtChunk) nch = (int)((j1 - j0 + kLtChunk - 1) / kLtChunk);
-    }
-    unsigned long long todo = __ballot(nch > 0);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int s_row = (int)__shfl((int)row, src), s_n = __shfl(nch, src);
-      int first = 0, slot = 0;
-      if (lane == 0) {
-        first = atomicAdd(w.counters, s_n);
-        slot = atomicAdd(w.counters + 1, 1);
-        if (slot < w.long_cap) {
-          w.long_row[slot] = s_row;
-          w.long_base[slot] = first;
-        }
-      }
-      first = __shfl(first, 0);
-      for (int k = lane; k < s_n; k += 64) {
-        if ((int64_t)first + k < w.item_cap) {
-          w.item_row[first + k] = s_row;
-          w.item_k[first + k] = k;
-        }
-      }
-    }
-  }
 }
 
 // ---- d. feature kernels -----------------------------------------------------------------------------------------------------
@@ -530,30 +396,18 @@ __device__ __forceinline__ float4 lt_row_sum(const float4* __restrict__ f, const
 // L lanes (a power of two <= 64) own one list: ITEMS = false, a whole row (longer ones are skipped when `split`); ITEMS = true,
 // one chunk of a long row into the partials.  Rows wider than L pieces take several trips.
 template <bool ITEMS>
-__global__ __launch_bounds__(kLtThreads) void lt_splat_kernel(const float4* __restrict__ f, const float* __restrict__ w,
+__global__ __launch_bounds__(kRowThreads) void lt_splat_kernel(const float4* __restrict__ f, const float* __restrict__ w,
                                                               const int64_t* __restrict__ offsets,
                                                               const int64_t* __restrict__ entries, int64_t m, int64_t nnz,
                                                               uint32_t K, int P4, int L, float alpha, int split,
-                                                              float4* __restrict__ out, LtPlan plan, float4* __restrict__ part) {
-  const int groups = kLtThreads / L;
+                                                              float4* __restrict__ out, RowList plan, float4* __restrict__ part) {
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
-  int64_t total = m;
-  if (ITEMS) {
-    total = plan.counters[0];
-    if (total > plan.item_cap) total = plan.item_cap;
-  }
+  const int64_t total = ITEMS ? row_list_items(plan) : m;
   for (int64_t t = (int64_t)blockIdx.x * groups + g; t < total; t += (int64_t)gridDim.x * groups) {
-    const int64_t row = ITEMS ? plan.item_row[t] : t;
-    if (row < 0 || row >= m) continue;
-    int64_t j0 = offsets[row], j1 = offsets[row + 1];
-    if (j0 < 0 || j1 > nnz || j1 < j0) j1 = j0 = 0;  // offsets that do not describe the list: an empty row
-    if (ITEMS) {
-      j0 += (int64_t)plan.item_k[t] * kLtChunk;
-      if (j0 > j1) j0 = j1;
-      if (j1 - j0 > kLtChunk) j1 = j0 + kLtChunk;
-    } else if (split && j1 - j0 > kLtChunk) {
-      continue;
-    }
+    int64_t row = t, j0, j1;
+    if (!(ITEMS ? row_list_item(plan, t, offsets, m, nnz, row, j0, j1) : row_span(offsets, m, nnz, row, j0, j1))) continue;
+    if (!ITEMS && split && j1 - j0 > kRowChunk) continue;
     for (int p = sub; p < P4; p += L) {
       const float4 acc = lt_row_sum(f, w, entries, j0, j1, nnz, K, P4, p);
       if (ITEMS) part[t * P4 + p] = acc;
@@ -563,19 +417,15 @@ __global__ __launch_bounds__(kLtThreads) void lt_splat_kernel(const float4* __re
 }
 
 // L lanes per long row: its partials in chunk order
-__global__ __launch_bounds__(kLtThreads) void lt_combine_kernel(const int64_t* __restrict__ offsets, int64_t m, int P4, int L,
-                                                                float alpha, float4* __restrict__ out, LtPlan plan,
+__global__ __launch_bounds__(kRowThreads) void lt_combine_kernel(const int64_t* __restrict__ offsets, int64_t m, int P4, int L,
+                                                                float alpha, float4* __restrict__ out, RowList plan,
                                                                 const float4* __restrict__ part) {
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
-  int64_t total = plan.counters[1];
-  if (total > plan.long_cap) total = plan.long_cap;
+  const int64_t total = row_list_long_rows(plan);
   for (int64_t t = (int64_t)blockIdx.x * groups + g; t < total; t += (int64_t)gridDim.x * groups) {
-    const int64_t row = plan.long_row[t], first = plan.long_base[t];
-    if (row < 0 || row >= m) continue;
-    const int64_t len = offsets[row + 1] - offsets[row];
-    const int64_t nch = (len + kLtChunk - 1) / kLtChunk;
-    if (first < 0 || nch < 1 || first + nch > plan.item_cap) continue;
+    int64_t row, len, first, nch;
+    if (!row_list_long_row(plan, t, offsets, m, row, len, first, nch)) continue;
     for (int p = sub; p < P4; p += L) {
       float4 acc = part[first * P4 + p];
       for (int64_t k = 1; k < nch; ++k) {
@@ -591,10 +441,10 @@ __device__ __forceinline__ float4 lt_row_or_zero(const float4* __restrict__ x, i
   return (r >= 0 && r < m) ? x[r * P4 + p] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__global__ __launch_bounds__(kLtThreads) void lt_blur_kernel(const float4* __restrict__ x, const int32_t* __restrict__ n1,
+__global__ __launch_bounds__(kRowThreads) void lt_blur_kernel(const float4* __restrict__ x, const int32_t* __restrict__ n1,
                                                              const int32_t* __restrict__ n2, float s0, float s1, float s2,
                                                              int64_t m, int P4, int L, float4* __restrict__ y) {
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
   for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
     const int64_t a = n1[v], b = n2 ? n2[v] : -1;
@@ -608,10 +458,10 @@ __global__ __launch_bounds__(kLtThreads) void lt_blur_kernel(const float4* __res
   }
 }
 
-__global__ __launch_bounds__(kLtThreads) void lt_slice_kernel(const float4* __restrict__ x, const int64_t* __restrict__ idx,
+__global__ __launch_bounds__(kRowThreads) void lt_slice_kernel(const float4* __restrict__ x, const int64_t* __restrict__ idx,
                                                               const float* __restrict__ w, int64_t n, int K, int64_t m, int P4,
                                                               int L, float alpha, float4* __restrict__ out) {
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
   for (int64_t i = (int64_t)blockIdx.x * groups + g; i < n; i += (int64_t)gridDim.x * groups) {
     for (int p = sub; p < P4; p += L) {
@@ -639,7 +489,7 @@ constexpr int kPcgIters = 5;      // updates of y carried out
 constexpr int kPcgNonFinite = 6;  // a residual norm was not finite
 constexpr int kPcgWords = 8;
 
-// the workgroup's sum of one double per thread, the same bits in every thread; `s_red`: kLtThreads / 64 doubles
+// the workgroup's sum of one double per thread, the same bits in every thread; `s_red`: kRowThreads / 64 doubles
 __device__ __forceinline__ double lt_block_sum(double v, double* s_red) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
@@ -648,13 +498,13 @@ __device__ __forceinline__ double lt_block_sum(double v, double* s_red) {
   __syncthreads();
   double t = 0.0;
 #pragma unroll
-  for (int w = 0; w < kLtThreads / 64; ++w) t += s_red[w];
+  for (int w = 0; w < kRowThreads / 64; ++w) t += s_red[w];
   return t;
 }
 
 __device__ __forceinline__ double lt_sum_partials(const double* __restrict__ part, int n, double* s_red) {
   double acc = 0.0;
-  for (int j = threadIdx.x; j < n; j += kLtThreads) acc += part[j];
+  for (int j = threadIdx.x; j < n; j += kRowThreads) acc += part[j];
   return lt_block_sum(acc, s_red);
 }
 
@@ -665,12 +515,12 @@ __device__ __forceinline__ double f4_dot(const float4& a, const float4& b) {
 __device__ __forceinline__ double clamp_min_keep_nan(double v, double lo) { return v < lo ? lo : v; }
 
 // the first pass of the matvec: a blur pass over scale[.] * x[.]
-__global__ __launch_bounds__(kLtThreads) void lt_blur_scaled_kernel(const float4* __restrict__ x, const float* __restrict__ scale,
+__global__ __launch_bounds__(kRowThreads) void lt_blur_scaled_kernel(const float4* __restrict__ x, const float* __restrict__ scale,
                                                                     const int32_t* __restrict__ n1, float s0, float s1, int64_t m,
                                                                     int P4, int L, const double* __restrict__ skip,
                                                                     float4* __restrict__ y) {
   if (skip && *skip != 0.0) return;
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
   for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
     const int64_t a = n1[v];
@@ -683,15 +533,15 @@ __global__ __launch_bounds__(kLtThreads) void lt_blur_scaled_kernel(const float4
 }
 
 // the last pass: t = s0 x[v] + s1 x[n1[v]], Ap[v] = dc[v] p[v] - lam n[v] t, partial[workgroup] = sum p . Ap
-__global__ __launch_bounds__(kLtThreads) void lt_matvec_last_kernel(const float4* __restrict__ x, const int32_t* __restrict__ n1,
+__global__ __launch_bounds__(kRowThreads) void lt_matvec_last_kernel(const float4* __restrict__ x, const int32_t* __restrict__ n1,
                                                                     float s0, float s1, const float4* __restrict__ pv,
                                                                     const float* __restrict__ nvec, const float* __restrict__ dc,
                                                                     float lam, int64_t m, int P4, int L,
                                                                     const double* __restrict__ skip, float4* __restrict__ Ap,
                                                                     double* __restrict__ partial) {
-  __shared__ double s_red[kLtThreads / 64];
+  __shared__ double s_red[kRowThreads / 64];
   if (skip && *skip != 0.0) return;
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
   double sum = 0.0;
   for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
@@ -713,21 +563,21 @@ __global__ __launch_bounds__(kLtThreads) void lt_matvec_last_kernel(const float4
 // INIT: r = tbar - Ap (Ap = A y0), z = minv r, p = z.  Otherwise alpha = rz_old / max(sum of the p . Ap partials, 1e-20),
 // y += alpha p, r -= alpha Ap, z = minv r.  Both leave the partials of sum r . r and sum r . z.
 template <bool INIT>
-__global__ __launch_bounds__(kLtThreads) void lt_pcg_update_kernel(const double* __restrict__ st, int it,
+__global__ __launch_bounds__(kRowThreads) void lt_pcg_update_kernel(const double* __restrict__ st, int it,
                                                                    const double* __restrict__ pap_part, int nparts,
                                                                    float4* __restrict__ p, const float4* __restrict__ Ap,
                                                                    const float* __restrict__ minv, const float4* __restrict__ tbar,
                                                                    float4* __restrict__ y, float4* __restrict__ r,
                                                                    float4* __restrict__ z, int64_t m, int P4, int L,
                                                                    double* __restrict__ rr_part, double* __restrict__ rz_part) {
-  __shared__ double s_red[kLtThreads / 64];
+  __shared__ double s_red[kRowThreads / 64];
   float alpha = 0.f;
   if (!INIT) {
     if (st[kPcgDone + (it & 1)] != 0.0) return;
     const double pap = lt_sum_partials(pap_part, nparts, s_red);
     alpha = (float)(st[kPcgRz + (it & 1)] / clamp_min_keep_nan(pap, 1e-20));
   }
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
   double rr = 0.0, rz = 0.0;
   for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups) {
@@ -760,9 +610,9 @@ __global__ __launch_bounds__(kLtThreads) void lt_pcg_update_kernel(const double*
 }
 
 // ONE workgroup: the state block from the partials of the first residual
-__global__ __launch_bounds__(kLtThreads) void lt_pcg_start_kernel(double* __restrict__ st, const double* __restrict__ rr_part,
+__global__ __launch_bounds__(kRowThreads) void lt_pcg_start_kernel(double* __restrict__ st, const double* __restrict__ rr_part,
                                                                   const double* __restrict__ rz_part, int nparts) {
-  __shared__ double s_red[kLtThreads / 64];
+  __shared__ double s_red[kRowThreads / 64];
   const double rr = lt_sum_partials(rr_part, nparts, s_red), rz = lt_sum_partials(rz_part, nparts, s_red);
   if (threadIdx.x == 0) {
     const double norm = sqrt(rr);
@@ -777,12 +627,12 @@ __global__ __launch_bounds__(kLtThreads) void lt_pcg_start_kernel(double* __rest
 }
 
 // the stop test |r| / |r0| < tol on the reduced norm, then beta = rz_new / max(rz_old, 1e-20), p = z + beta p
-__global__ __launch_bounds__(kLtThreads) void lt_pcg_direction_kernel(double* __restrict__ st, int it, double tol,
+__global__ __launch_bounds__(kRowThreads) void lt_pcg_direction_kernel(double* __restrict__ st, int it, double tol,
                                                                       const double* __restrict__ rr_part,
                                                                       const double* __restrict__ rz_part, int nparts,
                                                                       const float4* __restrict__ z, float4* __restrict__ p,
                                                                       int64_t m, int P4, int L) {
-  __shared__ double s_red[kLtThreads / 64];
+  __shared__ double s_red[kRowThreads / 64];
   const int cur = it & 1, nxt = cur ^ 1;
   if (st[kPcgDone + cur] != 0.0) {
     if (blockIdx.x == 0 && threadIdx.x == 0) st[kPcgDone + nxt] = 1.0;
@@ -799,7 +649,7 @@ __global__ __launch_bounds__(kLtThreads) void lt_pcg_direction_kernel(double* __
   }
   if (stop) return;
   const float beta = (float)(rz_new / clamp_min_keep_nan(st[kPcgRz + cur], 1e-20));
-  const int groups = kLtThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
   for (int64_t v = (int64_t)blockIdx.x * groups + g; v < m; v += (int64_t)gridDim.x * groups)
     for (int q = sub; q < P4; q += L) p[v * P4 + q] = f4_fma(beta, p[v * P4 + q], z[v * P4 + q]);
@@ -808,14 +658,14 @@ __global__ __launch_bounds__(kLtThreads) void lt_pcg_direction_kernel(double* __
 // ---- f. weights of the kNN bilateral filter (reference: nn/functional/bilateral.py) ---------------------------------------------
 // one thread per query: w[s] = exp(-|dxyz|^2 ix - |dfeat|^2 if) over its k neighbours, the row sum in slot order, then
 // w / max(sum, 1e-20).  A neighbour index outside [0, n) weighs nothing.
-__global__ __launch_bounds__(kLtThreads) void bilateral_knn_weights_kernel(const float* __restrict__ src_xyz,
+__global__ __launch_bounds__(kRowThreads) void bilateral_knn_weights_kernel(const float* __restrict__ src_xyz,
                                                                            const float* __restrict__ src_feat,
                                                                            const float* __restrict__ q_xyz,
                                                                            const float* __restrict__ q_feat,
                                                                            const int64_t* __restrict__ nbr, int64_t n, int64_t m,
                                                                            int K, int dx, int df, float inv_xyz, float inv_feat,
                                                                            float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * kLtThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kLtThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kRowThreads) {
     float sum = 0.f;
     for (int s = 0; s < K; ++s) {
       const int64_t r = nbr[i * K + s];
@@ -840,12 +690,6 @@ __global__ __launch_bounds__(kLtThreads) void bilateral_knn_weights_kernel(const
   }
 }
 
-static int lt_lanes(int64_t pieces) {
-  int L = 1;
-  while (L < pieces && L < 64) L <<= 1;
-  return L;
-}
-
 static bool lt_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
 }  // namespace wcn
@@ -854,7 +698,7 @@ using namespace wcn;
 
 extern "C" {
 
-int32_t wcn_lattice_chunk_rows(void) { return kLtChunk; }
+int32_t wcn_lattice_chunk_rows(void) { return kRowChunk; }
 
 int wcn_hash128_insert(int64_t* table_keys, int32_t* table_values, int64_t capacity, const int32_t* coords, int64_t n,
                        int32_t key_dim, int32_t* status, wcn_stream_t stream) {
@@ -864,7 +708,7 @@ int wcn_hash128_insert(int64_t* table_keys, int32_t* table_values, int64_t capac
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(table_values, 0xFF, (size_t)capacity * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
   if (n == 0) return WCN_SUCCESS;
-  hipLaunchKernelGGL(h128_insert_kernel, dim3(lt_grid(ceil_div(n, kLtThreads))), dim3(kLtThreads), 0, s,
+  hipLaunchKernelGGL(h128_insert_kernel, dim3(capped_grid(ceil_div(n, kRowThreads))), dim3(kRowThreads), 0, s,
                      (ulonglong2*)table_keys, table_values, (uint32_t)(capacity - 1), coords, n, (int)key_dim, status);
   return launch_status();
 }
@@ -876,7 +720,7 @@ int wcn_hash128_search(const int64_t* table_keys, const int32_t* table_values, i
     return WCN_ERROR_INVALID_PARAMETERS;
   if (m == 0) return WCN_SUCCESS;
   if (!queries || !out) return WCN_ERROR_INVALID_PARAMETERS;
-  hipLaunchKernelGGL(h128_search_kernel, dim3(lt_grid(ceil_div(m, kLtThreads))), dim3(kLtThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(h128_search_kernel, dim3(capped_grid(ceil_div(m, kRowThreads))), dim3(kRowThreads), 0, (hipStream_t)stream,
                      (const ulonglong2*)table_keys, table_values, (uint32_t)(capacity - 1), queries, offsets, m, (int)k,
                      (int)key_dim, out);
   return launch_status();
@@ -897,7 +741,7 @@ int wcn_permuto_simplex(const float* positions, int64_t n, int32_t d, const floa
   if (n == 0) return WCN_SUCCESS;
   LtScale sc{};
   for (int j = 0; j < d; ++j) sc.v[j] = scale[j];
-  hipLaunchKernelGGL(permuto_simplex_kernel, dim3(lt_grid(ceil_div(n, kLtThreads))), dim3(kLtThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(permuto_simplex_kernel, dim3(capped_grid(ceil_div(n, kRowThreads))), dim3(kRowThreads), 0, (hipStream_t)stream,
                      positions, n, (int)d, sc, key_hi, key_lo, keys, bary, status);
   return launch_status();
 }
@@ -907,14 +751,14 @@ int wcn_grid_corners(const float* positions, int64_t n, int32_t d, int64_t* floo
   const int st = geometry_args_ok(positions, n, d, d >= 1 && d < kLtAxes ? (int64_t)1 << d : 1, weights, status);
   if (st != WCN_SUCCESS) return st;
   if (n == 0) return WCN_SUCCESS;
-  hipLaunchKernelGGL(grid_corners_kernel, dim3(lt_grid(ceil_div(n, kLtThreads))), dim3(kLtThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(grid_corners_kernel, dim3(capped_grid(ceil_div(n, kRowThreads))), dim3(kRowThreads), 0, (hipStream_t)stream,
                      positions, n, (int)d, floors, key_hi, key_lo, keys, weights, status);
   return launch_status();
 }
 
 size_t wcn_lattice_map_workspace_bytes(int64_t nnz) {
   if (nnz < 0) return 0;
-  return align256((size_t)ceil_div(nnz > 0 ? nnz : 1, kLtTile) * 4);
+  return align256((size_t)ceil_div(nnz > 0 ? nnz : 1, kRunTile) * 4);
 }
 
 int wcn_lattice_map(const int64_t* sorted_hi, const int64_t* sorted_lo, const int64_t* perm, int64_t nnz, int32_t key_dim,
@@ -929,28 +773,34 @@ int wcn_lattice_map(const int64_t* sorted_hi, const int64_t* sorted_lo, const in
   if (hipMemsetAsync(summary, 0, 8, s) != hipSuccess || hipMemsetAsync(row_offsets, 0, 8, s) != hipSuccess)
     return WCN_ERROR_KERNEL_EXECUTION;
   if (nnz == 0) return WCN_SUCCESS;
-  const int64_t ntiles = ceil_div(nnz, kLtTile);
+  const int64_t ntiles = ceil_div(nnz, kRunTile);
   int32_t* tile_sum = (int32_t*)workspace;
-  const dim3 block(kLtThreads), tiles(lt_grid(ntiles));
-  hipLaunchKernelGGL(lt_tile_count_kernel, tiles, block, 0, s, sorted_hi, sorted_lo, nnz, ntiles, tile_sum);
-  hipLaunchKernelGGL(lt_tile_scan_kernel, dim3(1), block, 0, s, tile_sum, ntiles, nnz, summary, row_offsets);
-  hipLaunchKernelGGL(lt_apply_kernel, tiles, block, 0, s, sorted_hi, sorted_lo, perm, nnz, ntiles, tile_sum, (int)key_dim,
-                     unique_keys, inverse, row_offsets);
-  hipLaunchKernelGGL(lt_longest_kernel, dim3(lt_grid(ceil_div(nnz, kLtThreads))), block, 0, s, row_offsets, nnz, summary);
+  const dim3 block(kRowThreads), tiles(capped_grid(ntiles));
+  const LtKeys keys{sorted_hi, sorted_lo};
+  hipLaunchKernelGGL(run_count_kernel<LtKeys>, tiles, block, 0, s, keys, nnz, ntiles, tile_sum);
+  hipLaunchKernelGGL(run_scan_kernel<>, dim3(1), block, 0, s, tile_sum, ntiles, nnz, summary, row_offsets);
+  hipLaunchKernelGGL((run_apply_kernel<LtKeys, LtWriter>), tiles, block, 0, s, keys, perm, nnz, ntiles, (const int32_t*)tile_sum,
+                     row_offsets, LtWriter{(int)key_dim, unique_keys, inverse});
+  hipLaunchKernelGGL(longest_row_kernel<>, dim3(capped_grid(ceil_div(nnz, kRowThreads))), block, 0, s, row_offsets, nnz,
+                     summary);
   return launch_status();
 }
 
 int64_t wcn_lattice_plan_items(int64_t nnz) { return nnz < 0 ? 0 : lt_carve(nullptr, nnz).item_cap; }
-int64_t wcn_lattice_plan_ints(int64_t nnz) { return nnz < 0 ? 0 : lt_carve(nullptr, nnz).ints; }
+int64_t wcn_lattice_plan_ints(int64_t nnz) {
+  int64_t ints = 0;
+  if (nnz >= 0) lt_carve(nullptr, nnz, &ints);
+  return ints;
+}
 
 int wcn_lattice_plan(const int64_t* row_offsets, int64_t v, int64_t nnz, int32_t* plan, wcn_stream_t stream) {
   if (v < 0 || v > INT32_MAX || nnz < 0 || nnz > INT32_MAX || !plan || (v > 0 && !row_offsets))
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(plan, 0, kLtCounterInts * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
+  if (hipMemsetAsync(plan, 0, kRowListCounterInts * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
   if (v == 0) return WCN_SUCCESS;
-  hipLaunchKernelGGL(lt_plan_kernel, dim3(lt_grid(ceil_div(v, kLtThreads))), dim3(kLtThreads), 0, s, row_offsets, v, nnz,
-                     lt_carve(plan, nnz));
+  hipLaunchKernelGGL(row_list_collect_kernel<>, dim3(capped_grid(ceil_div(v, kRowThreads))), dim3(kRowThreads), 0, s,
+                     row_offsets, v, nnz, lt_carve(plan, nnz));
   return launch_status();
 }
 
@@ -967,16 +817,16 @@ int wcn_lattice_splat(const float* f, const float* w, const int64_t* row_offsets
   if (v == 0) return WCN_SUCCESS;
   if (!out || !row_offsets || (nnz > 0 && (!f || !w || !row_entries))) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  const int P4 = pitch / 4, L = lt_lanes(P4), groups = kLtThreads / L;
-  const LtPlan p = plan ? lt_carve(const_cast<int32_t*>(plan), nnz) : LtPlan{};
-  hipLaunchKernelGGL(lt_splat_kernel<false>, dim3(lt_grid(ceil_div(v, groups))), dim3(kLtThreads), 0, s, (const float4*)f, w,
+  const int P4 = pitch / 4, L = row_lanes(P4), groups = kRowThreads / L;
+  const RowList p = plan ? lt_carve(const_cast<int32_t*>(plan), nnz) : RowList{};
+  hipLaunchKernelGGL(lt_splat_kernel<false>, dim3(capped_grid(ceil_div(v, groups))), dim3(kRowThreads), 0, s, (const float4*)f, w,
                      row_offsets, row_entries, v, nnz, (uint32_t)k, P4, L, alpha, plan ? 1 : 0, (float4*)out, p,
                      (float4*)partials);
   if (!plan) return launch_status();
-  hipLaunchKernelGGL(lt_splat_kernel<true>, dim3(lt_grid(ceil_div(p.item_cap, groups))), dim3(kLtThreads), 0, s,
+  hipLaunchKernelGGL(lt_splat_kernel<true>, dim3(capped_grid(ceil_div(p.item_cap, groups))), dim3(kRowThreads), 0, s,
                      (const float4*)f, w, row_offsets, row_entries, v, nnz, (uint32_t)k, P4, L, alpha, 1, (float4*)out, p,
                      (float4*)partials);
-  hipLaunchKernelGGL(lt_combine_kernel, dim3(lt_grid(ceil_div(p.long_cap, groups))), dim3(kLtThreads), 0, s, row_offsets, v, P4,
+  hipLaunchKernelGGL(lt_combine_kernel, dim3(capped_grid(ceil_div(p.long_cap, groups))), dim3(kRowThreads), 0, s, row_offsets, v, P4,
                      L, alpha, (float4*)out, p, (const float4*)partials);
   return launch_status();
 }
@@ -986,8 +836,8 @@ int wcn_lattice_blur(const float* x, const int32_t* n1, const int32_t* n2, float
   if (!feature_args_ok(v, pitch, x, y) || x == y) return WCN_ERROR_INVALID_PARAMETERS;
   if (v == 0) return WCN_SUCCESS;
   if (!x || !y || !n1) return WCN_ERROR_INVALID_PARAMETERS;
-  const int P4 = pitch / 4, L = lt_lanes(P4);
-  hipLaunchKernelGGL(lt_blur_kernel, dim3(lt_grid(ceil_div(v, kLtThreads / L))), dim3(kLtThreads), 0, (hipStream_t)stream,
+  const int P4 = pitch / 4, L = row_lanes(P4);
+  hipLaunchKernelGGL(lt_blur_kernel, dim3(capped_grid(ceil_div(v, kRowThreads / L))), dim3(kRowThreads), 0, (hipStream_t)stream,
                      (const float4*)x, n1, n2, s0, s1, s2, v, P4, L, (float4*)y);
   return launch_status();
 }
@@ -998,8 +848,8 @@ int wcn_lattice_slice(const float* x, const int64_t* idx, const float* w, int64_
     return WCN_ERROR_INVALID_PARAMETERS;
   if (n == 0) return WCN_SUCCESS;
   if (!out || !idx || !w || (v > 0 && !x)) return WCN_ERROR_INVALID_PARAMETERS;
-  const int P4 = pitch / 4, L = lt_lanes(P4);
-  hipLaunchKernelGGL(lt_slice_kernel, dim3(lt_grid(ceil_div(n, kLtThreads / L))), dim3(kLtThreads), 0, (hipStream_t)stream,
+  const int P4 = pitch / 4, L = row_lanes(P4);
+  hipLaunchKernelGGL(lt_slice_kernel, dim3(capped_grid(ceil_div(n, kRowThreads / L))), dim3(kRowThreads), 0, (hipStream_t)stream,
                      (const float4*)x, idx, w, n, (int)k, v, P4, L, alpha, (float4*)out);
   return launch_status();
 }
@@ -1016,8 +866,8 @@ struct PcgPasses {  // the grid's default blur: per axis y = b x + (c b) x[fwd],
 // A p into `Ap`, the partials of sum p . A p into `partial`; `spare`: two [v, pitch] buffers.  Returns the number of partials.
 static int pcg_matvec(const int32_t* nb, int d, int64_t v, int P4, const PcgPasses& ps, const float* nvec, const float* dc,
                       float lam, const float* p, float* spare, const double* skip, float* Ap, double* partial, hipStream_t s) {
-  const int L = lt_lanes(P4);
-  const dim3 grid(lt_grid(ceil_div(v, kLtThreads / L))), block(kLtThreads);
+  const int L = row_lanes(P4);
+  const dim3 grid(capped_grid(ceil_div(v, kRowThreads / L))), block(kRowThreads);
   float4* buf[2] = {(float4*)spare, (float4*)spare + v * P4};
   hipLaunchKernelGGL(lt_blur_scaled_kernel, grid, block, 0, s, (const float4*)p, nvec, nb, ps.s0[0], ps.s1[0], v, P4, L, skip,
                      buf[0]);
@@ -1034,11 +884,11 @@ static PcgPasses pcg_passes(float tap_a, float tap_b, float tap_c) {
   return PcgPasses{{tap_b, 1.f}, {(float)((double)tap_c * (double)tap_b), tap_a}};
 }
 
-int32_t wcn_lattice_max_grid(void) { return kLtMaxGrid; }
+int32_t wcn_lattice_max_grid(void) { return kRowMaxGrid; }
 
 int32_t wcn_lattice_row_grid(int64_t rows, int32_t pitch) {
   if (rows < 0 || pitch < 4 || pitch % 4 != 0) return 0;
-  return (int32_t)lt_grid(ceil_div(rows, kLtThreads / lt_lanes(pitch / 4)));
+  return (int32_t)capped_grid(ceil_div(rows, kRowThreads / row_lanes(pitch / 4)));
 }
 
 int wcn_bilateral_matvec(const int32_t* neighbours, int32_t d, int64_t v, int32_t pitch, float tap_a, float tap_b, float tap_c,
@@ -1061,12 +911,12 @@ int wcn_bilateral_pcg(const int32_t* neighbours, int32_t d, int64_t v, int32_t p
       tbar == y)
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  const int P4 = pitch / 4, L = lt_lanes(P4);
+  const int P4 = pitch / 4, L = row_lanes(P4);
   const int64_t rows = v * pitch;  // floats of one buffer
   float *r = work, *p = work + rows, *z = work + 2 * rows, *ap = work + 3 * rows, *spare = work + 4 * rows;
-  double *pap_part = partials, *rr_part = partials + kLtMaxGrid, *rz_part = partials + 2 * kLtMaxGrid;
+  double *pap_part = partials, *rr_part = partials + kRowMaxGrid, *rz_part = partials + 2 * kRowMaxGrid;
   const PcgPasses ps = pcg_passes(tap_a, tap_b, tap_c);
-  const dim3 block(kLtThreads);
+  const dim3 block(kRowThreads);
   // the first residual: A y0 through the same matvec, then r, z, p and the state block
   const int parts = pcg_matvec(neighbours, d, v, P4, ps, nvec, dc, lam, y, spare, nullptr, ap, pap_part, s);
   const dim3 grid(parts);
@@ -1095,7 +945,7 @@ int wcn_bilateral_knn_weights(const float* src_xyz, const float* src_feat, const
   if (!query_xyz || !query_feat || !nbr || !weights || (n > 0 && (!src_xyz || !src_feat))) return WCN_ERROR_INVALID_PARAMETERS;
   const float inv_xyz = (float)(1.0 / (2.0 * (double)sigma_xyz * (double)sigma_xyz));
   const float inv_feat = (float)(1.0 / (2.0 * (double)sigma_feat * (double)sigma_feat));
-  hipLaunchKernelGGL(bilateral_knn_weights_kernel, dim3(lt_grid(ceil_div(m, kLtThreads))), dim3(kLtThreads), 0,
+  hipLaunchKernelGGL(bilateral_knn_weights_kernel, dim3(capped_grid(ceil_div(m, kRowThreads))), dim3(kRowThreads), 0,
                      (hipStream_t)stream, src_xyz, src_feat, query_xyz, query_feat, nbr, n, m, (int)k, (int)dx, (int)df,
                      inv_xyz, inv_feat, weights);
   return launch_status();

@@ -6,56 +6,42 @@
 //                             the biased 18-bit fields of wcn_common.h, so that int64 order = lexicographic order of the
 //                             signed (b, x, y, z) rows.  The stable sort of the keys is the caller's (framework radix sort).
 //   b. wcn_voxel_map          sorted keys + permutation -> unique keys / coordinates, CSR offsets, voxel of every point,
-//                             first point of every voxel, voxel offsets per batch element, (M, longest segment).  Run heads
-//                             are counted per 2048-key tile, ONE workgroup scans the tile sums, the tiles are applied:
-//                             no kernel waits on another workgroup.
+//                             first point of every voxel, voxel offsets per batch element, (M, longest segment): the
+//                             runs -> map kernels of row_lists.h on int64 keys.
 //   c. wcn_csr_gather_reduce  out[m] = op over j in [offsets[m], offsets[m + 1]) of in[indices[j]]: pool forward, unpool
 //                             backward.  Lanes run along channels (16-B / 8-B / element pieces), a group of lanes owns one
 //                             segment and adds its rows in ascending j; narrow rows put 64 / group segments in one wave.
-//                             Segments longer than kCgChunk rows are cut into chunks of kCgChunk rows, each summed the same
-//                             way by its own group into an fp32 partial, and the partials are added in chunk order: the
-//                             bits of a row depend on the segment alone, never on the launch shape or the path taken.
+//                             Segments longer than kRowChunk rows go by the chunk rule of row_lists.h: the bits of a row
+//                             depend on the segment alone, never on the launch shape or the path taken.
 //   d. wcn_row_spread         out[i, :c] = scale(i) * src[to_orig[i]], out[i, c:c + cs] = skip[i]: unpool forward (with the
 //                             concatenation in the same pass), pool backward (1 / count, or the arg-match of max / min).
 // No float atomics anywhere; the integer atomics (status word, longest segment, the list of long segments) give the same
-// result in any order.  Every grid is capped at kVxMaxGrid workgroups and strides.
+// result in any order.  Every grid is capped at kRowMaxGrid workgroups and strides.
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
 #include <cfloat>
-#include <limits.h>
 
-#include "wcn_common.h"
+#include "row_lists.h"
 
 namespace wcn {
 
-constexpr int kVxThreads = 256;
-constexpr int kVxPer = 8;
-constexpr int kVxTile = kVxThreads * kVxPer;  // sorted keys of one scan tile
-constexpr int kVxMaxGrid = 4096;
-constexpr int kCgChunk = 256;                 // rows of one chunk of a long segment (the chunk rule)
-constexpr int kCgCounterInts = 64;            // [0] chunk items, [1] long segments; padded to 256 B
 constexpr int64_t kCoordBias = -(int64_t)kCoordMin;
 
 enum { kVxFlagRange = 1, kVxFlagOffsets = 2 };
 enum { kOpSum = 0, kOpMean = 1, kOpMax = 2, kOpMin = 3 };
 enum { kSpreadPlain = 0, kSpreadInvCount = 1, kSpreadArgMatch = 2 };
 
-static unsigned vx_grid(int64_t items) {
-  const int64_t g = items < 1 ? 1 : items;
-  return (unsigned)(g < kVxMaxGrid ? g : kVxMaxGrid);
-}
-
 // ---- a. keys ----------------------------------------------------------------------------------------------------------------
 // cell = floor(p * inv_voxel_size), the reciprocal formed by the CALLER: the framework evaluates `points / voxel_size` for a
 // host scalar on the device as a product with fp32(1.0 / voxel_size), the quotient taken in double (measured, DESIGN.md
 // "Quantisation finding"), and a point on a cell face lands in another cell under a true division or a reciprocal rounded
 // differently.  A cell outside the 18-bit range (NaN included) or a row that belongs to no batch element raises the status.
-__global__ __launch_bounds__(kVxThreads) void vx_keys_kernel(const float* __restrict__ points, int64_t n,
+__global__ __launch_bounds__(kRowThreads) void vx_keys_kernel(const float* __restrict__ points, int64_t n,
                                                              const int32_t* __restrict__ batch_offsets, int num_batches,
                                                              float inv, int64_t* __restrict__ keys,
                                                              int32_t* __restrict__ status) {
-  for (int64_t i = (int64_t)blockIdx.x * kVxThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kVxThreads) {
+  for (int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowThreads) {
     int b = 0, hi = num_batches;
     while (b < hi) {
       const int mid = (b + hi) >> 1;
@@ -80,117 +66,55 @@ __global__ __launch_bounds__(kVxThreads) void vx_keys_kernel(const float* __rest
 }
 
 // ---- b. runs -> map ---------------------------------------------------------------------------------------------------------
-// thread t of a tile owns the sorted positions tile * kVxTile + t * kVxPer .. + kVxPer - 1; head = first position of a run
-__device__ __forceinline__ int vx_load_heads(const int64_t* __restrict__ keys, int64_t n, int64_t i0, int64_t (&k)[kVxPer],
-                                             bool (&head)[kVxPer]) {
-  if (i0 + kVxPer <= n) {
-    const longlong2* p = reinterpret_cast<const longlong2*>(keys + i0);  // i0 is a multiple of 8, keys 16-B aligned
+struct VxKeys {  // key policy of row_lists.h: one int64 per position
+  using Key = int64_t;
+  const int64_t* keys;
+  __device__ __forceinline__ void load(int64_t n, int64_t i0, Key (&k)[kRunPer]) const {
+    if (i0 + kRunPer <= n) {
+      const longlong2* p = reinterpret_cast<const longlong2*>(keys + i0);  // i0 is a multiple of 8, keys 16-B aligned
 #pragma unroll
-    for (int j = 0; j < kVxPer; j += 2) {
-      const longlong2 q = p[j >> 1];
-      k[j] = q.x;
-      k[j + 1] = q.y;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kVxPer; ++j) k[j] = i0 + j < n ? keys[i0 + j] : 0;
-  }
-  int64_t prev = (i0 > 0 && i0 < n) ? keys[i0 - 1] : 0;
-  int cnt = 0;
-#pragma unroll
-  for (int j = 0; j < kVxPer; ++j) {
-    head[j] = i0 + j < n && (i0 + j == 0 || k[j] != prev);
-    prev = k[j];
-    cnt += head[j] ? 1 : 0;
-  }
-  return cnt;
-}
-
-__global__ __launch_bounds__(kVxThreads) void vx_tile_count_kernel(const int64_t* __restrict__ keys, int64_t n, int64_t ntiles,
-                                                                   int32_t* __restrict__ tile_sum) {
-  __shared__ int s_wave[kVxThreads / 64];
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int64_t k[kVxPer];
-    bool head[kVxPer];
-    const int cnt = vx_load_heads(keys, n, tile * kVxTile + (int64_t)threadIdx.x * kVxPer, k, head);
-    int tot;
-    block_excl_scan<kVxThreads>(cnt, s_wave, &tot);
-    if (threadIdx.x == 0) tile_sum[tile] = tot;
-    __syncthreads();  // s_wave is rewritten by the next trip
-  }
-}
-
-// ONE workgroup: exclusive scan of the tile sums in place; summary[0] = M and the closing boundary offsets[M] = n
-__global__ __launch_bounds__(kVxThreads) void vx_tile_scan_kernel(int32_t* __restrict__ tile_sum, int64_t ntiles, int64_t n,
-                                                                  int32_t* __restrict__ summary,
-                                                                  int64_t* __restrict__ csr_offsets) {
-  __shared__ int s_wave[kVxThreads / 64];
-  int carry = 0;
-  for (int64_t base = 0; base < ntiles; base += kVxThreads) {
-    const int64_t i = base + threadIdx.x;
-    const int v = i < ntiles ? tile_sum[i] : 0;
-    int tot;
-    const int e = block_excl_scan<kVxThreads>(v, s_wave, &tot);
-    if (i < ntiles) tile_sum[i] = carry + e;
-    carry += tot;
-    __syncthreads();  // s_wave is rewritten by the next trip
-  }
-  if (threadIdx.x == 0) {
-    summary[0] = carry;
-    csr_offsets[carry] = n;  // carry <= n: the caller's buffer holds n + 1 words
-  }
-}
-
-__global__ __launch_bounds__(kVxThreads) void vx_apply_kernel(const int64_t* __restrict__ keys, const int64_t* __restrict__ perm,
-                                                              int64_t n, int64_t ntiles, const int32_t* __restrict__ tile_sum,
-                                                              int64_t* __restrict__ unique_keys,
-                                                              int32_t* __restrict__ unique_coords,
-                                                              int64_t* __restrict__ csr_offsets,
-                                                              int64_t* __restrict__ to_orig, int64_t* __restrict__ to_unique) {
-  __shared__ int s_wave[kVxThreads / 64];
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t i0 = tile * kVxTile + (int64_t)threadIdx.x * kVxPer;
-    int64_t k[kVxPer];
-    bool head[kVxPer];
-    const int cnt = vx_load_heads(keys, n, i0, k, head);
-    int tot;
-    int64_t vid = (int64_t)tile_sum[tile] + block_excl_scan<kVxThreads>(cnt, s_wave, &tot) - 1;  // voxel of position i0 - 1
-#pragma unroll
-    for (int j = 0; j < kVxPer; ++j) {
-      const int64_t i = i0 + j;
-      if (i >= n) break;
-      const int64_t row = perm[i];
-      if (head[j]) {
-        ++vid;
-        if (vid >= 0 && vid < n) {
-          csr_offsets[vid] = i;
-          unique_keys[vid] = k[j];
-          to_unique[vid] = row;  // stable sort: the first position of a run holds the run's smallest row
-          if (unique_coords) {
-            unique_coords[3 * vid] = (int32_t)(((k[j] >> 36) & kCoordMask) - kCoordBias);
-            unique_coords[3 * vid + 1] = (int32_t)(((k[j] >> 18) & kCoordMask) - kCoordBias);
-            unique_coords[3 * vid + 2] = (int32_t)((k[j] & kCoordMask) - kCoordBias);
-          }
-        }
+      for (int j = 0; j < kRunPer; j += 2) {
+        const longlong2 q = p[j >> 1];
+        k[j] = q.x;
+        k[j + 1] = q.y;
       }
-      if (row >= 0 && row < n) to_orig[row] = vid;
+    } else {
+#pragma unroll
+      for (int j = 0; j < kRunPer; ++j) k[j] = i0 + j < n ? keys[i0 + j] : 0;
     }
-    __syncthreads();  // s_wave is rewritten by the next trip
   }
-}
+  __device__ __forceinline__ Key at(int64_t i) const { return keys[i]; }
+  static __device__ __forceinline__ bool differ(Key a, Key b) { return a != b; }
+};
+
+struct VxWriter {  // what a voxel and a point get
+  int64_t* unique_keys;
+  int32_t* unique_coords;  // optional
+  int64_t* to_orig;
+  int64_t* to_unique;
+  __device__ __forceinline__ void head(int64_t vid, int64_t row, int64_t key) const {
+    unique_keys[vid] = key;
+    to_unique[vid] = row;  // stable sort: the first position of a run holds the run's smallest row
+    if (unique_coords) {
+      unique_coords[3 * vid] = (int32_t)(((key >> 36) & kCoordMask) - kCoordBias);
+      unique_coords[3 * vid + 1] = (int32_t)(((key >> 18) & kCoordMask) - kCoordBias);
+      unique_coords[3 * vid + 2] = (int32_t)((key & kCoordMask) - kCoordBias);
+    }
+  }
+  __device__ __forceinline__ void each(int64_t row, int64_t vid) const { to_orig[row] = vid; }
+};
 
 // per voxel: the longest segment (integer atomic max) and, where the batch field of the key steps, the voxel offsets of the
 // batch elements in between (every word written once: voxels are key-sorted, so the batch field ascends)
-__global__ __launch_bounds__(kVxThreads) void vx_finish_kernel(const int64_t* __restrict__ unique_keys,
+__global__ __launch_bounds__(kRowThreads) void vx_finish_kernel(const int64_t* __restrict__ unique_keys,
                                                                const int64_t* __restrict__ csr_offsets, int64_t n,
                                                                int32_t* __restrict__ summary,
                                                                int32_t* __restrict__ batch_voxel_offsets, int num_batches) {
   int64_t M = summary[0];
   if (M > n) M = n;
   int longest = 0;
-  for (int64_t v = (int64_t)blockIdx.x * kVxThreads + threadIdx.x; v < M; v += (int64_t)gridDim.x * kVxThreads) {
-    const int64_t len = csr_offsets[v + 1] - csr_offsets[v];
-    longest = max(longest, (int)(len < INT_MAX ? len : INT_MAX));
+  for (int64_t v = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; v < M; v += (int64_t)gridDim.x * kRowThreads) {
+    longest = max(longest, row_length(csr_offsets, v));
     if (batch_voxel_offsets) {
       int b = (int)(unique_keys[v] >> 54);
       b = b < 0 ? 0 : (b > num_batches - 1 ? num_batches - 1 : b);
@@ -200,9 +124,7 @@ __global__ __launch_bounds__(kVxThreads) void vx_finish_kernel(const int64_t* __
         for (int q = b + 1; q <= num_batches; ++q) batch_voxel_offsets[q] = (int32_t)M;
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d));
-  if ((threadIdx.x & 63) == 0 && longest > 0) atomicMax(summary + 1, longest);
+  longest_row_max(longest, summary + 1);
 }
 
 // ---- element types ----------------------------------------------------------------------------------------------------------
@@ -246,31 +168,25 @@ __device__ __forceinline__ void st_pack(typename El<D>::S* p, const float (&f)[V
 }
 
 // ---- c. CSR gather-reduce ---------------------------------------------------------------------------------------------------
-struct CgLong {  // the long segments and their chunks, listed per call
-  int32_t* counters;   // [0] chunk items, [1] long segments
-  int32_t* item_seg;   // [item_cap]
-  int32_t* item_k;     // [item_cap] chunk number inside the segment
-  int32_t* long_seg;   // [long_cap]
-  int32_t* long_base;  // [long_cap] first item of the segment
-  float* part;         // [item_cap][c]
-  int64_t* part_arg;   // [item_cap][c] (max / min)
-  int64_t item_cap, long_cap;
+struct CgLong : RowList {  // the long segments and their chunks, listed per call, and the chunks' partials
+  float* part;        // [item_cap][c]
+  int64_t* part_arg;  // [item_cap][c] (max / min)
   size_t bytes;
 };
 
+// the list and the partials in the byte workspace, every array 256-B aligned
 static CgLong cg_carve(void* base, int64_t nnz, int64_t c, bool with_arg) {
   CgLong w;
-  w.long_cap = nnz / kCgChunk + 1;  // a long segment holds more than kCgChunk rows
-  w.item_cap = 2 * w.long_cap;      // ceil(len / chunk) <= len / chunk + 1 per long segment
+  row_list_caps(nnz, w);
   char* p = (char*)base;
   size_t at = 0;
   w.counters = (int32_t*)(p + at);
-  at = align256(at + kCgCounterInts * 4);
-  w.item_seg = (int32_t*)(p + at);
+  at = align256(at + kRowListCounterInts * 4);
+  w.item_row = (int32_t*)(p + at);
   at = align256(at + (size_t)w.item_cap * 4);
   w.item_k = (int32_t*)(p + at);
   at = align256(at + (size_t)w.item_cap * 4);
-  w.long_seg = (int32_t*)(p + at);
+  w.long_row = (int32_t*)(p + at);
   at = align256(at + (size_t)w.long_cap * 4);
   w.long_base = (int32_t*)(p + at);
   at = align256(at + (size_t)w.long_cap * 4);
@@ -333,32 +249,20 @@ __device__ __forceinline__ void cg_rows(const typename El<D>::S* __restrict__ in
 // L lanes (a power of two <= 64) own one list: ITEMS = false, a whole segment (longer ones are skipped when `split`);
 // ITEMS = true, one chunk of a long segment into the fp32 partials.  Rows wider than L * V channels take several trips.
 template <int D, int V, bool ITEMS>
-__global__ __launch_bounds__(kVxThreads) void cg_reduce_kernel(const typename El<D>::S* __restrict__ in, int64_t ld_in,
+__global__ __launch_bounds__(kRowThreads) void cg_reduce_kernel(const typename El<D>::S* __restrict__ in, int64_t ld_in,
                                                                int64_t n_in, const int64_t* __restrict__ indices,
                                                                const int64_t* __restrict__ offsets, int64_t m, int64_t nnz,
                                                                int c, int L, int op, int split,
                                                                typename El<D>::S* __restrict__ out, int64_t* __restrict__ arg,
                                                                CgLong w) {
-  const int groups = kVxThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
-  int64_t total = m;
-  if (ITEMS) {
-    total = w.counters[0];
-    if (total > w.item_cap) total = w.item_cap;
-  }
+  const int64_t total = ITEMS ? row_list_items(w) : m;
   for (int64_t t = (int64_t)blockIdx.x * groups + g; t < total; t += (int64_t)gridDim.x * groups) {
-    const int64_t seg = ITEMS ? w.item_seg[t] : t;
-    if (seg < 0 || seg >= m) continue;
-    int64_t j0 = offsets[seg], j1 = offsets[seg + 1];
-    if (j0 < 0 || j1 > nnz || j1 < j0) j1 = j0 = 0;  // offsets that do not describe the list: an empty segment
-    const int64_t len = j1 - j0;
-    if (ITEMS) {
-      j0 += (int64_t)w.item_k[t] * kCgChunk;
-      if (j0 > j1) j0 = j1;
-      if (j1 - j0 > kCgChunk) j1 = j0 + kCgChunk;
-    } else if (split && len > kCgChunk) {
-      continue;
-    }
+    int64_t seg = t, j0, j1;
+    if (!(ITEMS ? row_list_item(w, t, offsets, m, nnz, seg, j0, j1) : row_span(offsets, m, nnz, seg, j0, j1))) continue;
+    const int64_t len = j1 - j0;  // of the whole segment where it is used
+    if (!ITEMS && split && len > kRowChunk) continue;
     for (int col = sub * V; col < c; col += L * V) {
       float acc[V];
       int64_t best[V];
@@ -386,59 +290,17 @@ __global__ __launch_bounds__(kVxThreads) void cg_reduce_kernel(const typename El
   }
 }
 
-// one wave looks at 64 segments; every long one takes its run of items with one integer atomic and the wave writes the run
-__global__ __launch_bounds__(kVxThreads) void cg_collect_kernel(const int64_t* __restrict__ offsets, int64_t m, int64_t nnz,
-                                                                CgLong w) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (kVxThreads / 64) + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * (kVxThreads / 64);
-  for (int64_t base = wave * 64; base < m; base += nwaves * 64) {
-    const int64_t seg = base + lane;
-    int nch = 0;
-    if (seg < m) {
-      const int64_t j0 = offsets[seg], j1 = offsets[seg + 1];
-      if (j0 >= 0 && j1 <= nnz && j1 - j0 > kCgChunk) nch = (int)((j1 - j0 + kCgChunk - 1) / kCgChunk);
-    }
-    unsigned long long todo = __ballot(nch > 0);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int s_seg = (int)__shfl((int)seg, src), s_n = __shfl(nch, src);
-      int first = 0, slot = 0;
-      if (lane == 0) {
-        first = atomicAdd(w.counters, s_n);
-        slot = atomicAdd(w.counters + 1, 1);
-        if (slot < w.long_cap) {
-          w.long_seg[slot] = s_seg;
-          w.long_base[slot] = first;
-        }
-      }
-      first = __shfl(first, 0);
-      for (int k = lane; k < s_n; k += 64) {
-        if ((int64_t)first + k < w.item_cap) {
-          w.item_seg[first + k] = s_seg;
-          w.item_k[first + k] = k;
-        }
-      }
-    }
-  }
-}
-
 // L lanes per long segment: its partials in chunk order
 template <int D>
-__global__ __launch_bounds__(kVxThreads) void cg_combine_kernel(const int64_t* __restrict__ offsets, int64_t m, int c, int L,
+__global__ __launch_bounds__(kRowThreads) void cg_combine_kernel(const int64_t* __restrict__ offsets, int64_t m, int c, int L,
                                                                 int op, typename El<D>::S* __restrict__ out,
                                                                 int64_t* __restrict__ arg, CgLong w) {
-  const int groups = kVxThreads / L;
+  const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
-  int64_t total = w.counters[1];
-  if (total > w.long_cap) total = w.long_cap;
+  const int64_t total = row_list_long_rows(w);
   for (int64_t t = (int64_t)blockIdx.x * groups + g; t < total; t += (int64_t)gridDim.x * groups) {
-    const int64_t seg = w.long_seg[t], first = w.long_base[t];
-    if (seg < 0 || seg >= m) continue;
-    const int64_t len = offsets[seg + 1] - offsets[seg];
-    const int64_t nch = (len + kCgChunk - 1) / kCgChunk;
-    if (first < 0 || first + nch > w.item_cap) continue;
+    int64_t seg, len, first, nch;
+    if (!row_list_long_row(w, t, offsets, m, seg, len, first, nch)) continue;
     for (int col = sub; col < c; col += L) {
       float acc = w.part[first * c + col];
       int64_t best = op >= kOpMax ? w.part_arg[first * c + col] : -1;
@@ -459,26 +321,20 @@ __global__ __launch_bounds__(kVxThreads) void cg_combine_kernel(const int64_t* _
   }
 }
 
-static int pow2_lanes(int64_t pieces) {
-  int L = 1;
-  while (L < pieces && L < 64) L <<= 1;
-  return L;
-}
-
-
 template <int D, int V>
 static void cg_launch(const void* in, int64_t ld_in, int64_t n_in, const int64_t* indices, const int64_t* offsets, int64_t m,
                       int64_t nnz, int c, int op, bool split, void* out, int64_t* arg, const CgLong& w, hipStream_t s) {
   using S = typename El<D>::S;
-  const int L = pow2_lanes(ceil_div(c, V)), groups = kVxThreads / L;
-  hipLaunchKernelGGL((cg_reduce_kernel<D, V, false>), dim3(vx_grid(ceil_div(m, groups))), dim3(kVxThreads), 0, s, (const S*)in,
-                     ld_in, n_in, indices, offsets, m, nnz, c, L, op, split ? 1 : 0, (S*)out, arg, w);
+  const int L = row_lanes(ceil_div(c, V)), groups = kRowThreads / L;
+  hipLaunchKernelGGL((cg_reduce_kernel<D, V, false>), dim3(capped_grid(ceil_div(m, groups))), dim3(kRowThreads), 0, s,
+                     (const S*)in, ld_in, n_in, indices, offsets, m, nnz, c, L, op, split ? 1 : 0, (S*)out, arg, w);
   if (!split) return;
-  hipLaunchKernelGGL(cg_collect_kernel, dim3(vx_grid(ceil_div(m, kVxThreads))), dim3(kVxThreads), 0, s, offsets, m, nnz, w);
-  hipLaunchKernelGGL((cg_reduce_kernel<D, V, true>), dim3(vx_grid(ceil_div(w.item_cap, groups))), dim3(kVxThreads), 0, s,
+  hipLaunchKernelGGL(row_list_collect_kernel<>, dim3(capped_grid(ceil_div(m, kRowThreads))), dim3(kRowThreads), 0, s, offsets, m,
+                     nnz, (const RowList&)w);
+  hipLaunchKernelGGL((cg_reduce_kernel<D, V, true>), dim3(capped_grid(ceil_div(w.item_cap, groups))), dim3(kRowThreads), 0, s,
                      (const S*)in, ld_in, n_in, indices, offsets, m, nnz, c, L, op, 1, (S*)out, arg, w);
-  const int Lc = pow2_lanes(c);
-  hipLaunchKernelGGL(cg_combine_kernel<D>, dim3(vx_grid(ceil_div(w.long_cap, kVxThreads / Lc))), dim3(kVxThreads), 0, s,
+  const int Lc = row_lanes(c);
+  hipLaunchKernelGGL(cg_combine_kernel<D>, dim3(capped_grid(ceil_div(w.long_cap, kRowThreads / Lc))), dim3(kRowThreads), 0, s,
                      offsets, m, c, Lc, op, (S*)out, arg, w);
 }
 
@@ -498,7 +354,7 @@ static int piece_elems(int dtype, int64_t c, int64_t c2, int64_t ld_a, int64_t l
 // ---- d. indexed row spread --------------------------------------------------------------------------------------------------
 // one thread per V-element piece of an output row: the first c / V pieces come from src[to_orig[i]], the next cs / V from skip[i]
 template <int D, int V>
-__global__ __launch_bounds__(kVxThreads) void row_spread_kernel(const typename El<D>::S* __restrict__ src,
+__global__ __launch_bounds__(kRowThreads) void row_spread_kernel(const typename El<D>::S* __restrict__ src,
                                                                 const int64_t* __restrict__ to_orig, int64_t n, int64_t m,
                                                                 int c, const typename El<D>::S* __restrict__ skip, int cs,
                                                                 int64_t ld_out, int mode, const int64_t* __restrict__ offsets,
@@ -506,7 +362,7 @@ __global__ __launch_bounds__(kVxThreads) void row_spread_kernel(const typename E
                                                                 typename El<D>::S* __restrict__ out) {
   const int pc = c / V, pw = pc + cs / V;
   const int64_t total = n * pw;
-  for (int64_t e = (int64_t)blockIdx.x * kVxThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kVxThreads) {
+  for (int64_t e = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kRowThreads) {
     const int64_t i = e / pw;
     const int p = (int)(e - i * pw);
     float f[V];
@@ -542,7 +398,7 @@ static void spread_launch(const void* src, const int64_t* to_orig, int64_t n, in
                           int64_t ld_out, int mode, const int64_t* offsets, const int64_t* arg, void* out, hipStream_t s) {
   using S = typename El<D>::S;
   const int64_t pieces = n * (int64_t)((c + cs) / V);
-  hipLaunchKernelGGL((row_spread_kernel<D, V>), dim3(vx_grid(ceil_div(pieces, kVxThreads))), dim3(kVxThreads), 0, s,
+  hipLaunchKernelGGL((row_spread_kernel<D, V>), dim3(capped_grid(ceil_div(pieces, kRowThreads))), dim3(kRowThreads), 0, s,
                      (const S*)src, to_orig, n, m, c, (const S*)skip, cs, ld_out, mode, offsets, arg, (S*)out);
 }
 
@@ -569,7 +425,7 @@ using namespace wcn;
 
 extern "C" {
 
-int32_t wcn_csr_chunk_rows(void) { return kCgChunk; }
+int32_t wcn_csr_chunk_rows(void) { return kRowChunk; }
 
 int wcn_voxel_keys(const float* points, int64_t n, const int32_t* batch_offsets, int32_t num_batches, float inv_voxel_size,
                    int64_t* keys, int32_t* status, wcn_stream_t stream) {
@@ -580,14 +436,14 @@ int wcn_voxel_keys(const float* points, int64_t n, const int32_t* batch_offsets,
   if (hipMemsetAsync(status, 0, 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
   if (n == 0 || !points) return WCN_SUCCESS;  // null points: the keys are the caller's own codes
   if (!batch_offsets || !keys) return WCN_ERROR_INVALID_PARAMETERS;
-  hipLaunchKernelGGL(vx_keys_kernel, dim3(vx_grid(ceil_div(n, kVxThreads))), dim3(kVxThreads), 0, s, points, n, batch_offsets,
+  hipLaunchKernelGGL(vx_keys_kernel, dim3(capped_grid(ceil_div(n, kRowThreads))), dim3(kRowThreads), 0, s, points, n, batch_offsets,
                      (int)num_batches, inv_voxel_size, keys, status);
   return launch_status();
 }
 
 size_t wcn_voxel_map_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return align256((size_t)ceil_div(n > 0 ? n : 1, kVxTile) * 4);
+  return align256((size_t)ceil_div(n > 0 ? n : 1, kRunTile) * 4);
 }
 
 int wcn_voxel_map(const int64_t* sorted_keys, const int64_t* perm, int64_t n, int32_t num_batches, int64_t* unique_keys,
@@ -607,14 +463,15 @@ int wcn_voxel_map(const int64_t* sorted_keys, const int64_t* perm, int64_t n, in
   if (batch_voxel_offsets && hipMemsetAsync(batch_voxel_offsets, 0, ((size_t)num_batches + 1) * 4, s) != hipSuccess)
     return WCN_ERROR_KERNEL_EXECUTION;
   if (n == 0) return WCN_SUCCESS;
-  const int64_t ntiles = ceil_div(n, kVxTile);
+  const int64_t ntiles = ceil_div(n, kRunTile);
   int32_t* tile_sum = (int32_t*)workspace;
-  const dim3 block(kVxThreads), tiles(vx_grid(ntiles));
-  hipLaunchKernelGGL(vx_tile_count_kernel, tiles, block, 0, s, sorted_keys, n, ntiles, tile_sum);
-  hipLaunchKernelGGL(vx_tile_scan_kernel, dim3(1), block, 0, s, tile_sum, ntiles, n, summary, csr_offsets);
-  hipLaunchKernelGGL(vx_apply_kernel, tiles, block, 0, s, sorted_keys, perm, n, ntiles, tile_sum, unique_keys, unique_coords,
-                     csr_offsets, to_orig, to_unique);
-  hipLaunchKernelGGL(vx_finish_kernel, dim3(vx_grid(ceil_div(n, kVxThreads))), block, 0, s, unique_keys, csr_offsets, n,
+  const dim3 block(kRowThreads), tiles(capped_grid(ntiles));
+  const VxKeys keys{sorted_keys};
+  hipLaunchKernelGGL(run_count_kernel<VxKeys>, tiles, block, 0, s, keys, n, ntiles, tile_sum);
+  hipLaunchKernelGGL(run_scan_kernel<>, dim3(1), block, 0, s, tile_sum, ntiles, n, summary, csr_offsets);
+  hipLaunchKernelGGL((run_apply_kernel<VxKeys, VxWriter>), tiles, block, 0, s, keys, perm, n, ntiles, (const int32_t*)tile_sum,
+                     csr_offsets, VxWriter{unique_keys, unique_coords, to_orig, to_unique});
+  hipLaunchKernelGGL(vx_finish_kernel, dim3(capped_grid(ceil_div(n, kRowThreads))), block, 0, s, unique_keys, csr_offsets, n,
                      summary, batch_voxel_offsets, (int)num_batches);
   return launch_status();
 }
@@ -638,14 +495,14 @@ int wcn_csr_gather_reduce(const void* in, int64_t ld_in, int64_t n_in, const int
   if (st != WCN_SUCCESS) return st;
   if (m == 0 || c == 0) return WCN_SUCCESS;
   if (!offsets || !out || (!in && nnz > 0) || (arg && op < kOpMax)) return WCN_ERROR_INVALID_PARAMETERS;
-  const bool split = max_segment < 0 || max_segment > kCgChunk;  // < 0: the caller does not know the longest segment
+  const bool split = max_segment < 0 || max_segment > kRowChunk;  // < 0: the caller does not know the longest segment
   CgLong w{};
   hipStream_t s = (hipStream_t)stream;
   if (split) {
     if (!workspace || !aligned_to(workspace, 16)) return WCN_ERROR_INVALID_PARAMETERS;
     w = cg_carve(workspace, nnz, c, op >= kOpMax);
     if (workspace_bytes < w.bytes) return WCN_ERROR_INVALID_PARAMETERS;
-    if (hipMemsetAsync(w.counters, 0, kCgCounterInts * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
+    if (hipMemsetAsync(w.counters, 0, kRowListCounterInts * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
   }
   const int v = piece_elems(dtype, c, 0, ld_in, 0, in, out, nullptr);
   WCN_VX_DISPATCH(cg_launch, dtype, v, in, ld_in, n_in, indices, offsets, m, nnz, (int)c, (int)op, split, out, arg, w, s);

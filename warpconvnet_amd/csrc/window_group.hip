@@ -14,17 +14,17 @@
 // 2-4 are the block-sums / scan-of-sums / apply pattern: no kernel waits on another workgroup.  The slot a voxel takes in
 // step 5 depends on the order the atomics retire, but the SET of rows of a segment does not; sorting the segment ascending
 // makes perm the stable sort by code, the same bits in every run.  Segments longer than kWgSegMax are left unwritten: the
-// caller sees max_count in the summary and takes another path.
+// caller sees max_count in the summary and takes another path.  Every grid is capped at kRowMaxGrid workgroups (row_lists.h)
+// and strides.
 #include <limits.h>
 
-#include "wcn_common.h"
+#include "row_lists.h"
 
 namespace wcn {
 
 constexpr int kWgThreads = 256;
 constexpr int kWgPer = 8;
 constexpr int kWgTile = kWgThreads * kWgPer;  // bins of one scan tile
-constexpr int kWgMaxGrid = 4096;              // every grid is capped here and strides
 constexpr int kWgSegMax = 8192;               // rows of the longest segment sorted in LDS (32 KiB of the 160 KiB)
 constexpr int kWgRankMax = 1024;              // up to here a segment is ranked by counting, above by a bitonic network
 constexpr int kWgFlagInts = 64;               // the error word and its padding, behind the histogram (one memset)
@@ -308,11 +308,6 @@ __global__ __launch_bounds__(kWgThreads) void wg_sort_block_kernel(const int32_t
   }
 }
 
-static unsigned wg_grid(int64_t items) {
-  const int64_t g = items < 1 ? 1 : items;
-  return (unsigned)(g < kWgMaxGrid ? g : kWgMaxGrid);
-}
-
 }  // namespace wcn
 
 using namespace wcn;
@@ -357,7 +352,7 @@ int wcn_window_group(const int32_t* coords, int64_t n, const int32_t* batch_offs
   const I3 win{window[0], window[1], window[2]}, sh{shift[0], shift[1], shift[2]};
   const I3 lo{min_coord[0], min_coord[1], min_coord[2]}, gs{grid_shape[0], grid_shape[1], grid_shape[2]};
   const dim3 block(kWgThreads);
-  const dim3 rows(wg_grid(ceil_div(n, kWgThreads))), tiles(wg_grid(c.ntiles));
+  const dim3 rows(capped_grid(ceil_div(n, kWgThreads))), tiles(capped_grid(c.ntiles));
   hipLaunchKernelGGL(wg_code_kernel, rows, block, 0, s, coords, n, batch_offsets, (int)num_batches, win, sh, lo, gs, W, codes,
                      c.hist, c.flag);
   hipLaunchKernelGGL(wg_tile_reduce_kernel, tiles, block, 0, s, c.hist, c.ntiles, c.tile_sum, c.tile_nz, c.tile_max);
@@ -366,9 +361,9 @@ int wcn_window_group(const int32_t* coords, int64_t n, const int32_t* batch_offs
   hipLaunchKernelGGL(wg_apply_kernel, tiles, block, 0, s, c.hist, c.ntiles, c.tile_sum, c.tile_nz, cu_seqlens, counts,
                      seg_capacity);
   hipLaunchKernelGGL(wg_scatter_kernel, rows, block, 0, s, codes, n, c.hist, c.slots, c.flag);
-  hipLaunchKernelGGL(wg_sort_wave_kernel, dim3(wg_grid(ceil_div(seg_capacity, kWgThreads / 64))), block, 0, s, c.slots,
+  hipLaunchKernelGGL(wg_sort_wave_kernel, dim3(capped_grid(ceil_div(seg_capacity, kWgThreads / 64))), block, 0, s, c.slots,
                      cu_seqlens, summary, n, perm, inverse_perm);
-  hipLaunchKernelGGL(wg_sort_block_kernel, dim3(wg_grid(seg_capacity)), block, 0, s, c.slots, cu_seqlens, summary, n, perm,
+  hipLaunchKernelGGL(wg_sort_block_kernel, dim3(capped_grid(seg_capacity)), block, 0, s, c.slots, cu_seqlens, summary, n, perm,
                      inverse_perm);
   return launch_status();
 }
