@@ -1064,6 +1064,48 @@ int wcn_grid_sample_backward(const void* dy, int64_t dy_pitch, int64_t col0, con
                              int64_t max_cell_points, void* d_grid, void* workspace, size_t workspace_bytes,
                              wcn_stream_t stream);
 
+/* ---- segmented statistics and arithmetic on a ragged batch (ABI 16, additions only) ------------------------------------------
+ * Reference: nn/functional/segmented_arithmetics.py, nn/functional/normalizations.py (segmented_norm / _layer_norm /
+ * _range_norm) and global_scale of nn/functional/global_pool.py.  Rows are contiguous [rows, channels] in `dtype`, any
+ * channels >= 1; `cu` int32 [num_segs + 1] on the device, segment b = rows [cu[b], cu[b + 1]), empty segments allowed, never
+ * read on the host (spans are clamped to [0, rows]).  16-B pieces per lane where channels and every pointer allow, single
+ * elements otherwise.  fp32 arithmetic, one rounding to `dtype`; no float atomics.  A segment is cut into chunks of
+ * wcn_seg_chunk_rows() rows counted from its own first row, one workgroup per chunk, the chunks merged in chunk order by a
+ * second launch: a segment's statistics depend bit for bit on that segment alone, and two calls agree bit for bit.
+ *   wcn_seg_chunk_rows   rows of one chunk of a segment = rows of one tile of wcn_seg_apply (256).
+ *   wcn_seg_max_grid     the cap of every grid of these kernels (4096); they stride beyond it.
+ *   wcn_seg_stats_workspace_bytes  host-only: 256-B aligned int32 [num_segs + 1] plus (ceil(rows / chunk) + num_segs) chunk
+ *                    slots of 2 (MOMENTS, DOT) or 4 (RANGE) fp32 [channels] planes.
+ *   wcn_seg_stats    one read pass; writes the fp32 [num_segs, channels] planes out0 / out1.
+ *                    WCN_SEG_MOMENTS (x): mean and the biased variance, centred (Welford / Chan merges), never E[x^2] - mean^2.
+ *                    WCN_SEG_RANGE (x): min and max; arg0 / arg1 int64 [num_segs, channels] (each may be NULL) = the row of
+ *                    the FIRST extremum.  An empty segment gives 0 and -1.  A NaN never compares and is passed over.
+ *                    WCN_SEG_DOT (g, x, center): sum g and sum g (x - center[b]); `center` fp32 [num_segs, channels], NULL = 0;
+ *                    with x NULL only out0 is written and out1 may be NULL.
+ *                    Three launches (the chunk plan, the chunks, the merge).
+ *   wcn_seg_apply    one streaming pass, out [rows, channels] in `dtype`:
+ *                    WCN_SEG_ADD / SUB / MUL / DIV   out = x op y[b]; y [num_segs, channels] in `y_dtype` = `dtype` or
+ *                    WCN_F32; DIV is a true division.
+ *                    WCN_SEG_NORM       out = ((x - a[b]) r[b]) gamma + beta; a, r fp32 [num_segs, channels] (a NULL = 0),
+ *                    gamma, beta fp32 [channels], each may be NULL.
+ *                    WCN_SEG_NORM_BWD   out = r[b] (g gamma - s0[b] / n_b - xhat s1[b] / n_b), xhat = (x - a[b]) r[b], n_b the
+ *                    segment's length, s0 / s1 the DOT planes of g gamma (center = a, then scaled by r).
+ * WCN_ERROR_INVALID_PARAMETERS: an op / mode outside the lists, negative sizes, channels < 1, rows above INT32_MAX, a missing
+ * required pointer, a misaligned pointer, a short or misaligned (16 B) workspace, a y_dtype that is neither `dtype` nor
+ * WCN_F32.  WCN_ERROR_UNSUPPORTED_CONFIG: an unknown dtype.  Checked before any launch.  rows == 0 or num_segs == 0: success
+ * without a launch; the statistics planes are zero-filled (arg planes -1). */
+enum wcn_seg_mode { WCN_SEG_MOMENTS = 0, WCN_SEG_RANGE = 1, WCN_SEG_DOT = 2 };
+enum wcn_seg_op { WCN_SEG_ADD = 0, WCN_SEG_SUB = 1, WCN_SEG_MUL = 2, WCN_SEG_DIV = 3, WCN_SEG_NORM = 4, WCN_SEG_NORM_BWD = 5 };
+int32_t wcn_seg_chunk_rows(void);
+int32_t wcn_seg_max_grid(void);
+size_t wcn_seg_stats_workspace_bytes(int64_t rows, int64_t num_segs, int32_t channels, int32_t mode);
+int wcn_seg_stats(int32_t mode, const void* x, const void* g, const float* center, const int32_t* cu, int64_t num_segs,
+                  int64_t rows, int32_t channels, int32_t dtype, float* out0, float* out1, int64_t* arg0, int64_t* arg1,
+                  void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_seg_apply(int32_t op, const void* x, const void* g, const void* y, int32_t y_dtype, const float* a, const float* r,
+                  const float* gamma, const float* beta, const float* s0, const float* s1, const int32_t* cu, int64_t num_segs,
+                  int64_t rows, int32_t channels, int32_t dtype, void* out, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ from torch import Tensor
 from torch.autograd import Function
 
 from warpconvnet_amd import _lib
+from warpconvnet_amd.nn.functional.segmented_arithmetics import Segments, check_rows, resolve_backend, seg_apply, seg_stats
 
 
 def hip_batch_norm_supported(x: Tensor) -> bool:
@@ -183,3 +184,115 @@ def batch_norm_module_forward(norm: torch.nn.modules.batchnorm._BatchNorm, x: Te
     (``num_batches_tracked``, cumulative average when ``momentum is None``) followed by :func:`hip_batch_norm`."""
     use_batch_stats, momentum, eps, rm, rv, counter, _ = bn_module_state(norm, x)
     return hip_batch_norm(x, rm, rv, norm.weight, norm.bias, use_batch_stats, momentum, eps, relu, counter)
+
+
+# ---- per-segment normalisation of a ragged batch ---------------------------------------------------------------------------
+# Reference `nn/functional/normalizations.py:24-290`.  Statistics are taken over the ROWS of a segment, per channel.  Built on
+# the two primitives of `segmented_arithmetics.py` (`csrc/segmented.hip` on the GPU, the torch composition elsewhere).  Unlike
+# the reference: the variance is centred (its E[x^2] - mean^2 cancels, goes negative and gives NaN on rows far from zero),
+# results are bitwise repeatable and a segment's do not depend on the rest of the batch, an empty segment is legal, and
+# ``detach_stats=False`` gives the true gradient.
+class _SegmentedNorm(Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], S, eps: float, detach_stats: bool,
+                backend: str) -> Tensor:
+        x = x.contiguous()
+        mean, var, _, _ = seg_stats("moments", S, backend, x=x)
+        rstd = torch.rsqrt(var + eps)
+        gamma_d = None if gamma is None else gamma.detach()
+        ctx.save_for_backward(x, mean, rstd, gamma_d)
+        ctx.S, ctx.detach_stats, ctx.backend = S, detach_stats, backend
+        ctx.param_dtypes = (None if gamma is None else gamma.dtype, None if beta is None else beta.dtype)
+        return seg_apply("norm", x, S, backend, a=mean, r=rstd, gamma=gamma_d, beta=None if beta is None else beta.detach())
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        x, mean, rstd, gamma = ctx.saved_tensors
+        S, backend = ctx.S, ctx.backend
+        grad = grad.to(x.dtype).contiguous()
+        need_x, need_gamma, need_beta = ctx.needs_input_grad[:3]
+        sum_g = sum_gx = None
+        if need_gamma or need_beta or (need_x and not ctx.detach_stats):
+            sum_g, sum_gx, _, _ = seg_stats("dot", S, backend, g=grad, x=x, center=mean)  # sum g, sum g (x - mean)
+        dx = dgamma = dbeta = None
+        if need_x:
+            if ctx.detach_stats:  # mean and std are constants (the reference): dx = g gamma / std
+                dx = seg_apply("norm", grad, S, backend, r=rstd, gamma=gamma)
+            else:
+                gm = 1.0 if gamma is None else gamma.to(sum_g.dtype)
+                dx = seg_apply("norm_bwd", x, S, backend, g=grad, a=mean, r=rstd, gamma=gamma, s0=sum_g * gm,
+                               s1=sum_gx * rstd * gm)
+        if need_gamma:
+            dgamma = (sum_gx * rstd).sum(0).to(ctx.param_dtypes[0])
+        if need_beta:
+            dbeta = sum_g.sum(0).to(ctx.param_dtypes[1])
+        return dx, dgamma, dbeta, None, None, None, None
+
+
+class _SegmentedRangeNorm(Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, S, eps: float, backend: str) -> Tensor:
+        x = x.contiguous()
+        mn, mx, arg_min, arg_max = seg_stats("range", S, backend, x=x)
+        diff = mx - mn + eps
+        ctx.save_for_backward(x, mn, diff, arg_min, arg_max)
+        ctx.S, ctx.backend = S, backend
+        return seg_apply("norm", x, S, backend, a=mn, r=1.0 / diff)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        x, mn, diff, arg_min, arg_max = ctx.saved_tensors
+        S, backend = ctx.S, ctx.backend
+        n, c = x.shape
+        if n == 0:
+            return torch.empty_like(x), None, None, None
+        grad = grad.to(x.dtype).contiguous()
+        sum_g, sum_gx, _, _ = seg_stats("dot", S, backend, g=grad, x=x, center=mn)  # sum g, sum g (x - min)
+        grad_max = -sum_gx / (diff * diff)
+        grad_min = -grad_max - sum_g / diff
+        # one row more than x has: the target of the segments without rows (arg = -1), cut off at the end
+        full = torch.empty(n + 1, c, dtype=x.dtype, device=x.device)
+        full[n].zero_()
+        seg_apply("divide", grad, S, backend, y=diff, out=full[:n])
+        # The extremum rows take grad_min / grad_max on top of g / diff: formed in the planes' precision and rounded once, then
+        # put in place by two index_put_ calls whose targets are unique (but for the cut-off row).  Where a segment's arg-min
+        # and arg-max are one row (a one-row segment) both calls write the same bits: repeatable whichever lands last.
+        cols = torch.arange(c, device=x.device).expand(S.num, c)
+        same = arg_min == arg_max
+        at_min = grad[arg_min.clamp(min=0), cols].to(diff.dtype) / diff + grad_min
+        at_min = torch.where(same, at_min + grad_max, at_min)
+        at_max = torch.where(same, at_min, grad[arg_max.clamp(min=0), cols].to(diff.dtype) / diff + grad_max)
+        full.index_put_((torch.where(arg_min < 0, n, arg_min), cols), at_min.to(x.dtype))
+        full.index_put_((torch.where(arg_max < 0, n, arg_max), cols), at_max.to(x.dtype))
+        return full[:n], None, None, None
+
+
+def _segmented_norm(x: Tensor, offsets, gamma: Optional[Tensor], beta: Optional[Tensor], eps: float, detach_stats: bool,
+                    backend: Optional[str]) -> Tensor:
+    check_rows(x)
+    for name, p in (("gamma", gamma), ("beta", beta)):
+        if p is not None and (tuple(p.shape) != (x.shape[1],) or p.device != x.device):
+            raise ValueError(f"{name} must be [C] = ({x.shape[1]},) on {x.device}, got {tuple(p.shape)} on {p.device}")
+    S = offsets if isinstance(offsets, Segments) else Segments(offsets, x.shape[0], x.device)
+    return _SegmentedNorm.apply(x, gamma, beta, S, float(eps), bool(detach_stats), resolve_backend(backend, x, "layer_norm"))
+
+
+def segmented_norm(x: Tensor, offsets: Tensor, eps: float = 1e-5, detach_stats: bool = True,
+                   backend: Optional[str] = None) -> Tensor:
+    """``(x - mean_b) / sqrt(var_b + eps)`` with the mean and the biased variance of every channel over the rows of segment
+    ``b``.  ``detach_stats=True`` (the reference) treats both as constants in the backward, ``False`` differentiates them."""
+    return _segmented_norm(x, offsets, None, None, eps, detach_stats, backend)
+
+
+def segmented_layer_norm(x: Tensor, offsets: Tensor, gamma: Optional[Tensor] = None, beta: Optional[Tensor] = None,
+                         eps: float = 1e-5, detach_stats: bool = True, backend: Optional[str] = None) -> Tensor:
+    """:func:`segmented_norm` times ``gamma`` [C] plus ``beta`` [C] (each optional), applied in the same pass."""
+    return _segmented_norm(x, offsets, gamma, beta, eps, detach_stats, backend)
+
+
+def segmented_range_norm(features: Tensor, row_offsets: Tensor, eps: float = 1e-6, backend: Optional[str] = None) -> Tensor:
+    """``(x - min_b) / (max_b - min_b + eps)`` per channel over the rows of segment ``b``: every segment into [0, 1].  The
+    gradient is the full one, through the minimum and the maximum (to the first row that holds each)."""
+    check_rows(features, "features")
+    S = row_offsets if isinstance(row_offsets, Segments) else Segments(row_offsets, features.shape[0], features.device)
+    return _SegmentedRangeNorm.apply(features, S, float(eps), resolve_backend(backend, features, "range_norm"))

@@ -6,7 +6,7 @@ from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGri
                           FactorGridProjection, FactorGridToPoint, FactorGridTransform, PointToFactorGrid)
 from .grid_conv import GridConv
 from .mlp import Linear, MLPBlock
-from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase
+from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase, SegmentedLayerNorm
 from .bilateral import BilateralFilter, BilateralFilterGrid, BilateralFilterGridCached, FastBilateralSolver
 from .permutohedral import (BilateralPermutohedralFilter, BilateralPermutohedralFilterCached, PermutohedralFilter,
                             PermutohedralFilterCached)
@@ -42,4 +42,4 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",
            "FastBilateralSolver",
            "FactorGridCat", "FactorGridIntraCommunication", "FactorGridPadToMatch", "FactorGridPool", "FactorGridToPoint",
-           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "GridConv"]
+           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "GridConv", "SegmentedLayerNorm"]

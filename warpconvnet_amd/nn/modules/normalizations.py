@@ -6,7 +6,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from warpconvnet_amd.geometry.base.geometry import Geometry
-from warpconvnet_amd.nn.functional.normalizations import batch_norm_module_forward, hip_batch_norm_supported
+from warpconvnet_amd.nn.functional.normalizations import (batch_norm_module_forward, hip_batch_norm_supported,
+                                                          segmented_layer_norm)
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 
 
@@ -53,6 +54,27 @@ class MultiHeadRMSNorm(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         return (nn.functional.normalize(x.float(), dim=-1) * self.gamma * self.scale).to(x.dtype)
+
+
+class SegmentedLayerNorm(nn.LayerNorm):
+    """Layer normalisation over the rows of every batch element of a geometry, per channel, with ``nn.LayerNorm``'s
+    ``weight`` / ``bias`` [channels] (reference `nn/modules/normalizations.py:102-141`).  ``detach_stats=True`` is the
+    reference's backward (mean and std are constants), ``False`` the true gradient."""
+
+    def __init__(self, channels: int, eps: float = 1e-5, elementwise_affine: bool = True, bias: bool = True,
+                 detach_stats: bool = True):
+        super().__init__([channels], eps=eps, elementwise_affine=elementwise_affine, bias=bias)
+        self.detach_stats = detach_stats
+
+    def forward(self, x: Geometry):
+        assert isinstance(x, Geometry), f"SegmentedLayerNorm only works for Geometry, got {type(x)}"
+        out = segmented_layer_norm(x.feature_tensor, x.offsets, gamma=self.weight, beta=self.bias, eps=self.eps,
+                                   detach_stats=self.detach_stats)
+        return x.replace(batched_features=out)
+
+    def __repr__(self):
+        shape = None if self.weight is None else self.weight.shape
+        return f"{self.__class__.__name__}({shape}, eps={self.eps}, elementwise_affine={self.elementwise_affine})"
 
 
 class LayerNorm32(nn.LayerNorm):
