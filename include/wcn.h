@@ -1106,6 +1106,37 @@ int wcn_seg_apply(int32_t op, const void* x, const void* g, const void* y, int32
                   const float* gamma, const float* beta, const float* s0, const float* s1, const int32_t* cu, int64_t num_segs,
                   int64_t rows, int32_t channels, int32_t dtype, void* out, wcn_stream_t stream);
 
+/* ---- farthest point sampling on a ragged batch (ABI 17, additions only) -------------------------------------------------------
+ * Reference: ops/sampling.py, csrc/farthest_point_sampling.cu.  `points` fp32 [n, 3] contiguous; `cu` int32 [total_segs + 1]
+ * on the device, segment b = rows [cu[b], cu[b + 1]); `idx` int32 [total_segs, k] receives global rows.  A call serves the
+ * num_segs segments named by `seg_ids` (int32 [num_segs] on the device; NULL = the segments 0 .. num_segs - 1) and writes
+ * their rows of `idx` only; `max_len` is the caller's bound on their lengths, the only thing the host knows about them: it
+ * picks the tier and the resident instantiation.  `start` int32 [total_segs] on the device holds the local row of sample 0
+ * (NULL = 0).  Sample j > 0 is the row with the largest running distance min_s d(i, s) over the earlier samples, of equal
+ * ones the lowest row; d = (dx dx + dy dy) + dz dz in fp32, every operation rounded once.  Once every row is taken the first
+ * row repeats; an empty segment gets -1 in its k entries.  Both tiers give the same indices.
+ *   WCN_FPS_RESIDENT  max_len <= wcn_fps_resident_max_points(): one workgroup of wcn_fps_block_threads() threads per segment,
+ *                     points and distances in registers, all k samples in ONE launch; the grid is capped at
+ *                     wcn_fps_max_grid() and strides over the segments.  No workspace.
+ *   WCN_FPS_STREAMED  any length: wcn_fps_blocks_per_segment() workgroups per segment, k - 1 step launches and a last one,
+ *                     enqueued back to back; running distances and per-workgroup partials live in the workspace
+ *                     (wcn_fps_workspace_bytes, host-only; 16-B aligned).  A segment longer than blocks x threads strides.
+ *   WCN_FPS_AUTO      resident where max_len allows, streamed otherwise.
+ * cu, seg_ids and start are device data and are not trusted: a segment id outside [0, total_segs) is skipped, spans are
+ * clamped to [0, n] (in the resident tier also to the instantiation's capacity), start to its segment.
+ * WCN_ERROR_INVALID_PARAMETERS, before any launch: negative sizes, k < 1, n above INT32_MAX, an unknown tier, seg_ids NULL
+ * with num_segs > total_segs, a missing or misaligned pointer, WCN_FPS_RESIDENT with max_len above the cap, a missing or short
+ * workspace in the streamed tier.  num_segs == 0: success without a launch. */
+enum wcn_fps_tier { WCN_FPS_AUTO = 0, WCN_FPS_RESIDENT = 1, WCN_FPS_STREAMED = 2 };
+int64_t wcn_fps_resident_max_points(void);
+int32_t wcn_fps_block_threads(void);
+int32_t wcn_fps_blocks_per_segment(void);
+int32_t wcn_fps_max_grid(void);
+size_t wcn_fps_workspace_bytes(int64_t n, int64_t num_segs, int32_t k);
+int wcn_fps(const float* points, const int32_t* cu, int64_t total_segs, const int32_t* seg_ids, int64_t num_segs, int64_t n,
+            int32_t k, int64_t max_len, const int32_t* start, int32_t tier, void* workspace, size_t workspace_bytes,
+            int32_t* idx, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ WCN_MASK_U8 = 3  # mask_dtype of wcn_resample_expand: a bool / uint8 mask
 WCN_GRID_KEY_CELL, WCN_GRID_KEY_CORNER = 0, 1  # mode of wcn_grid_point_keys (csrc/grid.hip)
 WCN_SEG_MOMENTS, WCN_SEG_RANGE, WCN_SEG_DOT = 0, 1, 2  # mode of wcn_seg_stats (csrc/segmented.hip)
 WCN_SEG_ADD, WCN_SEG_SUB, WCN_SEG_MUL, WCN_SEG_DIV, WCN_SEG_NORM, WCN_SEG_NORM_BWD = 0, 1, 2, 3, 4, 5  # op of wcn_seg_apply
+WCN_FPS_AUTO, WCN_FPS_RESIDENT, WCN_FPS_STREAMED = 0, 1, 2  # tier of wcn_fps (csrc/fps.hip)
 
 _I32P = c_void_p  # all pointers travel as void*
 _3I = c_int32 * 3
@@ -366,6 +367,13 @@ SIGNATURES = {
                       [c_size_t, c_void_p]),
     "wcn_seg_apply": (c_int, [c_int32] + [c_void_p] * 3 + [c_int32] + [c_void_p] * 7 + [c_int64, c_int64, c_int32, c_int32,
                                                                                        c_void_p, c_void_p]),
+    "wcn_fps_resident_max_points": (c_int64, []),
+    "wcn_fps_block_threads": (c_int32, []),
+    "wcn_fps_blocks_per_segment": (c_int32, []),
+    "wcn_fps_max_grid": (c_int32, []),
+    "wcn_fps_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "wcn_fps": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int32, c_void_p,
+                        c_size_t, c_void_p, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

@@ -17,7 +17,7 @@ from warpconvnet_amd.geometry.coords.integer import IntCoords
 from warpconvnet_amd.geometry.coords.ops.batch_index import offsets_from_offsets
 from warpconvnet_amd.geometry.coords.ops.voxel import voxel_downsample_csr_mapping, voxel_downsample_random_indices
 from warpconvnet_amd.geometry.coords.real import RealCoords
-from warpconvnet_amd.geometry.coords.sample import random_sample_per_batch
+from warpconvnet_amd.geometry.coords.sample import farthest_sample_per_batch, random_sample_per_batch
 from warpconvnet_amd.geometry.coords.search.knn import batched_knn_search
 from warpconvnet_amd.geometry.coords.search.search_results import RealSearchResult
 from warpconvnet_amd.ops.csr_rows import csr_pool
@@ -66,10 +66,17 @@ def _pool_by_random_sample(pc, voxel_size: float, return_type: str):
                                       voxel_size=voxel_size)
 
 
-def _pool_by_max_num_points(pc, reduction, max_num_points: int, return_type: str, return_neighbor_search_result: bool):
-    """At most ``max_num_points`` random points per batch element survive; every point is pooled onto its nearest survivor."""
+def _pool_by_max_num_points(pc, reduction, max_num_points: int, return_type: str, return_neighbor_search_result: bool,
+                            sample_method: str = "random"):
+    """At most ``max_num_points`` points per batch element survive, drawn at random (with replacement) or by farthest point
+    sampling from the element's first point (``sample_method="fps"``: the same cloud gives the same survivors); every point
+    is pooled onto its nearest survivor."""
     dev = pc.coordinate_tensor.device
-    sample_idx, sampled_offsets = random_sample_per_batch(pc.offsets, max_num_points)
+    if sample_method == "fps":
+        assert bool((pc.offsets.diff() > 0).all()), "sample_method='fps' needs at least one point in every batch element"
+        sample_idx, sampled_offsets = farthest_sample_per_batch(pc.coordinate_tensor, pc.offsets, max_num_points)
+    else:
+        sample_idx, sampled_offsets = random_sample_per_batch(pc.offsets, max_num_points)
     sample_idx = sample_idx.to(dev, torch.int64)
     sampled_coords = pc.coordinate_tensor[sample_idx]
     nearest = batched_knn_search(sampled_coords, sampled_offsets, pc.coordinate_tensor, pc.offsets, k=1).reshape(-1)
@@ -107,23 +114,27 @@ def point_pool(
     return_neighbor_search_result: bool = False,
     return_to_unique: bool = False,
     unique_method: str = "torch",
+    sample_method: str = "random",
 ):
     """Pool ``pc`` onto voxels of edge ``downsample_voxel_size`` or onto at most ``downsample_max_num_points`` points per
-    batch element (the latter wins when both are given, like the reference).  Returns ``Points`` (``return_type="point"``)
-    or ``Voxels`` (``"voxel"`` / ``"sparse"``), followed by the ``ToUnique`` (``return_to_unique``) or a ``RealSearchResult``
-    (``return_neighbor_search_result``) when asked."""
+    batch element (the latter wins when both are given, like the reference).  ``sample_method`` picks those points:
+    ``"random"`` (the reference's draw with replacement) or ``"fps"`` (farthest point sampling, repeatable).
+    Returns ``Points`` (``return_type="point"``) or ``Voxels`` (``"voxel"`` / ``"sparse"``), followed by the ``ToUnique``
+    (``return_to_unique``) or a ``RealSearchResult`` (``return_neighbor_search_result``) when asked."""
     if isinstance(reduction, str):
         reduction = REDUCTIONS(reduction)
     assert (
         downsample_max_num_points is not None or downsample_voxel_size is not None
     ), "Either downsample_num_points or downsample_voxel_size must be provided."
     assert return_type in ("point", "voxel", "sparse"), "return_type must be either point or voxel."
+    assert sample_method in ("random", "fps"), "sample_method must be either random or fps."
     if return_type != "point":
         assert not average_pooled_coordinates, "averaging pooled coordinates is not supported for Voxels return type"
 
     if downsample_max_num_points is not None:
         assert not return_to_unique, "return_to_unique must be False when downsample_max_num_points is provided."
-        return _pool_by_max_num_points(pc, reduction, downsample_max_num_points, return_type, return_neighbor_search_result)
+        return _pool_by_max_num_points(pc, reduction, downsample_max_num_points, return_type, return_neighbor_search_result,
+                                       sample_method)
 
     if reduction == REDUCTIONS.RANDOM:
         assert not return_to_unique, "return_to_unique must be False when reduction is RANDOM."

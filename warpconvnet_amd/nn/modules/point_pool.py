@@ -12,7 +12,8 @@ __all__ = ["PointPoolBase", "PointMaxPool", "PointAvgPool", "PointSumPool", "Poi
 
 class PointPoolBase(BaseSpatialModule):
     """``point_pool`` as a module.  ``return_type`` is ``"point"`` or ``"sparse"`` (``"voxel"``); the misspelt
-    ``avereage_pooled_coordinates`` is the reference's argument name."""
+    ``avereage_pooled_coordinates`` is the reference's argument name.  ``sample_method`` ("random" / "fps") picks the
+    survivors of ``downsample_max_num_points``."""
 
     def __init__(
         self,
@@ -23,6 +24,7 @@ class PointPoolBase(BaseSpatialModule):
         unique_method: str = "torch",
         avereage_pooled_coordinates: bool = False,
         return_neighbor_search_result: bool = False,
+        sample_method: str = "random",
     ):
         super().__init__()
         if isinstance(reduction, str):
@@ -34,6 +36,7 @@ class PointPoolBase(BaseSpatialModule):
         self.return_neighbor_search_result = return_neighbor_search_result
         self.unique_method = unique_method
         self.avereage_pooled_coordinates = avereage_pooled_coordinates
+        self.sample_method = sample_method
 
     def forward(self, pc: Points):
         return point_pool(
@@ -45,6 +48,7 @@ class PointPoolBase(BaseSpatialModule):
             return_neighbor_search_result=self.return_neighbor_search_result,
             unique_method=self.unique_method,
             average_pooled_coordinates=self.avereage_pooled_coordinates,
+            sample_method=self.sample_method,
         )
 
 
@@ -57,6 +61,7 @@ class _FixedReductionPool(PointPoolBase):
         downsample_voxel_size: Optional[float] = None,
         return_type: str = "point",
         return_neighbor_search_result: bool = False,
+        sample_method: str = "random",
     ):
         super().__init__(
             reduction=self.REDUCTION,
@@ -64,6 +69,7 @@ class _FixedReductionPool(PointPoolBase):
             downsample_voxel_size=downsample_voxel_size,
             return_type=return_type,
             return_neighbor_search_result=return_neighbor_search_result,
+            sample_method=sample_method,
         )
 
 
