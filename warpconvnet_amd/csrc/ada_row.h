@@ -2,16 +2,14 @@
 // of 8 elements (one 16-B access of f16 / bf16, two of f32); G = the power of two >= min(C / 8, 64) lanes stand side by side
 // on a row and hold it in registers, NCH = ceil(C / 8 / G) <= 4 pieces each; 64 / G rows share a wave; sums over a row
 // cross its G lanes with an xor butterfly.  Stated here once, for every kernel of that shape:
-//   the lane's place (row_lane), the 16-B piece load / store, the group sum;
+//   the lane's place (row_lane), the group sum;
 //   the forward's two-pass statistics (row_mean, row_dev, row_stats): the mean, then the sums of the deviations and of
 //     their squares - the first corrects the mean's own rounding, which at |mean| >> sigma is what limits xhat;
 //   the layout of stats (row_stats_st, row_stats_ld);
 //   the backward's row step (row_xhat, row_mean_rcp, row_dx): dx = rstd (g - mean(g) - xhat mean(g xhat));
-//   the host's geometry: lanes per row, pieces per lane, the two grids, the NCH and dtype dispatch.
+//   the host's geometry: lanes per row, pieces per lane, the two grids, the NCH dispatch.
 // What differs between the kernels stays in them: what is loaded into the row, what g is, which column sums are kept.
 #pragma once
-
-#include <type_traits>
 
 #include "wcn_common.h"
 
@@ -23,31 +21,6 @@ constexpr int kAdaMaxChannels = 2048;
 constexpr int kAdaFwdBlocks = 4096;  // the forward's grid is capped here; its lane groups stride over the rows
 
 // ---- device side ----------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void ada_ld8(const T* __restrict__ p, float (&f)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-  } else {
-    const Vec<T, 8> v = *reinterpret_cast<const Vec<T, 8>*>(p);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = (float)v.v[e];
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void ada_st8(T* __restrict__ p, const float (&f)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
-  } else {
-    Vec<T, 8> v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v.v[e] = (T)f[e];
-    *reinterpret_cast<Vec<T, 8>*>(p) = v;
-  }
-}
-
 // sum over the G = 1 << glog lanes of a group; every lane of the group receives the same bits
 __device__ __forceinline__ float ada_group_sum(float v, int glog) {
   for (int m = 0; m < glog; ++m) v += __shfl_xor(v, 1 << m);
@@ -150,12 +123,6 @@ inline void row_with_nch(int channels, int glog, F&& f) {
     case 3: f(std::integral_constant<int, 3>{}); break;
     default: f(std::integral_constant<int, 4>{}); break;
   }
-}
-
-// f(T{}) for the element type of a dtype code (dtype_ok), in the C-cast convention of ada_ld8 / ada_st8
-template <typename F>
-inline int row_with_dtype(int dtype, F&& f) {
-  return dtype == WCN_F32 ? f(float{}) : dtype == WCN_F16 ? f(_Float16{}) : f(__bf16{});
 }
 
 }  // namespace wcn

@@ -56,14 +56,14 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_fwd_kernel(const T* __restr
       const int c = l.gl + k * l.G;
       if (act && c < l.nvec) {
         const int64_t at = t * C + c * 8;
-        ada_ld8(x + at, f[k]);
+        ld_vec(x + at, f[k]);
         if constexpr (RES) {
           float hv[8], gv[8];
-          ada_ld8(h + at, hv);
-          ada_ld8(gate + b * g.mod_ld + c * 8, gv);
+          ld_vec(h + at, hv);
+          ld_vec(gate + b * g.mod_ld + c * 8, gv);
 #pragma unroll
           for (int e = 0; e < 8; ++e) f[k][e] += hv[e] * gv[e];
-          ada_st8(x1 + at, f[k]);
+          st_vec(x1 + at, f[k]);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += f[k][e];
@@ -88,11 +88,11 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_fwd_kernel(const T* __restr
         const int c = l.gl + k * l.G;
         if (act && c < l.nvec) {
           float sc[8], sh[8], o[8];
-          ada_ld8(scale + b * g.mod_ld + c * 8, sc);
-          ada_ld8(shift + b * g.mod_ld + c * 8, sh);
+          ld_vec(scale + b * g.mod_ld + c * 8, sc);
+          ld_vec(shift + b * g.mod_ld + c * 8, sh);
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - st.delta) * st.rstd * (1.0f + sc[e]) + sh[e];
-          ada_st8(y + t * C + c * 8, o);
+          st_vec(y + t * C + c * 8, o);
         }
       }
     }
@@ -129,8 +129,8 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
     for (int k = 0; k < NCH; ++k) {
       const int c = l.gl + k * l.G;
       if (c < l.nvec) {
-        if constexpr (RES) ada_st8(p + c * 8, a_gate[k]);
-        if constexpr (NORM) { ada_st8(p + C + c * 8, a_shift[k]); ada_st8(p + 2 * C + c * 8, a_scale[k]); }
+        if constexpr (RES) st_vec(p + c * 8, a_gate[k]);
+        if constexpr (NORM) { st_vec(p + C + c * 8, a_shift[k]); st_vec(p + 2 * C + c * 8, a_scale[k]); }
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -174,16 +174,16 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
         if (act && c < l.nvec) {
           const int64_t at = t * C + c * 8;
           float xv[8], sc[8];
-          ada_ld8(dy + at, gd[k]);
-          ada_ld8(x + at, xv);
+          ld_vec(dy + at, gd[k]);
+          ld_vec(x + at, xv);
           if constexpr (RES) {  // what LN read is the forward's fp32 x1, formed again with the same operations
             float gv[8];
-            ada_ld8(h + at, hk[k]);
-            ada_ld8(gate + bb * g.mod_ld + c * 8, gv);
+            ld_vec(h + at, hk[k]);
+            ld_vec(gate + bb * g.mod_ld + c * 8, gv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) xv[e] += hk[k][e] * gv[e];
           }
-          ada_ld8(scale + bb * g.mod_ld + c * 8, sc);
+          ld_vec(scale + bb * g.mod_ld + c * 8, sc);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float d = gd[k][e];
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
         const int64_t at = t * C + c * 8;
         float r[8];
         if (has_dx1) {
-          ada_ld8(dx1 + at, r);
+          ld_vec(dx1 + at, r);
         } else {
 #pragma unroll
           for (int e = 0; e < 8; ++e) r[e] = 0.f;
@@ -218,22 +218,22 @@ __global__ __launch_bounds__(kAdaThreads) void adaln_bwd_kernel(const T* __restr
 #pragma unroll
           for (int e = 0; e < 8; ++e) r[e] += row_dx(rstd, gd[k][e], xh[k][e], s1, s2);
         }
-        if (NORM || dx != nullptr) ada_st8(dx + at, r);
+        if (NORM || dx != nullptr) st_vec(dx + at, r);
         if constexpr (RES) {
           float hv[8], gv[8], o[8];
           if constexpr (NORM) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) hv[e] = hk[k][e];
           } else {
-            ada_ld8(h + at, hv);
+            ld_vec(h + at, hv);
           }
-          ada_ld8(gate + bb * g.mod_ld + c * 8, gv);
+          ld_vec(gate + bb * g.mod_ld + c * 8, gv);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             o[e] = r[e] * gv[e];
             a_gate[k][e] += r[e] * hv[e];
           }
-          ada_st8(dh + at, o);
+          st_vec(dh + at, o);
         }
       }
     }
@@ -323,7 +323,7 @@ static int ada_bwd_t(const void* dx1, const void* dy, const void* x, const void*
   (norm && res ? FN<T, true, true>(__VA_ARGS__)                       \
                : norm ? FN<T, true, false>(__VA_ARGS__) : FN<T, false, true>(__VA_ARGS__))
 #define WCN_ADA_DTYPES(FN, ...) \
-  row_with_dtype(dtype, [&](auto el) { return WCN_ADA_USES(FN, decltype(el), __VA_ARGS__); })
+  with_dtype(dtype, [&](auto el) { return WCN_ADA_USES(FN, decltype(el), __VA_ARGS__); })
 
 }  // namespace wcn
 

@@ -563,29 +563,27 @@ static int attn_bwd_t(const AttnCall& c, const void* dout, const void* out, cons
 }
 
 static int attn_fwd_dispatch(const AttnCall& c, int head_dim, int dtype, void* out, float* lse, hipStream_t s) {
-#define WCN_ATTN_FWD(DD) \
-  return dtype == WCN_BF16 ? attn_fwd_t<__bf16, DD>(c, out, lse, s) : attn_fwd_t<_Float16, DD>(c, out, lse, s);
-  switch (head_dim) {
-    case 16: WCN_ATTN_FWD(16);
-    case 32: WCN_ATTN_FWD(32);
-    default: WCN_ATTN_FWD(64);
-  }
-#undef WCN_ATTN_FWD
+  return with_dtype16(dtype, [&](auto t) {
+    using T = decltype(t);
+    switch (head_dim) {
+      case 16: return attn_fwd_t<T, 16>(c, out, lse, s);
+      case 32: return attn_fwd_t<T, 32>(c, out, lse, s);
+      default: return attn_fwd_t<T, 64>(c, out, lse, s);
+    }
+  });
 }
 
 static int attn_bwd_dispatch(const AttnCall& c, int head_dim, int dtype, const void* dout, const void* out, const float* lse,
                              void* dq, int64_t dq_stride, void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part,
                              float* delta, hipStream_t s) {
-#define WCN_ATTN_BWD(DD)                                                                                                      \
-  return dtype == WCN_BF16                                                                                                    \
-             ? attn_bwd_t<__bf16, DD>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s)         \
-             : attn_bwd_t<_Float16, DD>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
-  switch (head_dim) {
-    case 16: WCN_ATTN_BWD(16);
-    case 32: WCN_ATTN_BWD(32);
-    default: WCN_ATTN_BWD(64);
-  }
-#undef WCN_ATTN_BWD
+  return with_dtype16(dtype, [&](auto t) {
+    using T = decltype(t);
+    switch (head_dim) {
+      case 16: return attn_bwd_t<T, 16>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
+      case 32: return attn_bwd_t<T, 32>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
+      default: return attn_bwd_t<T, 64>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
+    }
+  });
 }
 
 // Shared argument checks of both directions of the packed form.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing

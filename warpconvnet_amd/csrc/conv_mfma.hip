@@ -411,7 +411,7 @@ int conv_gather_gemm_grouped(const void* in, const void* wp, void* out, const in
                              const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int groups,
                              int K, int dtype, hipStream_t s) {
   if (groups < 1 || groups > 65535 || !mfma_grouped_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  return dispatch_dtype(dtype, [&](auto t) {
+  return with_dtype16(dtype, [&](auto t) {
     return dispatch_cic<decltype(t)>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, nullptr, s, groups);
   });
 }
@@ -425,7 +425,7 @@ int conv_gather_gemm_mfma(const void* in, const void* wp, void* out, const int32
     case GemmFamily::Mfma16:
       return conv_gather_gemm16(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, dtype, out32, s);
     case GemmFamily::Mfma32:
-      return dispatch_dtype(dtype, [&](auto t) {
+      return with_dtype16(dtype, [&](auto t) {
         return dispatch_cic<decltype(t)>(cin, cout, in, wp, out, nbr, mask, perm, epi, n_out, K, out32, s);
       });
     case GemmFamily::None: break;
@@ -563,7 +563,7 @@ static int launch_pack(const Layout& L, const void* w, int w_is_f32, int dtype, 
                        (uint16_t*)packed, transpose, flip);
     return launch_status();
   }
-  return dispatch_dtype(dtype, [&](auto t) {
+  return with_dtype16(dtype, [&](auto t) {
     typedef decltype(t) TD;
     hipLaunchKernelGGL((pack_weight_kernel<Layout, float, TD>), grid, block, 0, s, L, (const float*)w, (TD*)packed,
                        transpose, flip);
@@ -606,7 +606,7 @@ int pack_weight_cs_pair(const float* w, int K, int cin, int cout, int dtype, int
   const PackCs fwd{{K, cin, cout, 1}, cs_col_block(cout)}, dgrad{{K, cout, cin, 1}, cs_col_block(cin)};
   const int64_t total = fwd.elements() > dgrad.elements() ? fwd.elements() : dgrad.elements();
   const dim3 grid((unsigned)ceil_div(total, 256), 2), block(256);
-  return dispatch_dtype(dtype, [&](auto t) {
+  return with_dtype16(dtype, [&](auto t) {
     typedef decltype(t) TD;
     hipLaunchKernelGGL((pack_weight_cs_pair_kernel<TD>), grid, block, 0, s, fwd, dgrad, w, (TD*)packed_fwd, (TD*)packed_dgrad,
                        flip_dgrad);

@@ -512,7 +512,7 @@ int conv_gather_gemm_cs(const void* in, const void* wp, void* out, const int32_t
                         const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int K, int dtype,
                         float* out32, hipStream_t s) {
   if (!gather_gemm_cs_supported(cin, cout, K, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
-  return dispatch_dtype(dtype, [&](auto t) {
+  return with_dtype16(dtype, [&](auto t) {
     return dispatch_cs<decltype(t)>(in, wp, out, nbr, mask, perm, epi, n_out, cin, cout, K, out32, s);
   });
 }

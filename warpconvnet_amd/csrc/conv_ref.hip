@@ -3,8 +3,6 @@
 // production path is conv_mfma.hip.  Semantics: reference explicit gather-matmul-scatter
 // (warpconvnet/nn/functional/sparse_conv/detail/explicit.py:22-101), restated over the row-major
 // neighbour table so no atomics are needed for forward/dgrad.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include "wcn_common.h"
 
@@ -29,15 +27,15 @@ __global__ __launch_bounds__(256) void gather_gemm_ref_kernel(const T* __restric
     const T* xin = in + (int64_t)idx * cin;
     if (!w_transposed) {
       const T* wk = w + (int64_t)kw * cin * cout + co;  // w[kw][ci][co]
-      for (int ci = 0; ci < cin; ++ci) acc += Cvt<T>::ld(xin[ci]) * Cvt<T>::ld(wk[(int64_t)ci * cout]);
+      for (int ci = 0; ci < cin; ++ci) acc += (float)xin[ci] * (float)wk[(int64_t)ci * cout];
     } else {
       const T* wk = w + ((int64_t)kw * cout + co) * cin;  // w_fwd[kw][co][ci]
-      for (int ci = 0; ci < cin; ++ci) acc += Cvt<T>::ld(xin[ci]) * Cvt<T>::ld(wk[ci]);
+      for (int ci = 0; ci < cin; ++ci) acc += (float)xin[ci] * (float)wk[ci];
     }
   }
   if (bias) acc += bias[co];
   T* dst = out + e;
-  *dst = Cvt<T>::st(acc);
+  *dst = (T)acc;
 }
 
 // colsum[c] = sum_r in[r][c] (fp32): bias gradient.  Two deterministic passes: per-workgroup partial sums over a
@@ -67,9 +65,9 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict
           T tmp[VEC];
           *reinterpret_cast<uint4*>(tmp) = *reinterpret_cast<const uint4*>(p);  // VEC * sizeof(T) == 16
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(tmp[v]);
+          for (int v = 0; v < VEC; ++v) acc[v] += (float)tmp[v];
         } else {
-          acc[0] += Cvt<T>::ld(*p);
+          acc[0] += (float)(*p);
         }
       }
     }
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(256) void wgrad_ref_kernel(const T* __restrict__ x,
   const int p0 = offsets[k], p1 = offsets[k + 1];
   float acc = 0.f;
   for (int p = p0; p < p1; ++p)
-    acc += Cvt<T>::ld(x[(int64_t)in_maps[p] * cin + ci]) * Cvt<T>::ld(dy[(int64_t)out_maps[p] * cout + co]);
+    acc += (float)(x[(int64_t)in_maps[p] * cin + ci]) * (float)(dy[(int64_t)out_maps[p] * cout + co]);
   dw[e] = acc;
 }
 
@@ -129,13 +127,10 @@ static int launch_gather_gemm_ref(const void* in, const void* w, void* out, cons
 
 int conv_gather_gemm_ref(const void* in, const void* w, void* out, const int32_t* nbr, const float* bias, int64_t n_out,
                          int cin, int cout, int K, int dtype, int w_transposed, int k_flip, hipStream_t s) {
-  switch (dtype) {
-    case WCN_F32: return launch_gather_gemm_ref<float>(in, w, out, nbr, bias, n_out, cin, cout, K, w_transposed, k_flip, s);
-    case WCN_F16: return launch_gather_gemm_ref<__half>(in, w, out, nbr, bias, n_out, cin, cout, K, w_transposed, k_flip, s);
-    case WCN_BF16:
-      return launch_gather_gemm_ref<__hip_bfloat16>(in, w, out, nbr, bias, n_out, cin, cout, K, w_transposed, k_flip, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) {
+    return launch_gather_gemm_ref<decltype(t)>(in, w, out, nbr, bias, n_out, cin, cout, K, w_transposed, k_flip, s);
+  });
 }
 
 constexpr int kColsumBlocks = 512;
@@ -156,12 +151,8 @@ static int launch_colsum(const void* in, int64_t n, int c, float* out, float* pa
 
 int colsum(const void* in, int64_t n, int c, int dtype, float* out, void* workspace, size_t workspace_bytes, hipStream_t s) {
   if (!workspace || workspace_bytes < colsum_workspace(c)) return WCN_ERROR_INVALID_PARAMETERS;
-  switch (dtype) {
-    case WCN_F32: return launch_colsum<float>(in, n, c, out, (float*)workspace, s);
-    case WCN_F16: return launch_colsum<__half>(in, n, c, out, (float*)workspace, s);
-    case WCN_BF16: return launch_colsum<__hip_bfloat16>(in, n, c, out, (float*)workspace, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) { return launch_colsum<decltype(t)>(in, n, c, out, (float*)workspace, s); });
 }
 
 template <typename T>
@@ -175,12 +166,10 @@ static int launch_wgrad_ref(const void* x, const void* dy, float* dw, const int3
 
 int conv_wgrad_ref(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                    const int32_t* offsets, int cin, int cout, int K, int dtype, hipStream_t s) {
-  switch (dtype) {
-    case WCN_F32: return launch_wgrad_ref<float>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, s);
-    case WCN_F16: return launch_wgrad_ref<__half>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, s);
-    case WCN_BF16: return launch_wgrad_ref<__hip_bfloat16>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) {
+    return launch_wgrad_ref<decltype(t)>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, s);
+  });
 }
 
 }  // namespace wcn

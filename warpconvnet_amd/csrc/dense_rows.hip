@@ -207,9 +207,9 @@ int wcn_dense_rows(const void* x, int32_t x_is_f32, const void* w, int32_t w_is_
   // `w` is the layer's [rows, cols] matrix as stored: [cin, cout], or [cout, cin] when it is applied transposed
   const int ldw = w_transposed ? cin : cout;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == WCN_BF16)
-    return dispatch_dense_rows<__bf16>(x, x_is_f32, w, w_is_f32, ldw, w_transposed, bias, y, n, cin, cout, s);
-  return dispatch_dense_rows<_Float16>(x, x_is_f32, w, w_is_f32, ldw, w_transposed, bias, y, n, cin, cout, s);
+  return with_dtype16(dtype, [&](auto t) {
+    return dispatch_dense_rows<decltype(t)>(x, x_is_f32, w, w_is_f32, ldw, w_transposed, bias, y, n, cin, cout, s);
+  });
 }
 
 }  // extern "C"

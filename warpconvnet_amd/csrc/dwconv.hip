@@ -13,8 +13,6 @@
 //
 // Reference semantics: warpconvnet/nn/functional/sparse_conv_depth.py:227-306 (explicit depthwise forward/backward);
 // role of _C.fma.implicit_fma / implicit_reduction (csrc/implicit_fma_kernel.cu, csrc/implicit_reduction.cu).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include "wcn_common.h"
 
@@ -58,13 +56,13 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_gather_kernel(const T* __re
         *reinterpret_cast<uint4*>(xv) = *reinterpret_cast<const uint4*>(in + (int64_t)idx * C + piece * VEC);
         *reinterpret_cast<uint4*>(wv) = *reinterpret_cast<const uint4*>(s_w + kw * C + piece * VEC);
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(xv[v]) * Cvt<T>::ld(wv[v]);
+        for (int v = 0; v < VEC; ++v) acc[v] += (float)xv[v] * (float)wv[v];
       }
     }
     if (live) {
       T ov[VEC];
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) ov[v] = Cvt<T>::st(acc[v] + (bias ? bias[piece * VEC + v] : 0.f));
+      for (int v = 0; v < VEC; ++v) ov[v] = (T)(acc[v] + (bias ? bias[piece * VEC + v] : 0.f));
       *reinterpret_cast<uint4*>(out + r * C + piece * VEC) = *reinterpret_cast<const uint4*>(ov);
     }
   }
@@ -86,9 +84,9 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_gather_generic_kernel(const
     const int32_t idx = tbl[r * kp + kt];
     if (idx < 0) continue;
     const int kw = k_flip ? (K - 1 - kt) : kt;
-    acc += Cvt<T>::ld(in[(int64_t)idx * C + c]) * Cvt<T>::ld(w[(int64_t)kw * C + c]);
+    acc += (float)in[(int64_t)idx * C + c] * (float)w[(int64_t)kw * C + c];
   }
-  out[e] = Cvt<T>::st(acc + (bias ? bias[c] : 0.f));
+  out[e] = (T)(acc + (bias ? bias[c] : 0.f));
 }
 
 // ---- wgrad ---------------------------------------------------------------------------------------------------------------
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_wgrad_kernel(const T* __res
     *reinterpret_cast<uint4*>(xv) = *reinterpret_cast<const uint4*>(x + (int64_t)i * C + piece * VEC);
     *reinterpret_cast<uint4*>(gv) = *reinterpret_cast<const uint4*>(dy + (int64_t)o * C + piece * VEC);
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] += Cvt<T>::ld(xv[v]) * Cvt<T>::ld(gv[v]);
+    for (int v = 0; v < VEC; ++v) acc[v] += (float)xv[v] * (float)gv[v];
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) s_acc[grp * C + piece * VEC + v] = acc[v];
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(kDwThreads) void dwconv_wgrad_generic_kernel(const 
   for (int c = threadIdx.x; c < C; c += kDwThreads) {
     float t = 0.f;
     for (int64_t p = p0; p < p1; ++p)
-      t += Cvt<T>::ld(x[(int64_t)in_maps[p] * C + c]) * Cvt<T>::ld(dy[(int64_t)out_maps[p] * C + c]);
+      t += (float)(x[(int64_t)in_maps[p] * C + c]) * (float)(dy[(int64_t)out_maps[p] * C + c]);
     partial[((int64_t)k * kDwSplits + s) * C + c] = t;
   }
 }
@@ -196,12 +194,8 @@ static int launch_dw_gather(const void* in, const void* w, void* out, const int3
 
 int dwconv_gather(const void* in, const void* w, void* out, const int32_t* tbl, const float* bias, int64_t n_out, int C,
                   int K, int dtype, int k_flip, hipStream_t s) {
-  switch (dtype) {
-    case WCN_F32: return launch_dw_gather<float>(in, w, out, tbl, bias, n_out, C, K, k_flip, s);
-    case WCN_F16: return launch_dw_gather<__half>(in, w, out, tbl, bias, n_out, C, K, k_flip, s);
-    case WCN_BF16: return launch_dw_gather<__hip_bfloat16>(in, w, out, tbl, bias, n_out, C, K, k_flip, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) { return launch_dw_gather<decltype(t)>(in, w, out, tbl, bias, n_out, C, K, k_flip, s); });
 }
 
 size_t dwconv_wgrad_workspace(int K, int C) { return (size_t)K * kDwSplits * C * sizeof(float); }
@@ -228,12 +222,10 @@ int dwconv_wgrad(const void* x, const void* dy, float* dw, const int32_t* in_map
                  const int32_t* offsets, int C, int K, int dtype, void* workspace, size_t workspace_bytes, hipStream_t s) {
   if (!workspace || workspace_bytes < dwconv_wgrad_workspace(K, C)) return WCN_ERROR_INVALID_PARAMETERS;
   float* partial = (float*)workspace;
-  switch (dtype) {
-    case WCN_F32: return launch_dw_wgrad<float>(x, dy, dw, in_maps, out_maps, offsets, C, K, partial, s);
-    case WCN_F16: return launch_dw_wgrad<__half>(x, dy, dw, in_maps, out_maps, offsets, C, K, partial, s);
-    case WCN_BF16: return launch_dw_wgrad<__hip_bfloat16>(x, dy, dw, in_maps, out_maps, offsets, C, K, partial, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) {
+    return launch_dw_wgrad<decltype(t)>(x, dy, dw, in_maps, out_maps, offsets, C, K, partial, s);
+  });
 }
 
 }  // namespace wcn

@@ -138,12 +138,6 @@ __device__ __forceinline__ F add_residual(F o, F rv, int relu) {
   return o;
 }
 // ---- host side -------------------------------------------------------------------------------------------------------
-// f(T{}) with T the 16-bit storage type of `dtype` (WCN_BF16, else WCN_F16: the callers have checked)
-template <typename F>
-inline int dispatch_dtype(int dtype, F&& f) {
-  return dtype == WCN_BF16 ? f(__bf16{}) : f(_Float16{});
-}
-
 // The K <= 32 / K > 32 pair of a register-gather kernel (K0: one mask word, K1: MULTI; 256-thread kernels): raise the
 // dynamic-LDS limit of both once per device, launch the one `multi` selects.
 template <auto K0, auto K1, typename... Args>

@@ -127,11 +127,11 @@ __global__ __launch_bounds__(kRowThreads) void gs_fwd_rows_kernel(GsShape sh, co
       for (int k = 0; k < 8; ++k) {
         const Vec<T, VEC> x = *reinterpret_cast<const Vec<T, VEC>*>(grid + pt.off[k] + c);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = fmaf(pt.w[k], Cvt<T>::ld(x.v[i]), acc[i]);
+        for (int i = 0; i < VEC; ++i) acc[i] = fmaf(pt.w[k], (float)x.v[i], acc[i]);
       }
       Vec<T, VEC> y;
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) y.v[i] = Cvt<T>::st(acc[i]);
+      for (int i = 0; i < VEC; ++i) y.v[i] = (T)acc[i];
       *reinterpret_cast<Vec<T, VEC>*>(row + c) = y;
     }
   }
@@ -158,8 +158,8 @@ __global__ __launch_bounds__(kRowThreads) void gs_fwd_planar_kernel(GsShape sh, 
       const int64_t oc = c * sh.stride[4];
       float acc = 0.0f;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc = fmaf(pt.w[k], Cvt<T>::ld(grid[pt.off[k] + oc]), acc);
-      row[c] = Cvt<T>::st(acc);
+      for (int k = 0; k < 8; ++k) acc = fmaf(pt.w[k], (float)(grid[pt.off[k] + oc]), acc);
+      row[c] = (T)acc;
     }
   }
 }
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(kRowThreads) void gs_bwd_chunk_kernel(int channels,
           const int64_t p = perm[start + i];
           float w[8];
           gs_weights(frac[p * 3], frac[p * 3 + 1], frac[p * 3 + 2], w);
-          const float g = Cvt<T>::ld(dy[p * pitch + col0 + c]);
+          const float g = (float)dy[p * pitch + col0 + c];
 #pragma unroll
           for (int k = 0; k < 8; ++k) acc[k] = fmaf(w[k], g, acc[k]);
         }
@@ -264,11 +264,11 @@ __global__ __launch_bounds__(kRowThreads) void gs_bwd_vertex_kernel(GsShape sh, 
             const float fx = frac[p * 3], fy = frac[p * 3 + 1], fz = frac[p * 3 + 2];
             const float wx = (corner & 4) ? fx : 1.0f - fx, wy = (corner & 2) ? fy : 1.0f - fy,
                         wz = (corner & 1) ? fz : 1.0f - fz;
-            acc = fmaf(wx * wy * wz, Cvt<T>::ld(dy[p * pitch + col0 + c]), acc);
+            acc = fmaf(wx * wy * wz, (float)dy[p * pitch + col0 + c], acc);
           }
         }
       }
-      dst[c * sh.stride[4]] = Cvt<T>::st(acc);
+      dst[c * sh.stride[4]] = (T)acc;
     }
   }
 }
@@ -386,10 +386,10 @@ int wcn_grid_sample(const void* grid, const int64_t* strides, const int32_t* dim
   if (!grid || !sorted_keys || !perm || !fractions || !out || vertices == 0) return WCN_ERROR_INVALID_PARAMETERS;
   const GsShape sh = gs_shape(dims, strides, channels);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == WCN_F32) gs_launch_forward<float>(sh, grid, sorted_keys, perm, fractions, n, out, out_pitch, col0, s);
-  else if (dtype == WCN_F16) gs_launch_forward<__half>(sh, grid, sorted_keys, perm, fractions, n, out, out_pitch, col0, s);
-  else gs_launch_forward<__hip_bfloat16>(sh, grid, sorted_keys, perm, fractions, n, out, out_pitch, col0, s);
-  return launch_status();
+  return with_dtype(dtype, [&](auto t) {
+    gs_launch_forward<decltype(t)>(sh, grid, sorted_keys, perm, fractions, n, out, out_pitch, col0, s);
+    return launch_status();
+  });
 }
 
 size_t wcn_grid_sample_backward_workspace_bytes(int64_t n, int32_t channels) {
@@ -412,16 +412,11 @@ int wcn_grid_sample_backward(const void* dy, int64_t dy_pitch, int64_t col0, con
   const GsShape sh = gs_shape(dims, strides, channels);
   hipStream_t s = (hipStream_t)stream;
   float* part = chunks ? (float*)workspace : nullptr;
-  if (dtype == WCN_F32)
-    gs_launch_backward<float>(sh, vertices, dy, dy_pitch, col0, sorted_keys, perm, cell_offsets, fractions, n, chunks, part,
-                              d_grid, s);
-  else if (dtype == WCN_F16)
-    gs_launch_backward<__half>(sh, vertices, dy, dy_pitch, col0, sorted_keys, perm, cell_offsets, fractions, n, chunks, part,
-                               d_grid, s);
-  else
-    gs_launch_backward<__hip_bfloat16>(sh, vertices, dy, dy_pitch, col0, sorted_keys, perm, cell_offsets, fractions, n, chunks,
-                                       part, d_grid, s);
-  return launch_status();
+  return with_dtype(dtype, [&](auto t) {
+    gs_launch_backward<decltype(t)>(sh, vertices, dy, dy_pitch, col0, sorted_keys, perm, cell_offsets, fractions, n, chunks, part,
+                                    d_grid, s);
+    return launch_status();
+  });
 }
 
 }  // extern "C"

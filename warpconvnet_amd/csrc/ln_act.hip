@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_fwd_kernel(const T* __rest
     for (int k = 0; k < NCH; ++k) {
       const int c = l.gl + k * l.G;
       if (act && c < l.nvec) {
-        ada_ld8(x + t * C + c * 8, f[k]);
+        ld_vec(x + t * C + c * 8, f[k]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += f[k][e];
       } else {
@@ -77,8 +77,8 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_fwd_kernel(const T* __rest
         for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - st.delta) * st.rstd;
         if constexpr (AFFINE) {
           float w[8], b[8];
-          ada_ld8(weight + c * 8, w);
-          ada_ld8(bias + c * 8, b);
+          ld_vec(weight + c * 8, w);
+          ld_vec(bias + c * 8, b);
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = o[e] * w[e] + b[e];
         }
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_fwd_kernel(const T* __rest
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] *= ln_sigmoid(o[e]);
         }
-        ada_st8(y + t * C + c * 8, o);
+        st_vec(y + t * C + c * 8, o);
       }
     }
   }
@@ -125,11 +125,11 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
       if (act && c < l.nvec) {
         const int64_t at = t * C + c * 8;
         float xv[8], w[8], b[8];
-        ada_ld8(dy + at, gd[k]);
-        ada_ld8(x + at, xv);
+        ld_vec(dy + at, gd[k]);
+        ld_vec(x + at, xv);
         if constexpr (AFFINE) {
-          ada_ld8(weight + c * 8, w);
-          ada_ld8(bias + c * 8, b);
+          ld_vec(weight + c * 8, w);
+          ld_vec(bias + c * 8, b);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
         float r[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) r[e] = row_dx(rstd, gd[k][e], xh[k][e], s1, s2);
-        ada_st8(dx + t * C + c * 8, r);
+        st_vec(dx + t * C + c * 8, r);
       }
     }
   }
@@ -175,8 +175,8 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
       for (int k = 0; k < NCH; ++k) {
         const int c = l.gl + k * l.G;
         if (c < l.nvec) {
-          ada_st8(p + c * 8, a_w[k]);
-          ada_st8(p + C + c * 8, a_b[k]);
+          st_vec(p + c * 8, a_w[k]);
+          st_vec(p + C + c * 8, a_b[k]);
         }
       }
     }
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(kAdaThreads) void channel_pieces_kernel(const T* __
       if constexpr (FOLD) {
         float f[R][8];
 #pragma unroll
-        for (int k = 0; k < R; ++k) ada_ld8(x + t * cx + ((int64_t)p * R + k) * 8, f[k]);
+        for (int k = 0; k < R; ++k) ld_vec(x + t * cx + ((int64_t)p * R + k) * 8, f[k]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float s = 0.f;
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kAdaThreads) void channel_pieces_kernel(const T* __
           o[e] = g.alpha * s;
         }
       } else if constexpr (R == 1) {
-        ada_ld8(x + t * cx + p * 8, o);
+        ld_vec(x + t * cx + p * 8, o);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] *= g.alpha;
       } else {
@@ -257,11 +257,11 @@ __global__ __launch_bounds__(kAdaThreads) void channel_pieces_kernel(const T* __
       const int64_t at = t * g.cout + p * 8;
       if (h != nullptr) {  // the same in every lane
         float hv[8];
-        ada_ld8(h + at, hv);
+        ld_vec(h + at, hv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] += hv[e];
       }
-      ada_st8(out + at, o);
+      st_vec(out + at, o);
     }
   }
 }
@@ -335,7 +335,7 @@ static int ln_bwd_t(const void* dy, const void* x, const float* weight, const fl
   (affine ? (act ? FN<T, true, true>(__VA_ARGS__) : FN<T, true, false>(__VA_ARGS__))           \
           : (act ? FN<T, false, true>(__VA_ARGS__) : FN<T, false, false>(__VA_ARGS__)))
 #define WCN_LN_DTYPES(FN, ...) \
-  row_with_dtype(dtype, [&](auto el) { return WCN_LN_USES(FN, decltype(el), __VA_ARGS__); })
+  with_dtype(dtype, [&](auto el) { return WCN_LN_USES(FN, decltype(el), __VA_ARGS__); })
 
 template <typename T, bool FOLD>
 static int skip_t(const void* x, const void* h, void* out, SkipGeom g, bool pieces, hipStream_t s) {
@@ -382,7 +382,7 @@ static int skip_run(bool fold, const void* x, const void* h, int64_t rows, int64
   // 16-B pieces: every row of both sides starts on the 16-B grid, and a piece's indices are compile-time constants
   const bool pieces = narrow % 8 == 0 && (ratio == 1 || ratio == 2 || ratio == 4 || ratio == 8) && aligned_to(x, 16) &&
                       aligned_to(h, 16) && aligned_to(out, 16);
-  return row_with_dtype(dtype, [&](auto el) {
+  return with_dtype(dtype, [&](auto el) {
     using T = decltype(el);
     return fold ? skip_t<T, true>(x, h, out, g, pieces, s) : skip_t<T, false>(x, h, out, g, pieces, s);
   });

@@ -15,8 +15,6 @@
 //                           (reference models/mink_unet.py:160-172: `out += identity; out = relu(out)`), in the same two
 //                           passes: the forward adds r while it applies, the backward masks with the stored z and also
 //                           writes the masked gradient (the residual branch's share).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include "wcn_common.h"
 
@@ -50,7 +48,7 @@ __device__ __forceinline__ float bn_affine(float xf, float sc, float sh) {
 }
 template <typename T>
 __device__ __forceinline__ bool bn_relu_passes(float xf, float sc, float sh) {
-  return Cvt<T>::ld(Cvt<T>::st(fmaxf(bn_affine(xf, sc, sh), 0.f))) > 0.f;  // what the forward stored, compared with zero
+  return (float)((T)(fmaxf(bn_affine(xf, sc, sh), 0.f))) > 0.f;  // what the forward stored, compared with zero
 }
 
 // Thread layout of the column reductions: lanes_c threads side by side cover one row (VEC channels each), the
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const T* __restrict__ 
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         if (ch0 + v < c) {
-          if (MODE == 0) a[v] = Cvt<T>::ld(x[ch0 + v]);  // pivot: row 0
+          if (MODE == 0) a[v] = (float)x[ch0 + v];  // pivot: row 0
           else {
             a[v] = mean[ch0 + v]; b[v] = rstd[ch0 + v];
             if (rscale) { sc[v] = rscale[ch0 + v]; sh[v] = rshift[ch0 + v]; }
@@ -115,14 +113,14 @@ __global__ __launch_bounds__(256) void norm_reduce_kernel(const T* __restrict__ 
           if (r + (int64_t)q * rsteps >= r1) continue;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) {
-            const float xf = Cvt<T>::ld(xv[q].v[v]);
+            const float xf = (float)xv[q].v[v];
             if (MODE == 0) {
               const float d = xf - a[v];
               s0[v] += d;
               s1[v] += d * d;
             } else {
-              float g = Cvt<T>::ld(gv[q].v[v]);
-              if (zmask) { if (!(Cvt<T>::ld(zv[q].v[v]) > 0.f)) g = 0.f; }
+              float g = (float)gv[q].v[v];
+              if (zmask) { if (!((float)zv[q].v[v] > 0.f)) g = 0.f; }
               else if (rscale && !bn_relu_passes<T>(xf, sc[v], sh[v])) g = 0.f;
               s0[v] += g;
               s1[v] += g * ((xf - a[v]) * b[v]);
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(64) void norm_final_kernel(const float* __restrict_
       const float inv = 1.0f / (float)n;
       const float md = t0 * inv;                       // mean of (x - pivot)
       const float var = fmaxf(t1 * inv - md * md, 0.f);
-      const float mean = Cvt<T>::ld(x[ch]) + md;
+      const float mean = (float)x[ch] + md;
       out0[ch] = mean;
       out1[ch] = var;
       if (f.rstd) {
@@ -255,12 +253,12 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const T* __restrict__ x
     if (res) rv = *reinterpret_cast<const Vec<T, VEC>*>(res + e * VEC);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-      float f = bn_affine(Cvt<T>::ld(xv.v[v]), s_coef[ch0 + v], s_coef[c + ch0 + v]);
+      float f = bn_affine((float)xv.v[v], s_coef[ch0 + v], s_coef[c + ch0 + v]);
       // round, then add in fp32 and round again: what the framework's elementwise add of two 16-bit tensors does (for fp16 the
       // fp32 sum is exact enough that this equals one rounding of the exact sum - checked on 84 M pairs)
-      if (res) f = Cvt<T>::ld(Cvt<T>::st(Cvt<T>::ld(Cvt<T>::st(f)) + Cvt<T>::ld(rv.v[v])));
+      if (res) f = (float)((T)((float)((T)f) + (float)rv.v[v]));
       if (relu) f = fmaxf(f, 0.f);
-      yv.v[v] = Cvt<T>::st(f);
+      yv.v[v] = (T)f;
     }
     *reinterpret_cast<Vec<T, VEC>*>(y + e * VEC) = yv;
   }
@@ -301,12 +299,12 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const T* __restrict
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       const int ch = ch0 + v;
-      const float xf = Cvt<T>::ld(xv.v[v]);
-      float g = Cvt<T>::ld(gv.v[v]);
-      if (zmask) { if (!(Cvt<T>::ld(zv.v[v]) > 0.f)) g = 0.f; }
+      const float xf = (float)xv.v[v];
+      float g = (float)gv.v[v];
+      if (zmask) { if (!((float)zv.v[v] > 0.f)) g = 0.f; }
       else if (rscale && !bn_relu_passes<T>(xf, s_coef[3 * c + ch], s_coef[4 * c + ch])) g = 0.f;
-      mv.v[v] = Cvt<T>::st(g);
-      ov.v[v] = Cvt<T>::st(s_coef[ch] * g + s_coef[c + ch] * xf + s_coef[2 * c + ch]);
+      mv.v[v] = (T)g;
+      ov.v[v] = (T)(s_coef[ch] * g + s_coef[c + ch] * xf + s_coef[2 * c + ch]);
     }
     *reinterpret_cast<Vec<T, VEC>*>(dx + e * VEC) = ov;
     if (dres) *reinterpret_cast<Vec<T, VEC>*>(dres + e * VEC) = mv;
@@ -395,11 +393,9 @@ int wcn_bn_stats(const void* x, int64_t n, int32_t channels, int32_t dtype, floa
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
   float* p = (float*)workspace;
-  switch (dtype) {
-    case WCN_F32: return bn_reduce_t<float>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s);
-    case WCN_F16: return bn_reduce_t<__half>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s);
-    default: return bn_reduce_t<__hip_bfloat16>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return bn_reduce_t<decltype(t)>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s);
+  });
 }
 
 int wcn_bn_stats_fold(const void* x, int64_t n, int32_t channels, int32_t dtype, const float* gamma, const float* beta,
@@ -415,11 +411,9 @@ int wcn_bn_stats_fold(const void* x, int64_t n, int32_t channels, int32_t dtype,
   f.batches = reinterpret_cast<long long*>(num_batches_tracked);
   hipStream_t s = (hipStream_t)stream;
   float* p = (float*)workspace;
-  switch (dtype) {
-    case WCN_F32: return bn_reduce_t<float>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s, f);
-    case WCN_F16: return bn_reduce_t<__half>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s, f);
-    default: return bn_reduce_t<__hip_bfloat16>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s, f);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return bn_reduce_t<decltype(t)>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s, f);
+  });
 }
 
 int wcn_bn_fold(const float* running_mean, const float* running_var, const float* gamma, const float* beta, float eps,
@@ -438,11 +432,7 @@ int wcn_bn_apply(const void* x, int64_t n, int32_t channels, int32_t dtype, cons
   if (n == 0) return WCN_SUCCESS;
   if (!x || !y || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case WCN_F32: return bn_apply_t<float>(x, n, channels, scale, shift, relu, y, s);
-    case WCN_F16: return bn_apply_t<__half>(x, n, channels, scale, shift, relu, y, s);
-    default: return bn_apply_t<__hip_bfloat16>(x, n, channels, scale, shift, relu, y, s);
-  }
+  return with_dtype(dtype, [&](auto t) { return bn_apply_t<decltype(t)>(x, n, channels, scale, shift, relu, y, s); });
 }
 
 static int bn_backward_reduce_ld(const void* dy, int64_t dy_ld, const void* x, const float* relu_scale, const float* relu_shift,
@@ -453,15 +443,10 @@ static int bn_backward_reduce_ld(const void* dy, int64_t dy_ld, const void* x, c
     return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
   float* p = (float*)workspace;
-  switch (dtype) {
-    case WCN_F32:
-      return bn_reduce_t<float>(1, x, dy, relu_scale, relu_shift, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, BnFold(), nullptr, dy_ld);
-    case WCN_F16:
-      return bn_reduce_t<__half>(1, x, dy, relu_scale, relu_shift, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, BnFold(), nullptr, dy_ld);
-    default:
-      return bn_reduce_t<__hip_bfloat16>(1, x, dy, relu_scale, relu_shift, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, BnFold(),
-                                         nullptr, dy_ld);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return bn_reduce_t<decltype(t)>(1, x, dy, relu_scale, relu_shift, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s,
+                                    BnFold(), nullptr, dy_ld);
+  });
 }
 int wcn_bn_backward_reduce(const void* dy, const void* x, const float* relu_scale, const float* relu_shift, int64_t n,
                            int32_t channels, int32_t dtype, const float* mean, const float* rstd, float* sum_dy,
@@ -478,17 +463,10 @@ static int bn_backward_apply_ld(const void* dy, int64_t dy_ld, const void* x, co
   if (n == 0) return WCN_SUCCESS;
   if (!dy || !x || !dx || !mean || !rstd || !sum_dy || !sum_dy_xhat) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case WCN_F32:
-      return bn_bwd_apply_t<float>(dy, x, relu_scale, relu_shift, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, nullptr,
-                                   nullptr, dy_ld);
-    case WCN_F16:
-      return bn_bwd_apply_t<__half>(dy, x, relu_scale, relu_shift, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, nullptr,
-                                    nullptr, dy_ld);
-    default:
-      return bn_bwd_apply_t<__hip_bfloat16>(dy, x, relu_scale, relu_shift, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s,
-                                            nullptr, nullptr, dy_ld);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return bn_bwd_apply_t<decltype(t)>(dy, x, relu_scale, relu_shift, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx,
+                                       s, nullptr, nullptr, dy_ld);
+  });
 }
 int wcn_bn_backward_apply(const void* dy, const void* x, const float* relu_scale, const float* relu_shift, int64_t n,
                           int32_t channels, int32_t dtype, const float* mean, const float* rstd, const float* gamma,
@@ -504,11 +482,7 @@ int wcn_bn_apply_residual(const void* x, const void* residual, int64_t n, int32_
   if (n == 0) return WCN_SUCCESS;
   if (!x || !residual || !y || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case WCN_F32: return bn_apply_t<float>(x, n, channels, scale, shift, relu, y, s, residual);
-    case WCN_F16: return bn_apply_t<__half>(x, n, channels, scale, shift, relu, y, s, residual);
-    default: return bn_apply_t<__hip_bfloat16>(x, n, channels, scale, shift, relu, y, s, residual);
-  }
+  return with_dtype(dtype, [&](auto t) { return bn_apply_t<decltype(t)>(x, n, channels, scale, shift, relu, y, s, residual); });
 }
 
 static int bn_backward_reduce_masked_ld(const void* dy, int64_t dy_ld, const void* x, const void* z, int64_t n, int32_t channels,
@@ -520,12 +494,9 @@ static int bn_backward_reduce_masked_ld(const void* dy, int64_t dy_ld, const voi
   hipStream_t s = (hipStream_t)stream;
   float* p = (float*)workspace;
   const BnFold nf;
-  switch (dtype) {
-    case WCN_F32: return bn_reduce_t<float>(1, x, dy, nullptr, nullptr, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, nf, z, dy_ld);
-    case WCN_F16: return bn_reduce_t<__half>(1, x, dy, nullptr, nullptr, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, nf, z, dy_ld);
-    default:
-      return bn_reduce_t<__hip_bfloat16>(1, x, dy, nullptr, nullptr, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, nf, z, dy_ld);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return bn_reduce_t<decltype(t)>(1, x, dy, nullptr, nullptr, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, nf, z, dy_ld);
+  });
 }
 int wcn_bn_backward_reduce_masked(const void* dy, const void* x, const void* z, int64_t n, int32_t channels, int32_t dtype,
                                   const float* mean, const float* rstd, float* sum_dy, float* sum_dy_xhat, void* workspace,
@@ -540,15 +511,10 @@ static int bn_backward_apply_masked_ld(const void* dy, int64_t dy_ld, const void
   if (n == 0) return WCN_SUCCESS;
   if (!dy || !x || !z || !dx || !mean || !rstd || !sum_dy || !sum_dy_xhat) return WCN_ERROR_INVALID_PARAMETERS;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case WCN_F32:
-      return bn_bwd_apply_t<float>(dy, x, nullptr, nullptr, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, z, dres, dy_ld);
-    case WCN_F16:
-      return bn_bwd_apply_t<__half>(dy, x, nullptr, nullptr, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, z, dres, dy_ld);
-    default:
-      return bn_bwd_apply_t<__hip_bfloat16>(dy, x, nullptr, nullptr, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, z,
-                                            dres, dy_ld);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return bn_bwd_apply_t<decltype(t)>(dy, x, nullptr, nullptr, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, z,
+                                       dres, dy_ld);
+  });
 }
 int wcn_bn_backward_apply_masked(const void* dy, const void* x, const void* z, int64_t n, int32_t channels, int32_t dtype,
                                  const float* mean, const float* rstd, const float* gamma, const float* sum_dy,

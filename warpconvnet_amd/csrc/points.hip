@@ -10,8 +10,6 @@
 //   wcn_segment_reduce out[m][c] = reduce over rows [row_splits[m], row_splits[m+1]) of in[.][c], reduce in
 //                      {sum, mean, max, min}; max/min also return the arg row (first extremum) for the backward pass
 //                      (role of torch_scatter.segment_csr in warpconvnet/ops/reductions.py:36-75).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include <cfloat>
 
@@ -201,14 +199,14 @@ __global__ __launch_bounds__(256) void segment_reduce_kernel(const T* __restrict
   float acc = (op == kRedMax) ? -FLT_MAX : (op == kRedMin ? FLT_MAX : 0.f);
   int64_t best = -1;
   for (int64_t r = r0; r < r1; ++r) {
-    const float v = Cvt<T>::ld(in[r * c + ch]);
+    const float v = (float)in[r * c + ch];
     if (op == kRedMax) { if (v > acc || best < 0) { acc = v; best = r; } }
     else if (op == kRedMin) { if (v < acc || best < 0) { acc = v; best = r; } }
     else acc += v;
   }
   if (op == kRedMean && r1 > r0) acc /= (float)(r1 - r0);
   if ((op == kRedMax || op == kRedMin) && r1 == r0) acc = 0.f;  // empty segment: zero (torch_scatter convention)
-  out[e] = Cvt<T>::st(acc);
+  out[e] = (T)acc;
   if (arg) arg[e] = best;
 }
 
@@ -217,20 +215,12 @@ int segment_reduce(const void* in, const int64_t* splits, int64_t m, int c, int 
   if (op < kRedSum || op > kRedMin) return WCN_ERROR_INVALID_PARAMETERS;
   if (m == 0 || c == 0) return WCN_SUCCESS;
   const dim3 grid((unsigned)ceil_div(m * c, 256)), block(256);
-  switch (dtype) {
-    case WCN_F32:
-      hipLaunchKernelGGL(segment_reduce_kernel<float>, grid, block, 0, s, (const float*)in, splits, m, c, op, (float*)out, arg);
-      break;
-    case WCN_F16:
-      hipLaunchKernelGGL(segment_reduce_kernel<__half>, grid, block, 0, s, (const __half*)in, splits, m, c, op, (__half*)out, arg);
-      break;
-    case WCN_BF16:
-      hipLaunchKernelGGL(segment_reduce_kernel<__hip_bfloat16>, grid, block, 0, s, (const __hip_bfloat16*)in, splits, m, c,
-                         op, (__hip_bfloat16*)out, arg);
-      break;
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
-  return launch_status();
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(segment_reduce_kernel<T>, grid, block, 0, s, (const T*)in, splits, m, c, op, (T*)out, arg);
+    return launch_status();
+  });
 }
 
 }  // namespace wcn

@@ -10,8 +10,6 @@
 // hold adjacent 16-B pieces of one feature row, so every neighbour access is a whole-row (coalesced) read; fp32
 // accumulation.  The reference runs this as to_csr (a device sort) + feature gather + torch_scatter.segment_csr
 // (warpconvnet/nn/functional/sparse_pool.py:84-110); here it is one pass over the table with no intermediate tensor.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include <cfloat>
 
@@ -42,7 +40,7 @@ __global__ __launch_bounds__(256) void pool_gather_kernel(const T* __restrict__ 
     const Vec<T, VEC> x = *reinterpret_cast<const Vec<T, VEC>*>(in + (int64_t)r * c + (int64_t)v * VEC);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const float f = Cvt<T>::ld(x.v[j]);
+      const float f = (float)x.v[j];
       if (op == kPoolMax) { if (n == 0 || f > acc[j]) { acc[j] = f; best[j] = r; } }
       else if (op == kPoolMin) { if (n == 0 || f < acc[j]) { acc[j] = f; best[j] = r; } }
       else acc[j] += f;
@@ -52,7 +50,7 @@ __global__ __launch_bounds__(256) void pool_gather_kernel(const T* __restrict__ 
   Vec<T, VEC> y;
   const float scale = (op == kPoolMean && n > 0) ? 1.0f / (float)n : 1.0f;
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) y.v[j] = Cvt<T>::st(acc[j] * scale);
+  for (int j = 0; j < VEC; ++j) y.v[j] = (T)(acc[j] * scale);
   *reinterpret_cast<Vec<T, VEC>*>(out + row * c + (int64_t)v * VEC) = y;
   if (arg) {
 #pragma unroll
@@ -81,11 +79,11 @@ __global__ __launch_bounds__(256) void pool_select_kernel(const T* __restrict__ 
     const Vec<T, VEC> g = *reinterpret_cast<const Vec<T, VEC>*>(dy + at);
 #pragma unroll
     for (int j = 0; j < VEC; ++j)
-      if (arg[at + j] == (int32_t)row) acc[j] += Cvt<T>::ld(g.v[j]);
+      if (arg[at + j] == (int32_t)row) acc[j] += (float)g.v[j];
   }
   Vec<T, VEC> y;
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) y.v[j] = Cvt<T>::st(acc[j]);
+  for (int j = 0; j < VEC; ++j) y.v[j] = (T)acc[j];
   *reinterpret_cast<Vec<T, VEC>*>(dx + row * c + (int64_t)v * VEC) = y;
 }
 
@@ -131,12 +129,10 @@ int wcn_pool_gather(const void* in, const int32_t* tbl, int64_t n_in, int64_t n_
   if (!tbl || !out || (n_in > 0 && !in)) return WCN_ERROR_INVALID_PARAMETERS;
   const int kp = wcn_kmap_row_pitch(num_offsets);
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case WCN_F32: return pool_gather_t<float>(in, tbl, n_out, channels, num_offsets, kp, op, out, arg, count, s);
-    case WCN_F16: return pool_gather_t<__half>(in, tbl, n_out, channels, num_offsets, kp, op, out, arg, count, s);
-    case WCN_BF16: return pool_gather_t<__hip_bfloat16>(in, tbl, n_out, channels, num_offsets, kp, op, out, arg, count, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) {
+    return pool_gather_t<decltype(t)>(in, tbl, n_out, channels, num_offsets, kp, op, out, arg, count, s);
+  });
 }
 
 int wcn_pool_select(const void* dy, const int32_t* arg, const int32_t* tbl, int64_t n_in, int64_t n_out, int32_t channels,
@@ -146,12 +142,10 @@ int wcn_pool_select(const void* dy, const int32_t* arg, const int32_t* tbl, int6
   if (!tbl || !dx || (n_out > 0 && (!dy || !arg))) return WCN_ERROR_INVALID_PARAMETERS;
   const int kp = wcn_kmap_row_pitch(num_offsets);
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case WCN_F32: return pool_select_t<float>(dy, arg, tbl, n_in, channels, num_offsets, kp, dx, s);
-    case WCN_F16: return pool_select_t<__half>(dy, arg, tbl, n_in, channels, num_offsets, kp, dx, s);
-    case WCN_BF16: return pool_select_t<__hip_bfloat16>(dy, arg, tbl, n_in, channels, num_offsets, kp, dx, s);
-    default: return WCN_ERROR_UNSUPPORTED_CONFIG;
-  }
+  if (!dtype_ok(dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  return with_dtype(dtype, [&](auto t) {
+    return pool_select_t<decltype(t)>(dy, arg, tbl, n_in, channels, num_offsets, kp, dx, s);
+  });
 }
 
 }  // extern "C"

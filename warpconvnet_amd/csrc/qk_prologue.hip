@@ -133,12 +133,9 @@ __global__ __launch_bounds__(kQkThreads) void qk_fwd_kernel(const TI* __restrict
     for (int k = 0; k < NCH; ++k) {
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
-        const Vec<TI, EPL> v = *reinterpret_cast<const Vec<TI, EPL>*>(x + t * row_elems + col0 + c * EPL);
+        ld_vec(x + t * row_elems + col0 + c * EPL, f[k]);
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-          f[k][e] = (float)v.v[e];
-          ss += f[k][e] * f[k][e];
-        }
+        for (int e = 0; e < EPL; ++e) ss += f[k][e] * f[k][e];
       } else {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) f[k][e] = 0.f;
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(kQkThreads) void qk_fwd_kernel(const TI* __restrict
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
         if (qk && g.rot_pairs > 0) qk_rotate<EPL>(f[k], table + t * (2 * (int64_t)g.rot_pairs), c * (EPL / 2), g.rot_pairs, sgn);
-        Vec<TO, EPL> o;
+        Vec<TO, EPL> o;  // not st_vec, nor ld_vec for x in the backward: the compiler orders and allocates them differently
 #pragma unroll
         for (int e = 0; e < EPL; ++e) o.v[e] = (TO)f[k][e];
         *reinterpret_cast<Vec<TO, EPL>*>(out + t * row_elems + col0 + c * EPL) = o;
@@ -213,9 +210,7 @@ __global__ __launch_bounds__(kQkThreads) void qk_bwd_kernel(const TG* __restrict
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
         const int64_t at = t * row_elems + col0 + c * EPL;
-        const Vec<TG, EPL> gv = *reinterpret_cast<const Vec<TG, EPL>*>(dout + at);
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) dy[k][e] = (float)gv.v[e];
+        ld_vec(dout + at, dy[k]);
         if (qk) {
           const Vec<TX, EPL> xv = *reinterpret_cast<const Vec<TX, EPL>*>(x + at);
           if (g.rot_pairs > 0) qk_rotate<EPL>(dy[k], table + t * (2 * (int64_t)g.rot_pairs), c * (EPL / 2), g.rot_pairs, -1.f);
@@ -241,10 +236,10 @@ __global__ __launch_bounds__(kQkThreads) void qk_bwd_kernel(const TG* __restrict
     for (int k = 0; k < NCH; ++k) {
       const int c = l.gl + k * g.group;
       if (mine[k] && act) {
-        Vec<TX, EPL> o;
+        float o[EPL];
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) o.v[e] = (TX)(qk ? (dy[k][e] - xh[k][e] * dot) * inv : dy[k][e]);
-        *reinterpret_cast<Vec<TX, EPL>*>(dx + t * row_elems + col0 + c * EPL) = o;
+        for (int e = 0; e < EPL; ++e) o[e] = qk ? (dy[k][e] - xh[k][e] * dot) * inv : dy[k][e];
+        st_vec(dx + t * row_elems + col0 + c * EPL, o);
       }
     }
   }
@@ -299,7 +294,6 @@ __global__ __launch_bounds__(256) void rope_table_kernel(const TC* __restrict__ 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static int qk_elem_size(int dtype) { return dtype == WCN_F32 ? 4 : 2; }
 static int qk_pow2_ceil(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -363,18 +357,11 @@ static int qk_bwd_t(const void* dout, const void* x, void* dx, const float* tabl
 // in dtype x out dtype of the one-pass kernel (the backward without a norm writes the input's dtype, f32 included)
 static int qk_fwd_any(const void* x, int in_dtype, void* out, int out_dtype, const float* table, const float* gq,
                       const float* gk, float* inv_norm, const QkPath& p, int conjugate, hipStream_t s) {
-#define WCN_QK_OUT(TI)                                                                                        \
-  switch (out_dtype) {                                                                                        \
-    case WCN_F32: return qk_fwd_t<TI, float>(x, out, table, gq, gk, inv_norm, p, conjugate, s);               \
-    case WCN_F16: return qk_fwd_t<TI, _Float16>(x, out, table, gq, gk, inv_norm, p, conjugate, s);            \
-    default: return qk_fwd_t<TI, __bf16>(x, out, table, gq, gk, inv_norm, p, conjugate, s);                   \
-  }
-  switch (in_dtype) {
-    case WCN_F32: WCN_QK_OUT(float)
-    case WCN_F16: WCN_QK_OUT(_Float16)
-    default: WCN_QK_OUT(__bf16)
-  }
-#undef WCN_QK_OUT
+  return with_dtype(in_dtype, [&](auto ti) {
+    return with_dtype(out_dtype, [&](auto to) {
+      return qk_fwd_t<decltype(ti), decltype(to)>(x, out, table, gq, gk, inv_norm, p, conjugate, s);
+    });
+  });
 }
 
 // Shared argument checks.  Returns WCN_SUCCESS, an error, or 1 = valid but nothing to launch.
@@ -389,7 +376,7 @@ static int qk_check(const void* a, int a_dtype, const void* b, int b_dtype, bool
   if (total == 0) return 1;
   if (!a || !b || (rot_pairs > 0 && !table)) return WCN_ERROR_INVALID_PARAMETERS;
   // whole pairs are the smallest access; 8-B table entries
-  if (!aligned_to(a, 2 * (size_t)qk_elem_size(a_dtype)) || !aligned_to(b, 2 * (size_t)qk_elem_size(b_dtype)) ||
+  if (!aligned_to(a, 2 * (size_t)dtype_bytes(a_dtype)) || !aligned_to(b, 2 * (size_t)dtype_bytes(b_dtype)) ||
       (table && !aligned_to(table, 8)))
     return WCN_ERROR_INVALID_PARAMETERS;
   return WCN_SUCCESS;
@@ -437,7 +424,7 @@ int wcn_qk_prologue_fwd(const void* qkv, int32_t in_dtype, int64_t total, int32_
   int st = qk_check(qkv, in_dtype, out, out_dtype, true, total, heads, head_dim, table, rot_pairs, gamma_q, gamma_k);
   if (st == WCN_SUCCESS && gamma_q && !inv_norm) st = WCN_ERROR_INVALID_PARAMETERS;
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
-  const QkPath p = qk_path(total, heads, head_dim, rot_pairs, qk_elem_size(in_dtype), qk_elem_size(out_dtype), qk_all_aligned16(qkv, out));
+  const QkPath p = qk_path(total, heads, head_dim, rot_pairs, dtype_bytes(in_dtype), dtype_bytes(out_dtype), qk_all_aligned16(qkv, out));
   return qk_fwd_any(qkv, in_dtype, out, out_dtype, table, gamma_q, gamma_k, inv_norm, p, conjugate ? 1 : 0, (hipStream_t)stream);
 }
 
@@ -451,26 +438,22 @@ int wcn_qk_prologue_bwd(const void* dout, int32_t dout_dtype, const void* qkv, i
   if ((st == WCN_SUCCESS || st == 1) && norm && workspace_bytes < wcn_qk_prologue_workspace_bytes(total, heads, head_dim))
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st == WCN_SUCCESS && norm &&
-      (!qkv || !inv_norm || !dgamma_q || !dgamma_k || !workspace || !aligned_to(qkv, 2 * (size_t)qk_elem_size(in_dtype))))
+      (!qkv || !inv_norm || !dgamma_q || !dgamma_k || !workspace || !aligned_to(qkv, 2 * (size_t)dtype_bytes(in_dtype))))
     st = WCN_ERROR_INVALID_PARAMETERS;
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
   hipStream_t s = (hipStream_t)stream;
-  const int sx = qk_elem_size(in_dtype), sg = qk_elem_size(dout_dtype);
+  const int sx = dtype_bytes(in_dtype), sg = dtype_bytes(dout_dtype);
   if (!norm) {
     const QkPath p = qk_path(total, heads, head_dim, rot_pairs, sg, sx, qk_all_aligned16(dout, dqkv));
     return qk_fwd_any(dout, dout_dtype, dqkv, in_dtype, table, nullptr, nullptr, nullptr, p, 1, s);
   }
   const QkPath p = qk_path(total, heads, head_dim, rot_pairs, sx, sg, qk_all_aligned16(dout, dqkv, qkv));
   float* partial = (float*)workspace;
-#define WCN_QK_G(TX)                                                                                              \
-  st = dout_dtype == WCN_F16 ? qk_bwd_t<TX, _Float16>(dout, qkv, dqkv, table, gamma_q, gamma_k, inv_norm, partial, p, s) \
-                             : qk_bwd_t<TX, __bf16>(dout, qkv, dqkv, table, gamma_q, gamma_k, inv_norm, partial, p, s);
-  switch (in_dtype) {
-    case WCN_F32: WCN_QK_G(float) break;
-    case WCN_F16: WCN_QK_G(_Float16) break;
-    default: WCN_QK_G(__bf16) break;
-  }
-#undef WCN_QK_G
+  st = with_dtype(in_dtype, [&](auto tx) {
+    return with_dtype16(dout_dtype, [&](auto tg) {
+      return qk_bwd_t<decltype(tx), decltype(tg)>(dout, qkv, dqkv, table, gamma_q, gamma_k, inv_norm, partial, p, s);
+    });
+  });
   if (st != WCN_SUCCESS) return st;
   const int hd = heads * head_dim;
   hipLaunchKernelGGL(qk_dgamma_final_kernel, dim3((unsigned)ceil_div(2 * (int64_t)hd, 16)), dim3(256), 0, s,

@@ -17,8 +17,6 @@
 // all lanes that share it.  No LDS, no atomics; the results do not depend on the launch shape.
 // Reference (pure torch): zeros + indexed write / indexed read, unique, repeat_interleave, nonzero
 // (warpconvnet/nn/modules/sparse_resample.py:155-287, nn/functional/sparse_ops.py:33-65).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include "wcn_common.h"
 
@@ -100,8 +98,6 @@ static int unpack_u(const void* src, const int32_t* tbl, int64_t P, int64_t n_ds
                      P, n_dst, n_per, pitch, sc, u, rows, broadcast, (U*)dst);
   return launch_status();
 }
-
-static inline int elem_bytes(int dtype) { return dtype == WCN_F32 ? 4 : (dtype == WCN_F16 || dtype == WCN_BF16) ? 2 : 0; }
 
 // ---- expand --------------------------------------------------------------------------------------------------------------
 struct ExpandWs {
@@ -210,7 +206,7 @@ extern "C" {
 int wcn_resample_pack(const void* src, const int32_t* tbl, int64_t n_src, int64_t n_parent, int32_t channels, int32_t n_per,
                       int32_t factor, int32_t pitch, int32_t slot_order, int32_t dtype, void* dst, wcn_stream_t stream) {
   if (n_src < 0 || n_parent < 0 || channels < 1 || n_per < 1 || pitch < n_per) return WCN_ERROR_INVALID_PARAMETERS;
-  const int eb = elem_bytes(dtype);
+  const int eb = dtype_ok(dtype) ? dtype_bytes(dtype) : 0;
   SlotCols sc;
   if (!eb || n_per > kRsMaxPer || !slot_cols(n_per, factor, slot_order, &sc)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if ((int64_t)channels * n_per * eb > (1ll << 24)) return WCN_ERROR_UNSUPPORTED_CONFIG;
@@ -228,7 +224,7 @@ int wcn_resample_unpack(const void* src, const int32_t* tbl, int64_t n_parent, i
                         int32_t factor, int32_t pitch, int32_t slot_order, int32_t broadcast, int32_t dtype, void* dst,
                         wcn_stream_t stream) {
   if (n_dst < 0 || n_parent < 0 || channels < 1 || n_per < 1 || (tbl && pitch < n_per)) return WCN_ERROR_INVALID_PARAMETERS;
-  const int eb = elem_bytes(dtype);
+  const int eb = dtype_ok(dtype) ? dtype_bytes(dtype) : 0;
   SlotCols sc;
   if (!eb || n_per > kRsMaxPer || !slot_cols(n_per, factor, slot_order, &sc)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if ((int64_t)channels * n_per * eb > (1ll << 24)) return WCN_ERROR_UNSUPPORTED_CONFIG;

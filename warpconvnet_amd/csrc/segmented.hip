@@ -23,7 +23,6 @@
 #include <float.h>
 
 #include <initializer_list>
-#include <type_traits>
 
 #include "row_lists.h"
 
@@ -46,48 +45,6 @@ struct SegGeom {
 };
 
 __host__ __device__ constexpr int seg_planes(int mode) { return mode == kSegRange ? 4 : 2; }
-
-// ---- element access -------------------------------------------------------------------------------------------------------
-template <typename T, int VEC>
-__device__ __forceinline__ void seg_ld(const T* __restrict__ p, float (&o)[VEC]) {
-  const Vec<T, VEC> v = *reinterpret_cast<const Vec<T, VEC>*>(p);
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) o[e] = Cvt<T>::ld(v.v[e]);
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void seg_st(T* __restrict__ p, const float (&o)[VEC]) {
-  Vec<T, VEC> v;
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) v.v[e] = Cvt<T>::st(o[e]);
-  *reinterpret_cast<Vec<T, VEC>*>(p) = v;
-}
-
-// fp32 planes in 16-B pieces (VEC = 4 or 8) or single floats (VEC = 1)
-template <int VEC>
-__device__ __forceinline__ void seg_ldf(const float* __restrict__ p, float (&o)[VEC]) {
-  if constexpr (VEC % 4 == 0) {
-#pragma unroll
-    for (int e = 0; e < VEC; e += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(p + e);
-      o[e] = v.x; o[e + 1] = v.y; o[e + 2] = v.z; o[e + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) o[e] = p[e];
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void seg_stf(float* __restrict__ p, const float (&o)[VEC]) {
-  if constexpr (VEC % 4 == 0) {
-#pragma unroll
-    for (int e = 0; e < VEC; e += 4) *reinterpret_cast<float4*>(p + e) = make_float4(o[e], o[e + 1], o[e + 2], o[e + 3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) p[e] = o[e];
-  }
-}
 
 // rows [lo, hi) of segment k, inside [0, rows] whatever cu holds
 __device__ __forceinline__ void seg_span(const int32_t* __restrict__ cu, int k, int64_t rows, int64_t& lo, int64_t& hi) {
@@ -185,7 +142,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_chunk_kernel(const T* __restr
 #pragma unroll
       for (int e = 0; e < VEC; ++e) ctr[e] = 0.f;
       if constexpr (MODE == kSegDot) {
-        if (has_center) seg_ldf<VEC>(center + (int64_t)k * C + c0, ctr);
+        if (has_center) ld_vec<float, VEC>(center + (int64_t)k * C + c0, ctr);
       }
       float n = 0.f;
       for (int i = rs; i < len; i += R) {
@@ -193,7 +150,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_chunk_kernel(const T* __restr
         const int64_t at = row * C + c0;
         float v[VEC];
         if constexpr (MODE == kSegMoments) {
-          seg_ld<T, VEC>(x + at, v);
+          ld_vec<T, VEC>(x + at, v);
           n += 1.f;
           const float inv = 1.f / n;
 #pragma unroll
@@ -203,7 +160,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_chunk_kernel(const T* __restr
             b[e] += d * (v[e] - a[e]);
           }
         } else if constexpr (RANGE) {
-          seg_ld<T, VEC>(x + at, v);
+          ld_vec<T, VEC>(x + at, v);
           const bool first = i == rs;  // the slot's first row is taken as it is
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {  // rows ascend: a strict comparison keeps the first
@@ -211,12 +168,12 @@ __global__ __launch_bounds__(kSegThreads) void seg_chunk_kernel(const T* __restr
             if (first || v[e] > b[e]) { b[e] = v[e]; ib[e] = (int)row; }
           }
         } else {
-          seg_ld<T, VEC>(g + at, v);
+          ld_vec<T, VEC>(g + at, v);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) a[e] += v[e];
           if (has_x) {
             float xv[VEC];
-            seg_ld<T, VEC>(x + at, xv);
+            ld_vec<T, VEC>(x + at, xv);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) b[e] += v[e] * (xv[e] - ctr[e]);
           }
@@ -258,14 +215,14 @@ __global__ __launch_bounds__(kSegThreads) void seg_chunk_kernel(const T* __restr
     }
     if (rs == 0 && col_ok) {
       float* p = part + (w * PL) * (int64_t)C + c0;
-      seg_stf<VEC>(p, a);
-      seg_stf<VEC>(p + C, b);
+      st_vec<float, VEC>(p, a);
+      st_vec<float, VEC>(p + C, b);
       if constexpr (RANGE) {
         float fa[VEC], fb[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) { fa[e] = __int_as_float(ia[e]); fb[e] = __int_as_float(ib[e]); }
-        seg_stf<VEC>(p + 2 * (int64_t)C, fa);
-        seg_stf<VEC>(p + 3 * (int64_t)C, fb);
+        st_vec<float, VEC>(p + 2 * (int64_t)C, fa);
+        st_vec<float, VEC>(p + 3 * (int64_t)C, fb);
       }
     }
   }
@@ -399,8 +356,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_apply_kernel(const SegApplyAr
       for (int e = 0; e < VEC; ++e) { gm[e] = 1.f; bt[e] = 0.f; u[e] = 0.f; v[e] = 0.f; }
       float m0[KIND == kSegNormBwd ? VEC : 1], m1[KIND == kSegNormBwd ? VEC : 1];
       if constexpr (KIND != kSegArith) {
-        if (p.gamma) seg_ldf<VEC>(p.gamma + c0, gm);
-        if (p.beta) seg_ldf<VEC>(p.beta + c0, bt);
+        if (p.gamma) ld_vec<float, VEC>(p.gamma + c0, gm);
+        if (p.beta) ld_vec<float, VEC>(p.beta + c0, bt);
       }
       int b = b0;
       int64_t next = b + 1 < K ? (int64_t)cu[b + 1] : LLONG_MAX;
@@ -415,25 +372,24 @@ __global__ __launch_bounds__(kSegThreads) void seg_apply_kernel(const SegApplyAr
           fresh = false;
           const int64_t at = (int64_t)b * C + c0;
           if constexpr (KIND == kSegArith) {
-            if constexpr (std::is_same<Y, float>::value) seg_ldf<VEC>(y + at, u);
-            else seg_ld<Y, VEC>(y + at, u);
+            ld_vec<Y, VEC>(y + at, u);
           } else {
-            if (p.a) seg_ldf<VEC>(p.a + at, u);
-            seg_ldf<VEC>(p.r + at, v);
+            if (p.a) ld_vec<float, VEC>(p.a + at, u);
+            ld_vec<float, VEC>(p.r + at, v);
           }
           if constexpr (KIND == kSegNormBwd) {
             int64_t lo, hi;
             seg_span(cu, b, q.rows, lo, hi);
             const float inv_n = 1.f / (float)(hi - lo > 1 ? hi - lo : 1);
-            seg_ldf<VEC>(p.s0 + at, m0);
-            seg_ldf<VEC>(p.s1 + at, m1);
+            ld_vec<float, VEC>(p.s0 + at, m0);
+            ld_vec<float, VEC>(p.s1 + at, m1);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) { m0[e] *= inv_n; m1[e] *= inv_n; }
           }
         }
         const int64_t at = t * C + c0;
         float xv[VEC], o[VEC];
-        seg_ld<T, VEC>(x + at, xv);
+        ld_vec<T, VEC>(x + at, xv);
         if constexpr (KIND == kSegArith) {
 #pragma unroll
           for (int e = 0; e < VEC; ++e)
@@ -444,7 +400,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_apply_kernel(const SegApplyAr
           for (int e = 0; e < VEC; ++e) o[e] = ((xv[e] - u[e]) * v[e]) * gm[e] + bt[e];
         } else {
           float gv[VEC];
-          seg_ld<T, VEC>(g + at, gv);
+          ld_vec<T, VEC>(g + at, gv);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
             // No contraction here: g gamma is rounded on its own, as it was inside s0.  In a one-row segment (r = 1 /
@@ -456,7 +412,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_apply_kernel(const SegApplyAr
             o[e] = v[e] * ((gg - m0[e]) - xhat * m1[e]);
           }
         }
-        seg_st<T, VEC>(out + at, o);
+        st_vec<T, VEC>(out + at, o);
       }
     }
   }
@@ -520,19 +476,6 @@ static void seg_apply_launch(int kind, const SegApplyArgs& a, const SegGeom& q, 
     hipLaunchKernelGGL((seg_apply_kernel<T, T, VEC, kSegNormBwd>), grid, dim3(kSegThreads), 0, s, a, q);
 }
 
-// FN<T, VEC>(...) for the dtype and the piece width
-#define WCN_SEG_DISPATCH(FN, dtype, vec, ...)                                          \
-  do {                                                                                 \
-    if ((dtype) == WCN_F32) {                                                          \
-      if ((vec) == 1) FN<float, 1>(__VA_ARGS__); else FN<float, 4>(__VA_ARGS__);       \
-    } else if ((dtype) == WCN_F16) {                                                   \
-      if ((vec) == 1) FN<__half, 1>(__VA_ARGS__); else FN<__half, 8>(__VA_ARGS__);     \
-    } else {                                                                           \
-      if ((vec) == 1) FN<__hip_bfloat16, 1>(__VA_ARGS__);                              \
-      else FN<__hip_bfloat16, 8>(__VA_ARGS__);                                         \
-    }                                                                                  \
-  } while (0)
-
 template <typename T, int VEC>
 static void seg_apply_y(int kind, bool y_f32, const SegApplyArgs& a, const SegGeom& q, hipStream_t s) {
   if (y_f32) seg_apply_launch<T, float, VEC>(kind, a, q, s);
@@ -580,7 +523,7 @@ int wcn_seg_stats(int32_t mode, const void* x, const void* g, const float* cente
   if (!aligned_to(cu, 4) || !aligned_to(workspace, 16) || !aligned_to(center, 4) ||
       workspace_bytes < wcn_seg_stats_workspace_bytes(rows, num_segs, channels, mode))
     return WCN_ERROR_INVALID_PARAMETERS;
-  const size_t el = dtype == WCN_F32 ? 4 : 2;
+  const size_t el = dtype_bytes(dtype);
   if (!aligned_to(x, el) || !aligned_to(g, el)) return WCN_ERROR_INVALID_PARAMETERS;
 
   const int vec = seg_vec(dtype, channels, {x, g, center});
@@ -588,8 +531,10 @@ int wcn_seg_stats(int32_t mode, const void* x, const void* g, const float* cente
   int32_t* cs = (int32_t*)workspace;
   float* part = (float*)((char*)workspace + seg_plan_bytes(num_segs));
   hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(kSegThreads), 0, s, cu, q.num_segs, rows, q.cap, cs);
-  WCN_SEG_DISPATCH(seg_stats_launch, dtype, vec, mode, x, dot ? g : nullptr, dot ? center : nullptr, cu, (const int32_t*)cs, part,
-                   q, s);
+  with_dtype_vec<false>(dtype, vec, [&](auto t, auto v) {
+    seg_stats_launch<decltype(t), v()>(mode, x, dot ? g : nullptr, dot ? center : nullptr, cu, (const int32_t*)cs, part, q, s);
+    return 0;
+  });
   const dim3 mgrid(capped_grid(num_segs), (unsigned)ceil_div(channels, kSegMergeCols));
   const dim3 mblock(kSegMergeCols * kSegMergeSlices);
   if (mode == WCN_SEG_MOMENTS)
@@ -617,8 +562,8 @@ int wcn_seg_apply(int32_t op, const void* x, const void* g, const void* y, int32
   if (!x || !cu || !out) return WCN_ERROR_INVALID_PARAMETERS;
   if (kind == kSegArith ? !y : !r) return WCN_ERROR_INVALID_PARAMETERS;
   if (kind == kSegNormBwd && (!g || !s0 || !s1)) return WCN_ERROR_INVALID_PARAMETERS;
-  const size_t el = dtype == WCN_F32 ? 4 : 2;
-  if (!aligned_to(x, el) || !aligned_to(g, el) || !aligned_to(out, el) || !aligned_to(y, y_dtype == WCN_F32 ? 4 : 2) ||
+  const size_t el = dtype_bytes(dtype);
+  if (!aligned_to(x, el) || !aligned_to(g, el) || !aligned_to(out, el) || !aligned_to(y, dtype_bytes(y_dtype)) ||
       !aligned_to(a, 4) || !aligned_to(r, 4) || !aligned_to(gamma, 4) || !aligned_to(beta, 4) || !aligned_to(s0, 4) ||
       !aligned_to(s1, 4) || !aligned_to(cu, 4))
     return WCN_ERROR_INVALID_PARAMETERS;
@@ -640,6 +585,9 @@ int wcn_seg_apply(int32_t op, const void* x, const void* g, const void* y, int32
   // a [K, c] plane in the row dtype is read in pieces of the row's width, an fp32 one in 16-B pieces of floats
   const int vec = seg_vec(dtype, channels, {x, args.g, args.y, args.a, args.r, args.gamma, args.beta, args.s0, args.s1, out});
   const SegGeom q = seg_geom(rows, num_segs, channels, vec);
-  WCN_SEG_DISPATCH(seg_apply_y, dtype, vec, kind, y_f32, args, q, (hipStream_t)stream);
+  with_dtype_vec<false>(dtype, vec, [&](auto t, auto v) {
+    seg_apply_y<decltype(t), v()>(kind, y_f32, args, q, (hipStream_t)stream);
+    return 0;
+  });
   return launch_status();
 }

@@ -17,8 +17,6 @@
 //                             concatenation in the same pass), pool backward (1 / count, or the arg-match of max / min).
 // No float atomics anywhere; the integer atomics (status word, longest segment, the list of long segments) give the same
 // result in any order.  Every grid is capped at kRowMaxGrid workgroups and strides.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include <cfloat>
 
@@ -127,46 +125,6 @@ __global__ __launch_bounds__(kRowThreads) void vx_finish_kernel(const int64_t* _
   longest_row_max(longest, summary + 1);
 }
 
-// ---- element types ----------------------------------------------------------------------------------------------------------
-template <int D> struct El;
-template <> struct El<WCN_F32> {
-  using S = float;
-  static __device__ __forceinline__ float ld(S s) { return s; }
-  static __device__ __forceinline__ S st(float f) { return f; }
-};
-template <> struct El<WCN_F16> {
-  using S = uint16_t;
-  static __device__ __forceinline__ float ld(S s) { return __half2float(__ushort_as_half(s)); }
-  static __device__ __forceinline__ S st(float f) { return __half_as_ushort(__float2half(f)); }
-};
-template <> struct El<WCN_BF16> {
-  using S = uint16_t;
-  static __device__ __forceinline__ float ld(S s) { return __uint_as_float((uint32_t)s << 16); }
-  static __device__ __forceinline__ S st(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-};
-
-template <typename S, int V>
-struct __attribute__((aligned(sizeof(S) * V))) Pack {
-  S v[V];
-};
-
-template <int D, int V>
-__device__ __forceinline__ void ld_pack(const typename El<D>::S* p, float (&f)[V]) {
-  using S = typename El<D>::S;
-  const Pack<S, V> q = *reinterpret_cast<const Pack<S, V>*>(p);
-#pragma unroll
-  for (int e = 0; e < V; ++e) f[e] = El<D>::ld(q.v[e]);
-}
-
-template <int D, int V>
-__device__ __forceinline__ void st_pack(typename El<D>::S* p, const float (&f)[V]) {
-  using S = typename El<D>::S;
-  Pack<S, V> q;
-#pragma unroll
-  for (int e = 0; e < V; ++e) q.v[e] = El<D>::st(f[e]);
-  *reinterpret_cast<Pack<S, V>*>(p) = q;
-}
-
 // ---- c. CSR gather-reduce ---------------------------------------------------------------------------------------------------
 struct CgLong : RowList {  // the long segments and their chunks, listed per call, and the chunks' partials
   float* part;        // [item_cap][c]
@@ -199,8 +157,8 @@ static CgLong cg_carve(void* base, int64_t nnz, int64_t c, bool with_arg) {
 }
 
 // rows [j0, j1) of one list, ascending, into acc (and the first extremum's row into best); `col` .. col + V - 1 of every row
-template <int D, int V>
-__device__ __forceinline__ void cg_rows(const typename El<D>::S* __restrict__ in, int64_t ld_in, int64_t n_in,
+template <typename T, int V>
+__device__ __forceinline__ void cg_rows(const T* __restrict__ in, int64_t ld_in, int64_t n_in,
                                         const int64_t* __restrict__ indices, int64_t j0, int64_t j1, int col, int op,
                                         float (&acc)[V], int64_t (&best)[V]) {
   auto take = [&](int64_t row, const float (&f)[V]) {
@@ -224,7 +182,7 @@ __device__ __forceinline__ void cg_rows(const typename El<D>::S* __restrict__ in
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (r[u] >= 0 && r[u] < n_in) {
-        ld_pack<D, V>(in + r[u] * ld_in + col, f[u]);
+        ld_vec<T, V>(in + r[u] * ld_in + col, f[u]);
       } else {
 #pragma unroll
         for (int e = 0; e < V; ++e) f[u][e] = 0.f;
@@ -237,7 +195,7 @@ __device__ __forceinline__ void cg_rows(const typename El<D>::S* __restrict__ in
     const int64_t r = indices ? indices[j] : j;
     float f[V];
     if (r >= 0 && r < n_in) {
-      ld_pack<D, V>(in + r * ld_in + col, f);
+      ld_vec<T, V>(in + r * ld_in + col, f);
     } else {
 #pragma unroll
       for (int e = 0; e < V; ++e) f[e] = 0.f;
@@ -248,12 +206,12 @@ __device__ __forceinline__ void cg_rows(const typename El<D>::S* __restrict__ in
 
 // L lanes (a power of two <= 64) own one list: ITEMS = false, a whole segment (longer ones are skipped when `split`);
 // ITEMS = true, one chunk of a long segment into the fp32 partials.  Rows wider than L * V channels take several trips.
-template <int D, int V, bool ITEMS>
-__global__ __launch_bounds__(kRowThreads) void cg_reduce_kernel(const typename El<D>::S* __restrict__ in, int64_t ld_in,
+template <typename T, int V, bool ITEMS>
+__global__ __launch_bounds__(kRowThreads) void cg_reduce_kernel(const T* __restrict__ in, int64_t ld_in,
                                                                int64_t n_in, const int64_t* __restrict__ indices,
                                                                const int64_t* __restrict__ offsets, int64_t m, int64_t nnz,
                                                                int c, int L, int op, int split,
-                                                               typename El<D>::S* __restrict__ out, int64_t* __restrict__ arg,
+                                                               T* __restrict__ out, int64_t* __restrict__ arg,
                                                                CgLong w) {
   const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
@@ -268,7 +226,7 @@ __global__ __launch_bounds__(kRowThreads) void cg_reduce_kernel(const typename E
       int64_t best[V];
 #pragma unroll
       for (int e = 0; e < V; ++e) { acc[e] = 0.f; best[e] = -1; }
-      cg_rows<D, V>(in, ld_in, n_in, indices, j0, j1, col, op, acc, best);
+      cg_rows<T, V>(in, ld_in, n_in, indices, j0, j1, col, op, acc, best);
       if (ITEMS) {
 #pragma unroll
         for (int e = 0; e < V; ++e) {
@@ -280,7 +238,7 @@ __global__ __launch_bounds__(kRowThreads) void cg_reduce_kernel(const typename E
 #pragma unroll
           for (int e = 0; e < V; ++e) acc[e] /= (float)len;
         }
-        st_pack<D, V>(out + seg * c + col, acc);
+        st_vec<T, V>(out + seg * c + col, acc);
         if (arg) {
 #pragma unroll
           for (int e = 0; e < V; ++e) arg[seg * c + col + e] = best[e];
@@ -291,9 +249,9 @@ __global__ __launch_bounds__(kRowThreads) void cg_reduce_kernel(const typename E
 }
 
 // L lanes per long segment: its partials in chunk order
-template <int D>
+template <typename T>
 __global__ __launch_bounds__(kRowThreads) void cg_combine_kernel(const int64_t* __restrict__ offsets, int64_t m, int c, int L,
-                                                                int op, typename El<D>::S* __restrict__ out,
+                                                                int op, T* __restrict__ out,
                                                                 int64_t* __restrict__ arg, CgLong w) {
   const int groups = kRowThreads / L;
   const int g = threadIdx.x / L, sub = threadIdx.x % L;
@@ -315,33 +273,32 @@ __global__ __launch_bounds__(kRowThreads) void cg_combine_kernel(const int64_t* 
         }
       }
       if (op == kOpMean) acc /= (float)len;
-      out[seg * c + col] = El<D>::st(acc);
+      out[seg * c + col] = (T)acc;
       if (arg) arg[seg * c + col] = best;
     }
   }
 }
 
-template <int D, int V>
+template <typename T, int V>
 static void cg_launch(const void* in, int64_t ld_in, int64_t n_in, const int64_t* indices, const int64_t* offsets, int64_t m,
                       int64_t nnz, int c, int op, bool split, void* out, int64_t* arg, const CgLong& w, hipStream_t s) {
-  using S = typename El<D>::S;
   const int L = row_lanes(ceil_div(c, V)), groups = kRowThreads / L;
-  hipLaunchKernelGGL((cg_reduce_kernel<D, V, false>), dim3(capped_grid(ceil_div(m, groups))), dim3(kRowThreads), 0, s,
-                     (const S*)in, ld_in, n_in, indices, offsets, m, nnz, c, L, op, split ? 1 : 0, (S*)out, arg, w);
+  hipLaunchKernelGGL((cg_reduce_kernel<T, V, false>), dim3(capped_grid(ceil_div(m, groups))), dim3(kRowThreads), 0, s,
+                     (const T*)in, ld_in, n_in, indices, offsets, m, nnz, c, L, op, split ? 1 : 0, (T*)out, arg, w);
   if (!split) return;
   hipLaunchKernelGGL(row_list_collect_kernel<>, dim3(capped_grid(ceil_div(m, kRowThreads))), dim3(kRowThreads), 0, s, offsets, m,
                      nnz, (const RowList&)w);
-  hipLaunchKernelGGL((cg_reduce_kernel<D, V, true>), dim3(capped_grid(ceil_div(w.item_cap, groups))), dim3(kRowThreads), 0, s,
-                     (const S*)in, ld_in, n_in, indices, offsets, m, nnz, c, L, op, 1, (S*)out, arg, w);
+  hipLaunchKernelGGL((cg_reduce_kernel<T, V, true>), dim3(capped_grid(ceil_div(w.item_cap, groups))), dim3(kRowThreads), 0, s,
+                     (const T*)in, ld_in, n_in, indices, offsets, m, nnz, c, L, op, 1, (T*)out, arg, w);
   const int Lc = row_lanes(c);
-  hipLaunchKernelGGL(cg_combine_kernel<D>, dim3(capped_grid(ceil_div(w.long_cap, kRowThreads / Lc))), dim3(kRowThreads), 0, s,
-                     offsets, m, c, Lc, op, (S*)out, arg, w);
+  hipLaunchKernelGGL(cg_combine_kernel<T>, dim3(capped_grid(ceil_div(w.long_cap, kRowThreads / Lc))), dim3(kRowThreads), 0, s,
+                     offsets, m, c, Lc, op, (T*)out, arg, w);
 }
 
 // widest piece (elements per lane) that the channel count, the row strides and the pointers allow: 16 B, 8 B or one element
 static int piece_elems(int dtype, int64_t c, int64_t c2, int64_t ld_a, int64_t ld_b, const void* p0, const void* p1,
                        const void* p2) {
-  const int es = dtype == WCN_F32 ? 4 : 2;
+  const int es = dtype_bytes(dtype);
   for (int bytes = 16; bytes >= 8; bytes >>= 1) {
     const int v = bytes / es;
     if (c % v == 0 && c2 % v == 0 && ld_a % v == 0 && ld_b % v == 0 && aligned_to(p0, bytes) && aligned_to(p1, bytes) &&
@@ -353,13 +310,13 @@ static int piece_elems(int dtype, int64_t c, int64_t c2, int64_t ld_a, int64_t l
 
 // ---- d. indexed row spread --------------------------------------------------------------------------------------------------
 // one thread per V-element piece of an output row: the first c / V pieces come from src[to_orig[i]], the next cs / V from skip[i]
-template <int D, int V>
-__global__ __launch_bounds__(kRowThreads) void row_spread_kernel(const typename El<D>::S* __restrict__ src,
+template <typename T, int V>
+__global__ __launch_bounds__(kRowThreads) void row_spread_kernel(const T* __restrict__ src,
                                                                 const int64_t* __restrict__ to_orig, int64_t n, int64_t m,
-                                                                int c, const typename El<D>::S* __restrict__ skip, int cs,
+                                                                int c, const T* __restrict__ skip, int cs,
                                                                 int64_t ld_out, int mode, const int64_t* __restrict__ offsets,
                                                                 const int64_t* __restrict__ arg,
-                                                                typename El<D>::S* __restrict__ out) {
+                                                                T* __restrict__ out) {
   const int pc = c / V, pw = pc + cs / V;
   const int64_t total = n * pw;
   for (int64_t e = (int64_t)blockIdx.x * kRowThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kRowThreads) {
@@ -368,8 +325,8 @@ __global__ __launch_bounds__(kRowThreads) void row_spread_kernel(const typename 
     float f[V];
     if (p >= pc) {
       const int col = (p - pc) * V;
-      ld_pack<D, V>(skip + i * cs + col, f);
-      st_pack<D, V>(out + i * ld_out + c + col, f);
+      // the piece as it is: through floats the compiler merges this store with the one below and splits both
+      *reinterpret_cast<Vec<T, V>*>(out + i * ld_out + c + col) = *reinterpret_cast<const Vec<T, V>*>(skip + i * cs + col);
       continue;
     }
     const int col = p * V;
@@ -378,7 +335,7 @@ __global__ __launch_bounds__(kRowThreads) void row_spread_kernel(const typename 
 #pragma unroll
       for (int q = 0; q < V; ++q) f[q] = 0.f;
     } else {
-      ld_pack<D, V>(src + v * c + col, f);
+      ld_vec<T, V>(src + v * c + col, f);
       if (mode == kSpreadInvCount) {
         const int64_t len = offsets[v + 1] - offsets[v];
         const float cnt = (float)(len > 0 ? len : 1);
@@ -389,39 +346,21 @@ __global__ __launch_bounds__(kRowThreads) void row_spread_kernel(const typename 
         for (int q = 0; q < V; ++q) f[q] = arg[v * c + col + q] == i ? f[q] : 0.f;
       }
     }
-    st_pack<D, V>(out + i * ld_out + col, f);
+    st_vec<T, V>(out + i * ld_out + col, f);
   }
 }
 
-template <int D, int V>
+template <typename T, int V>
 static void spread_launch(const void* src, const int64_t* to_orig, int64_t n, int64_t m, int c, const void* skip, int cs,
                           int64_t ld_out, int mode, const int64_t* offsets, const int64_t* arg, void* out, hipStream_t s) {
-  using S = typename El<D>::S;
   const int64_t pieces = n * (int64_t)((c + cs) / V);
-  hipLaunchKernelGGL((row_spread_kernel<D, V>), dim3(capped_grid(ceil_div(pieces, kRowThreads))), dim3(kRowThreads), 0, s,
-                     (const S*)src, to_orig, n, m, c, (const S*)skip, cs, ld_out, mode, offsets, arg, (S*)out);
+  hipLaunchKernelGGL((row_spread_kernel<T, V>), dim3(capped_grid(ceil_div(pieces, kRowThreads))), dim3(kRowThreads), 0, s,
+                     (const T*)src, to_orig, n, m, c, (const T*)skip, cs, ld_out, mode, offsets, arg, (T*)out);
 }
 
 }  // namespace wcn
 
 using namespace wcn;
-
-#define WCN_VX_DISPATCH(FN, dtype, v, ...)                                              \
-  do {                                                                                  \
-    if (dtype == WCN_F32) {                                                             \
-      if (v == 4) FN<WCN_F32, 4>(__VA_ARGS__);                                          \
-      else if (v == 2) FN<WCN_F32, 2>(__VA_ARGS__);                                     \
-      else FN<WCN_F32, 1>(__VA_ARGS__);                                                 \
-    } else if (dtype == WCN_F16) {                                                      \
-      if (v == 8) FN<WCN_F16, 8>(__VA_ARGS__);                                          \
-      else if (v == 4) FN<WCN_F16, 4>(__VA_ARGS__);                                     \
-      else FN<WCN_F16, 1>(__VA_ARGS__);                                                 \
-    } else {                                                                            \
-      if (v == 8) FN<WCN_BF16, 8>(__VA_ARGS__);                                         \
-      else if (v == 4) FN<WCN_BF16, 4>(__VA_ARGS__);                                    \
-      else FN<WCN_BF16, 1>(__VA_ARGS__);                                                \
-    }                                                                                   \
-  } while (0)
 
 extern "C" {
 
@@ -505,7 +444,10 @@ int wcn_csr_gather_reduce(const void* in, int64_t ld_in, int64_t n_in, const int
     if (hipMemsetAsync(w.counters, 0, kRowListCounterInts * 4, s) != hipSuccess) return WCN_ERROR_KERNEL_EXECUTION;
   }
   const int v = piece_elems(dtype, c, 0, ld_in, 0, in, out, nullptr);
-  WCN_VX_DISPATCH(cg_launch, dtype, v, in, ld_in, n_in, indices, offsets, m, nnz, (int)c, (int)op, split, out, arg, w, s);
+  with_dtype_vec<true>(dtype, v, [&](auto t, auto vc) {
+    cg_launch<decltype(t), vc()>(in, ld_in, n_in, indices, offsets, m, nnz, (int)c, (int)op, split, out, arg, w, s);
+    return 0;
+  });
   return launch_status();
 }
 
@@ -521,8 +463,11 @@ int wcn_row_spread(const void* src, const int64_t* to_orig, int64_t n, int64_t m
       (mode == kSpreadArgMatch && !arg))
     return WCN_ERROR_INVALID_PARAMETERS;
   const int v = piece_elems(dtype, c, cs, ld_out, 0, src, skip, out);
-  WCN_VX_DISPATCH(spread_launch, dtype, v, src, to_orig, n, m, (int)c, skip, (int)cs, ld_out, (int)mode, offsets, arg, out,
-                  (hipStream_t)stream);
+  with_dtype_vec<true>(dtype, v, [&](auto t, auto vc) {
+    spread_launch<decltype(t), vc()>(src, to_orig, n, m, (int)c, skip, (int)cs, ld_out, (int)mode, offsets, arg, out,
+                                     (hipStream_t)stream);
+    return 0;
+  });
   return launch_status();
 }
 

@@ -4,10 +4,10 @@
 // wrap-around behaviour are identical (reference: warpconvnet/csrc/include/cuhash/hash_functions.cuh:29-84).
 #pragma once
 
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/wcn.h"
 
@@ -98,31 +98,66 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool valid_k(int64_t num_offsets) { return num_offsets >= 1 && num_offsets <= 4096; }  // kernel volumes the library takes
 
-// ---- element types --------------------------------------------------------------------------------------------------------
-// The storage dtypes (WCN_F32 / WCN_F16 / WCN_BF16) as HIP's own types, converted with HIP's intrinsics.  Two other
-// conventions exist and are not this one: ada_row.h and qk_prologue.hip take _Float16 / __bf16 and convert with C casts,
-// voxelize.hip's El<D> works on raw 16-bit patterns keyed by the dtype code.
-template <typename T> struct Cvt;
-template <> struct Cvt<float> {
-  static __device__ __forceinline__ float ld(float v) { return v; }
-  static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct Cvt<__half> {
-  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
-};
-template <> struct Cvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
-};
+// ---- elements ------------------------------------------------------------------------------------------------------------
+// The one convention: a storage dtype (WCN_F32 / WCN_F16 / WCN_BF16) is float / _Float16 / __bf16 - the types the MFMA
+// fragments take - and becomes a float, and a float it, by a C cast (round to nearest even).
 
 // N elements moved as one access
 template <typename T, int N> struct alignas(sizeof(T) * N) Vec { T v[N]; };
 
-// a = a power of two; true for null (an absent optional buffer)
-inline bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// V elements at p <-> floats: one access of sizeof(T) * V bytes up to 16, beyond that 16-B pieces in ascending order
+template <typename T, int V>
+__device__ __forceinline__ void ld_vec(const T* __restrict__ p, float (&f)[V]) {
+  constexpr int P = sizeof(T) * V <= 16 ? V : 16 / (int)sizeof(T);
+  static_assert(V % P == 0, "whole pieces");
+#pragma unroll
+  for (int i = 0; i < V; i += P) {
+    const Vec<T, P> v = *reinterpret_cast<const Vec<T, P>*>(p + i);
+#pragma unroll
+    for (int e = 0; e < P; ++e) f[i + e] = (float)v.v[e];
+  }
+}
+template <typename T, int V>
+__device__ __forceinline__ void st_vec(T* __restrict__ p, const float (&f)[V]) {
+  constexpr int P = sizeof(T) * V <= 16 ? V : 16 / (int)sizeof(T);
+  static_assert(V % P == 0, "whole pieces");
+#pragma unroll
+  for (int i = 0; i < V; i += P) {
+    Vec<T, P> v;
+#pragma unroll
+    for (int e = 0; e < P; ++e) v.v[e] = (T)f[i + e];
+    *reinterpret_cast<Vec<T, P>*>(p + i) = v;
+  }
+}
 
 inline bool dtype_ok(int dtype) { return dtype == WCN_F32 || dtype == WCN_F16 || dtype == WCN_BF16; }
+inline int dtype_bytes(int dtype) { return dtype == WCN_F32 ? 4 : 2; }
+
+// f(T{}) for the element type of a dtype code (dtype_ok); with_dtype16 where the caller has ruled out WCN_F32
+template <typename F>
+inline int with_dtype(int dtype, F&& f) {
+  return dtype == WCN_F32 ? f(float{}) : dtype == WCN_F16 ? f(_Float16{}) : f(__bf16{});
+}
+template <typename F>
+inline int with_dtype16(int dtype, F&& f) {
+  return dtype == WCN_F16 ? f(_Float16{}) : f(__bf16{});
+}
+
+// f(T{}, std::integral_constant<int, V>{}) for the dtype and a piece of `vec` elements: a 16-B piece, half of one (only
+// with HALF) or, for every other `vec`, one element
+template <bool HALF, typename F>
+inline int with_dtype_vec(int dtype, int vec, F&& f) {
+  return with_dtype(dtype, [&](auto t) {
+    constexpr int W = 16 / (int)sizeof(t);
+    if (vec == W) return f(t, std::integral_constant<int, W>{});
+    if constexpr (HALF)
+      if (vec == W / 2) return f(t, std::integral_constant<int, W / 2>{});
+    return f(t, std::integral_constant<int, 1>{});
+  });
+}
+
+// a = a power of two; true for null (an absent optional buffer)
+inline bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // ---- prefix sums (wave64) -------------------------------------------------------------------------------------------------
 // inclusive scan over the first WIDTH (64 or 32) lanes of a wave; with 32 the upper half's results are unspecified

@@ -485,9 +485,10 @@ int conv_wgrad_mfma(const void* x, const void* dy, float* dw, const int32_t* in_
   if (!mfma_wgrad_supported(cin, cout, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (bias_grad && (!mfma_wgrad_bias_supported(cin, cout, dtype) || cs_k < 0 || cs_k >= K)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!workspace || workspace_bytes < wgrad_mfma_workspace(K, cin, cout)) return WCN_ERROR_INVALID_PARAMETERS;
-  if (dtype == WCN_BF16)
-    return dispatch_wgrad<__bf16>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-  return dispatch_wgrad<_Float16>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
+  return with_dtype16(dtype, [&](auto t) {
+    return dispatch_wgrad<decltype(t)>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound,
+                                       s);
+  });
 }
 
 }  // namespace wcn
