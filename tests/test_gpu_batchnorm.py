@@ -451,7 +451,7 @@ def test_backward_reads_a_column_slice_of_a_wider_gradient_in_place(dtype, c, le
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and (not tail or torch.equal(a[2], b[2]))
     else:
         # a misaligned slice takes the element path: another reduction order than the 16-B path of the contiguous copy
-        # (`block._grad_rows` hands such slices over as copies, so a network never sees the difference)
+        # (`normalizations.bn_grad_rows` hands such slices over as copies, so a network never sees the difference)
         assert rel_max_err(a[0], b[0]) < 1e-5 and rel_max_err(a[1].float(), b[1].float()) < 2e-2
         assert not tail or torch.equal(a[2], b[2])  # (the masked gradient is elementwise)
     assert L.wcn_bn_train_backward_ld(_lib.ptr(g), c - 1, _lib.ptr(y), None, 1, n, c, code, _lib.ptr(stats), _lib.ptr(gamma), 1,
@@ -461,7 +461,7 @@ def test_backward_reads_a_column_slice_of_a_wider_gradient_in_place(dtype, c, le
 def test_fused_blocks_under_a_channel_concatenation_take_the_sliced_gradient():
     """Two fused conv -> BN -> ReLU blocks whose outputs are concatenated and fed to a third (the decoder pattern of
     `models/mink_unet.py`): gradients equal the module-by-module run bit for bit - the sliced gradients reach the BatchNorm
-    backward without a contiguous copy (`block._grad_rows`)."""
+    backward without a contiguous copy (`normalizations.bn_grad_rows`)."""
     import os
 
     from warpconvnet_amd.geometry.types.voxels import Voxels
@@ -532,3 +532,90 @@ def test_narrow_stem_node_reads_fp32_rows_and_returns_an_fp32_gradient(cin, cout
 
     for u, v in zip(run(True), run(False)):
         assert torch.equal(u, v)
+
+
+def _bn_by_passes(x, g, gamma, beta, rm, rv, counter, training, relu, momentum=0.1, eps=1e-5):
+    """The BatchNorm step composed from the pass-level entries of include/wcn.h, one C call per pass.
+    -> (y, dx, dgamma, dbeta); the running statistics and the counter are updated in place."""
+    from warpconvnet_amd import _lib
+
+    L = _lib.lib()
+    dev = x.device
+    st = _lib.stream_handle(dev)
+    n, c = x.shape
+    code = _lib.dtype_code(x.dtype)
+    p = _lib.ptr
+    mean, var, rstd, scale, shift, s0, s1 = (torch.empty(c, device=dev) for _ in range(7))
+    ws = torch.empty(L.wcn_bn_workspace(c), dtype=torch.uint8, device=dev)
+    if training:
+        _lib.check(L.wcn_bn_stats_fold(p(x), n, c, code, p(gamma), p(beta), p(rm), p(rv), momentum, eps, p(mean), p(var), p(rstd),
+                                       p(scale), p(shift), p(counter), p(ws), ws.numel(), st), "wcn_bn_stats_fold")
+    else:
+        _lib.check(L.wcn_bn_fold(p(rm), p(rv), p(gamma), p(beta), eps, c, p(mean), p(rstd), p(scale), p(shift), st), "wcn_bn_fold")
+    y, dx = torch.empty_like(x), torch.empty_like(x)
+    _lib.check(L.wcn_bn_apply(p(x), n, c, code, p(scale), p(shift), int(relu), p(y), st), "wcn_bn_apply")
+    rsc, rsh = (scale, shift) if relu else (None, None)
+    _lib.check(L.wcn_bn_backward_reduce(p(g), p(x), p(rsc), p(rsh), n, c, code, p(mean), p(rstd), p(s0), p(s1), p(ws), ws.numel(), st),
+               "wcn_bn_backward_reduce")
+    a0, a1 = (s0, s1) if training else (torch.zeros(c, device=dev),) * 2  # eval: the statistics are constants
+    _lib.check(L.wcn_bn_backward_apply(p(g), p(x), p(rsc), p(rsh), n, c, code, p(mean), p(rstd), p(gamma), p(a0), p(a1), p(dx), st),
+               "wcn_bn_backward_apply")
+    return y, dx, s1, s0
+
+
+@pytest.mark.parametrize("n,c,dtype,mode", [(n, c, dtype, mode)
+                                            for n, c, dtype in ((129, 24, torch.bfloat16), (130, 40, torch.float16),
+                                                                (7, 13, torch.float32), (1, 8, torch.bfloat16))
+                                            for mode in ("train", "train_relu", "eval", "eval_relu")
+                                            if n > 1 or mode.startswith("eval")])
+def test_layer_entries_equal_the_pass_entries_bit_for_bit(n, c, dtype, mode):
+    """include/wcn.h: wcn_bn_train_forward = wcn_bn_stats_fold + wcn_bn_apply, wcn_bn_train_backward = wcn_bn_backward_reduce +
+    wcn_bn_backward_apply.  `hip_batch_norm` (the one Python caller, on the layer entries) against the same step composed here
+    from the pass entries: output, the three gradients, running statistics and the batch counter, bitwise.  Shapes: two
+    first-level workgroups with 16-B pieces in three piece columns (129 x 24 bf16), fp16 (130 x 40), the element path with
+    c % VEC != 0 (7 x 13 fp32), a single row (eval only: training refuses it)."""
+    from warpconvnet_amd.nn.functional.normalizations import hip_batch_norm
+
+    training, relu = mode.startswith("train"), mode.endswith("relu")
+    torch.manual_seed(n * c)
+    x = (torch.randn(n, c, device=DEV) * 1.5 + 0.3).to(dtype)
+    g = torch.randn(n, c, device=DEV).to(dtype)
+    gamma, beta = torch.rand(c, device=DEV) + 0.5, torch.randn(c, device=DEV) * 0.3
+    rm0, rv0 = torch.randn(c, device=DEV) * 0.2, torch.rand(c, device=DEV) + 0.5
+    rm_a, rv_a, rm_b, rv_b = rm0.clone(), rv0.clone(), rm0.clone(), rv0.clone()
+    cnt_a, cnt_b = (torch.tensor(3, device=DEV) for _ in range(2)) if training else (None, None)
+    want = _bn_by_passes(x, g, gamma, beta, rm_a, rv_a, cnt_a, training, relu)
+    xl, wl, bl = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    y = hip_batch_norm(xl, rm_b, rv_b, wl, bl, training=training, momentum=0.1, eps=1e-5, relu=relu, num_batches_tracked=cnt_b)
+    y.backward(g)
+    for name, u, v in zip(("y", "dx", "dgamma", "dbeta"), (y.detach(), xl.grad, wl.grad, bl.grad), want):
+        assert torch.equal(u, v), name
+    assert torch.equal(rm_a, rm_b) and torch.equal(rv_a, rv_b)
+    if training:
+        assert int(cnt_a) == int(cnt_b) == 4 and not torch.equal(rm_b, rm0)
+    else:
+        assert torch.equal(rm_b, rm0) and torch.equal(rv_b, rv0)
+
+
+@pytest.mark.parametrize("lo", [8, 3])
+def test_stand_alone_backward_takes_a_column_slice_of_a_wider_gradient(lo):
+    """`hip_batch_norm(...).backward` with the incoming gradient a column slice of a wider tensor: columns 8:32 of 129 x 40 bf16 have
+    16-B aligned rows and are read in place (`bn_grad_rows`), columns 3:27 are misaligned and copied.  Either way the gradients
+    equal the run on a contiguous copy bit for bit."""
+    from warpconvnet_amd.nn.functional.normalizations import bn_grad_rows, hip_batch_norm
+
+    n, c = 129, 24
+    torch.manual_seed(lo)
+    x = (torch.randn(n, c, device=DEV) + 0.2).to(torch.bfloat16)
+    gamma, beta = torch.rand(c, device=DEV) + 0.5, torch.randn(c, device=DEV) * 0.3
+    wide = torch.randn(n, 40, device=DEV).to(torch.bfloat16)
+    g = wide[:, lo:lo + c]
+    assert not g.is_contiguous() and (bn_grad_rows(g, x)[0] is g) == (lo == 8)
+
+    def run(grad):
+        xl, wl, bl = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+        hip_batch_norm(xl, None, None, wl, bl, training=True, relu=True).backward(grad)
+        return xl.grad, wl.grad, bl.grad
+
+    for name, u, v in zip(("dx", "dgamma", "dbeta"), run(g), run(g.contiguous())):
+        assert torch.equal(u, v), name

@@ -29,7 +29,7 @@ wrap(helper, "generate_output_coords_and_kernel_map")
 wrap(helper, "generate_kernel_map")
 wrap(helper, "wrap_conv_output")
 wrap(helper, "stride_coords")
-wrap(blk, "_bn_forward"); wrap(blk, "_bn_backward")
+wrap(blk, "bn_forward"); wrap(blk, "bn_backward")
 wrap(mu, "conv_bn_act")
 wrap(mu, "cat")
 for cls, nm in ((blk._ConvBnAct, "forward"), (blk._ConvBnAct, "backward"), (blk._PointwiseBnAct, "forward"), (blk._PointwiseBnAct, "backward")):

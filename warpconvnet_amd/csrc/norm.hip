@@ -320,61 +320,112 @@ static inline unsigned norm_grid(int64_t items, int cap = 2048) {
   return (unsigned)(g < cap ? (g < 1 ? 1 : g) : cap);
 }
 
-template <typename T>
-static int bn_reduce_t(int mode, const void* x, const void* dy, const float* rscale, const float* rshift, int64_t n, int c,
-                       const float* mean,
-                       const float* rstd, float* out0, float* out1, float* partial, hipStream_t s,
-                       const BnFold& fold = BnFold(), const void* zmask = nullptr, int64_t dy_ld = 0) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  if (dy_ld <= 0) dy_ld = c;
+// One pass over the rows [n, c], as the host side states it: which tensors it reads and where its ReLU mask comes from.
+// Absent parts stay null / 0; the launchers below take it plus what is per call (outputs, workspace, stream).
+struct BnPass {
+  const void* x = nullptr;            // [n, c] input of the BatchNorm
+  const void* dy = nullptr;           // backward passes: incoming gradient, rows of c elements ...
+  int64_t dy_ld = 0;                  // ... dy_ld elements apart (a column slice of a wider tensor, read in place); 0 = c
+  // ReLU mask of the backward passes, one source or none:
+  bool tail = false;                  // residual tail: the sign of the stored output z = ReLU(BN(x) + r), z is required
+  const void* z = nullptr;            // [n, c]
+  const float* relu_scale = nullptr;  // [c] else the forward's scale / shift (both or neither): recomputed from x
+  const float* relu_shift = nullptr;
+  const float* mean = nullptr;        // [c]
+  const float* rstd = nullptr;        // [c]
+  const float* gamma = nullptr;       // [c] or null (= 1)
+  const float* sum_dy = nullptr;      // [c] backward apply: what the backward reduce produced
+  const float* sum_dy_xhat = nullptr;
+  int64_t n = 0;
+  int c = 0;
+  int dtype = WCN_F32;
+
+  int64_t pitch() const { return dy_ld > 0 ? dy_ld : c; }
+  bool shape_ok(int64_t min_rows) const {
+    return n >= min_rows && c >= 1 && dtype_ok(dtype) && ((relu_scale == nullptr) == (relu_shift == nullptr));
+  }
+  // elements per access: 16-B pieces where the channel count, the pitch and the address of dy allow them
+  int vec() const {
+    const int w = 16 / dtype_bytes(dtype);
+    return (c % w == 0 && pitch() % w == 0 && aligned_to(dy, 16)) ? w : 1;
+  }
+};
+
+// Both column reductions with their second level.  `mode` 0: statistics of p.x into out0 = mean, out1 = biased variance
+// (+ `fold`); 1: backward sums of p.dy into out0 = sum_dy, out1 = sum_dy_xhat.  Arguments are the callers' to check.
+static int bn_reduce(int mode, const BnPass& p, float* out0, float* out1, float* partial, wcn_stream_t stream,
+                     const BnFold& fold = BnFold()) {
+  hipStream_t s = (hipStream_t)stream;
   // first-level workgroups: at least 128 rows each (small tensors: fewer partial sums for the second level), kNormBlocks at most
-  int64_t nb = ceil_div(n < 1 ? 1 : n, 128);
+  int64_t nb = ceil_div(p.n < 1 ? 1 : p.n, 128);
   const int nblocks = (int)(nb < kNormBlocks ? nb : kNormBlocks);
-  const bool vec = c % VEC == 0 && dy_ld % VEC == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
-#define WCN_NR(V, M)                                                                                                  \
-  hipLaunchKernelGGL((norm_reduce_kernel<T, V, M>), dim3(nblocks), dim3(256), 0, s, (const T*)x, (const T*)dy,          \
-                     rscale, rshift, n, c, mean, rstd, partial, (const T*)zmask, dy_ld)
-  if (mode == 0) { if (vec) WCN_NR(VEC, 0); else WCN_NR(1, 0); }
-  else { if (vec) WCN_NR(VEC, 1); else WCN_NR(1, 1); }
-#undef WCN_NR
-  if (mode == 0)
-    hipLaunchKernelGGL((norm_final_kernel<T, 0>), dim3((unsigned)c), dim3(64), 0, s, (const float*)partial, nblocks, c, n,
-                       (const T*)x, out0, out1, fold);
-  else
-    hipLaunchKernelGGL((norm_final_kernel<T, 1>), dim3((unsigned)c), dim3(64), 0, s, (const float*)partial, nblocks, c, n,
-                       (const T*)x, out0, out1, BnFold());
-  return launch_status();
+  return with_dtype_vec<false>(p.dtype, p.vec(), [&](auto t, auto v) {
+    using T = decltype(t);
+    constexpr int VEC = decltype(v)::value;
+    auto launch = [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      hipLaunchKernelGGL((norm_reduce_kernel<T, VEC, MODE>), dim3(nblocks), dim3(256), 0, s, (const T*)p.x, (const T*)p.dy,
+                         p.relu_scale, p.relu_shift, p.n, p.c, p.mean, p.rstd, partial, (const T*)p.z, p.pitch());
+      hipLaunchKernelGGL((norm_final_kernel<T, MODE>), dim3((unsigned)p.c), dim3(64), 0, s, (const float*)partial, nblocks, p.c,
+                         p.n, (const T*)p.x, out0, out1, fold);
+    };
+    if (mode == 0) launch(std::integral_constant<int, 0>{});
+    else launch(std::integral_constant<int, 1>{});
+    return launch_status();
+  });
 }
 
-template <typename T>
-static int bn_apply_t(const void* x, int64_t n, int c, const float* scale, const float* shift, int relu, void* y,
-                      hipStream_t s, const void* res = nullptr) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  if (c % VEC == 0)
-    hipLaunchKernelGGL((norm_apply_kernel<T, VEC>), dim3(norm_grid(n * (c / VEC))), dim3(256), (size_t)2 * c * 4, s,
-                       (const T*)x, n, c, scale, shift, relu, (T*)y, (const T*)res);
-  else
-    hipLaunchKernelGGL((norm_apply_kernel<T, 1>), dim3(norm_grid(n * c)), dim3(256), (size_t)2 * c * 4, s, (const T*)x, n, c,
-                       scale, shift, relu, (T*)y, (const T*)res);
-  return launch_status();
+// wcn_bn_stats[_fold]: the checks the two share, then the statistics pass
+static int bn_stats(const BnPass& p, float* mean, float* var, void* workspace, size_t workspace_bytes, wcn_stream_t stream,
+                    const BnFold& fold = BnFold()) {
+  if (!p.shape_ok(1) || !p.x || !mean || !var || !workspace || workspace_bytes < wcn_bn_workspace(p.c))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  return bn_reduce(0, p, mean, var, (float*)workspace, stream, fold);
 }
 
-template <typename T>
-static int bn_bwd_apply_t(const void* dy, const void* x, const float* rscale, const float* rshift, int64_t n, int c,
-                          const float* mean,
-                          const float* rstd, const float* gamma, const float* sum_dy, const float* sum_dy_xhat, void* dx,
-                          hipStream_t s, const void* zmask = nullptr, void* dres = nullptr, int64_t dy_ld = 0) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  if (dy_ld <= 0) dy_ld = c;
-  if (c % VEC == 0 && dy_ld % VEC == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0)
-    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, VEC>), dim3(norm_grid(n * (c / VEC), 4096)), dim3(256), (size_t)5 * c * 4, s,
-                       (const T*)dy, (const T*)x, rscale, rshift, n, c, mean, rstd, gamma, sum_dy, sum_dy_xhat, (T*)dx,
-                       (const T*)zmask, (T*)dres, dy_ld);
-  else
-    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, 1>), dim3(norm_grid(n * c, 4096)), dim3(256), (size_t)5 * c * 4, s, (const T*)dy,
-                       (const T*)x, rscale, rshift, n, c, mean, rstd, gamma, sum_dy, sum_dy_xhat, (T*)dx, (const T*)zmask,
-                       (T*)dres, dy_ld);
-  return launch_status();
+// y = [ReLU](x * scale + shift [+ res]); p.tail: `res` is required
+static int bn_apply(const BnPass& p, const float* scale, const float* shift, int relu, const void* res, void* y,
+                    wcn_stream_t stream) {
+  if (!p.shape_ok(0)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (p.n == 0) return WCN_SUCCESS;
+  if (!p.x || !y || !scale || !shift || (p.tail && !res)) return WCN_ERROR_INVALID_PARAMETERS;
+  return with_dtype_vec<false>(p.dtype, p.vec(), [&](auto t, auto v) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((norm_apply_kernel<T, v()>), dim3(norm_grid(p.n * (p.c / v()))), dim3(256), (size_t)2 * p.c * 4,
+                       (hipStream_t)stream, (const T*)p.x, p.n, p.c, scale, shift, relu, (T*)y, (const T*)res);
+    return launch_status();
+  });
+}
+
+// sum_dy / sum_dy_xhat of the masked gradient
+static int bn_backward_reduce(const BnPass& p, float* sum_dy, float* sum_dy_xhat, void* workspace, size_t workspace_bytes,
+                              wcn_stream_t stream) {
+  if (!p.shape_ok(1) || !p.dy || !p.x || (p.tail && !p.z) || !p.mean || !p.rstd || !sum_dy || !sum_dy_xhat || !workspace ||
+      workspace_bytes < wcn_bn_workspace(p.c))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  return bn_reduce(1, p, sum_dy, sum_dy_xhat, (float*)workspace, stream);
+}
+
+// dx from p.sum_dy / p.sum_dy_xhat; `dres` (residual tails, may be null) also receives the masked gradient
+static int bn_backward_apply(const BnPass& p, void* dx, void* dres, wcn_stream_t stream) {
+  if (!p.shape_ok(0)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (p.n == 0) return WCN_SUCCESS;
+  if (!p.dy || !p.x || (p.tail && !p.z) || !dx || !p.mean || !p.rstd || !p.sum_dy || !p.sum_dy_xhat)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  return with_dtype_vec<false>(p.dtype, p.vec(), [&](auto t, auto v) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, v()>), dim3(norm_grid(p.n * (p.c / v()), 4096)), dim3(256), (size_t)5 * p.c * 4,
+                       (hipStream_t)stream, (const T*)p.dy, (const T*)p.x, p.relu_scale, p.relu_shift, p.n, p.c, p.mean, p.rstd,
+                       p.gamma, p.sum_dy, p.sum_dy_xhat, (T*)dx, (const T*)p.z, (T*)dres, p.pitch());
+    return launch_status();
+  });
+}
+
+// the fields every pass fills
+static BnPass bn_rows(const void* x, int64_t n, int32_t channels, int32_t dtype) {
+  BnPass p;
+  p.x = x; p.n = n; p.c = channels; p.dtype = dtype;
+  return p;
 }
 
 }  // namespace wcn
@@ -388,32 +439,19 @@ size_t wcn_bn_workspace(int32_t channels) { return channels > 0 ? (size_t)kNormB
 
 int wcn_bn_stats(const void* x, int64_t n, int32_t channels, int32_t dtype, float* mean, float* var, void* workspace,
                  size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !x || !mean || !var || !workspace ||
-      workspace_bytes < wcn_bn_workspace(channels))
-    return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  float* p = (float*)workspace;
-  return with_dtype(dtype, [&](auto t) {
-    return bn_reduce_t<decltype(t)>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s);
-  });
+  return bn_stats(bn_rows(x, n, channels, dtype), mean, var, workspace, workspace_bytes, stream);
 }
 
 int wcn_bn_stats_fold(const void* x, int64_t n, int32_t channels, int32_t dtype, const float* gamma, const float* beta,
                       float* running_mean, float* running_var, float momentum, float eps, float* mean, float* var,
                       float* rstd, float* scale, float* shift, int64_t* num_batches_tracked, void* workspace,
                       size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !x || !mean || !var || !rstd || !scale || !shift || !workspace ||
-      workspace_bytes < wcn_bn_workspace(channels) || ((running_mean == nullptr) != (running_var == nullptr)))
-    return WCN_ERROR_INVALID_PARAMETERS;
+  if (!rstd || !scale || !shift || ((running_mean == nullptr) != (running_var == nullptr))) return WCN_ERROR_INVALID_PARAMETERS;
   BnFold f;
   f.gamma = gamma; f.beta = beta; f.running_mean = running_mean; f.running_var = running_var;
   f.momentum = momentum; f.eps = eps; f.rstd = rstd; f.scale = scale; f.shift = shift;
   f.batches = reinterpret_cast<long long*>(num_batches_tracked);
-  hipStream_t s = (hipStream_t)stream;
-  float* p = (float*)workspace;
-  return with_dtype(dtype, [&](auto t) {
-    return bn_reduce_t<decltype(t)>(0, x, nullptr, nullptr, nullptr, n, channels, nullptr, nullptr, mean, var, p, s, f);
-  });
+  return bn_stats(bn_rows(x, n, channels, dtype), mean, var, workspace, workspace_bytes, stream, f);
 }
 
 int wcn_bn_fold(const float* running_mean, const float* running_var, const float* gamma, const float* beta, float eps,
@@ -428,98 +466,50 @@ int wcn_bn_fold(const float* running_mean, const float* running_var, const float
 
 int wcn_bn_apply(const void* x, int64_t n, int32_t channels, int32_t dtype, const float* scale, const float* shift,
                  int32_t relu, void* y, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
-  if (n == 0) return WCN_SUCCESS;
-  if (!x || !y || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  return with_dtype(dtype, [&](auto t) { return bn_apply_t<decltype(t)>(x, n, channels, scale, shift, relu, y, s); });
+  return bn_apply(bn_rows(x, n, channels, dtype), scale, shift, relu, nullptr, y, stream);
 }
 
-static int bn_backward_reduce_ld(const void* dy, int64_t dy_ld, const void* x, const float* relu_scale, const float* relu_shift,
-                                int64_t n, int32_t channels, int32_t dtype, const float* mean, const float* rstd, float* sum_dy,
-                                float* sum_dy_xhat, void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !dy || !x || !mean || !rstd || !sum_dy || !sum_dy_xhat ||
-      !workspace || workspace_bytes < wcn_bn_workspace(channels) || ((relu_scale == nullptr) != (relu_shift == nullptr)))
-    return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  float* p = (float*)workspace;
-  return with_dtype(dtype, [&](auto t) {
-    return bn_reduce_t<decltype(t)>(1, x, dy, relu_scale, relu_shift, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s,
-                                    BnFold(), nullptr, dy_ld);
-  });
-}
 int wcn_bn_backward_reduce(const void* dy, const void* x, const float* relu_scale, const float* relu_shift, int64_t n,
                            int32_t channels, int32_t dtype, const float* mean, const float* rstd, float* sum_dy,
                            float* sum_dy_xhat, void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
-  return bn_backward_reduce_ld(dy, 0, x, relu_scale, relu_shift, n, channels, dtype, mean, rstd, sum_dy, sum_dy_xhat, workspace,
-                               workspace_bytes, stream);
+  BnPass p = bn_rows(x, n, channels, dtype);
+  p.dy = dy; p.relu_scale = relu_scale; p.relu_shift = relu_shift; p.mean = mean; p.rstd = rstd;
+  return bn_backward_reduce(p, sum_dy, sum_dy_xhat, workspace, workspace_bytes, stream);
 }
 
-static int bn_backward_apply_ld(const void* dy, int64_t dy_ld, const void* x, const float* relu_scale, const float* relu_shift,
-                               int64_t n, int32_t channels, int32_t dtype, const float* mean, const float* rstd, const float* gamma,
-                               const float* sum_dy, const float* sum_dy_xhat, void* dx, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !dtype_ok(dtype) || ((relu_scale == nullptr) != (relu_shift == nullptr)))
-    return WCN_ERROR_INVALID_PARAMETERS;
-  if (n == 0) return WCN_SUCCESS;
-  if (!dy || !x || !dx || !mean || !rstd || !sum_dy || !sum_dy_xhat) return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  return with_dtype(dtype, [&](auto t) {
-    return bn_bwd_apply_t<decltype(t)>(dy, x, relu_scale, relu_shift, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx,
-                                       s, nullptr, nullptr, dy_ld);
-  });
-}
 int wcn_bn_backward_apply(const void* dy, const void* x, const float* relu_scale, const float* relu_shift, int64_t n,
                           int32_t channels, int32_t dtype, const float* mean, const float* rstd, const float* gamma,
                           const float* sum_dy, const float* sum_dy_xhat, void* dx, wcn_stream_t stream) {
-  return bn_backward_apply_ld(dy, 0, x, relu_scale, relu_shift, n, channels, dtype, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, stream);
+  BnPass p = bn_rows(x, n, channels, dtype);
+  p.dy = dy; p.relu_scale = relu_scale; p.relu_shift = relu_shift; p.mean = mean; p.rstd = rstd; p.gamma = gamma;
+  p.sum_dy = sum_dy; p.sum_dy_xhat = sum_dy_xhat;
+  return bn_backward_apply(p, dx, nullptr, stream);
 }
 
 // ---- residual tail: z = [ReLU](BN(x) + residual), reference models/mink_unet.py:160-172 ----
 
 int wcn_bn_apply_residual(const void* x, const void* residual, int64_t n, int32_t channels, int32_t dtype, const float* scale,
                           const float* shift, int32_t relu, void* y, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
-  if (n == 0) return WCN_SUCCESS;
-  if (!x || !residual || !y || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  return with_dtype(dtype, [&](auto t) { return bn_apply_t<decltype(t)>(x, n, channels, scale, shift, relu, y, s, residual); });
+  BnPass p = bn_rows(x, n, channels, dtype);
+  p.tail = true;
+  return bn_apply(p, scale, shift, relu, residual, y, stream);
 }
 
-static int bn_backward_reduce_masked_ld(const void* dy, int64_t dy_ld, const void* x, const void* z, int64_t n, int32_t channels,
-                                       int32_t dtype, const float* mean, const float* rstd, float* sum_dy, float* sum_dy_xhat,
-                                       void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
-  if (n < 1 || channels < 1 || !dtype_ok(dtype) || !dy || !x || !z || !mean || !rstd || !sum_dy || !sum_dy_xhat ||
-      !workspace || workspace_bytes < wcn_bn_workspace(channels))
-    return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  float* p = (float*)workspace;
-  const BnFold nf;
-  return with_dtype(dtype, [&](auto t) {
-    return bn_reduce_t<decltype(t)>(1, x, dy, nullptr, nullptr, n, channels, mean, rstd, sum_dy, sum_dy_xhat, p, s, nf, z, dy_ld);
-  });
-}
 int wcn_bn_backward_reduce_masked(const void* dy, const void* x, const void* z, int64_t n, int32_t channels, int32_t dtype,
                                   const float* mean, const float* rstd, float* sum_dy, float* sum_dy_xhat, void* workspace,
                                   size_t workspace_bytes, wcn_stream_t stream) {
-  return bn_backward_reduce_masked_ld(dy, 0, x, z, n, channels, dtype, mean, rstd, sum_dy, sum_dy_xhat, workspace, workspace_bytes, stream);
+  BnPass p = bn_rows(x, n, channels, dtype);
+  p.dy = dy; p.tail = true; p.z = z; p.mean = mean; p.rstd = rstd;
+  return bn_backward_reduce(p, sum_dy, sum_dy_xhat, workspace, workspace_bytes, stream);
 }
 
-static int bn_backward_apply_masked_ld(const void* dy, int64_t dy_ld, const void* x, const void* z, int64_t n, int32_t channels,
-                                      int32_t dtype, const float* mean, const float* rstd, const float* gamma, const float* sum_dy,
-                                      const float* sum_dy_xhat, void* dx, void* dres, wcn_stream_t stream) {
-  if (n < 0 || channels < 1 || !dtype_ok(dtype)) return WCN_ERROR_INVALID_PARAMETERS;
-  if (n == 0) return WCN_SUCCESS;
-  if (!dy || !x || !z || !dx || !mean || !rstd || !sum_dy || !sum_dy_xhat) return WCN_ERROR_INVALID_PARAMETERS;
-  hipStream_t s = (hipStream_t)stream;
-  return with_dtype(dtype, [&](auto t) {
-    return bn_bwd_apply_t<decltype(t)>(dy, x, nullptr, nullptr, n, channels, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, s, z,
-                                       dres, dy_ld);
-  });
-}
 int wcn_bn_backward_apply_masked(const void* dy, const void* x, const void* z, int64_t n, int32_t channels, int32_t dtype,
                                  const float* mean, const float* rstd, const float* gamma, const float* sum_dy,
                                  const float* sum_dy_xhat, void* dx, void* dres, wcn_stream_t stream) {
-  return bn_backward_apply_masked_ld(dy, 0, x, z, n, channels, dtype, mean, rstd, gamma, sum_dy, sum_dy_xhat, dx, dres, stream);
+  BnPass p = bn_rows(x, n, channels, dtype);
+  p.dy = dy; p.tail = true; p.z = z; p.mean = mean; p.rstd = rstd; p.gamma = gamma;
+  p.sum_dy = sum_dy; p.sum_dy_xhat = sum_dy_xhat;
+  return bn_backward_apply(p, dx, dres, stream);
 }
 
 // ---- layer entries: the BatchNorm of a training step in one call per direction ----
@@ -551,28 +541,24 @@ int wcn_bn_train_backward_ld(const void* dy, int64_t dy_ld, const void* x, const
                              int32_t dtype, const float* stats, const float* gamma, int32_t training, float* sums, void* dx,
                              void* dres, void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
   if (!stats || !sums || channels < 1 || (dy_ld != 0 && dy_ld < channels)) return WCN_ERROR_INVALID_PARAMETERS;
-  const float* mean = stats;
-  const float* rstd = stats + channels;
-  const float* rsc = (relu && !z) ? stats + 2 * (int64_t)channels : nullptr;
-  const float* rsh = (relu && !z) ? stats + 3 * (int64_t)channels : nullptr;
-  float* sum_dy = sums;
-  float* sum_dy_xhat = sums + channels;
-  const bool masked = z && relu;
-  int rc = masked ? bn_backward_reduce_masked_ld(dy, dy_ld, x, z, n, channels, dtype, mean, rstd, sum_dy, sum_dy_xhat, workspace,
-                                                 workspace_bytes, stream)
-                  : bn_backward_reduce_ld(dy, dy_ld, x, rsc, rsh, n, channels, dtype, mean, rstd, sum_dy, sum_dy_xhat, workspace,
-                                          workspace_bytes, stream);
+  BnPass p = bn_rows(x, n, channels, dtype);
+  p.dy = dy; p.dy_ld = dy_ld; p.mean = stats; p.rstd = stats + channels; p.gamma = gamma;
+  p.tail = z && relu;
+  if (p.tail) p.z = z;
+  else if (relu) { p.relu_scale = stats + 2 * (int64_t)channels; p.relu_shift = stats + 3 * (int64_t)channels; }
+  const int rc = bn_backward_reduce(p, sums, sums + channels, workspace, workspace_bytes, stream);
   if (rc != WCN_SUCCESS || !dx) return rc;
-  const float* a0 = sum_dy;
-  const float* a1 = sum_dy_xhat;
-  if (!training) {  // constants: the second half of the workspace is zeroed and stands in for the sums
+  p.sum_dy = sums;
+  p.sum_dy_xhat = sums + channels;
+  if (!training) {
+    // constants: the first `channels` floats of the workspace stand in for both sums - zeroed here, behind the reduce pass
+    // that was the last to use the workspace (same stream)
     float* zeros = reinterpret_cast<float*>(workspace);
     if (hipMemsetAsync(zeros, 0, (size_t)channels * sizeof(float), (hipStream_t)stream) != hipSuccess)
       return WCN_ERROR_KERNEL_EXECUTION;
-    a0 = a1 = zeros;
+    p.sum_dy = p.sum_dy_xhat = zeros;
   }
-  return masked ? bn_backward_apply_masked_ld(dy, dy_ld, x, z, n, channels, dtype, mean, rstd, gamma, a0, a1, dx, dres, stream)
-                : bn_backward_apply_ld(dy, dy_ld, x, rsc, rsh, n, channels, dtype, mean, rstd, gamma, a0, a1, dx, stream);
+  return bn_backward_apply(p, dx, p.tail ? dres : nullptr, stream);
 }
 
 int wcn_bn_train_backward(const void* dy, const void* x, const void* z, int32_t relu, int64_t n, int32_t channels, int32_t dtype,

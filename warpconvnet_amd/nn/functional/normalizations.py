@@ -28,7 +28,7 @@ def hip_batch_norm_supported(x: Tensor) -> bool:
 _WS = {}
 
 
-def _workspace(c: int, dev) -> Tensor:
+def bn_workspace(c: int, dev) -> Tensor:
     """Partial-sum workspace of the two reduction passes: kept per (device, stream, width) - the passes of one stream are
     ordered, so they can share it - instead of a fresh allocation per call."""
     key = (str(dev), _lib.stream_handle(dev), int(c))
@@ -40,14 +40,99 @@ def _workspace(c: int, dev) -> Tensor:
     return ws
 
 
-def _apply(x: Tensor, scale: Tensor, shift: Tensor, relu: bool) -> Tensor:
-    y = torch.empty_like(x)
-    _lib.check(
-        _lib.lib().wcn_bn_apply(_lib.ptr(x), x.shape[0], x.shape[1], _lib.dtype_code(x.dtype), _lib.ptr(scale), _lib.ptr(shift),
-                                int(relu), _lib.ptr(y), _lib.stream_handle(x.device)),
-        "wcn_bn_apply",
-    )
-    return y
+def _f32_in_place(a: Optional[Tensor], b: Optional[Tensor]) -> bool:
+    """Running statistics the kernels can take as they are (`float*`): there, fp32 and contiguous."""
+    return (a is not None and a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous())
+
+
+# The BatchNorm step itself, once, on the layer entries of include/wcn.h: `_HipBatchNorm` below and the fused
+# conv -> BatchNorm nodes (`sparse_conv/block.py`) are its callers.  gamma / beta and, in eval, the running statistics are
+# fp32 and contiguous here (the kernels read them as `const float*`); converting anything else is the caller's business.
+def bn_forward(x: Tensor, residual: Optional[Tensor], gamma: Optional[Tensor], beta: Optional[Tensor], state, relu: bool):
+    """BatchNorm (+ residual) (+ ReLU) of the contiguous rows ``x`` [N, C].  ``state``: what :func:`bn_module_state` returns.
+    Training is one C call (`wcn_bn_train_forward`: statistics + fold + apply), eval the fold of the running statistics, then
+    the apply pass.  -> (out, stats [5, C] = mean, rstd, scale, shift, biased variance)"""
+    training, momentum, eps, running_mean, running_var, counter, fused_running = state
+    L = _lib.lib()
+    dev = x.device
+    stream = _lib.stream_handle(dev)
+    n, c = x.shape
+    code = _lib.dtype_code(x.dtype)
+    stats = torch.empty((5, c), dtype=torch.float32, device=dev)  # one allocation for the five per-channel vectors
+    out = torch.empty_like(x)
+    gp, bp, xp = _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(x)
+    s0 = stats.data_ptr()
+    if training:
+        ws = bn_workspace(c, dev)
+        # running statistics are updated inside the kernel when they are fp32 (the usual case), else below
+        _lib.check(L.wcn_bn_train_forward(xp, _lib.ptr(residual), n, c, code, gp, bp, _lib.ptr(running_mean) if fused_running else None,
+                                          _lib.ptr(running_var) if fused_running else None, momentum, eps, _lib.ptr(counter),
+                                          int(relu), s0, _lib.ptr(out), _lib.ptr(ws), ws.numel(), stream), "wcn_bn_train_forward")
+        if running_mean is not None and not fused_running:  # in place, like F.batch_norm: unbiased variance
+            unbias = float(n) / float(max(n - 1, 1))
+            running_mean.mul_(1.0 - momentum).add_(stats[0].to(running_mean.dtype), alpha=momentum)
+            running_var.mul_(1.0 - momentum).add_(stats[4].to(running_var.dtype), alpha=momentum * unbias)
+        return out, stats
+    mean, rstd, scale, shift = (s0 + 4 * c * i for i in range(4))
+    _lib.check(L.wcn_bn_fold(_lib.ptr(running_mean), _lib.ptr(running_var), gp, bp, eps, c, mean, rstd, scale, shift, stream),
+               "wcn_bn_fold")
+    if residual is not None:
+        _lib.check(L.wcn_bn_apply_residual(xp, _lib.ptr(residual), n, c, code, scale, shift, int(relu), _lib.ptr(out), stream),
+                   "wcn_bn_apply_residual")
+    else:
+        _lib.check(L.wcn_bn_apply(xp, n, c, code, scale, shift, int(relu), _lib.ptr(out), stream), "wcn_bn_apply")
+    return out, stats
+
+
+def bn_grad_rows(grad_out: Tensor, like: Tensor):
+    """-> (tensor to read, row pitch in elements).  The gradient a channel concatenation hands to one of its inputs is a column
+    slice of a wider row-major tensor (`torch.cat` backward: `narrow`): the BatchNorm backward kernels read it in place."""
+    g = grad_out
+    if g.dtype != like.dtype:
+        return g.contiguous().to(like.dtype), like.shape[1]
+    if g.is_contiguous():
+        return g, g.shape[1]
+    if (g.ndim == 2 and g.stride(1) == 1 and g.stride(0) >= g.shape[1] and g.shape[0] > 0
+            and g.data_ptr() % 16 == 0 and (g.stride(0) * g.element_size()) % 16 == 0):
+        # (16-B aligned rows only: a misaligned slice would take the kernels' element path, whose reduction order differs from
+        # the one a contiguous tensor gets - results must not depend on the layout of the incoming gradient)
+        return g, g.stride(0)
+    return g.contiguous(), g.shape[1]
+
+
+def bn_backward(grad_out: Tensor, x: Tensor, z: Optional[Tensor], stats: Tensor, gamma: Optional[Tensor], relu: bool,
+                training: bool, need_dx: bool, need_dres: bool = False):
+    """One C call (`wcn_bn_train_backward_ld`: reduce + apply).  -> (gradient of ``x`` or None, sums [2, C] = sum_dy (bias
+    gradient), sum_dy_xhat (weight gradient), gradient of the residual or None).  ``z``: the stored output of a residual tail
+    ReLU(BN(x) + r) - the ReLU mask is its sign; without it the mask is recomputed from x and the forward's scale / shift (the
+    output is not saved for it).  ``training`` False: the statistics were constants, dx = gamma * rstd * g."""
+    dev = x.device
+    n, c = x.shape
+    g, g_ld = bn_grad_rows(grad_out, x)
+    sums = torch.empty((2, c), dtype=torch.float32, device=dev)
+    ws = bn_workspace(c, dev)
+    masked = z is not None and relu  # (BN(x) + r without activation: the gradient reaches both branches unmasked)
+    want_dx = need_dx or (masked and need_dres)
+    dx = torch.empty_like(x) if want_dx else None
+    dres = torch.empty_like(x) if (masked and need_dres) else None
+    _lib.check(_lib.lib().wcn_bn_train_backward_ld(_lib.ptr(g), g_ld, _lib.ptr(x), _lib.ptr(z) if masked else None, int(relu), n, c,
+                                                   _lib.dtype_code(x.dtype), stats.data_ptr(), _lib.ptr(gamma), int(training),
+                                                   sums.data_ptr(), _lib.ptr(dx), _lib.ptr(dres), _lib.ptr(ws), ws.numel(),
+                                                   _lib.stream_handle(dev)), "wcn_bn_train_backward_ld")
+    if need_dres and not masked:
+        dres = g
+    return (dx if need_dx else None), sums, dres
+
+
+def bn_affine_grads(ctx, sums: Tensor, at: int):
+    """gamma / beta gradients from ``sums`` in the parameters' dtypes (``ctx.gdtype`` / ``ctx.bdtype``, None: no parameter);
+    ``at``: position of gamma among the node's inputs, beta follows it."""
+    dgamma = dbeta = None
+    if ctx.gdtype is not None and ctx.needs_input_grad[at]:
+        dgamma = sums[1] if ctx.gdtype == torch.float32 else sums[1].to(ctx.gdtype)
+    if ctx.bdtype is not None and ctx.needs_input_grad[at + 1]:
+        dbeta = sums[0] if ctx.bdtype == torch.float32 else sums[0].to(ctx.bdtype)
+    return dgamma, dbeta
 
 
 class _HipBatchNorm(Function):
@@ -55,83 +140,27 @@ class _HipBatchNorm(Function):
     def forward(ctx, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], running_mean: Optional[Tensor],
                 running_var: Optional[Tensor], training: bool, momentum: float, eps: float, relu: bool,
                 batches: Optional[Tensor] = None) -> Tensor:
-        x = x.contiguous()
-        n, c = x.shape
-        dev = x.device
-        L = _lib.lib()
-        def f32(t):  # parameters / buffers are fp32 in practice: no copy
+        def f32(t):  # parameters / buffers are fp32 in practice: no copy (a module cast with `.half()` gets one)
             return None if t is None else (t.detach() if t.dtype == torch.float32 and t.is_contiguous() else t.detach().float().contiguous())
 
-        gamma, beta = f32(weight), f32(bias)
-        stats = torch.empty((5, c), dtype=torch.float32, device=dev)  # one allocation for the five per-channel vectors
-        mean, rstd, scale, shift = stats[0], stats[1], stats[2], stats[3]
+        x = x.contiguous()
+        gamma = f32(weight)
         if training:
-            var = stats[4]
-            ws = _workspace(c, dev)
-            # running statistics are updated inside the kernel when they are fp32 (the usual case), else below
-            fused_running = (running_mean is not None and running_mean.dtype == torch.float32
-                             and running_var.dtype == torch.float32 and running_mean.is_contiguous() and running_var.is_contiguous())
-            _lib.check(
-                L.wcn_bn_stats_fold(_lib.ptr(x), n, c, _lib.dtype_code(x.dtype), _lib.ptr(gamma), _lib.ptr(beta),
-                                    _lib.ptr(running_mean) if fused_running else None,
-                                    _lib.ptr(running_var) if fused_running else None, momentum, eps, _lib.ptr(mean),
-                                    _lib.ptr(var), _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(batches), _lib.ptr(ws),
-                                    ws.numel(), _lib.stream_handle(dev)),
-                "wcn_bn_stats_fold",
-            )
-            if running_mean is not None and not fused_running:  # in place, like F.batch_norm: unbiased variance
-                unbias = float(n) / float(max(n - 1, 1))
-                running_mean.mul_(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
-                running_var.mul_(1.0 - momentum).add_(var.to(running_var.dtype), alpha=momentum * unbias)
+            state = (True, momentum, eps, running_mean, running_var, batches, _f32_in_place(running_mean, running_var))
         else:
-            _lib.check(
-                L.wcn_bn_fold(_lib.ptr(f32(running_mean)), _lib.ptr(f32(running_var)), _lib.ptr(gamma), _lib.ptr(beta), eps, c,
-                              _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift), _lib.stream_handle(dev)),
-                "wcn_bn_fold",
-            )
-        y = _apply(x, scale, shift, relu)
-        # (the ReLU mask is recomputed from x and scale / shift in the backward passes: the output is not saved for it)
+            state = (False, momentum, eps, f32(running_mean), f32(running_var), None, False)
+        y, stats = bn_forward(x, None, gamma, f32(bias), state, relu)
         ctx.save_for_backward(x, stats, gamma)
-        ctx.training, ctx.relu, ctx.has_bias = training, relu, bias is not None
-        ctx.wdtype = weight.dtype if weight is not None else None
+        ctx.training, ctx.relu = training, relu
+        ctx.gdtype = weight.dtype if weight is not None else None
         ctx.bdtype = bias.dtype if bias is not None else None
         return y
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
         x, stats, gamma = ctx.saved_tensors
-        mean, rstd = stats[0], stats[1]
-        rsc, rsh = (stats[2], stats[3]) if ctx.relu else (None, None)
-        n, c = x.shape
-        dev = x.device
-        L = _lib.lib()
-        dy = grad_out.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
-        sums = torch.empty((2, c), dtype=torch.float32, device=dev)
-        sum_dy, sum_dy_xhat = sums[0], sums[1]
-        ws = _workspace(c, dev)
-        _lib.check(
-            L.wcn_bn_backward_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(rsc), _lib.ptr(rsh), n, c, _lib.dtype_code(x.dtype), _lib.ptr(mean),
-                                     _lib.ptr(rstd), _lib.ptr(sum_dy), _lib.ptr(sum_dy_xhat), _lib.ptr(ws), ws.numel(),
-                                     _lib.stream_handle(dev)),
-            "wcn_bn_backward_reduce",
-        )
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            if ctx.training:
-                s0, s1 = sum_dy, sum_dy_xhat
-            else:  # eval: the statistics are constants, dx = gamma * rstd * g
-                s0 = s1 = torch.zeros(c, dtype=torch.float32, device=dev)
-            _lib.check(
-                L.wcn_bn_backward_apply(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(rsc), _lib.ptr(rsh), n, c, _lib.dtype_code(x.dtype), _lib.ptr(mean),
-                                        _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(s0), _lib.ptr(s1), _lib.ptr(dx),
-                                        _lib.stream_handle(dev)),
-                "wcn_bn_backward_apply",
-            )
-        dw = sum_dy_xhat.to(ctx.wdtype) if (ctx.wdtype is not None and ctx.needs_input_grad[1]) else None
-        db = sum_dy.to(ctx.bdtype) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        dx, sums, _ = bn_backward(grad_out, x, None, stats, gamma, ctx.relu, ctx.training, ctx.needs_input_grad[0])
+        dw, db = bn_affine_grads(ctx, sums, 1)
         return dx, dw, db, None, None, None, None, None, None, None
 
 
@@ -161,8 +190,7 @@ def bn_module_state(norm: torch.nn.modules.batchnorm._BatchNorm, x: Tensor):
     statistics are fp32 and get updated inside that kernel."""
     momentum = 0.0 if norm.momentum is None else norm.momentum
     counter = None
-    rm_ok = (norm.running_mean is not None and norm.running_mean.dtype == torch.float32 and norm.running_var.dtype == torch.float32
-             and norm.running_mean.is_contiguous() and norm.running_var.is_contiguous())
+    rm_ok = _f32_in_place(norm.running_mean, norm.running_var)
     if norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
         nbt = norm.num_batches_tracked
         if norm.momentum is not None and nbt.dtype == torch.int64 and nbt.device == x.device and rm_ok:

@@ -28,8 +28,8 @@ from torch.autograd import Function
 
 from warpconvnet_amd import _lib
 from warpconvnet_amd.dist import claim_grad_slot
-from warpconvnet_amd.nn.functional.normalizations import _workspace as _bn_workspace
-from warpconvnet_amd.nn.functional.normalizations import bn_module_state
+from warpconvnet_amd.nn.functional.normalizations import (bn_affine_grads, bn_backward, bn_forward, bn_grad_rows, bn_module_state,
+                                                          bn_workspace)
 
 from .detail import hip_gemm
 
@@ -43,92 +43,7 @@ _OBSERVER = None
 class _Plan:
     """Per-call constants of one fused block (plain attributes: cheaper than threading a dozen Function arguments)."""
 
-    __slots__ = ("km", "num_in", "num_out", "cin", "cout", "K", "code", "relu", "training", "momentum", "eps", "running_mean",
-                 "running_var", "counter", "fused_running")
-
-
-def _bn_forward(plan: _Plan, y: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], residual: Optional[Tensor] = None):
-    """BatchNorm (+ residual) (+ ReLU) of the convolution's output ``y``: statistics + fold (training) or fold of the running
-    statistics (eval), then apply - one C call in training (`wcn_bn_train_forward`).
-    -> (out, stats [5, C] = mean, rstd, scale, shift, var)"""
-    L = _lib.lib()
-    dev = y.device
-    stream = _lib.stream_handle(dev)
-    M, cout, code = plan.num_out, plan.cout, plan.code
-    stats = torch.empty((5, cout), dtype=torch.float32, device=dev)
-    out = torch.empty_like(y)
-    gp, bp, yp = _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y)
-    s0 = stats.data_ptr()
-    if plan.training:
-        ws = _bn_workspace(cout, dev)
-        fr = plan.fused_running
-        _lib.check(L.wcn_bn_train_forward(yp, _lib.ptr(residual), M, cout, code, gp, bp, _lib.ptr(plan.running_mean) if fr else None,
-                                          _lib.ptr(plan.running_var) if fr else None, plan.momentum, plan.eps,
-                                          _lib.ptr(plan.counter), int(plan.relu), s0, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                          stream), "wcn_bn_train_forward")
-        if plan.running_mean is not None and not fr:  # (non-fp32 running statistics: the module's own arithmetic)
-            unbias = float(M) / float(max(M - 1, 1))
-            plan.running_mean.mul_(1.0 - plan.momentum).add_(stats[0].to(plan.running_mean.dtype), alpha=plan.momentum)
-            plan.running_var.mul_(1.0 - plan.momentum).add_(stats[4].to(plan.running_var.dtype), alpha=plan.momentum * unbias)
-        return out, stats
-    mean, rstd, scale, shift = (s0 + 4 * cout * i for i in range(4))
-    _lib.check(L.wcn_bn_fold(_lib.ptr(plan.running_mean), _lib.ptr(plan.running_var), gp, bp, plan.eps, cout, mean, rstd,
-                             scale, shift, stream), "wcn_bn_fold")
-    if residual is not None:
-        _lib.check(L.wcn_bn_apply_residual(yp, _lib.ptr(residual), M, cout, code, scale, shift, int(plan.relu), _lib.ptr(out),
-                                           stream), "wcn_bn_apply_residual")
-    else:
-        _lib.check(L.wcn_bn_apply(yp, M, cout, code, scale, shift, int(plan.relu), _lib.ptr(out), stream), "wcn_bn_apply")
-    return out, stats
-
-
-def _grad_rows(grad_out: Tensor, like: Tensor):
-    """-> (tensor to read, row pitch in elements).  The gradient a channel concatenation hands to one of its inputs is a column
-    slice of a wider row-major tensor (`torch.cat` backward: `narrow`): the BatchNorm backward kernels read it in place."""
-    g = grad_out
-    if g.dtype != like.dtype:
-        return g.contiguous().to(like.dtype), like.shape[1]
-    if g.is_contiguous():
-        return g, g.shape[1]
-    if (g.ndim == 2 and g.stride(1) == 1 and g.stride(0) >= g.shape[1] and g.shape[0] > 0
-            and g.data_ptr() % 16 == 0 and (g.stride(0) * g.element_size()) % 16 == 0):
-        # (16-B aligned rows only: a misaligned slice would take the kernels' element path, whose reduction order differs from
-        # the one a contiguous tensor gets - results must not depend on the layout of the incoming gradient)
-        return g, g.stride(0)
-    return g.contiguous(), g.shape[1]
-
-
-def _bn_backward(plan: _Plan, grad_out: Tensor, y: Tensor, stats: Tensor, gamma: Optional[Tensor], need_dy: bool,
-                 z: Optional[Tensor] = None, need_dres: bool = False):
-    """One C call (`wcn_bn_train_backward`: reduce + apply).  -> (gradient of the convolution's output or None, sums [2, C] =
-    sum_dy (bias gradient), sum_dy_xhat (weight gradient), gradient of the residual or None).  ``z``: the stored output of a
-    residual tail ReLU(BN(y) + r) - the ReLU mask is its sign."""
-    L = _lib.lib()
-    dev = y.device
-    M, cout, code = plan.num_out, plan.cout, plan.code
-    g, g_ld = _grad_rows(grad_out, y)
-    sums = torch.empty((2, cout), dtype=torch.float32, device=dev)
-    ws = _bn_workspace(cout, dev)
-    masked = z is not None and plan.relu  # (BN(y) + r without activation: the gradient reaches both branches unmasked)
-    want_dx = need_dy or (masked and need_dres)
-    dyc = torch.empty_like(y) if want_dx else None
-    dres = torch.empty_like(y) if (masked and need_dres) else None
-    _lib.check(L.wcn_bn_train_backward_ld(_lib.ptr(g), g_ld, _lib.ptr(y), _lib.ptr(z) if masked else None, int(plan.relu), M, cout,
-                                          code, stats.data_ptr(), _lib.ptr(gamma), int(plan.training), sums.data_ptr(),
-                                          _lib.ptr(dyc), _lib.ptr(dres), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
-               "wcn_bn_train_backward_ld")
-    if need_dres and not masked:
-        dres = g
-    return (dyc if need_dy else None), sums, dres
-
-
-def _affine_grads(ctx, sums: Tensor):
-    dgamma = dbeta = None
-    if ctx.gdtype is not None and ctx.needs_input_grad[2]:
-        dgamma = sums[1] if ctx.gdtype == torch.float32 else sums[1].to(ctx.gdtype)
-    if ctx.bdtype is not None and ctx.needs_input_grad[3]:
-        dbeta = sums[0] if ctx.bdtype == torch.float32 else sums[0].to(ctx.bdtype)
-    return dgamma, dbeta
+    __slots__ = ("km", "num_in", "num_out", "cin", "cout", "K", "code", "relu", "bn")  # bn: what bn_module_state() returned
 
 
 class _ConvBnAct(Function):
@@ -158,7 +73,7 @@ class _ConvBnAct(Function):
             launch()
         if _OBSERVER is not None:
             _OBSERVER("forward", dict(x=x, w=w, km=km, y=y, num_in=plan.num_in, num_out=M))
-        out, stats = _bn_forward(plan, y, gamma, beta, residual)
+        out, stats = bn_forward(y, residual, gamma, beta, plan.bn, plan.relu)
         ctx.has_res = residual is not None
         if ctx.has_res and plan.relu:
             ctx.save_for_backward(x, w, y, stats, gamma, out)  # (the output's sign is the ReLU mask of a residual tail)
@@ -183,16 +98,17 @@ class _ConvBnAct(Function):
         need_dres = ctx.has_res and ctx.needs_input_grad[5]
         if km._has_duplicates or not (need_dx or need_dw):
             # repeated coordinates (the general path's pair-list dgrad), or nothing behind the BatchNorm: the passes one by one
-            dyc, sums, dres = _bn_backward(plan, grad_out, y, stats, gamma, need_dx or need_dw, z if ctx.has_res else None, need_dres)
+            dyc, sums, dres = bn_backward(grad_out, y, z if ctx.has_res else None, stats, gamma, plan.relu, plan.bn[0],
+                                          need_dx or need_dw, need_dres)
             dx = hip_gemm.hip_dgrad(dyc, w, km, plan.num_in, "auto") if need_dx else None
             dw = hip_gemm.hip_wgrad(x, dyc, km, (K, cin, cout), "auto").to(w.dtype) if need_dw else None
             if _OBSERVER is not None:
                 _OBSERVER("backward", dict(x=x, w=w, km=km, dy=dyc, dx=dx, dw=dw, num_in=plan.num_in, num_out=M))
-            dgamma, dbeta = _affine_grads(ctx, sums)
+            dgamma, dbeta = bn_affine_grads(ctx, sums, 2)
             ctx.plan = None
             return dx, dw, dgamma, dbeta, None, dres
         # one C call: BatchNorm reduce + apply -> dgrad on the reverse tables -> wgrad (wcn_conv_bn_backward)
-        g, g_ld = _grad_rows(grad_out, y)
+        g, g_ld = bn_grad_rows(grad_out, y)
         masked = z is not None and plan.relu
         sums = torch.empty((2, cout), dtype=torch.float32, device=dev)
         dyc = torch.empty_like(y)
@@ -217,10 +133,10 @@ class _ConvBnAct(Function):
                 dw = torch.empty((K, cin, cout), dtype=torch.float32, device=dev)
             ws_bytes = hip_gemm._wgrad_workspace(K, cin, cout, _lib.WCN_ALGO_MFMA)
             wws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        bws = _bn_workspace(cout, dev)
+        bws = bn_workspace(cout, dev)
         _lib.check(L.wcn_conv_bn_backward_ld(
             _lib.ptr(g), g_ld, _lib.ptr(x), _lib.ptr(y), _lib.ptr(z) if masked else None, int(plan.relu), stats.data_ptr(), _lib.ptr(gamma),
-            int(plan.training), sums.data_ptr(), _lib.ptr(dyc), _lib.ptr(dres), _lib.ptr(wpd), _lib.ptr(tbl), _lib.ptr(msk),
+            int(plan.bn[0]), sums.data_ptr(), _lib.ptr(dyc), _lib.ptr(dres), _lib.ptr(wpd), _lib.ptr(tbl), _lib.ptr(msk),
             _lib.ptr(perm), int(flip), _lib.ptr(dx), _lib.ptr(km.in_maps_device) if need_dw else None,
             _lib.ptr(km.out_maps_device) if need_dw else None, _lib.ptr(km._offsets_dev) if need_dw else None, _lib.ptr(dw),
             _lib.ptr(wws), ws_bytes, plan.num_in, M, cin, cout, K, code, _lib.ptr(bws), bws.numel(), stream), "wcn_conv_bn_backward_ld")
@@ -230,7 +146,7 @@ class _ConvBnAct(Function):
             dw = dw.to(w.dtype)
         if _OBSERVER is not None:
             _OBSERVER("backward", dict(x=x, w=w, km=km, dy=dyc, dx=dx, dw=dw, num_in=plan.num_in, num_out=M))
-        dgamma, dbeta = _affine_grads(ctx, sums)
+        dgamma, dbeta = bn_affine_grads(ctx, sums, 2)
         ctx.plan = None
         return dx, dw, dgamma, dbeta, None, dres
 
@@ -247,7 +163,7 @@ class _PointwiseBnAct(Function):
         if y is None:  # (shapes outside the streaming kernels: the vendor GEMM on a cast copy of the weight)
             xc = x if x.dtype == _lib.torch_dtype(plan.code) else x.to(_lib.torch_dtype(plan.code))  # (fp32 rows under autocast)
             y = xc @ (w[0] if w.dtype == xc.dtype else w[0].to(xc.dtype))
-        out, stats = _bn_forward(plan, y, gamma, beta)
+        out, stats = bn_forward(y, None, gamma, beta, plan.bn, plan.relu)
         ctx.save_for_backward(x, y, stats, gamma, w)  # (w: the parameter itself - no copy, and autograd's version check applies)
         ctx.plan, ctx.wdtype = plan, w.dtype
         ctx.gdtype = gamma.dtype if gamma is not None else None
@@ -261,7 +177,7 @@ class _PointwiseBnAct(Function):
         x, y, stats, gamma, w3 = ctx.saved_tensors
         plan = ctx.plan
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dyc, sums, _ = _bn_backward(plan, grad_out, y, stats, gamma, need_dx or need_dw)
+        dyc, sums, _ = bn_backward(grad_out, y, None, stats, gamma, plan.relu, plan.bn[0], need_dx or need_dw)
         dx = dw = None
         if need_dx:
             from .pointwise import dense_rows
@@ -273,7 +189,7 @@ class _PointwiseBnAct(Function):
             dw = dense_wgrad(x, dyc).unsqueeze(0)
             if dw.dtype != ctx.wdtype:
                 dw = dw.to(ctx.wdtype)
-        dgamma, dbeta = _affine_grads(ctx, sums)
+        dgamma, dbeta = bn_affine_grads(ctx, sums, 2)
         ctx.plan = None
         return dx, dw, dgamma, dbeta, None
 
@@ -356,8 +272,7 @@ def conv_bn_act(x, conv, norm, relu: bool, residual=None, out_spatial=None):
                 feats = feats.to(dtype)
         feats = feats.contiguous()
         plan.km, plan.num_in, plan.num_out = None, feats.shape[0], feats.shape[0]
-        (plan.training, plan.momentum, plan.eps, plan.running_mean, plan.running_var, plan.counter,
-         plan.fused_running) = bn_module_state(norm, feats)
+        plan.bn = bn_module_state(norm, feats)
         return x.replace(batched_features=_PointwiseBnAct.apply(feats, conv.weight, norm.weight, norm.bias, plan))
     if not (hip_gemm._gather_ok(cin, cout, K, code) and hip_gemm._gather_ok(cout, cin, K, code) and hip_gemm._wgrad_ok(cin, cout, code)):
         return None
@@ -396,8 +311,7 @@ def conv_bn_act(x, conv, norm, relu: bool, residual=None, out_spatial=None):
             res = res.to(dtype)
     # every `return None` is above this line: bn_module_state() bumps `num_batches_tracked` when the kernel cannot, and a
     # bail-out after it would count the batch twice (the modules then run one by one)
-    (plan.training, plan.momentum, plan.eps, plan.running_mean, plan.running_var, plan.counter,
-     plan.fused_running) = bn_module_state(norm, feats)
+    plan.bn = bn_module_state(norm, feats)
     if res is not None:
         out = _ConvBnAct.apply(feats, conv.weight, norm.weight, norm.bias, plan, res.contiguous())
     else:
