@@ -1137,6 +1137,45 @@ int wcn_fps(const float* points, const int32_t* cu, int64_t total_segs, const in
             int32_t k, int64_t max_len, const int32_t* start, int32_t tier, void* workspace, size_t workspace_bytes,
             int32_t* idx, wcn_stream_t stream);
 
+/* ---- axial rotary table and shared-tile attention kernels (ABI 18, additions only) ----------------------------------------------
+ * wcn_rope_table_axes is wcn_rope_table with one frequency count per axis (the Volt volume transformer rotates 12 / 12 / 8
+ * pairs by x / y / z): `freqs` is the concatenation float[counts[0] + counts[1] + counts[2]] on the device, `counts` a HOST
+ * array; pair j of a token belongs to the axis a whose run holds j and turns by pos[a] * freqs[j], pos[a] =
+ * float(coord[a]) - origin[a] + bias (fp32, one rounding per operation; a negative coordinate is a negative angle).  table
+ * [total, sum(counts), 2] fp32 = (cos, sin); wcn_qk_prologue_fwd / _bwd consume it unchanged with rot_pairs = sum(counts).
+ * 2 * sum(counts) > 256 -> WCN_ERROR_UNSUPPORTED_CONFIG; a negative count, counts NULL -> WCN_ERROR_INVALID_PARAMETERS.
+ *
+ * The attention kernels above are one wave per workgroup: every wave streams each 32-key (or 32-query) tile of its sequence
+ * from global memory itself.  WCN_ATTN_SHARED runs the same products in workgroups of four waves: a work item is (sequence,
+ * 128-row block, head), wave w owns rows 32 w .. 32 w + 31 of the block, and the workgroup stages every tile of the swept side
+ * ONCE in LDS (row-major and as the transposed image the one-wave kernel builds), double-buffered, for all four waves.  Each
+ * wave then issues exactly the one-wave kernel's sequence - same tile order, same MFMA chains, same exp2-domain softmax, same
+ * stores - so out, lse, dq, dk, dv carry the same bits under either variant, and everything said above holds for both: empty
+ * sides, rows outside every sequence not written, fixed-order sums, q_splits (partials in the same layout), the host never reads
+ * cu_*.
+ *   wcn_attn_varlen_variant   host-only: the variant WCN_ATTN_AUTO resolves to for `direction` (0 = forward, 1 = backward), a
+ *                             pure function of these numbers: WCN_ATTN_SHARED when the longest swept side (max_seqlen_k
+ *                             forward; max(max_seqlen_q, max_seqlen_k) backward, whose dQ kernel sweeps the keys and whose
+ *                             dK/dV kernel the queries) is at least 512 rows, WCN_ATTN_ONE_WAVE otherwise (and for an empty
+ *                             call).  Measured: docs/OPTIMISATION_LOG.md section AG.
+ *   wcn_attn_varlen_kv_fwd_v / wcn_attn_varlen_kv_bwd_v   the entry points above with `variant` (an unknown value ->
+ *                             WCN_ERROR_INVALID_PARAMETERS).  The entry points without it, packed and separate, call
+ *                             WCN_ATTN_AUTO. */
+enum wcn_attn_variant { WCN_ATTN_AUTO = 0, WCN_ATTN_ONE_WAVE = 1, WCN_ATTN_SHARED = 2 };
+int wcn_rope_table_axes(const void* coords, int32_t coords_float, int64_t total, const float* origin, float bias,
+                        const float* freqs, const int32_t counts[3], float* table, wcn_stream_t stream);
+int32_t wcn_attn_varlen_variant(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads, int32_t direction);
+int wcn_attn_varlen_kv_fwd_v(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                             int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                             int32_t dtype, void* out, float* lse, int32_t variant, wcn_stream_t stream);
+int wcn_attn_varlen_kv_bwd_v(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                             int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                             int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                             void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
+                             int32_t variant, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ WCN_GRID_KEY_CELL, WCN_GRID_KEY_CORNER = 0, 1  # mode of wcn_grid_point_keys (cs
 WCN_SEG_MOMENTS, WCN_SEG_RANGE, WCN_SEG_DOT = 0, 1, 2  # mode of wcn_seg_stats (csrc/segmented.hip)
 WCN_SEG_ADD, WCN_SEG_SUB, WCN_SEG_MUL, WCN_SEG_DIV, WCN_SEG_NORM, WCN_SEG_NORM_BWD = 0, 1, 2, 3, 4, 5  # op of wcn_seg_apply
 WCN_FPS_AUTO, WCN_FPS_RESIDENT, WCN_FPS_STREAMED = 0, 1, 2  # tier of wcn_fps (csrc/fps.hip)
+WCN_ATTN_AUTO, WCN_ATTN_ONE_WAVE, WCN_ATTN_SHARED = 0, 1, 2  # variant of wcn_attn_varlen_kv_*_v (csrc/attn_varlen.hip)
 
 _I32P = c_void_p  # all pointers travel as void*
 _3I = c_int32 * 3
@@ -266,7 +267,20 @@ SIGNATURES = {
          c_int64, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
          c_int32, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_attn_varlen_variant": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "wcn_attn_varlen_kv_fwd_v": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
+         c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p, c_int32, c_void_p],
+    ),
+    "wcn_attn_varlen_kv_bwd_v": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+         c_int64, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+         c_int32, c_void_p, c_size_t, c_int32, c_void_p],
+    ),
     "wcn_rope_table": (c_int, [c_void_p, c_int32, c_int64, c_void_p, ctypes.c_float, c_void_p, c_int32, c_void_p, c_void_p]),
+    "wcn_rope_table_axes": (c_int, [c_void_p, c_int32, c_int64, c_void_p, ctypes.c_float, c_void_p, _3I, c_void_p, c_void_p]),
     "wcn_qk_prologue_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_qk_prologue_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "wcn_qk_prologue_fwd": (

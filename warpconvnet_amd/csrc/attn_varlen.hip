@@ -29,6 +29,21 @@
 // pass has only nblk_k * H waves per sequence, each sweeping every query block.  With q_splits > 1 an item is (sequence,
 // key block, split, head): split j sweeps its contiguous share of the query blocks and writes unscaled fp32 partials to
 // part [q_splits, total_k, 2, H, D]; attn_dkdv_reduce_kernel sums them in the order 0 .. q_splits - 1, scales, casts.
+// Shared-tile variants (WCN_ATTN_SHARED: attn_fwd_shared_kernel, attn_bwd_dq_shared_kernel, attn_bwd_dkdv_shared_kernel).
+// The kernels above are one wave per workgroup: every wave streams each 32-row tile of the side it sweeps from global
+// memory itself - 8 KB per tile at D = 64 for eight MFMAs.  The shared variants run four waves (256 threads) on one
+// (sequence, 128-row block, head): wave w owns rows 32 w .. 32 w + 31, and the WORKGROUP stages each tile of the swept side
+// once in LDS - row-major (what load8 returns) and as the transposed image the one-wave kernel builds - so global operand
+// traffic per owned row drops 4 x.  Staging is double-buffered: the next tile's loads are issued before the current tile's
+// MFMAs and written to the other buffer after them, one barrier per tile.  Each wave then issues exactly the one-wave
+// kernel's sequence on its rows (same tile order, MFMA chains, exp2-domain softmax, stores): the operands hold the same
+// values wherever they were read from, so every output element carries the same bits (tests/test_gpu_attention_shared.py).
+// Loop bounds are uniform over the workgroup (one sequence, one split share); a wave whose block lies past the end of its
+// side computes on zero rows, stages, reaches every barrier and stores nothing.
+// LDS at D = 64, both buffers: forward K rows 32 x 72 x 2 B + V^T 64 x 36 x 2 B = 9 216 B per buffer, 18 KiB -> 8 workgroups
+// (32 waves) per CU by LDS, 3 per SIMD by registers (116 VGPRs); dQ K rows + V rows + K^T = 13 824 B, 27 KiB -> 5 workgroups,
+// 2 per SIMD by registers (138 VGPRs); dK/dV Q rows + dO rows + Q^T + dO^T + lse + delta = 18 688 B, 36.5 KiB -> 4
+// workgroups, 2 per SIMD by registers (161 VGPRs).  Of the 160 KiB of a CU none of them is bound by LDS.
 // D in {16, 32, 64}: D / 16 k-steps per score product, one (D <= 32) or two 32-row halves of d per output product
 // (D = 16 computes 16 rows it drops; the bound at that size is the exp and the softmax VALU work, not the MFMA).
 #include "wcn_common.h"
@@ -72,11 +87,11 @@ struct AttnItem {
   int len_q, len_k, b0, hd;
 };
 __device__ __forceinline__ void attn_item(int64_t id, int nblk, int heads, const int32_t* __restrict__ cu_q,
-                                          const int32_t* __restrict__ cu_k, AttnItem& it) {
+                                          const int32_t* __restrict__ cu_k, AttnItem& it, int block_rows = kAttnBlock) {
   it.hd = (int)(id % heads);
   const int64_t t = id / heads;
   const int64_t seq = t / nblk;
-  it.b0 = (int)(t % nblk) * kAttnBlock;
+  it.b0 = (int)(t % nblk) * block_rows;
   it.beg_q = cu_q[seq];
   it.len_q = cu_q[seq + 1] - (int)it.beg_q;
   it.beg_k = cu_k[seq];
@@ -501,6 +516,363 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const AttnOperands<T> a
   }
 }
 
+// ---- shared-tile variants: four waves per workgroup, every tile of the swept side staged once in LDS ------------------
+// One tile is 32 rows x D elements = 4 D pieces of 16 bytes: thread c < 4 D of the workgroup owns piece (row c & 31,
+// d-chunk c >> 5) - the walk of stage_transposed - loads it into a register while the previous tile is multiplied, and
+// writes it to the other buffer afterwards (one barrier per tile).
+constexpr int kAttnWaves = 4;
+constexpr int kAttnWgRows = kAttnWaves * kAttnBlock;  // rows of a shared-tile work item
+template <int D>
+struct SharedTile {
+  static constexpr int kRowPitch = D + 8;                       // row-major image: 16-B aligned rows, elements
+  static constexpr int kRows = kAttnBlock * kRowPitch;          // elements of a row-major image
+  static constexpr int kTr = ((D + 31) / 32) * 32 * kAttnPitch; // elements of a transposed image
+};
+
+template <typename T, int D>
+__device__ __forceinline__ void put_rows(T* __restrict__ rows, const typename AFrag<T>::type& v, int row, int dch) {
+  *reinterpret_cast<typename AFrag<T>::type*>(rows + row * SharedTile<D>::kRowPitch + 8 * dch) = v;
+}
+template <typename T>
+__device__ __forceinline__ void put_tr(T* __restrict__ img, const typename AFrag<T>::type& v, int row, int dch) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) img[(8 * dch + e) * kAttnPitch + row] = v[e];
+}
+// The fragment load8 returns for (row r, d 16 s + 8 h .. + 7), from a row-major image.
+template <typename T, int D>
+__device__ __forceinline__ typename AFrag<T>::type get_row(const T* __restrict__ rows, int r, int s, int h) {
+  return *reinterpret_cast<const typename AFrag<T>::type*>(rows + r * SharedTile<D>::kRowPitch + 16 * s + 8 * h);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_fwd_shared_kernel(const AttnOperands<T> a, int64_t items, int nblk, float c2,
+                                                              T* __restrict__ out, float* __restrict__ lse) {
+  typedef typename AFrag<T>::type frag;
+  typedef SharedTile<D> Tile;
+  constexpr int NS = D / 16, NMB = (D + 31) / 32;
+  __shared__ __attribute__((aligned(16))) T kr[2][Tile::kRows];
+  __shared__ __attribute__((aligned(16))) T vt[2][Tile::kTr];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int srow = tid & 31, sdch = tid >> 5;
+  const bool stager = tid < 4 * D;
+  const int heads = a.heads;
+  const int64_t qp = a.q_stride, kp = a.kv_stride;
+  for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
+    AttnItem w;
+    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    if (w.b0 >= w.len_q) continue;  // (the same for every wave of the workgroup)
+    const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
+    const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
+    const int rb = w.b0 + kAttnBlock * wave;  // this wave's rows; past the end they are zeros and nothing is stored
+    frag qf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) qf[s] = load8<T>(q, qp, rb + r, w.len_q, 16 * s + 8 * h);
+    a_f32x16 acc[NMB];
+#pragma unroll
+    for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[mb][i] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    frag kreg, vreg;
+    if (stager && w.len_k > 0) {
+      put_rows<T, D>(kr[0], load8<T>(k, kp, srow, w.len_k, 8 * sdch), srow, sdch);
+      put_tr<T>(vt[0], load8<T>(v, kp, srow, w.len_k, 8 * sdch), srow, sdch);
+    }
+    __syncthreads();
+    for (int k0 = 0, cur = 0; k0 < w.len_k; k0 += kAttnBlock, cur ^= 1) {
+      const bool more = stager && k0 + kAttnBlock < w.len_k;
+      if (more) {  // the next tile's loads are in flight during this tile's MFMAs
+        kreg = load8<T>(k, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
+        vreg = load8<T>(v, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
+      }
+      a_f32x16 st;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) st[i] = 0.f;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) st = AFrag<T>::mfma(get_row<T, D>(kr[cur], r, s, h), qf[s], st);
+      float x[16];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        x[i] = k0 + acc_row(i, h) < w.len_k ? st[i] * c2 : -INFINITY;
+        mx = fmaxf(mx, x[i]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mn = fmaxf(m, mx);
+      const float alpha = __builtin_amdgcn_exp2f(m - mn);
+      float ls = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        x[i] = __builtin_amdgcn_exp2f(x[i] - mn);
+        ls += x[i];
+      }
+      ls += __shfl_xor(ls, 32);
+      l = l * alpha + ls;
+      m = mn;
+#pragma unroll
+      for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[mb][i] *= alpha;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const frag pf = acc_frag<T>(x, s);
+#pragma unroll
+        for (int mb = 0; mb < NMB; ++mb) acc[mb] = AFrag<T>::mfma(read_tr<T>(vt[cur], mb, s, r, h), pf, acc[mb]);
+      }
+      if (more) {
+        put_rows<T, D>(kr[cur ^ 1], kreg, srow, sdch);
+        put_tr<T>(vt[cur ^ 1], vreg, srow, sdch);
+      }
+      __syncthreads();  // the next tile is staged, and this tile's reads are done before its buffer is written again
+    }
+    const int row = rb + r;
+    if (row < w.len_q) {
+      const bool any = w.len_k > 0;
+      const int64_t t = w.beg_q + row;
+      store_dcol<T, D>(out + (t * heads + w.hd) * D, acc, any ? 1.f / l : 0.f, h);
+      if (h == 0) lse[t * heads + w.hd] = any ? (m + __log2f(l)) * kLn2 : -INFINITY;
+    }
+  }
+}
+
+// dQ of one (sequence, 128-query block, head): K and V rows and the K^T image staged once per key tile.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_bwd_dq_shared_kernel(const AttnOperands<T> a, const T* __restrict__ dout,
+                                                                 const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                 int64_t items, int nblk, float c2, float scale,
+                                                                 T* __restrict__ dq_out, int64_t dq_stride) {
+  typedef typename AFrag<T>::type frag;
+  typedef SharedTile<D> Tile;
+  constexpr int NS = D / 16, NMB = (D + 31) / 32;
+  __shared__ __attribute__((aligned(16))) T kr[2][Tile::kRows];
+  __shared__ __attribute__((aligned(16))) T vr[2][Tile::kRows];
+  __shared__ __attribute__((aligned(16))) T kt[2][Tile::kTr];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int srow = tid & 31, sdch = tid >> 5;
+  const bool stager = tid < 4 * D;
+  const int heads = a.heads;
+  const int64_t qp = a.q_stride, kp = a.kv_stride, opitch = (int64_t)heads * D;
+  for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
+    AttnItem w;
+    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    if (w.b0 >= w.len_q) continue;
+    const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
+    const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* dO = dout + w.beg_q * opitch + (int64_t)w.hd * D;
+    const int row = w.b0 + kAttnBlock * wave + r;
+    const bool ok = row < w.len_q;
+    frag qf[NS], df[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      qf[s] = load8<T>(q, qp, row, w.len_q, 16 * s + 8 * h);
+      df[s] = load8<T>(dO, opitch, row, w.len_q, 16 * s + 8 * h);
+    }
+    float L = ok ? lse[(w.beg_q + row) * heads + w.hd] : 0.f;
+    L = L > -INFINITY ? L * kLog2e : INFINITY;
+    const float E = ok ? delta[(w.beg_q + row) * heads + w.hd] : 0.f;
+    a_f32x16 dq[NMB];
+#pragma unroll
+    for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dq[mb][i] = 0.f;
+    frag kreg, vreg;
+    if (stager && w.len_k > 0) {
+      kreg = load8<T>(k, kp, srow, w.len_k, 8 * sdch);
+      put_rows<T, D>(kr[0], kreg, srow, sdch);
+      put_tr<T>(kt[0], kreg, srow, sdch);
+      put_rows<T, D>(vr[0], load8<T>(v, kp, srow, w.len_k, 8 * sdch), srow, sdch);
+    }
+    __syncthreads();
+    for (int k0 = 0, cur = 0; k0 < w.len_k; k0 += kAttnBlock, cur ^= 1) {
+      const bool more = stager && k0 + kAttnBlock < w.len_k;
+      if (more) {
+        kreg = load8<T>(k, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
+        vreg = load8<T>(v, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
+      }
+      a_f32x16 st, dpt;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) st[i] = dpt[i] = 0.f;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        st = AFrag<T>::mfma(get_row<T, D>(kr[cur], r, s, h), qf[s], st);
+        dpt = AFrag<T>::mfma(get_row<T, D>(vr[cur], r, s, h), df[s], dpt);
+      }
+      float ds[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float p = k0 + acc_row(i, h) < w.len_k ? __builtin_amdgcn_exp2f(st[i] * c2 - L) : 0.f;
+        ds[i] = p * (dpt[i] - E);
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const frag dsf = acc_frag<T>(ds, s);
+#pragma unroll
+        for (int mb = 0; mb < NMB; ++mb) dq[mb] = AFrag<T>::mfma(read_tr<T>(kt[cur], mb, s, r, h), dsf, dq[mb]);
+      }
+      if (more) {
+        put_rows<T, D>(kr[cur ^ 1], kreg, srow, sdch);
+        put_tr<T>(kt[cur ^ 1], kreg, srow, sdch);
+        put_rows<T, D>(vr[cur ^ 1], vreg, srow, sdch);
+      }
+      __syncthreads();
+    }
+    if (ok) store_dcol<T, D>(dq_out + (w.beg_q + row) * dq_stride + (int64_t)w.hd * D, dq, scale, h);
+  }
+}
+
+// dK, dV of one (sequence, 128-key block, [split,] head): Q and dO rows, their transposed images, lse and delta staged
+// once per query tile.  SPLIT as in attn_bwd_dkdv_kernel (same shares, same partial layout).
+template <typename T, int D, bool SPLIT>
+__global__ __launch_bounds__(256) void attn_bwd_dkdv_shared_kernel(const AttnOperands<T> a, const T* __restrict__ dout,
+                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                   int64_t items, int nblk, float c2, float scale,
+                                                                   T* __restrict__ dk_out, T* __restrict__ dv_out,
+                                                                   int64_t dkv_stride, int q_splits, int64_t total_k,
+                                                                   float* __restrict__ part) {
+  typedef typename AFrag<T>::type frag;
+  typedef SharedTile<D> Tile;
+  constexpr int NS = D / 16, NMB = (D + 31) / 32;
+  __shared__ __attribute__((aligned(16))) T qr[2][Tile::kRows];
+  __shared__ __attribute__((aligned(16))) T dr[2][Tile::kRows];
+  __shared__ __attribute__((aligned(16))) T qt[2][Tile::kTr];
+  __shared__ __attribute__((aligned(16))) T dot[2][Tile::kTr];
+  __shared__ __attribute__((aligned(16))) float s_lse[2][kAttnBlock];
+  __shared__ __attribute__((aligned(16))) float s_del[2][kAttnBlock];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int srow = tid & 31, sdch = tid >> 5;
+  const bool stager = tid < 4 * D;
+  const int heads = a.heads;
+  const int64_t qp = a.q_stride, kp = a.kv_stride, opitch = (int64_t)heads * D;
+  for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
+    AttnItem w;
+    int split = 0;
+    if (SPLIT) {
+      const int64_t t = id / heads;
+      split = (int)(t % q_splits);
+      attn_item((t / q_splits) * heads + id % heads, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    } else {
+      attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    }
+    if (w.b0 >= w.len_k) continue;
+    int q_beg = 0, q_end = w.len_q;
+    if (SPLIT) {
+      const int64_t nq = (w.len_q + kAttnBlock - 1) / kAttnBlock, per = (nq + q_splits - 1) / q_splits;
+      const int64_t lo = split * per * kAttnBlock, hi = (split + 1) * per * kAttnBlock;
+      q_beg = (int)(lo < w.len_q ? lo : w.len_q);
+      q_end = (int)(hi < w.len_q ? hi : w.len_q);
+    }
+    const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
+    const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
+    const T* dO = dout + w.beg_q * opitch + (int64_t)w.hd * D;
+    const int key = w.b0 + kAttnBlock * wave + r;
+    frag kf[NS], vf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      kf[s] = load8<T>(k, kp, key, w.len_k, 16 * s + 8 * h);
+      vf[s] = load8<T>(v, kp, key, w.len_k, 16 * s + 8 * h);
+    }
+    a_f32x16 dk[NMB], dv[NMB];
+#pragma unroll
+    for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dk[mb][i] = dv[mb][i] = 0.f;
+    // the staged scalar of thread tid < 32: lse (exp2 domain, +inf for a query without a key) of query row q0 + tid; of
+    // 32 <= tid < 64: delta of row q0 + tid - 32
+    auto load_stat = [&](int q0) -> float {
+      const int qrow = q0 + srow;
+      const bool ok = qrow < w.len_q;
+      const int64_t t = w.beg_q + qrow;
+      if (tid < kAttnBlock) {
+        const float L = ok ? lse[t * heads + w.hd] : 0.f;
+        return L > -INFINITY ? L * kLog2e : INFINITY;
+      }
+      return ok ? delta[t * heads + w.hd] : 0.f;
+    };
+    auto put_stat = [&](int buf, float x) {
+      if (tid < kAttnBlock) s_lse[buf][srow] = x;
+      else s_del[buf][srow] = x;
+    };
+    frag qreg, dreg;
+    float stat = 0.f;
+    if (q_beg < q_end) {
+      if (stager) {
+        qreg = load8<T>(q, qp, q_beg + srow, w.len_q, 8 * sdch);
+        dreg = load8<T>(dO, opitch, q_beg + srow, w.len_q, 8 * sdch);
+        put_rows<T, D>(qr[0], qreg, srow, sdch);
+        put_tr<T>(qt[0], qreg, srow, sdch);
+        put_rows<T, D>(dr[0], dreg, srow, sdch);
+        put_tr<T>(dot[0], dreg, srow, sdch);
+      }
+      if (tid < 2 * kAttnBlock) put_stat(0, load_stat(q_beg));
+    }
+    __syncthreads();
+    for (int q0 = q_beg, cur = 0; q0 < q_end; q0 += kAttnBlock, cur ^= 1) {
+      const bool more = q0 + kAttnBlock < q_end;
+      if (more) {
+        if (stager) {
+          qreg = load8<T>(q, qp, q0 + kAttnBlock + srow, w.len_q, 8 * sdch);
+          dreg = load8<T>(dO, opitch, q0 + kAttnBlock + srow, w.len_q, 8 * sdch);
+        }
+        if (tid < 2 * kAttnBlock) stat = load_stat(q0 + kAttnBlock);
+      }
+      a_f32x16 sc, dp;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sc[i] = dp[i] = 0.f;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        sc = AFrag<T>::mfma(get_row<T, D>(qr[cur], r, s, h), kf[s], sc);
+        dp = AFrag<T>::mfma(get_row<T, D>(dr[cur], r, s, h), vf[s], dp);
+      }
+      float p[16], ds[16];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 L = *reinterpret_cast<const float4*>(s_lse[cur] + 8 * g + 4 * h);
+        const float4 E = *reinterpret_cast<const float4*>(s_del[cur] + 8 * g + 4 * h);
+        const float Lv[4] = {L.x, L.y, L.z, L.w}, Ev[4] = {E.x, E.y, E.z, E.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = 4 * g + e;
+          p[i] = key < w.len_k ? __builtin_amdgcn_exp2f(sc[i] * c2 - Lv[e]) : 0.f;
+          ds[i] = p[i] * (dp[i] - Ev[e]);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const frag pf = acc_frag<T>(p, s), dsf = acc_frag<T>(ds, s);
+#pragma unroll
+        for (int mb = 0; mb < NMB; ++mb) {
+          dv[mb] = AFrag<T>::mfma(read_tr<T>(dot[cur], mb, s, r, h), pf, dv[mb]);
+          dk[mb] = AFrag<T>::mfma(read_tr<T>(qt[cur], mb, s, r, h), dsf, dk[mb]);
+        }
+      }
+      if (more) {
+        if (stager) {
+          put_rows<T, D>(qr[cur ^ 1], qreg, srow, sdch);
+          put_tr<T>(qt[cur ^ 1], qreg, srow, sdch);
+          put_rows<T, D>(dr[cur ^ 1], dreg, srow, sdch);
+          put_tr<T>(dot[cur ^ 1], dreg, srow, sdch);
+        }
+        if (tid < 2 * kAttnBlock) put_stat(cur ^ 1, stat);
+      }
+      __syncthreads();
+    }
+    if (key < w.len_k) {
+      if (SPLIT) {
+        float* dst = part + (((int64_t)split * total_k + w.beg_k + key) * 2 * heads + w.hd) * D;
+        store_dcol_f32<D>(dst, dk, h);
+        store_dcol_f32<D>(dst + (int64_t)heads * D, dv, h);
+      } else {
+        const int64_t off = (w.beg_k + key) * dkv_stride + (int64_t)w.hd * D;
+        store_dcol<T, D>(dk_out + off, dk, scale, h);
+        store_dcol<T, D>(dv_out + off, dv, 1.f, h);
+      }
+    }
+  }
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------
 // One call's operands and sizes, already checked.
 struct AttnCall {
@@ -520,8 +892,25 @@ static AttnOperands<T> attn_operands(const AttnCall& c) {
   return AttnOperands<T>{(const T*)c.q, (const T*)c.k, (const T*)c.v, c.q_stride, c.kv_stride, c.cu_q, c.cu_k, c.heads};
 }
 
+static inline int attn_wg_blocks(int max_seqlen) { return (max_seqlen + kAttnWgRows - 1) / kAttnWgRows; }
+
+// The AUTO rule (see wcn.h; the measurements behind it: docs/OPTIMISATION_LOG.md).
+constexpr int kAttnSharedMinSweep = 512;  // rows of the swept side from which the shared kernels were measured ahead
+static int attn_variant(const AttnCall& c, int variant, int direction) {
+  if (variant != WCN_ATTN_AUTO) return variant;
+  return wcn_attn_varlen_variant(c.num_seqs, c.max_q, c.max_k, c.heads, direction);
+}
+
 template <typename T, int D>
-static int attn_fwd_t(const AttnCall& c, void* out, float* lse, hipStream_t s) {
+static int attn_fwd_t(const AttnCall& c, void* out, float* lse, int variant, hipStream_t s) {
+  if (attn_variant(c, variant, 0) == WCN_ATTN_SHARED) {
+    const int nblk = attn_wg_blocks(c.max_q);
+    const int64_t items = c.num_seqs * nblk * c.heads;
+    if (items > 0)
+      hipLaunchKernelGGL((attn_fwd_shared_kernel<T, D>), dim3(attn_grid(items)), dim3(64 * kAttnWaves), 0, s, attn_operands<T>(c),
+                         items, nblk, c.scale * kLog2e, (T*)out, lse);
+    return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
+  }
   const int nblk = attn_blocks(c.max_q);
   const int64_t items = c.num_seqs * nblk * c.heads;
   if (items > 0)
@@ -532,56 +921,74 @@ static int attn_fwd_t(const AttnCall& c, void* out, float* lse, hipStream_t s) {
 
 template <typename T, int D>
 static int attn_bwd_t(const AttnCall& c, const void* dout, const void* out, const float* lse, void* dq, int64_t dq_stride,
-                      void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part, float* delta, hipStream_t s) {
+                      void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part, float* delta, int variant,
+                      hipStream_t s) {
   const AttnOperands<T> a = attn_operands<T>(c);
   const float c2 = c.scale * kLog2e;
   const int64_t rows = c.total_q * c.heads;
-  const int nblk_q = attn_blocks(c.max_q), nblk_k = attn_blocks(c.max_k);
+  const bool shared = attn_variant(c, variant, 1) == WCN_ATTN_SHARED;
+  const int nblk_q = shared ? attn_wg_blocks(c.max_q) : attn_blocks(c.max_q);
+  const int nblk_k = shared ? attn_wg_blocks(c.max_k) : attn_blocks(c.max_k);
+  const dim3 wg(shared ? 64 * kAttnWaves : 64);
   const int64_t items_q = c.num_seqs * nblk_q * c.heads, items_k = c.num_seqs * nblk_k * c.heads;
   if (rows > 0)
     hipLaunchKernelGGL((attn_delta_kernel<T, D>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (const T*)dout,
                        (const T*)out, rows, delta);
   if (items_k > 0 && c.total_k > 0) {
     if (q_splits > 1) {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, true>), dim3(attn_grid(items_k * q_splits)), dim3(64), 0, s, a,
-                         (const T*)dout, lse, (const float*)delta, items_k * q_splits, nblk_k, c2, c.scale, (T*)dk, (T*)dv,
-                         dkv_stride, q_splits, c.total_k, part);
+      if (shared)
+        hipLaunchKernelGGL((attn_bwd_dkdv_shared_kernel<T, D, true>), dim3(attn_grid(items_k * q_splits)), wg, 0, s, a,
+                           (const T*)dout, lse, (const float*)delta, items_k * q_splits, nblk_k, c2, c.scale, (T*)dk, (T*)dv,
+                           dkv_stride, q_splits, c.total_k, part);
+      else
+        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, true>), dim3(attn_grid(items_k * q_splits)), wg, 0, s, a,
+                           (const T*)dout, lse, (const float*)delta, items_k * q_splits, nblk_k, c2, c.scale, (T*)dk, (T*)dv,
+                           dkv_stride, q_splits, c.total_k, part);
       const int64_t n = c.total_k * 2 * c.heads * (D / 4);
       hipLaunchKernelGGL((attn_dkdv_reduce_kernel<T, D>), dim3(attn_grid((n + 255) / 256)), dim3(256), 0, s,
                          (const float*)part, c.cu_k, c.num_seqs, c.total_k, c.heads, q_splits, c.scale, (T*)dk, (T*)dv,
                          dkv_stride);
+    } else if (shared) {
+      hipLaunchKernelGGL((attn_bwd_dkdv_shared_kernel<T, D, false>), dim3(attn_grid(items_k)), wg, 0, s, a, (const T*)dout, lse,
+                         (const float*)delta, items_k, nblk_k, c2, c.scale, (T*)dk, (T*)dv, dkv_stride, 1, c.total_k,
+                         (float*)nullptr);
     } else {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, false>), dim3(attn_grid(items_k)), dim3(64), 0, s, a, (const T*)dout, lse,
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, false>), dim3(attn_grid(items_k)), wg, 0, s, a, (const T*)dout, lse,
                          (const float*)delta, items_k, nblk_k, c2, c.scale, (T*)dk, (T*)dv, dkv_stride, 1, c.total_k,
                          (float*)nullptr);
     }
   }
-  if (items_q > 0 && c.total_q > 0)
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), dim3(attn_grid(items_q)), dim3(64), 0, s, a, (const T*)dout, lse,
-                       (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride);
+  if (items_q > 0 && c.total_q > 0) {
+    if (shared)
+      hipLaunchKernelGGL((attn_bwd_dq_shared_kernel<T, D>), dim3(attn_grid(items_q)), wg, 0, s, a, (const T*)dout, lse,
+                         (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride);
+    else
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), dim3(attn_grid(items_q)), wg, 0, s, a, (const T*)dout, lse,
+                         (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride);
+  }
   return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
 }
 
-static int attn_fwd_dispatch(const AttnCall& c, int head_dim, int dtype, void* out, float* lse, hipStream_t s) {
+static int attn_fwd_dispatch(const AttnCall& c, int head_dim, int dtype, void* out, float* lse, int variant, hipStream_t s) {
   return with_dtype16(dtype, [&](auto t) {
     using T = decltype(t);
     switch (head_dim) {
-      case 16: return attn_fwd_t<T, 16>(c, out, lse, s);
-      case 32: return attn_fwd_t<T, 32>(c, out, lse, s);
-      default: return attn_fwd_t<T, 64>(c, out, lse, s);
+      case 16: return attn_fwd_t<T, 16>(c, out, lse, variant, s);
+      case 32: return attn_fwd_t<T, 32>(c, out, lse, variant, s);
+      default: return attn_fwd_t<T, 64>(c, out, lse, variant, s);
     }
   });
 }
 
 static int attn_bwd_dispatch(const AttnCall& c, int head_dim, int dtype, const void* dout, const void* out, const float* lse,
                              void* dq, int64_t dq_stride, void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part,
-                             float* delta, hipStream_t s) {
+                             float* delta, int variant, hipStream_t s) {
   return with_dtype16(dtype, [&](auto t) {
     using T = decltype(t);
     switch (head_dim) {
-      case 16: return attn_bwd_t<T, 16>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
-      case 32: return attn_bwd_t<T, 32>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
-      default: return attn_bwd_t<T, 64>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, s);
+      case 16: return attn_bwd_t<T, 16>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, s);
+      case 32: return attn_bwd_t<T, 32>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, s);
+      default: return attn_bwd_t<T, 64>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, s);
     }
   });
 }
@@ -652,7 +1059,7 @@ int wcn_attn_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, int64_t num_
   if (st == WCN_SUCCESS && (!out || !lse)) st = WCN_ERROR_INVALID_PARAMETERS;
   if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
   const AttnCall c = attn_packed_call(qkv, cu_seqlens, num_seqs, total, heads, head_dim, max_seqlen, softmax_scale, 2);
-  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, (hipStream_t)stream);
+  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, WCN_ATTN_AUTO, (hipStream_t)stream);
 }
 
 int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, const float* lse, const int32_t* cu_seqlens,
@@ -668,7 +1075,7 @@ int wcn_attn_varlen_bwd(const void* dout, const void* qkv, const void* out, cons
   const int64_t hd = (int64_t)heads * head_dim;
   char* d = (char*)dqkv;
   return attn_bwd_dispatch(c, head_dim, dtype, dout, out, lse, d, 3 * hd, d + 2 * hd, d + 4 * hd, 3 * hd, 1, nullptr,
-                           (float*)workspace, (hipStream_t)stream);
+                           (float*)workspace, WCN_ATTN_AUTO, (hipStream_t)stream);
 }
 
 int32_t wcn_attn_varlen_kv_splits(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads) {
@@ -690,10 +1097,28 @@ size_t wcn_attn_varlen_kv_workspace_bytes(int64_t total_q, int64_t total_k, int3
   return bytes;
 }
 
+static bool attn_variant_ok(int32_t v) { return v == WCN_ATTN_AUTO || v == WCN_ATTN_ONE_WAVE || v == WCN_ATTN_SHARED; }
+
+int32_t wcn_attn_varlen_variant(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads, int32_t direction) {
+  if (num_seqs < 1 || max_seqlen_q < 1 || max_seqlen_k < 1 || heads < 1) return WCN_ATTN_ONE_WAVE;
+  // the forward sweeps the keys of a query block; of the backward's two kernels dQ sweeps the keys, dK/dV the queries
+  const int sweep = direction == 0 ? max_seqlen_k : (max_seqlen_q > max_seqlen_k ? max_seqlen_q : max_seqlen_k);
+  return sweep >= kAttnSharedMinSweep ? WCN_ATTN_SHARED : WCN_ATTN_ONE_WAVE;
+}
+
 int wcn_attn_varlen_kv_fwd(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
                            const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
                            int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
                            int32_t dtype, void* out, float* lse, wcn_stream_t stream) {
+  return wcn_attn_varlen_kv_fwd_v(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
+                                  max_seqlen_q, max_seqlen_k, softmax_scale, dtype, out, lse, WCN_ATTN_AUTO, stream);
+}
+
+int wcn_attn_varlen_kv_fwd_v(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                             int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                             int32_t dtype, void* out, float* lse, int32_t variant, wcn_stream_t stream) {
+  if (!attn_variant_ok(variant)) return WCN_ERROR_INVALID_PARAMETERS;
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
   if (st != WCN_SUCCESS) return st;
@@ -701,7 +1126,7 @@ int wcn_attn_varlen_kv_fwd(const void* q, int64_t q_stride, const void* k, const
   if (num_seqs == 0 || total_q == 0 || max_seqlen_q == 0) return WCN_SUCCESS;
   const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
                    softmax_scale};
-  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, (hipStream_t)stream);
+  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, variant, (hipStream_t)stream);
 }
 
 int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
@@ -710,6 +1135,18 @@ int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, co
                            int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
                            void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
                            wcn_stream_t stream) {
+  return wcn_attn_varlen_kv_bwd_v(dout, q, q_stride, k, v, kv_stride, out, lse, cu_q, cu_k, num_seqs, total_q, total_k, heads,
+                                  head_dim, max_seqlen_q, max_seqlen_k, softmax_scale, dtype, dq, dq_stride, dk, dv, dkv_stride,
+                                  q_splits, workspace, workspace_bytes, WCN_ATTN_AUTO, stream);
+}
+
+int wcn_attn_varlen_kv_bwd_v(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                             int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                             int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                             void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
+                             int32_t variant, wcn_stream_t stream) {
+  if (!attn_variant_ok(variant)) return WCN_ERROR_INVALID_PARAMETERS;
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
   if (st != WCN_SUCCESS) return st;
@@ -730,5 +1167,5 @@ int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, co
   const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
                    softmax_scale};
   return attn_bwd_dispatch(c, head_dim, dtype, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta,
-                           (hipStream_t)stream);
+                           variant, (hipStream_t)stream);
 }

@@ -264,7 +264,7 @@ extern "C" {
 // 11 (additions only): wcn_window_group (window grouping of voxels by a deterministic counting sort, csrc/window_group.hip)
 // 12 (additions only): wcn_voxel_keys / wcn_voxel_map / wcn_csr_gather_reduce / wcn_row_spread (points <-> voxels, csrc/voxelize.hip)
 // 13 (additions only): lattice filters - wcn_hash128_*, wcn_permuto_simplex, wcn_grid_corners, wcn_lattice_* (csrc/lattice.hip)
-int wcn_abi_version(void) { return 17; }
+int wcn_abi_version(void) { return 18; }
 
 const char* wcn_status_string(int status) {
   switch (status) {

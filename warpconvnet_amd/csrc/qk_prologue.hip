@@ -293,6 +293,30 @@ __global__ __launch_bounds__(256) void rope_table_kernel(const TC* __restrict__ 
   reinterpret_cast<float2*>(table)[i] = make_float2(cs, sn);
 }
 
+// The axial table: axis a owns its own frequency count; pair j of a token belongs to the axis whose run of the concatenated
+// frequency vector holds j.  Same operations, same order as rope_table_kernel.
+struct RopeAxes {
+  int n0, n1, n2;
+};
+template <typename TC>
+__global__ __launch_bounds__(256) void rope_table_axes_kernel(const TC* __restrict__ coords, const float* __restrict__ origin,
+                                                              float bias, const float* __restrict__ freqs, RopeAxes ax,
+                                                              int64_t entries, float* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= entries) return;
+  const int pairs = ax.n0 + ax.n1 + ax.n2;
+  const int64_t t = i / pairs;
+  const int j = (int)(i - t * pairs);
+  const int a = j < ax.n0 ? 0 : (j < ax.n0 + ax.n1 ? 1 : 2);
+  float pos = (float)coords[t * 3 + a];
+  pos = pos - (origin ? origin[a] : 0.f);
+  pos = pos + bias;
+  const float ang = pos * freqs[j];  // (freqs is the concatenation: entry j is axis a's own frequency)
+  float sn, cs;
+  sincosf(ang, &sn, &cs);
+  reinterpret_cast<float2*>(table)[i] = make_float2(cs, sn);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 static int qk_pow2_ceil(int v) {
   int p = 1;
@@ -415,6 +439,29 @@ int wcn_rope_table(const void* coords, int32_t coords_float, int64_t total, cons
   else
     hipLaunchKernelGGL((rope_table_kernel<int32_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const int32_t*)coords, origin,
                        bias, freqs, num_freqs, entries, table);
+  return launch_status();
+}
+
+int wcn_rope_table_axes(const void* coords, int32_t coords_float, int64_t total, const float* origin, float bias,
+                        const float* freqs, const int32_t counts[3], float* table, wcn_stream_t stream) {
+  if (total < 0 || !counts || !(bias == bias)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (counts[0] < 0 || counts[1] < 0 || counts[2] < 0) return WCN_ERROR_INVALID_PARAMETERS;
+  if (coords_float != 0 && coords_float != 1) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  const int64_t pairs = (int64_t)counts[0] + counts[1] + counts[2];
+  if (2 * pairs > kQkMaxHeadDim) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  const int64_t entries = total * pairs;
+  if (entries == 0) return WCN_SUCCESS;
+  if (!coords || !freqs || !table || !aligned_to(table, 8)) return WCN_ERROR_INVALID_PARAMETERS;
+  const int64_t blocks = ceil_div(entries, 256);
+  if (blocks > INT32_MAX) return WCN_ERROR_INVALID_PARAMETERS;
+  hipStream_t s = (hipStream_t)stream;
+  const RopeAxes ax{counts[0], counts[1], counts[2]};
+  if (coords_float)
+    hipLaunchKernelGGL((rope_table_axes_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)coords, origin,
+                       bias, freqs, ax, entries, table);
+  else
+    hipLaunchKernelGGL((rope_table_axes_kernel<int32_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const int32_t*)coords, origin,
+                       bias, freqs, ax, entries, table);
   return launch_status();
 }
 

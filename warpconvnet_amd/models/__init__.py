@@ -1,6 +1,10 @@
-"""Model definitions the hot path's configurations exercise (reference `warpconvnet/models/`: only the MinkUNet family)."""
+"""Model definitions the hot path's configurations exercise (reference `warpconvnet/models/`: the MinkUNet family and the Volt
+volume transformer)."""
 from .mink_unet import (BasicBlock, BottleneckBlock, ConvBlock, ConvTrBlock, MinkUNet14, MinkUNet18, MinkUNet34, MinkUNet50,
                         MinkUNet101, MinkUNetBase)
+from .volt import (Block, ConvBlockTokenizer, Decoder, Detokenizer, DropPath, LayerScale, Mlp, RoPE, RoPEAttention, SparseResBlock,
+                   TokenConv, Tokenizer, Volt)
 
 __all__ = ["BasicBlock", "BottleneckBlock", "ConvBlock", "ConvTrBlock", "MinkUNet14", "MinkUNet18", "MinkUNet34", "MinkUNet50",
-           "MinkUNet101", "MinkUNetBase"]
+           "MinkUNet101", "MinkUNetBase", "Block", "ConvBlockTokenizer", "Decoder", "Detokenizer", "DropPath", "LayerScale", "Mlp",
+           "RoPE", "RoPEAttention", "SparseResBlock", "TokenConv", "Tokenizer", "Volt"]

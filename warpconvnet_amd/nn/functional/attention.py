@@ -100,20 +100,42 @@ def _check_host_cu(cu: Tensor, total: int, max_seqlen: int) -> None:
         raise ValueError(f"a sequence of {int(lens.max())} rows is longer than max_seqlen = {max_seqlen}")
 
 
+_VARIANTS = {"auto": _lib.WCN_ATTN_AUTO, "one_wave": _lib.WCN_ATTN_ONE_WAVE, "shared": _lib.WCN_ATTN_SHARED}
+
+
+def _variant_code(variant) -> int:
+    """``"auto"`` (the library's rule, ``wcn_attn_varlen_variant``), ``"one_wave"`` or ``"shared"`` (or their codes): which kernels
+    run - the results carry the same bits either way."""
+    if isinstance(variant, str) and variant in _VARIANTS:
+        return _VARIANTS[variant]
+    if isinstance(variant, int) and not isinstance(variant, bool) and variant in _VARIANTS.values():
+        return variant
+    raise ValueError(f"variant must be one of {sorted(_VARIANTS)}, got {variant!r}")
+
+
 class _VarlenAttention(Function):
     @staticmethod
-    def forward(ctx, qkv: Tensor, cu: Tensor, max_seqlen: int, scale: float) -> Tensor:
+    def forward(ctx, qkv: Tensor, cu: Tensor, max_seqlen: int, scale: float, variant: int = 0) -> Tensor:
         t, _, h, d = qkv.shape
         dev = qkv.device
         out = torch.empty(t, h, d, dtype=qkv.dtype, device=dev)
         lse = torch.empty(t, h, dtype=torch.float32, device=dev)
-        _lib.check(
-            _lib.lib().wcn_attn_varlen_fwd(_lib.ptr(qkv), _lib.ptr(cu), cu.numel() - 1, t, h, d, int(max_seqlen), float(scale),
-                                           _lib.dtype_code(qkv.dtype), _lib.ptr(out), _lib.ptr(lse), _lib.stream_handle(dev)),
-            "wcn_attn_varlen_fwd",
-        )
+        if variant == _lib.WCN_ATTN_AUTO:
+            _lib.check(
+                _lib.lib().wcn_attn_varlen_fwd(_lib.ptr(qkv), _lib.ptr(cu), cu.numel() - 1, t, h, d, int(max_seqlen), float(scale),
+                                               _lib.dtype_code(qkv.dtype), _lib.ptr(out), _lib.ptr(lse), _lib.stream_handle(dev)),
+                "wcn_attn_varlen_fwd",
+            )
+        else:  # a named variant: the three slots as separate operands of the entry point that takes one
+            _lib.check(
+                _lib.lib().wcn_attn_varlen_kv_fwd_v(_lib.ptr(qkv[:, 0]), 3 * h * d, _lib.ptr(qkv[:, 1]), _lib.ptr(qkv[:, 2]),
+                                                    3 * h * d, _lib.ptr(cu), _lib.ptr(cu), cu.numel() - 1, t, t, h, d,
+                                                    int(max_seqlen), int(max_seqlen), float(scale), _lib.dtype_code(qkv.dtype),
+                                                    _lib.ptr(out), _lib.ptr(lse), variant, _lib.stream_handle(dev)),
+                "wcn_attn_varlen_kv_fwd_v",
+            )
         ctx.save_for_backward(qkv, cu, out, lse)
-        ctx.max_seqlen, ctx.scale = int(max_seqlen), float(scale)
+        ctx.max_seqlen, ctx.scale, ctx.variant = int(max_seqlen), float(scale), variant
         return out
 
     @staticmethod
@@ -125,23 +147,35 @@ class _VarlenAttention(Function):
         dqkv = torch.empty_like(qkv)
         L = _lib.lib()
         ws = torch.empty(L.wcn_attn_varlen_workspace_bytes(t, h), dtype=torch.uint8, device=dev)
-        _lib.check(
-            L.wcn_attn_varlen_bwd(_lib.ptr(dout), _lib.ptr(qkv), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu), cu.numel() - 1, t, h,
-                                  d, ctx.max_seqlen, ctx.scale, _lib.dtype_code(qkv.dtype), _lib.ptr(dqkv), _lib.ptr(ws),
-                                  ws.numel(), _lib.stream_handle(dev)),
-            "wcn_attn_varlen_bwd",
-        )
-        return dqkv, None, None, None
+        if ctx.variant == _lib.WCN_ATTN_AUTO:
+            _lib.check(
+                L.wcn_attn_varlen_bwd(_lib.ptr(dout), _lib.ptr(qkv), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu), cu.numel() - 1, t,
+                                      h, d, ctx.max_seqlen, ctx.scale, _lib.dtype_code(qkv.dtype), _lib.ptr(dqkv), _lib.ptr(ws),
+                                      ws.numel(), _lib.stream_handle(dev)),
+                "wcn_attn_varlen_bwd",
+            )
+        else:
+            _lib.check(
+                L.wcn_attn_varlen_kv_bwd_v(_lib.ptr(dout), _lib.ptr(qkv[:, 0]), 3 * h * d, _lib.ptr(qkv[:, 1]), _lib.ptr(qkv[:, 2]),
+                                           3 * h * d, _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu), _lib.ptr(cu), cu.numel() - 1, t,
+                                           t, h, d, ctx.max_seqlen, ctx.max_seqlen, ctx.scale, _lib.dtype_code(qkv.dtype),
+                                           _lib.ptr(dqkv[:, 0]), 3 * h * d, _lib.ptr(dqkv[:, 1]), _lib.ptr(dqkv[:, 2]), 3 * h * d, 1,
+                                           _lib.ptr(ws), ws.numel(), ctx.variant, _lib.stream_handle(dev)),
+                "wcn_attn_varlen_kv_bwd_v",
+            )
+        return dqkv, None, None, None, None
 
 
 @eager_unless_compiling
 def flash_attn_varlen_qkvpacked(qkv: Tensor, cu_seqlens: Tensor, max_seqlen: int, dropout_p: float = 0.0,
-                                softmax_scale: Optional[float] = None) -> Tensor:
+                                softmax_scale: Optional[float] = None, variant="auto") -> Tensor:
     """Attention of every row over the rows of its own sequence: ``qkv`` [T, 3, H, D] fp16 / bf16 on the GPU,
     ``cu_seqlens`` [S + 1] sequence boundaries, ``max_seqlen`` >= every sequence length -> [T, H, D] in the input dtype.
     The reference wrapper's name and signature (`nn/functional/flash_attn_utils.py`); differentiable with respect to
     ``qkv`` (deterministic backward).  A host ``cu_seqlens`` is checked (starts at 0, monotone, ends at T, no sequence
-    longer than ``max_seqlen``) and copied to the device; a device one is trusted as it stands (no host sync)."""
+    longer than ``max_seqlen``) and copied to the device; a device one is trusted as it stands (no host sync).  ``variant``:
+    ``"auto"`` (the library's rule), ``"one_wave"`` or ``"shared"`` (four waves share every staged tile) - the same bits."""
+    variant = _variant_code(variant)
     if dropout_p > 0.0:
         raise NotImplementedError("flash_attn_varlen_qkvpacked: dropout is not implemented (dropout_p must be 0)")
     if qkv.ndim != 4 or qkv.shape[1] != 3:
@@ -163,7 +197,7 @@ def flash_attn_varlen_qkvpacked(qkv: Tensor, cu_seqlens: Tensor, max_seqlen: int
     scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not math.isfinite(scale):
         raise ValueError(f"softmax_scale must be finite, got {scale}")
-    return _VarlenAttention.apply(qkv.contiguous(), cu, int(max_seqlen), scale)
+    return _VarlenAttention.apply(qkv.contiguous(), cu, int(max_seqlen), scale, variant)
 
 
 # ---- separate query and key/value operands (cross-attention) ----------------------------------------------------------------
@@ -221,7 +255,7 @@ class _CrossVarlenAttention(Function):
 
     @staticmethod
     def forward(ctx, q: Tensor, k: Tensor, v: Optional[Tensor], cu_q: Tensor, cu_k: Tensor, max_q: int, max_k: int,
-                scale: float, q_splits: int) -> Tensor:
+                scale: float, q_splits: int, variant: int = 0) -> Tensor:
         packed = v is None
         kk, vv = (k[:, 0], k[:, 1]) if packed else (k, v)
         tq, h, d = q.shape
@@ -229,14 +263,15 @@ class _CrossVarlenAttention(Function):
         out = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
         lse = torch.empty(tq, h, dtype=torch.float32, device=dev)
         _lib.check(
-            _lib.lib().wcn_attn_varlen_kv_fwd(_lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
-                                              _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, kk.shape[0], h, d, max_q,
-                                              max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(out), _lib.ptr(lse),
-                                              _lib.stream_handle(dev)),
+            _lib.lib().wcn_attn_varlen_kv_fwd_v(_lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
+                                                _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, kk.shape[0], h, d, max_q,
+                                                max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(out), _lib.ptr(lse), variant,
+                                                _lib.stream_handle(dev)),
             "wcn_attn_varlen_kv_fwd",
         )
         ctx.save_for_backward(q, k, v, cu_q, cu_k, out, lse)
         ctx.args = (max_q, max_k, scale, q_splits)
+        ctx.variant = variant
         return out
 
     @staticmethod
@@ -259,22 +294,23 @@ class _CrossVarlenAttention(Function):
         splits = q_splits if q_splits > 0 else L.wcn_attn_varlen_kv_splits(cu_q.numel() - 1, max_q, max_k, h)
         ws = torch.empty(L.wcn_attn_varlen_kv_workspace_bytes(tq, tk, h, d, splits), dtype=torch.uint8, device=dev)
         _lib.check(
-            L.wcn_attn_varlen_kv_bwd(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
-                                     _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h,
-                                     d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(dq), h * d, _lib.ptr(dk),
-                                     _lib.ptr(dv), (2 if packed else 1) * h * d, splits, _lib.ptr(ws), ws.numel(),
-                                     _lib.stream_handle(dev)),
+            L.wcn_attn_varlen_kv_bwd_v(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
+                                       _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h,
+                                       d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(dq), h * d, _lib.ptr(dk),
+                                       _lib.ptr(dv), (2 if packed else 1) * h * d, splits, _lib.ptr(ws), ws.numel(), ctx.variant,
+                                       _lib.stream_handle(dev)),
             "wcn_attn_varlen_kv_bwd",
         )
         if packed:
-            return dq, dkv, None, None, None, None, None, None, None
-        return dq, dk, dv, None, None, None, None, None, None
+            return dq, dkv, None, None, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                   max_seqlen_k: int, dropout_p: float, softmax_scale: Optional[float], kv: Optional[Tensor],
-                  q_splits: int) -> Tensor:
+                  q_splits: int, variant="auto") -> Tensor:
     """The checks of both public forms; ``k`` / ``v`` are the slots of ``kv`` when that is given."""
+    variant = _variant_code(variant)
     if dropout_p > 0.0:
         raise NotImplementedError(f"{name}: dropout is not implemented (dropout_p must be 0)")
     if q.ndim != 3:
@@ -313,32 +349,33 @@ def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tens
         q = q.contiguous()
     if kv is not None:
         return _CrossVarlenAttention.apply(q, kv.contiguous(), None, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), scale,
-                                           int(q_splits))
+                                           int(q_splits), variant)
     if not (_kernel_rows(k) and _kernel_rows(v) and _row_stride(k) == _row_stride(v)):
         k, v = k.contiguous(), v.contiguous()
-    return _CrossVarlenAttention.apply(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), scale, int(q_splits))
+    return _CrossVarlenAttention.apply(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), scale, int(q_splits), variant)
 
 
 @eager_unless_compiling
 def flash_attn_varlen_func(q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                            max_seqlen_k: int, dropout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                           q_splits: int = 0) -> Tensor:
+                           q_splits: int = 0, variant="auto") -> Tensor:
     """Attention of the queries of sequence s, rows [cu_q[s], cu_q[s+1]) of ``q`` [Tq, H, D], over its keys, rows
     [cu_k[s], cu_k[s+1]) of ``k`` / ``v`` [Tk, H, D] -> [Tq, H, D]; fp16 / bf16 on the GPU.  The call the reference makes
     into the flash_attn package, minus dropout; differentiable in q, k and v (deterministic backward).  Host boundaries are
     checked and copied, device ones trusted (no host sync).  A query with no key gets zeros.  ``q_splits`` forces the
-    split count of the backward's dK/dV sweep (0: the library's rule)."""
+    split count of the backward's dK/dV sweep (0: the library's rule), ``variant`` names the kernels as in
+    ``flash_attn_varlen_qkvpacked``."""
     return _cross_varlen("flash_attn_varlen_func", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
-                         dropout_p, softmax_scale, None, q_splits)
+                         dropout_p, softmax_scale, None, q_splits, variant)
 
 
 @eager_unless_compiling
 def flash_attn_varlen_kvpacked_func(q: Tensor, kv: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                                     max_seqlen_k: int, dropout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                                    q_splits: int = 0) -> Tensor:
+                                    q_splits: int = 0, variant="auto") -> Tensor:
     """``flash_attn_varlen_func`` with keys and values as the two slots of ``kv`` [Tk, 2, H, D].  The kernels read the
     slots through their strides, and write the gradient of ``kv`` as one [Tk, 2, H, D] tensor the same way (no ``cat``)."""
     if kv.ndim != 4 or kv.shape[1] != 2:
         raise ValueError(f"kv must be [Tk, 2, H, D], got {tuple(kv.shape)}")
     return _cross_varlen("flash_attn_varlen_kvpacked_func", q, kv[:, 0], kv[:, 1], cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
-                         max_seqlen_k, dropout_p, softmax_scale, kv, q_splits)
+                         max_seqlen_k, dropout_p, softmax_scale, kv, q_splits, variant)

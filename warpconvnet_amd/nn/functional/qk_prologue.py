@@ -15,7 +15,7 @@ from torch.autograd import Function
 
 from warpconvnet_amd import _lib
 
-__all__ = ["rope_table", "qk_prologue", "qk_prologue_reference", "rope_angles_reference", "fused_rope_qkv",
+__all__ = ["rope_table", "rope_table_axial", "qk_prologue", "qk_prologue_reference", "rope_angles_reference", "fused_rope_qkv",
            "sparse_scaled_dot_product_attention", "hip_qk_prologue_supported", "MAX_HEAD_DIM"]
 
 MAX_HEAD_DIM = 256
@@ -72,6 +72,45 @@ def rope_table(coords: Tensor, freqs: Tensor, origin: Optional[Tensor] = None, b
         _lib.lib().wcn_rope_table(_lib.ptr(coords), int(coords.dtype == torch.float32), t, _lib.ptr(origin), float(bias),
                                   _lib.ptr(freqs), f, _lib.ptr(table), _lib.stream_handle(dev)),
         "wcn_rope_table",
+    )
+    return table
+
+
+def rope_table_axial(coords: Tensor, freqs: Tuple[Tensor, Tensor, Tensor], origin: Optional[Tensor] = None,
+                     bias: float = 0.0) -> Tensor:
+    """``rope_table`` with one frequency vector PER AXIS: ``freqs = (fx [nx], fy [ny], fz [nz])`` -> fp32
+    ``[T, nx + ny + nz, 2]``; the pairs of axis x come first, then y, then z, and pair ``j`` of axis ``a`` turns by
+    ``pos[a] * freqs[a][j]`` (a negative coordinate is a negative angle).  ``qk_prologue`` consumes the table unchanged; any
+    split with ``2 (nx + ny + nz) <= head_dim`` is legal there."""
+    if coords.ndim != 2 or coords.shape[1] != 3:
+        raise ValueError(f"coords must be [T, 3], got {tuple(coords.shape)}")
+    if len(freqs) != 3 or any(f.ndim != 1 for f in freqs):
+        raise ValueError("freqs must be three 1-D tensors (fx, fy, fz)")
+    counts = [int(f.numel()) for f in freqs]
+    if 2 * sum(counts) > MAX_HEAD_DIM:
+        raise NotImplementedError(f"rope_table_axial: {sum(counts)} pairs need head_dim > {MAX_HEAD_DIM}")
+    if not coords.is_cuda:
+        # operation by operation as the kernel: pos = float(coord) - origin + bias, angle = pos * freq, one fp32 rounding each
+        pos = coords.to(torch.float32)
+        if origin is not None:
+            pos = pos - origin.to(device=pos.device, dtype=torch.float32)
+        pos = pos + torch.tensor(float(bias), dtype=torch.float32, device=pos.device)
+        ang = torch.cat([pos[:, a, None] * freqs[a].to(device=pos.device, dtype=torch.float32)[None, :] for a in range(3)], dim=1)
+        ang = ang.double()
+        return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).float()
+    if coords.dtype not in (torch.int32, torch.float32):
+        coords = coords.to(torch.float32 if coords.is_floating_point() else torch.int32)
+    dev = coords.device
+    coords = coords.contiguous()
+    cat = torch.cat([f.to(device=dev, dtype=torch.float32) for f in freqs]).contiguous()
+    if origin is not None:
+        origin = origin.to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+    t = coords.shape[0]
+    table = torch.empty(t, sum(counts), 2, dtype=torch.float32, device=dev)
+    _lib.check(
+        _lib.lib().wcn_rope_table_axes(_lib.ptr(coords), int(coords.dtype == torch.float32), t, _lib.ptr(origin), float(bias),
+                                       _lib.ptr(cat), _lib.i3(counts), _lib.ptr(table), _lib.stream_handle(dev)),
+        "wcn_rope_table_axes",
     )
     return table
 
