@@ -9,6 +9,7 @@ import torch
 
 from oracle import conv as oconv
 from oracle import kmap as okmap
+from tests import conv_bounds as cb
 from tests.util import rel_max_err
 
 pytestmark = pytest.mark.gpu
@@ -120,3 +121,22 @@ def test_conv_fwd_bwd_fuzz(seed):
     assert rel_max_err(conv.weight.grad, dw_ref) < tol
     if bias:
         assert rel_max_err(conv.bias.grad, dyq.sum(0)) < tol
+    # ... and element by element against the bounds of tests/conv_bounds.py: fp32 features take the fp16-operand term where the
+    # plan of the product says `via_fp16`, the plain fp32 bound where it says `ref`
+    from warpconvnet_amd.nn.functional.sparse_conv.detail.hip_gemm import _gather_plan, _wgrad_plan
+
+    K = int(np.prod(ksize))
+    via = {"Y": _gather_plan("auto", cin, cout, K, dtype, True)[0] == "via_fp16",
+           "dX": _gather_plan("auto", cout, cin, K, dtype, True)[0] == "via_fp16",
+           "dW": _wgrad_plan("auto", cin, cout, dtype, True)[0] == "via_fp16"}
+    got = {"Y": out.feature_tensor.detach(), "dX": gx, "dW": conv.weight.grad}
+    b = conv.bias.detach() if bias else None
+    wd = conv.weight.grad.dtype  # (the module hands dW back in the weight's type: the stored-dW term for 16-bit weights)
+    ref, plain = cb.reference_and_bounds(xq, w, dyq, r, o_np.shape[0], dtype, bias=b, dw_dtype=wd)
+    bound = (cb.reference_and_bounds(xq, w, dyq, r, o_np.shape[0], dtype, via_fp16=True, bias=b, dw_dtype=wd)[1]
+             if any(via.values()) else plain)
+    ratios = {n: cb.ratio(got[n], ref[n], (bound if via[n] else plain)[n]) for n in cb.NAMES}
+    print(f"[conv-bounds] fuzz seed {seed} {tuple(ksize)} stride {tuple(stride)} {cin}->{cout} {dtype} bias={bias} via_fp16={via}: "
+          + ", ".join(f"{n} {v:.3g}" for n, v in ratios.items()))
+    for n in cb.NAMES:
+        assert ratios[n] <= 1.0, (n, cb.worst(got[n], ref[n], (bound if via[n] else plain)[n]))

@@ -6,7 +6,8 @@ GEMM that is three more read+write passes.  `wcn_conv_gather_gemm_fused` applies
 
     y = act((conv + bias) * scale + shift + residual)
 
-in fp32 inside the epilogue of the MFMA gather GEMM, so the features are written once.  Forward only (no autograd):
+inside the epilogue of the MFMA gather GEMM, so the features are written once: bias, scale and shift in fp32 before the rounding;
+a residual row is added to the rounded piece, which is rounded again (`add_residual`, csrc/gather_gemm.h).  Forward only (no autograd):
 training-mode BatchNorm needs batch statistics of the convolution output, which is a different fusion.
 """
 from typing import Optional, Tuple
