@@ -524,6 +524,11 @@ int wcn_pool_select(const void* dy, const int32_t* arg, const int32_t* tbl, int6
  *                           multiply-add and rounding - the forward output is not read again.
  *   wcn_bn_backward_apply   dx = gamma * rstd * (g - sum_dy / n - xhat * sum_dy_xhat / n); gamma may be NULL (= 1). */
 size_t wcn_bn_workspace(int32_t channels);
+/* Widest layer the BatchNorm passes take (3276: the backward apply stages five fp32 coefficients per channel in 64 KB of LDS).
+ * Every wcn_bn_* entry below (and wcn_conv_bn_backward* through them) returns WCN_ERROR_UNSUPPORTED_CONFIG for `channels`
+ * above it, before any launch and whatever else is wrong with the arguments - forward and backward alike, so that a layer whose
+ * forward ran cannot fail in its backward. */
+int32_t wcn_bn_max_channels(void);
 /*   wcn_bn_stats_fold       wcn_bn_stats plus, in the same launches, everything a training step derives from the
  *                           statistics: rstd = 1/sqrt(var + eps), scale = gamma * rstd, shift = beta - mean * scale (gamma /
  *                           beta may be NULL) and the in-place update of the fp32 running statistics (NULL: none) with

@@ -6,12 +6,14 @@ first pass runs before the second one looks at it) are left out on purpose.
 The expected statuses were taken from the library as it was before the host half of csrc/norm.hip was rewritten around one
 pass description (that library is the yardstick): -5 (WCN_ERROR_INVALID_PARAMETERS) everywhere, except that the apply-type
 passes check shape / dtype (and the relu_scale / relu_shift pairing) first, then take n = 0 as success, then look at pointers.
+Since then: `channels` above wcn_bn_max_channels() is -4 (WCN_ERROR_UNSUPPORTED_CONFIG) in every `wcn_bn_*` entry, looked at first.
 include/wcn.h declares thirteen `wcn_bn_*` entries (one of them the workspace size) and the two `wcn_conv_bn_backward*`."""
 import ctypes
 
 import pytest
 
 INVALID = -5
+UNSUPPORTED = -4
 C, N = 8, 4
 _BUF = (ctypes.c_char * 256)()
 P = (ctypes.addressof(_BUF) + 15) & ~15  # "a pointer": 16-B aligned, valid-looking, never read or written
@@ -76,6 +78,10 @@ def _rows(name):
     if "n" in has:
         rows += [("n = 0", {"n": 0}, 0 if name in EMPTY_OK else INVALID), ("n = -1", {"n": -1}, INVALID)]
     rows += [("channels = 0", {"channels": 0}, INVALID)]
+    if name.startswith("wcn_bn_"):  # wider than wcn_bn_max_channels(): refused first, forward and backward alike
+        rows += [("channels = limit + 1", {"channels": "LIMIT+1"}, UNSUPPORTED)]
+        if "n" in has:
+            rows += [("channels = limit + 1, n = 0", {"channels": "LIMIT+1", "n": 0}, UNSUPPORTED)]
     if "dtype" in has:
         rows += [("dtype 3", {"dtype": 3}, INVALID)]
     if name in EMPTY_OK:  # the order of the checks: shape / dtype -> n == 0 is success -> pointers
@@ -109,7 +115,8 @@ def test_bn_entry_refuses_before_any_launch(hip_lib, name):
         vals = dict(args)
         vals.update(over)
         ws = hip_lib.wcn_bn_workspace(dict(args)["channels"])
-        call = [{"WS": ws, "WS-1": ws - 1}.get(vals[k], vals[k]) if isinstance(vals[k], str) else vals[k] for k, _ in args]
+        named = {"WS": ws, "WS-1": ws - 1, "LIMIT+1": hip_lib.wcn_bn_max_channels() + 1}
+        call = [named.get(vals[k], vals[k]) if isinstance(vals[k], str) else vals[k] for k, _ in args]
         rc = fn(*call)
         if rc != want:
             got.append(f"{what}: {rc}, expected {want}")
@@ -119,3 +126,9 @@ def test_bn_entry_refuses_before_any_launch(hip_lib, name):
 def test_bn_workspace_size(hip_lib):
     assert hip_lib.wcn_bn_workspace(0) == 0 and hip_lib.wcn_bn_workspace(-1) == 0
     assert hip_lib.wcn_bn_workspace(C) > 0 and hip_lib.wcn_bn_workspace(2 * C) == 2 * hip_lib.wcn_bn_workspace(C)
+
+
+def test_bn_channel_limit_is_the_backward_applys_lds(hip_lib):
+    """Five fp32 coefficients per channel in the 64 KB of dynamic LDS a launch gets without raising the kernel's limit."""
+    limit = hip_lib.wcn_bn_max_channels()
+    assert limit == 3276 and 5 * 4 * limit <= 65536 < 5 * 4 * (limit + 1)

@@ -19,7 +19,14 @@ CONSTANTS = [
     ("attn_varlen.hip", "kAttnMaxGrid", 1 << 22),
     ("attn_varlen.hip", "kAttnBlock", 32),
     ("norm.hip", "WCN_NORM_BLOCKS", 512),
+    ("norm.hip", "WCN_NORM_ROWS", 8),
+    ("norm.hip", "kNormApplyBlocks", 2048),
+    ("norm.hip", "kNormBwdApplyBlocks", 4096),
 ]
+# the BatchNorm layouts and apply grids belong to another file
+BN_WHY = ("tests/test_gpu_bn_bounds.py takes its shapes from tests/bn_bounds.py, which restates the layout with this value: change it "
+          "there, and tests/test_bn_bounds_api.py says which cases no longer reach their second trips")
+WHY_OF = {"WCN_NORM_ROWS": BN_WHY, "kNormApplyBlocks": BN_WHY, "kNormBwdApplyBlocks": BN_WHY}
 
 
 def _value(text, name):
@@ -35,7 +42,7 @@ def _value(text, name):
 def test_constant_is_what_the_grid_cap_tests_assume(source, name, want):
     with open(os.path.join(CSRC, source)) as f:
         got = _value(f.read(), name)
-    assert got == want, f"{source}: {name} = {got}, the grid-cap tests assume {want}. {WHY}"
+    assert got == want, f"{source}: {name} = {got}, the grid-cap tests assume {want}. {WHY_OF.get(name, WHY)}"
 
 
 def test_the_tests_use_the_same_values():
@@ -45,6 +52,10 @@ def test_the_tests_use_the_same_values():
     assert (caps.ADA_THREADS, caps.ADA_FWD_BLOCKS) == (want["kAdaThreads"], want["kAdaFwdBlocks"]), WHY
     assert (caps.VX_THREADS, caps.VX_PER, caps.VX_MAX_GRID) == (want["kRowThreads"], want["kRunPer"], want["kRowMaxGrid"]), WHY
     assert caps.CG_CHUNK == want["kRowChunk"] and (caps.ATTN_MAX_GRID, caps.ATTN_BLOCK) == (want["kAttnMaxGrid"], want["kAttnBlock"]), WHY
+    from tests import bn_bounds as bb
+
+    assert (bb.NORM_BLOCKS, bb.NORM_ROWS, bb.APPLY_BLOCKS, bb.BWD_APPLY_BLOCKS) == (
+        want["WCN_NORM_BLOCKS"], want["WCN_NORM_ROWS"], want["kNormApplyBlocks"], want["kNormBwdApplyBlocks"]), BN_WHY
 
 
 def test_chunk_rows_of_the_library(hip_lib):

@@ -32,6 +32,10 @@ namespace wcn {
 #endif
 constexpr int kNormBlocks = WCN_NORM_BLOCKS;
 constexpr int kNormRowsInFlight = WCN_NORM_ROWS;
+// Widest layer every pass takes: the backward apply stages five fp32 coefficients per channel in dynamic LDS and stays inside
+// the 64 KB a launch gets without raising the kernel's limit.  One limit for all passes: a layer whose forward runs must not
+// fail in its backward.
+constexpr int kNormMaxChannels = 65536 / (5 * 4);
 
 // y = x * scale + shift as ONE fused multiply-add, in the forward pass and wherever the backward passes need to know whether
 // the ReLU behind it let a value through: the mask (stored y > 0) is recomputed from x with the very same operation instead
@@ -315,7 +319,9 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const T* __restrict
 // [1 M, 32] / [290 k, 64] bf16, us): forward apply 2048: 70 / 21 / 13, 4096: 70 / 22 / 14; backward apply 2048: 128 / 33 / 21,
 // 4096: 114 / 31 / 20.  (Non-temporal loads / stores: 5 % faster on the tensor that exceeds the Infinity Cache, 10-15 % slower on
 // the ones a neighbouring kernel finds there - not used.)
-static inline unsigned norm_grid(int64_t items, int cap = 2048) {
+constexpr int kNormApplyBlocks = 2048;
+constexpr int kNormBwdApplyBlocks = 4096;
+static inline unsigned norm_grid(int64_t items, int cap) {
   const int64_t g = ceil_div(items, 256 * 4);
   return (unsigned)(g < cap ? (g < 1 ? 1 : g) : cap);
 }
@@ -341,6 +347,7 @@ struct BnPass {
   int dtype = WCN_F32;
 
   int64_t pitch() const { return dy_ld > 0 ? dy_ld : c; }
+  bool too_wide() const { return c > kNormMaxChannels; }  // refused first, whatever else is wrong: WCN_ERROR_UNSUPPORTED_CONFIG
   bool shape_ok(int64_t min_rows) const {
     return n >= min_rows && c >= 1 && dtype_ok(dtype) && ((relu_scale == nullptr) == (relu_shift == nullptr));
   }
@@ -378,6 +385,7 @@ static int bn_reduce(int mode, const BnPass& p, float* out0, float* out1, float*
 // wcn_bn_stats[_fold]: the checks the two share, then the statistics pass
 static int bn_stats(const BnPass& p, float* mean, float* var, void* workspace, size_t workspace_bytes, wcn_stream_t stream,
                     const BnFold& fold = BnFold()) {
+  if (p.too_wide()) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!p.shape_ok(1) || !p.x || !mean || !var || !workspace || workspace_bytes < wcn_bn_workspace(p.c))
     return WCN_ERROR_INVALID_PARAMETERS;
   return bn_reduce(0, p, mean, var, (float*)workspace, stream, fold);
@@ -386,13 +394,14 @@ static int bn_stats(const BnPass& p, float* mean, float* var, void* workspace, s
 // y = [ReLU](x * scale + shift [+ res]); p.tail: `res` is required
 static int bn_apply(const BnPass& p, const float* scale, const float* shift, int relu, const void* res, void* y,
                     wcn_stream_t stream) {
+  if (p.too_wide()) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!p.shape_ok(0)) return WCN_ERROR_INVALID_PARAMETERS;
   if (p.n == 0) return WCN_SUCCESS;
   if (!p.x || !y || !scale || !shift || (p.tail && !res)) return WCN_ERROR_INVALID_PARAMETERS;
   return with_dtype_vec<false>(p.dtype, p.vec(), [&](auto t, auto v) {
     using T = decltype(t);
-    hipLaunchKernelGGL((norm_apply_kernel<T, v()>), dim3(norm_grid(p.n * (p.c / v()))), dim3(256), (size_t)2 * p.c * 4,
-                       (hipStream_t)stream, (const T*)p.x, p.n, p.c, scale, shift, relu, (T*)y, (const T*)res);
+    hipLaunchKernelGGL((norm_apply_kernel<T, v()>), dim3(norm_grid(p.n * (p.c / v()), kNormApplyBlocks)), dim3(256),
+                       (size_t)2 * p.c * 4, (hipStream_t)stream, (const T*)p.x, p.n, p.c, scale, shift, relu, (T*)y, (const T*)res);
     return launch_status();
   });
 }
@@ -400,6 +409,7 @@ static int bn_apply(const BnPass& p, const float* scale, const float* shift, int
 // sum_dy / sum_dy_xhat of the masked gradient
 static int bn_backward_reduce(const BnPass& p, float* sum_dy, float* sum_dy_xhat, void* workspace, size_t workspace_bytes,
                               wcn_stream_t stream) {
+  if (p.too_wide()) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!p.shape_ok(1) || !p.dy || !p.x || (p.tail && !p.z) || !p.mean || !p.rstd || !sum_dy || !sum_dy_xhat || !workspace ||
       workspace_bytes < wcn_bn_workspace(p.c))
     return WCN_ERROR_INVALID_PARAMETERS;
@@ -408,14 +418,15 @@ static int bn_backward_reduce(const BnPass& p, float* sum_dy, float* sum_dy_xhat
 
 // dx from p.sum_dy / p.sum_dy_xhat; `dres` (residual tails, may be null) also receives the masked gradient
 static int bn_backward_apply(const BnPass& p, void* dx, void* dres, wcn_stream_t stream) {
+  if (p.too_wide()) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!p.shape_ok(0)) return WCN_ERROR_INVALID_PARAMETERS;
   if (p.n == 0) return WCN_SUCCESS;
   if (!p.dy || !p.x || (p.tail && !p.z) || !dx || !p.mean || !p.rstd || !p.sum_dy || !p.sum_dy_xhat)
     return WCN_ERROR_INVALID_PARAMETERS;
   return with_dtype_vec<false>(p.dtype, p.vec(), [&](auto t, auto v) {
     using T = decltype(t);
-    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, v()>), dim3(norm_grid(p.n * (p.c / v()), 4096)), dim3(256), (size_t)5 * p.c * 4,
-                       (hipStream_t)stream, (const T*)p.dy, (const T*)p.x, p.relu_scale, p.relu_shift, p.n, p.c, p.mean, p.rstd,
+    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, v()>), dim3(norm_grid(p.n * (p.c / v()), kNormBwdApplyBlocks)), dim3(256),
+                       (size_t)5 * p.c * 4, (hipStream_t)stream, (const T*)p.dy, (const T*)p.x, p.relu_scale, p.relu_shift, p.n, p.c, p.mean, p.rstd,
                        p.gamma, p.sum_dy, p.sum_dy_xhat, (T*)dx, (const T*)p.z, (T*)dres, p.pitch());
     return launch_status();
   });
@@ -436,6 +447,7 @@ extern "C" {
 
 size_t wcn_bn_workspace(int32_t channels) { return channels > 0 ? (size_t)kNormBlocks * 2 * channels * sizeof(float) : 0; }
 
+int32_t wcn_bn_max_channels(void) { return kNormMaxChannels; }
 
 int wcn_bn_stats(const void* x, int64_t n, int32_t channels, int32_t dtype, float* mean, float* var, void* workspace,
                  size_t workspace_bytes, wcn_stream_t stream) {
@@ -446,6 +458,7 @@ int wcn_bn_stats_fold(const void* x, int64_t n, int32_t channels, int32_t dtype,
                       float* running_mean, float* running_var, float momentum, float eps, float* mean, float* var,
                       float* rstd, float* scale, float* shift, int64_t* num_batches_tracked, void* workspace,
                       size_t workspace_bytes, wcn_stream_t stream) {
+  if (channels > kNormMaxChannels) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!rstd || !scale || !shift || ((running_mean == nullptr) != (running_var == nullptr))) return WCN_ERROR_INVALID_PARAMETERS;
   BnFold f;
   f.gamma = gamma; f.beta = beta; f.running_mean = running_mean; f.running_var = running_var;
@@ -456,6 +469,7 @@ int wcn_bn_stats_fold(const void* x, int64_t n, int32_t channels, int32_t dtype,
 
 int wcn_bn_fold(const float* running_mean, const float* running_var, const float* gamma, const float* beta, float eps,
                 int32_t channels, float* mean, float* rstd, float* scale, float* shift, wcn_stream_t stream) {
+  if (channels > kNormMaxChannels) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (channels < 1 || !running_mean || !running_var || !mean || !rstd || !scale || !shift) return WCN_ERROR_INVALID_PARAMETERS;
   BnFold f;
   f.gamma = gamma; f.beta = beta; f.eps = eps; f.rstd = rstd; f.scale = scale; f.shift = shift;
@@ -519,6 +533,7 @@ int wcn_bn_train_forward(const void* x, const void* residual, int64_t n, int32_t
                          const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                          int64_t* num_batches_tracked, int32_t relu, float* stats, void* y, void* workspace,
                          size_t workspace_bytes, wcn_stream_t stream) {
+  if (channels > kNormMaxChannels) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!stats) return WCN_ERROR_INVALID_PARAMETERS;
   float* mean = stats;
   float* rstd = stats + channels;
@@ -540,6 +555,7 @@ int wcn_bn_train_forward(const void* x, const void* residual, int64_t n, int32_t
 int wcn_bn_train_backward_ld(const void* dy, int64_t dy_ld, const void* x, const void* z, int32_t relu, int64_t n, int32_t channels,
                              int32_t dtype, const float* stats, const float* gamma, int32_t training, float* sums, void* dx,
                              void* dres, void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
+  if (channels > kNormMaxChannels) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!stats || !sums || channels < 1 || (dy_ld != 0 && dy_ld < channels)) return WCN_ERROR_INVALID_PARAMETERS;
   BnPass p = bn_rows(x, n, channels, dtype);
   p.dy = dy; p.dy_ld = dy_ld; p.mean = stats; p.rstd = stats + channels; p.gamma = gamma;

@@ -18,10 +18,22 @@ from warpconvnet_amd import _lib
 from warpconvnet_amd.nn.functional.segmented_arithmetics import Segments, check_rows, resolve_backend, seg_apply, seg_stats
 
 
+_MAX_CHANNELS = None
+
+
+def bn_max_channels() -> int:
+    """`wcn_bn_max_channels()`: the widest layer the kernels take (asked once)."""
+    global _MAX_CHANNELS
+    if _MAX_CHANNELS is None:
+        _MAX_CHANNELS = int(_lib.lib().wcn_bn_max_channels())
+    return _MAX_CHANNELS
+
+
 def hip_batch_norm_supported(x: Tensor) -> bool:
-    """2-D non-empty f32 / f16 / bf16 GPU tensor, and not switched off with WARPCONVNET_AMD_HIP_BATCHNORM=0."""
+    """2-D non-empty f32 / f16 / bf16 GPU tensor of at most `bn_max_channels()` columns (wider layers keep the stock module),
+    and not switched off with WARPCONVNET_AMD_HIP_BATCHNORM=0."""
     return (x.is_cuda and x.ndim == 2 and x.shape[0] > 0
-            and x.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and x.dtype in (torch.float32, torch.float16, torch.bfloat16) and x.shape[1] <= bn_max_channels()
             and os.environ.get("WARPCONVNET_AMD_HIP_BATCHNORM", "1") not in ("0", "false"))
 
 
@@ -171,7 +183,8 @@ def hip_batch_norm(x: Tensor, running_mean: Optional[Tensor], running_var: Optio
     batch statistics only; eval needs running statistics.  ``num_batches_tracked`` (training, int64 scalar on the same
     device): incremented by the statistics kernel instead of a launch of its own."""
     if not hip_batch_norm_supported(x):
-        raise RuntimeError(f"hip_batch_norm needs a non-empty 2-D f32/f16/bf16 GPU tensor, got {tuple(x.shape)} {x.dtype} {x.device}")
+        raise RuntimeError(f"hip_batch_norm needs a non-empty 2-D f32/f16/bf16 GPU tensor of at most {bn_max_channels()} channels, "
+                           f"got {tuple(x.shape)} {x.dtype} {x.device}")
     if not training and (running_mean is None or running_var is None):
         raise ValueError("hip_batch_norm in eval mode needs running statistics")
     if training and x.shape[0] == 1:  # same refusal as F.batch_norm: a single row has no variance
