@@ -1181,6 +1181,37 @@ int wcn_attn_varlen_kv_bwd_v(const void* dout, const void* q, int64_t q_stride, 
                              void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
                              int32_t variant, wcn_stream_t stream);
 
+/* ---- flexible-dual-grid mesh extraction (additions only; wcn_abi_version() stays 18, which tests/test_volt_api.py pins) --------
+ * Definition: DESIGN.md 4.28. Every voxel row carries three flags (`flags` uint8 [n, 3], non-zero = set): flag a says the
+ * surface crosses the primal edge along axis a through the voxel's maximum corner.  A flagged edge whose four surrounding
+ * voxels q0 .. q3 all exist yields quad (q0, q1, q2, q3) and two faces; the others are dropped.  The voxels come from `nbr`
+ * int32 [n, pitch], the kernel map of the voxel set onto itself with kernel_size (2, 2, 2) (column 4 i + 2 j + l = the row
+ * at +(i, j, l) or -1; pitch = wcn_kmap_row_pitch(8) = 8, 16-B aligned); an entry outside [0, n) counts as absent.  Quads are
+ * ordered by (row, axis), quad i owns faces 2 i and 2 i + 1; indices are local to the scene: row - offsets[b], b = column 0 of
+ * `coords` int32 [n, 4], `offsets` int32 [num_batches + 1] on the device.
+ *   wcn_fdg_supported  host-only: 1 if dual_dtype is f32 / f16 / bf16 and lerp_dtype is one of them or negative (no weights).
+ *   wcn_fdg_workspace  bytes of the workspace both calls share (16-B aligned), host-only.
+ *   wcn_fdg_count      kept (row, axis) pairs per row and 256-row tile into the workspace, then quad_offsets [num_batches + 1]:
+ *                      quads in front of every scene, the last entry the total.  n == 0 writes zeros.
+ *   wcn_fdg_emit       from the workspace a wcn_fdg_count call on the same nbr / flags left: verts fp32 [n, 3] =
+ *                      ((float(coord) + dual) * voxel_size) + lo, three fp32 operations each rounded once (`dual` [n, 3] in
+ *                      dual_dtype, widened first); quads int32 [capacity, 4]; faces int32 [2 capacity, 3].  Each of the three
+ *                      may be NULL (skipped); nothing is written for a quad at or beyond `capacity`.  Split of quad i: with
+ *                      `lerp` ([n, 1] in lerp_dtype, widened) faces (q0,q1,q2),(q0,q2,q3) iff w0 w2 > w1 w3, else
+ *                      (q0,q1,q3),(q3,q1,q2); without, the same choice iff |n(q0,q1,q2).n(q0,q2,q3)| > |n(q0,q1,q3).n(q3,q1,q2)|
+ *                      on the vertices above, n(a,b,c) = cross(b - a, c - a), every fp32 operation rounded once (DESIGN.md
+ *                      4.28 lists them).  No atomics: the output does not depend on the launch.
+ * WCN_ERROR_INVALID_PARAMETERS, before any launch: negative sizes, n >= 2^31 / 6, pitch != 8, a missing or misaligned pointer,
+ * a short workspace, verts without dual, faces without dual and lerp.  WCN_ERROR_UNSUPPORTED_CONFIG: an unknown dtype. */
+int wcn_fdg_supported(int32_t dual_dtype, int32_t lerp_dtype);
+size_t wcn_fdg_workspace(int64_t n);
+int wcn_fdg_count(const int32_t* nbr, int32_t pitch, const uint8_t* flags, int64_t n, const int32_t* offsets,
+                  int32_t num_batches, void* workspace, size_t workspace_bytes, int32_t* quad_offsets, wcn_stream_t stream);
+int wcn_fdg_emit(const int32_t* nbr, int32_t pitch, const uint8_t* flags, const int32_t* coords, int64_t n,
+                 const int32_t* offsets, int32_t num_batches, const void* dual, int32_t dual_dtype, const void* lerp,
+                 int32_t lerp_dtype, float voxel_size, const float lo[3], const void* workspace, size_t workspace_bytes,
+                 int64_t capacity, float* verts, int32_t* quads, int32_t* faces, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

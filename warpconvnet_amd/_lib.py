@@ -389,6 +389,12 @@ SIGNATURES = {
     "wcn_fps_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "wcn_fps": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int32, c_void_p,
                         c_size_t, c_void_p, c_void_p]),
+    "wcn_fdg_supported": (c_int, [c_int32, c_int32]),
+    "wcn_fdg_workspace": (c_size_t, [c_int64]),
+    "wcn_fdg_count": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "wcn_fdg_emit": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                             c_int32, ctypes.c_float, ctypes.c_float * 3, c_void_p, c_size_t, c_int64, c_void_p, c_void_p,
+                             c_void_p, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib
