@@ -9,12 +9,17 @@
 // million on MI355X for any scope or address spread, tools/cell_probe.hip, against 16 us for plain stores - and paid
 // four more passes for positions, sizes, scan and scatter.)
 //
-//   cell_prepare   clears the block table and the counters, builds the halo gather list for this kernel geometry
-//   cell_insert<0> every 16th voxel: find-or-create its block (CAS on first touch only); the creating WAVE hands out the
-//                  dense block id and clears the block's sub-grid
-//   cell_insert<1> every voxel: block lookup (plain cached reads) and cells[id][cell] = row.  Voxels of the few blocks
-//                  the sample missed are created here and marked deferred (their sub-grid is being cleared by another wave)
-//   cell_finish    the deferred voxels (normally < 2 %), and the ids of the 27 neighbour blocks of every block
+//   cell_prepare   clears the block table and the counters, builds the halo gather list for this kernel geometry, and
+//                  reduces the bounding box of the live voxels (block units) into up to 128 partial boxes
+//   cell_insert<0> every workgroup reduces the partial boxes and decides the build's mode (kmap_cells.h: box_is_direct).
+//                  DIRECT (the blocks fill their box): one wave per box block clears the sub-grid, writes key, the 27
+//                  neighbour ids (arithmetic) and the block's hash slot; block id = linear index in the box.
+//                  HASH: every 8th voxel: find-or-create its block (CAS on first touch only); the creating WAVE hands out
+//                  the dense block id and clears the block's sub-grid
+//   cell_insert<1> every voxel: cells[id][cell] = row, id from the box (direct) or a block lookup (plain cached reads).
+//                  Hash mode: voxels of the few blocks the sample missed are created here and marked deferred (their
+//                  sub-grid is being cleared by another wave)
+//   cell_finish    hash mode only: the deferred voxels (normally < 2 %), and the ids of the 27 neighbour blocks of every block
 //   cell_neighbors one wave per block: LDS grid from the block's own 2 KB + the halo list, occupied cells enumerated
 //                  by a wave prefix sum, then one LANE per (voxel, offset): the neighbour row is written as one
 //                  contiguous line and the mask is a wave ballot.  One barrier, no atomics; the next block's loads are
@@ -36,13 +41,21 @@ constexpr int kInsertSample = 8;  // cell_insert<0>: 1 voxel in 8 goes first (se
 // scene to the second pass, whose creation path is the expensive one: uniform 1 M scene 58.5 -> 53.4 us for the three insert launches, surface
 // scene 92 -> 76 us; 4 costs the sampled pass more than it saves: 60 / 70 us)
 constexpr int kInsertThreads = 512;
+constexpr int kPrepThreads = 1024;      // cell_prepare: 128 such workgroups hold the 8 coordinate loads a thread of a 1 M scene makes in two trips
+constexpr int kPrepCoordsPerPart = 4096;  // cell_prepare: no more partial boxes than this many coordinates each
+constexpr int kDirectMaxGrid = 1024;    // cell_insert<0>, direct role: workgroups of 8 waves, one wave per box block, grid-stride
 constexpr int kRowBufPitch = 66;  // cell_neighbors<COMPACT>: LDS row buffer [16 words + 1 spare][66]
 constexpr int kRowBufInts = (kCompactPitch + 1) * kRowBufPitch;
 #ifndef WCN_NB_WPE
 #define WCN_NB_WPE 3
 #endif
 constexpr int kNbWavesPerSimd = WCN_NB_WPE;  // cell_neighbors<COMPACT>: register budget 512 / this
-constexpr int kNbThreads = 256;    // cell_neighbors: up to 4 independent waves per workgroup (fewer when the LDS grid is large)
+#ifndef WCN_NB_XCD_RUNS
+#define WCN_NB_XCD_RUNS 1
+#endif
+// cell_neighbors, direct mode: the workgroups of an XCD walk a contiguous run of block ids (1 M uniform scene: 54.3 -> 46.8 us; 0 for A/B)
+constexpr bool kNbXcdRuns = WCN_NB_XCD_RUNS != 0;
+constexpr int kNbThreads = 256;   // cell_neighbors: up to 4 independent waves per workgroup (fewer when the LDS grid is large)
 
 __device__ __forceinline__ int wrap_blk(int v) {  // wrap to the signed range of the block coordinate field
   const int bits = kBlkCoordBits;
@@ -53,9 +66,50 @@ __device__ __forceinline__ int wrap_blk(int v) {  // wrap to the signed range of
 // Clears the block table, the counters and the caller's status word, and writes the halo gather list of this kernel
 // geometry: entry = dir (5 bits) << 27 | cell inside the neighbour's sub-grid (9 bits) << 16 | LDS grid index (16 bits),
 // ordered by direction and then by neighbour cell, so adjacent lanes read adjacent cells.
-__global__ void cell_prepare_kernel(uint4* __restrict__ slots, int64_t capacity, int32_t* __restrict__ ctr,
-                                    uint32_t* __restrict__ halo, CellGeom g, int32_t* __restrict__ status) {
+//
+// The first `parts` workgroups also reduce the bounding box of the live voxels, in block units: workgroup p strides over the
+// coordinates and writes ITS box into row p of `box` with plain stores - min of (b, x, y, z), then min of the negated
+// (b, x, y, z), so the reader takes one min over all eight columns; a part without a live voxel writes INT_MAX eight times.
+// (No atomics: same-address atomics serialise at ~11 ns each, and the rows need no initial value.)
+__global__ __launch_bounds__(kPrepThreads) void cell_prepare_kernel(uint4* __restrict__ slots, int64_t capacity, int32_t* __restrict__ ctr,
+                                    uint32_t* __restrict__ halo, CellGeom g, int32_t* __restrict__ status,
+                                    const int4* __restrict__ coords, int64_t n, int parts, int32_t* __restrict__ box) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if ((int)blockIdx.x < parts) {
+    __shared__ int s_box[kPrepThreads / 64][8];
+    int m[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) m[a] = INT_MAX;
+    const int64_t step = (int64_t)parts * kPrepThreads;
+    for (int64_t j = i; j < n; j += 4 * step) {  // four loads in flight (a lane past the end reads coords[j] again)
+      int4 c[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) c[u] = coords[j + u * step < n ? j + u * step : j];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (!coord_in_range(c[u].x, c[u].y, c[u].z, c[u].w)) continue;
+        const int v[4] = {c[u].x, c[u].y >> kBlkShift, c[u].z >> kBlkShift, c[u].w >> kBlkShift};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          m[a] = min(m[a], v[a]);
+          m[4 + a] = min(m[4 + a], -v[a]);
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+#pragma unroll
+      for (int a = 0; a < 8; ++a) m[a] = min(m[a], __shfl_xor(m[a], d));
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+      for (int a = 0; a < 8; ++a) s_box[threadIdx.x >> 6][a] = m[a];
+    __syncthreads();
+    if (threadIdx.x < 8) {
+      int r = INT_MAX;
+      for (int w = 0; w < kPrepThreads / 64; ++w) r = min(r, s_box[w][threadIdx.x]);
+      box[blockIdx.x * 8 + threadIdx.x] = r;
+    }
+  }
   if (i < capacity) slots[i] = make_uint4(0u, 0u, 0xFFFFFFFFu, 0u);
   if (i < 64) ctr[i] = 0;
   if (i == 0) *status = 0;
@@ -97,18 +151,107 @@ __device__ __forceinline__ void store_cell(int32_t* cell, int row, bool strict) 
 // wave store into the sub-grid" would need a device-scope release/acquire (an L2 write-back) per block.
 // Same-address atomics serialise at ~11 ns each on MI355X: deferred voxels are marked in place (a "deferred list" cursor
 // was ~10 k atomics = 110 us of this kernel's first version) and block ids are handed out once per WORKGROUP.
+//
+// DIRECT mode (kmap_cells.h): cell_insert<0> reduces the partial boxes of cell_prepare in EVERY workgroup (4 KB at most, no
+// hand-off inside the launch), and if the box passes box_is_direct the grid builds the box's blocks instead (direct_blocks)
+// and workgroup 0 leaves mode, box and block count in ctr for the later launches; cell_insert<1> then takes a voxel's
+// block id from the box without touching the slots, and nothing is created or deferred.
+
+// The bounding box out of the `parts` rows cell_prepare wrote; every thread of the (kInsertThreads) workgroup gets it.
+__device__ __forceinline__ BlockBox reduce_box(const int32_t* __restrict__ box, int parts) {
+  __shared__ __attribute__((aligned(16))) int s_red[kInsertThreads / 64][8];
+  int v = INT_MAX;  // column = threadIdx.x & 7 on every trip
+  for (int j = threadIdx.x; j < parts * 8; j += kInsertThreads) v = min(v, box[j]);
+  v = min(v, __shfl_xor(v, 8));
+  v = min(v, __shfl_xor(v, 16));
+  v = min(v, __shfl_xor(v, 32));
+  if ((threadIdx.x & 63) < 8) s_red[threadIdx.x >> 6][threadIdx.x & 7] = v;
+  __syncthreads();
+  int lo[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX}, nhi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
+#pragma unroll
+  for (int w = 0; w < kInsertThreads / 64; ++w) {
+    const int4 a = *reinterpret_cast<const int4*>(&s_red[w][0]), b = *reinterpret_cast<const int4*>(&s_red[w][4]);
+    lo[0] = min(lo[0], a.x); lo[1] = min(lo[1], a.y); lo[2] = min(lo[2], a.z); lo[3] = min(lo[3], a.w);
+    nhi[0] = min(nhi[0], b.x); nhi[1] = min(nhi[1], b.y); nhi[2] = min(nhi[2], b.z); nhi[3] = min(nhi[3], b.w);
+  }
+  const int hi[4] = {-nhi[0], -nhi[1], -nhi[2], -nhi[3]};  // (no live voxel: -INT_MAX < lo)
+  return make_block_box(lo, hi);
+}
+
+// Direct mode: one wave per box block, block id = linear index in the box.  Sub-grid cleared, key, the neighbour ids
+// cell_finish would look up (the box holds EVERY block there is, so a neighbour outside it is absent; the wrap rule of
+// box_is_direct keeps wrapped neighbour keys out), and the block's hash slot: keys are unique here, so one CAS per
+// probe step places it and nobody else ever writes its id.
+__device__ __forceinline__ void direct_blocks(BSlot* __restrict__ slots, uint32_t cmask, const CellTable& t, const BlockBox& box,
+                                              int nblocks, int hx, int hy, int hz, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int nwaves = gridDim.x * (kInsertThreads / 64);
+  const int ddx = lane / 9 - 1, ddy = (lane / 3) % 3 - 1, ddz = lane % 3 - 1;
+  const bool needed = lane < 27 && (ddx == 0 || hx > 0) && (ddy == 0 || hy > 0) && (ddz == 0 || hz > 0);
+  for (int id = blockIdx.x * (kInsertThreads / 64) + (threadIdx.x >> 6); id < nblocks; id += nwaves) {
+    int r[4];
+    box_block_pos(box, id, r);
+    int4* gcells = reinterpret_cast<int4*>(t.cells + (int64_t)id * kCells);
+    gcells[lane] = make_int4(-1, -1, -1, -1);
+    gcells[lane + 64] = make_int4(-1, -1, -1, -1);
+    if (lane < 32) t.nbtab[(int64_t)id * 32 + lane] = needed ? box_block_id(box, r[0], r[1] + ddx, r[2] + ddy, r[3] + ddz) : -1;
+    if (lane == 0) {
+      const uint64_t key = box_block_key(box, r);
+      t.blk_key[id] = key;
+      uint32_t s = hash_slot(key, cmask);
+      bool placed = false;
+      for (uint32_t a = 0; a <= cmask && !placed; ++a) {
+        if (atomicCAS(reinterpret_cast<unsigned long long*>(&slots[s].key), 0ull, (unsigned long long)key) == 0ull) {
+          slots[s].id = id;  // read by LATER launches only
+          placed = true;
+        }
+        s = (s + 1) & cmask;
+      }
+      if (!placed) atomicOr(status, (int)WCN_FLAG_TABLE_FULL);  // (cannot happen: nblocks <= max_blocks <= capacity / 2)
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    t.ctr[kCtrBlocks] = nblocks;
+    t.ctr[kCtrMode] = 1;
+    for (int a = 0; a < 4; ++a) {
+      t.ctr[kCtrBox + a] = box.o[a];
+      t.ctr[kCtrBox + 4 + a] = box.d[a];
+    }
+  }
+}
+
 template <int PHASE>
 __global__ __launch_bounds__(kInsertThreads) void cell_insert_kernel(BSlot* __restrict__ slots, uint32_t cmask,
                                                           const int4* __restrict__ coords, int64_t n, CellTable t,
                                                           int32_t* __restrict__ status, int kp, int mw,
                                                           int32_t* __restrict__ nbr, uint32_t* __restrict__ mask,
-                                                          int strict) {
+                                                          int strict, int box_parts, int halo3) {
   // kp: ints per table row - the dense pitch, or kCompactPitch with the top bit set for COMPACT rows (kmap_cells.h)
+  // box_parts: rows of t.box to reduce (PHASE 0; 0 = direct mode switched off); halo3: hx | hy << 8 | hz << 16
   const bool compact = kp < 0;
   kp &= 0x7FFFFFFF;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t i = PHASE == 0 ? tid * kInsertSample : tid;
   const int lane = threadIdx.x & 63;
+  bool direct = false;  // uniform over the grid
+  BlockBox box = {};
+  if (PHASE == 0) {
+    if (box_parts > 0) {
+      box = reduce_box(t.box, box_parts);
+      if (box_is_direct(box, n, t.max_blocks)) {
+        direct_blocks(slots, cmask, t, box, (int)box_blocks(box), halo3 & 255, (halo3 >> 8) & 255, (halo3 >> 16) & 255, status);
+        return;
+      }
+    }
+    if ((int64_t)blockIdx.x * kInsertThreads * kInsertSample >= n) return;  // a workgroup the direct role alone needs
+  } else {
+    direct = t.ctr[kCtrMode] != 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      box.o[a] = t.ctr[kCtrBox + a];
+      box.d[a] = t.ctr[kCtrBox + 4 + a];
+    }
+  }
   bool live = i < n;
   int4 c = make_int4(0, 0, 0, 0);
   if (live) {
@@ -128,7 +271,12 @@ __global__ __launch_bounds__(kInsertThreads) void cell_insert_kernel(BSlot* __re
   int id = -1;     // dense block id when it may be used by this launch
   bool created = false;
   uint64_t key = 0;
-  if (live) {
+  if (live && direct) {
+    // every live voxel lies in the box by construction; a miss would mean a corrupted ctr and stores nothing
+    id = box_block_id(box, c.x - box.o[0], (c.y >> kBlkShift) - box.o[1], (c.z >> kBlkShift) - box.o[2], (c.w >> kBlkShift) - box.o[3]);
+    if (id < 0) atomicOr(status, (int)WCN_FLAG_TABLE_FULL);
+  }
+  if (live && !direct) {
     key = pack_key(c.x, c.y >> kBlkShift, c.z >> kBlkShift, c.w >> kBlkShift);
     uint32_t s = hash_slot(key, cmask);
     int idv = -1;
@@ -224,6 +372,7 @@ __global__ __launch_bounds__(256) void cell_finish_kernel(const BSlot* __restric
                                                           const int4* __restrict__ coords, int64_t n, CellTable t,
                                                           CellGeom g, int mw, const uint32_t* __restrict__ mask,
                                                           int strict) {
+  if (t.ctr[kCtrMode] != 0) return;  // direct mode: nothing was deferred, and direct_blocks wrote the neighbour ids
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < n; i += nthreads) {
@@ -311,6 +460,17 @@ __global__ __launch_bounds__(kNbThreads) __attribute__((amdgpu_waves_per_eu(kNbW
   if (nblocks > t.max_blocks) nblocks = (int)t.max_blocks;
   const int gwave = blockIdx.x * (blockDim.x / 64) + wave;
   const int nwaves = gridDim.x * (blockDim.x / 64);
+  // the wave's blocks: first, first + stride, ... below end
+  int first = gwave, stride = nwaves, end = nblocks;
+  if (kNbXcdRuns && gridDim.x >= 8 && t.ctr[kCtrMode] != 0) {
+    // direct mode: ids are in spatial order.  The workgroups with the same blockIdx.x % 8 (observed to share an XCD; only speed
+    // depends on it) walk one contiguous eighth of the ids, so the halo cells a block reads were read by its neighbours' waves
+    // on the same L2
+    const int grp = blockIdx.x & 7, members = (gridDim.x - grp + 7) >> 3;
+    first = (int)(((int64_t)nblocks * grp) >> 3) + (blockIdx.x >> 3) * (blockDim.x / 64) + wave;
+    stride = members * (blockDim.x / 64);
+    end = (int)(((int64_t)nblocks * (grp + 1)) >> 3);
+  }
   constexpr int kVoxPerIter = 64 / LPR;
   const int sub = lane % LPR, vsel = lane / LPR;
   const int num_chunks = (kp + LPR - 1) / LPR;
@@ -330,18 +490,18 @@ __global__ __launch_bounds__(kNbThreads) __attribute__((amdgpu_waves_per_eu(kNbW
     nb = -1;
     v0 = make_int4(-1, -1, -1, -1);
     v1 = v0;
-    if (seq < nblocks) {
+    if (seq < end) {
       if (lane < 27) nb = t.nbtab[(int64_t)seq * 32 + lane];
       const int4* own = reinterpret_cast<const int4*>(t.cells + (int64_t)seq * kCells) + lane * 2;
       v0 = own[0];
       v1 = own[1];
     }
   };
-  int seq = gwave;
+  int seq = first;
   int nb_c, nb_n;
   int4 c0, c1, n0, n1;
   load_head(seq, nb_c, c0, c1);
-  load_head(seq + nwaves, nb_n, n0, n1);
+  load_head(seq + stride, nb_n, n0, n1);
   int hv[8];  // halo values of the current block (3x3x3: all of them; larger halos reload per 8 rounds below)
   auto gather = [&](int nb, int r0) {
 #pragma unroll
@@ -421,7 +581,7 @@ __global__ __launch_bounds__(kNbThreads) __attribute__((amdgpu_waves_per_eu(kNbW
 #ifdef WCN_PROF
   if (lane == 0 && gwave < 4096) g_bprof[gwave * 12 + 9] = wall_clock64();
 #endif
-  if (seq < nblocks) {
+  if (seq < end) {
     if (halo_regs) gather8(nb_c);
     else gather(nb_c, 0);
   }
@@ -429,7 +589,7 @@ __global__ __launch_bounds__(kNbThreads) __attribute__((amdgpu_waves_per_eu(kNbW
   unsigned long long prof_prev = wall_clock64(), prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_blocks = 0;
   const unsigned long long prof_loop0 = prof_prev;
 #endif
-  for (; seq < nblocks; seq += nwaves) {
+  for (; seq < end; seq += stride) {
     BSTAMP(0);
 #ifdef WCN_PROF
     ++prof_blocks;
@@ -471,12 +631,12 @@ __global__ __launch_bounds__(kNbThreads) __attribute__((amdgpu_waves_per_eu(kNbW
     BSTAMP(5);
     // ---- advance the pipeline: gather for block i+1, head loads for block i+2 ----
     nb_c = nb_n; c0 = n0; c1 = n1;
-    if (seq + nwaves < nblocks) {
+    if (seq + stride < end) {
       if (halo_regs) gather8(nb_c);
       else gather(nb_c, 0);
     }
     BSTAMP(6);
-    load_head(seq + 2 * nwaves, nb_n, n0, n1);
+    load_head(seq + 2 * stride, nb_n, n0, n1);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     BSTAMP(2);
@@ -604,20 +764,42 @@ __global__ __launch_bounds__(kNbThreads) __attribute__((amdgpu_waves_per_eu(kNbW
 #endif
 }
 
-// prepare -> sampled insert -> insert -> finish: the cell table of `coords` (and the halo list / neighbour-block ids of geometry g)
+// WARPCONVNET_AMD_KMAP_DIRECT=0 keeps every build in hash mode (A/B runs, tests).  Read at every call: a process may flip it.
+static bool direct_mode_enabled() {
+  const char* e = getenv("WARPCONVNET_AMD_KMAP_DIRECT");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+// prepare -> sampled insert or box blocks -> insert -> finish: the cell table of `coords` (and the halo list / neighbour-block
+// ids of geometry g).  The same four launches in both modes: the device decides the mode, the host never learns it.
 static void launch_cell_table(const CellTable& t, const CellGeom& g, const int4* coords, int64_t n, int kp, int mw, int32_t* nbr,
                               uint32_t* mask, int32_t* status, int strict, hipStream_t s) {
   const int64_t capacity = t.capacity;
   const uint32_t cmask = (uint32_t)(capacity - 1);
   const int64_t max_blocks = t.max_blocks;
-  const int64_t prep = capacity > g.halo_cells ? capacity : g.halo_cells;
-  hipLaunchKernelGGL(cell_prepare_kernel, dim3((unsigned)ceil_div(prep, 256)), dim3(256), 0, s, (uint4*)t.slots, capacity,
-                     t.ctr, t.halo, g, status);
+  const bool try_direct = direct_mode_enabled();
+  // partial bounding boxes: one per kPrepCoordsPerPart coordinates, kBoxParts at most (0: direct mode is switched off)
+  int64_t parts = try_direct ? ceil_div(n, kPrepCoordsPerPart) : 0;
+  if (parts > kBoxParts) parts = kBoxParts;
+  int64_t prep = ceil_div(capacity > g.halo_cells ? capacity : g.halo_cells, kPrepThreads);
+  if (prep < parts) prep = parts;
+  hipLaunchKernelGGL(cell_prepare_kernel, dim3((unsigned)prep), dim3(kPrepThreads), 0, s, (uint4*)t.slots, capacity,
+                     t.ctr, t.halo, g, status, coords, n, (int)parts, t.box);
   const int64_t n_first = ceil_div(n, kInsertSample);
-  hipLaunchKernelGGL(cell_insert_kernel<0>, dim3((unsigned)ceil_div(n_first, kInsertThreads)), dim3(kInsertThreads), 0, s, t.slots, cmask,
-                     coords, n, t, status, kp, mw, nbr, mask, strict);
+  // the grid serves either role: a thread per sampled voxel (hash), or a wave per box block, grid-stride (direct: at most
+  // min(max_blocks, n / kDirectFill) blocks)
+  int64_t first_wgs = ceil_div(n_first, kInsertThreads);
+  if (try_direct) {
+    const int64_t most = max_blocks < n / kDirectFill ? max_blocks : n / kDirectFill;
+    int64_t want = ceil_div(most, kInsertThreads / 64);
+    if (want > kDirectMaxGrid) want = kDirectMaxGrid;
+    if (first_wgs < want) first_wgs = want;
+  }
+  const int halo3 = g.hx | (g.hy << 8) | (g.hz << 16);  // (each <= kMaxHalo)
+  hipLaunchKernelGGL(cell_insert_kernel<0>, dim3((unsigned)first_wgs), dim3(kInsertThreads), 0, s, t.slots, cmask,
+                     coords, n, t, status, kp, mw, nbr, mask, strict, (int)parts, halo3);
   hipLaunchKernelGGL(cell_insert_kernel<1>, dim3((unsigned)ceil_div(n, kInsertThreads)), dim3(kInsertThreads), 0, s, t.slots, cmask,
-                     coords, n, t, status, kp, mw, nbr, mask, strict);
+                     coords, n, t, status, kp, mw, nbr, mask, strict, 0, halo3);
   {
     const int64_t work = n > 64 * max_blocks ? n : 64 * max_blocks;  // voxels vs one wave per block
     int64_t wgs = ceil_div(work, 256);

@@ -32,10 +32,76 @@ struct __attribute__((aligned(16))) BSlot {
   int32_t pad;
 };
 
+// The table is built in one of two modes, chosen on the device per build from the build's own coordinates:
+//   hash    block ids are handed out in creation order by a counter (two insert passes, neighbour ids by hash lookups)
+//   direct  the occupied 8^3 blocks fill their bounding box well enough (box_is_direct): a block's id is its linear index
+//           in the box, every box block exists (the empty ones hold an all -1 sub-grid), neighbour ids are arithmetic
+// Either way the hash slots hold (key, id) of every block, so block_id_of serves every other reader unchanged.
+//
+// ctr[64], cleared by cell_prepare:
+constexpr int kCtrBlocks = 0;  // number of blocks (dense ids 0 .. ctr[0]-1; hash mode: may exceed max_blocks on overflow)
+constexpr int kCtrMode = 1;    // 0 = hash, 1 = direct
+constexpr int kCtrBox = 2;     // direct mode: [2..5] box origin, [6..9] box dims; block units, axes (batch, x, y, z)
+
+constexpr int kDirectFill = 16;  // direct mode needs kDirectFill * box_blocks <= n: an average of 16 voxels per box block
+constexpr int kBoxParts = 128;   // most partial bounding boxes cell_prepare writes (8 ints each)
+
+// bounding box of the live voxels in block units, axes (batch, x >> 3, y >> 3, z >> 3)
+struct BlockBox {
+  int o[4];  // origin
+  int d[4];  // dims (all 0: no live voxel)
+};
+
+__host__ __device__ inline BlockBox make_block_box(const int lo[4], const int hi[4]) {
+  BlockBox b;
+  const bool empty = lo[0] > hi[0];
+  for (int a = 0; a < 4; ++a) {
+    b.o[a] = empty ? 0 : lo[a];
+    b.d[a] = empty ? 0 : hi[a] - lo[a] + 1;
+  }
+  return b;
+}
+
+__host__ __device__ inline int64_t box_blocks(const BlockBox& b) {
+  return (int64_t)b.d[0] * b.d[1] * b.d[2] * b.d[3];  // <= 2^9 * 2^45
+}
+
+// Fill rule: at least kDirectFill voxels per box block on average (so box_blocks <= n / 16 <= the default max_blocks).
+// Wrap rule: no spatial axis touches the ends of the signed block-coordinate range, so no neighbour key wraps.
+__host__ __device__ inline bool box_is_direct(const BlockBox& b, int64_t n, int64_t max_blocks) {
+  const int64_t blocks = box_blocks(b);
+  if (blocks < 1 || blocks > max_blocks || blocks > n / kDirectFill) return false;
+  const int lo = -(1 << (kBlkCoordBits - 1)), hi = (1 << (kBlkCoordBits - 1)) - 1;
+  for (int a = 1; a < 4; ++a)
+    if (b.o[a] <= lo || b.o[a] + b.d[a] - 1 >= hi) return false;
+  return true;
+}
+
+// id of the box block at box-relative position r, or -1 outside the box
+__host__ __device__ inline int box_block_id(const BlockBox& b, int r0, int r1, int r2, int r3) {
+  if ((unsigned)r0 >= (unsigned)b.d[0] || (unsigned)r1 >= (unsigned)b.d[1] || (unsigned)r2 >= (unsigned)b.d[2] ||
+      (unsigned)r3 >= (unsigned)b.d[3])
+    return -1;
+  return ((r0 * b.d[1] + r1) * b.d[2] + r2) * b.d[3] + r3;
+}
+
+// box-relative position of block id
+__host__ __device__ inline void box_block_pos(const BlockBox& b, int id, int r[4]) {
+  r[3] = id % b.d[3]; id /= b.d[3];
+  r[2] = id % b.d[2]; id /= b.d[2];
+  r[1] = id % b.d[1];
+  r[0] = id / b.d[1];
+}
+
+__host__ __device__ inline uint64_t box_block_key(const BlockBox& b, const int r[4]) {
+  return pack_key(b.o[0] + r[0], b.o[1] + r[1], b.o[2] + r[2], b.o[3] + r[3]);
+}
+
 struct CellTable {
   BSlot* slots;
   int64_t capacity;     // power of two >= 2 * max_blocks
-  int32_t* ctr;         // [0] = number of blocks (dense ids 0 .. ctr[0]-1; may exceed max_blocks on overflow)
+  int32_t* ctr;         // counters and the build mode: kCtr* above
+  int32_t* box;         // [kBoxParts][8] partial boxes of cell_prepare: min of (b, x, y, z), then min of the NEGATED (b, x, y, z)
   uint32_t* halo;       // halo gather list of the current kernel geometry
   uint64_t* blk_key;    // [max_blocks] dense id -> block key
   int32_t* nbtab;       // [max_blocks][32] ids of the 27 neighbour blocks (-1 = absent), [13] = the block itself
@@ -95,6 +161,7 @@ static inline CellTable carve_cells(void* ws, int64_t n, int64_t max_blocks) {
   t.max_blocks = max_blocks;
   t.capacity = cell_capacity(max_blocks);
   t.ctr = (int32_t*)take(256);
+  t.box = (int32_t*)take((size_t)kBoxParts * 8 * 4);
   t.halo = (uint32_t*)take((size_t)16384 * 4);  // (8 + 2*8)^3 - 512 = 13312 entries at most
   t.slots = (BSlot*)take((size_t)t.capacity * sizeof(BSlot));
   t.blk_key = (uint64_t*)take((size_t)max_blocks * 8);
