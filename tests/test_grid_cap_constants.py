@@ -22,11 +22,14 @@ CONSTANTS = [
     ("norm.hip", "WCN_NORM_ROWS", 8),
     ("norm.hip", "kNormApplyBlocks", 2048),
     ("norm.hip", "kNormBwdApplyBlocks", 4096),
+    ("pointconv.hip", "kPcMaxGrid", 256),
 ]
 # the BatchNorm layouts and apply grids belong to another file
 BN_WHY = ("tests/test_gpu_bn_bounds.py takes its shapes from tests/bn_bounds.py, which restates the layout with this value: change it "
           "there, and tests/test_bn_bounds_api.py says which cases no longer reach their second trips")
-WHY_OF = {"WCN_NORM_ROWS": BN_WHY, "kNormApplyBlocks": BN_WHY, "kNormBwdApplyBlocks": BN_WHY}
+PC_WHY = ("tests/test_gpu_pointconv_bounds.py runs tests/pointconv_bounds.py's large cases past this cap (backward: one 32-edge "
+          "tile a workgroup and trip; forward: eight): change BWD_GRID_CAP / FWD_WAVE_CAP there and the edge counts follow")
+WHY_OF = {"WCN_NORM_ROWS": BN_WHY, "kNormApplyBlocks": BN_WHY, "kNormBwdApplyBlocks": BN_WHY, "kPcMaxGrid": PC_WHY}
 
 
 def _value(text, name):
@@ -56,6 +59,9 @@ def test_the_tests_use_the_same_values():
 
     assert (bb.NORM_BLOCKS, bb.NORM_ROWS, bb.APPLY_BLOCKS, bb.BWD_APPLY_BLOCKS) == (
         want["WCN_NORM_BLOCKS"], want["WCN_NORM_ROWS"], want["kNormApplyBlocks"], want["kNormBwdApplyBlocks"]), BN_WHY
+    from tests import pointconv_bounds as pb
+
+    assert (pb.BWD_GRID_CAP, pb.FWD_WAVE_CAP) == (want["kPcMaxGrid"], 8 * want["kPcMaxGrid"]), PC_WHY
 
 
 def test_chunk_rows_of_the_library(hip_lib):

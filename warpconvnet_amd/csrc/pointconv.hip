@@ -21,11 +21,24 @@
 // pointconv_bwd_kernel - the backward of every list kind ("tensor parallel workgroup").  One tile per workgroup of 4
 //   waves: every wave holds the tile's x, wave w owns hidden channels [w*HID/4, (w+1)*HID/4) through the whole chain, so
 //   the weight-gradient blocks it accumulates (its rows of dW1 / dW2) live in registers for the lifetime of the kernel.
-//   * LayerNorm reduces over registers + one lane swap + a 1-KiB exchange between the waves;
+//   * LayerNorm reduces over registers + one lane swap + a 1.5-KiB exchange between the waves;
 //   * only the weight-gradient GEMMs (reduction over edges) need the other orientation: the operands take one trip
 //     through a wave-private LDS tile [channel][edge];
 //   * the forward operands (P1, P2) stay in registers, the transposed images (P2T, P1T) in LDS; the Linear shortcut's
 //     transposed image is read from global memory (L1/L2 resident, 16 B per lane).
+//
+// LayerNorm variance.  Never sum(v * v) / n - mu * mu: with a mean far from zero (a large Linear bias, W1 rows with a common
+// component) that difference of two large numbers loses the variance - at mean / sigma = 30 the normalised value is off by
+// 5e-4 in fp32, at 1000 by its own size.  Both kernels take the mean first and then sum the squared deviations, which are
+// differences of nearby numbers.  Padded channels hold exact zeros, not the mean, so they are kept out of that sum by
+// comparing the (compile-time) channel index with hid_t / co_t (a uniform branch skips the comparisons when the width is
+// the padded one); subtracting n_pad * mu^2 afterwards would bring the cancellation back.  Where one wave holds all channels of an edge (forward, LayerNorm 2 of the backward) this is a second
+// pass over the registers and one lane swap.  LayerNorm 1 of the backward spans the four waves and keeps its single
+// barrier: wave w deviates from its OWN mean m_w (of its n_w true channels) and sends m_w, q_w = sum (v - m_w)^2 and
+// r_w = sum (v - m_w), which is zero but for the rounding of m_w.  Every lane then merges, with mu = sum (n_w m_w + r_w) / n:
+//   sum (v - mu)^2 = sum_w [ q_w + 2 (m_w - mu) r_w + n_w (m_w - mu)^2 ]
+// (Chan's merge, with the r_w term the identity holds for ANY m_w, so the rounding of the wave means does not enter the
+// between-waves term in first order).
 #include <type_traits>
 
 #include "wcn_common.h"
@@ -37,6 +50,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int kPcWaves = 4;  // waves of a backward workgroup
+constexpr int kPcMaxGrid = 256;  // persistent workgroups of either kernel, one per CU (pinned in tests/test_grid_cap_constants.py)
 constexpr int kPitch = 36;  // floats per row of the [channel][32 edges] LDS tiles: b128 reads of 8 lanes hit 32 banks
 
 __host__ __device__ constexpr int sigma(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
@@ -80,8 +94,9 @@ struct PC {
   static constexpr int L_TH = L_TX + EIN * kPitch;            // [HID][kPitch]      per wave: H, later dHpre, channel-major
   static constexpr int L_TB = L_TH + HID * kPitch;            // [CO][kPitch]       dOpre channel-major
   static constexpr int L_PO = L_TB + CO * kPitch;             // [4][NBP][16][64]   partial tiles exchanged between the waves
-  static constexpr int L_ST = L_PO + kPcWaves * NBP * 1024;   // [2][4][32][2]      LayerNorm partial sums
-  static constexpr int L_DXT = L_ST + 2 * kPcWaves * 64;      // [32][EIN+1]        dX, edge-major; before that dy channel-major [CO][kPitch]
+  static constexpr int L_ST = L_PO + kPcWaves * NBP * 1024;   // [4][32][3] LayerNorm 1 statistics | [4][32][2] its backward sums
+  static constexpr int ST_LN1 = kPcWaves * 32 * 3;            //                    offset of the second part inside st
+  static constexpr int L_DXT = L_ST + kPcWaves * 32 * 5;      // [32][EIN+1]        dX, edge-major; before that dy channel-major [CO][kPitch]
   static constexpr int DXT_FLOATS = ((32 * (EIN + 1) > CO * kPitch ? 32 * (EIN + 1) : CO * kPitch) + 3) & ~3;
   static constexpr int L_DOUT = L_DXT + DXT_FLOATS;           // [32][CO] grad_out rows of the tile's queries ([32][CO+1] per edge when ragged)
   static constexpr int L_JT = L_DOUT + 32 * (CO + 1);         // [32] int           neighbour ids, then [32] int query ids (ragged lists)
@@ -90,7 +105,7 @@ struct PC {
   static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 };
 // the two layouts of the instantiated shape, pinned: a slip in an offset above fails here
-static_assert(PC<64, 128, 64>::LDS_FLOATS * 4 == 157312, "backward LDS layout");
+static_assert(PC<64, 128, 64>::LDS_FLOATS * 4 == 157824, "backward LDS layout");
 static_assert(PC<64, 128, 64>::LDS_FLOATS_WAVE * 4 == 84480, "forward LDS layout");
 
 struct PcArgs {
@@ -147,9 +162,12 @@ __global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
   const int64_t n_edges = ragged ? a.n_edges : (a.n_query << a.log2k);
   const int64_t ntiles = (n_edges + 31) >> 5;
   const float inv_hid = 1.f / (float)a.hid_t, inv_co = 1.f / (float)a.co_t;
+  const bool full1 = a.hid_t == HID, full2 = a.co_t == CO;  // no padded channels: the LayerNorm sums take every register
   const f32x4* pk4 = reinterpret_cast<const f32x4*>(a.packed);
   float* thw = tH + w * HB * 32 * kPitch;  // this wave's rows of tH
   const float* tab = smem + P::L_TAB;
+  // true (not padded) hidden channels among the HB * 32 that wave ww owns
+  auto true_channels = [&](int hid_t, int ww) { return min(max(hid_t - 32 * HB * ww, 0), 32 * HB); };
   for (int i = tid; i < (P::NB1 + NB2) * 96; i += 256) smem[P::L_TAB + i] = a.packed[P::OFF_T1 + i];
   // the transposed weight images (A operands of the dH and dX GEMMs) live in LDS: no global round trip per tile
   for (int i = tid; i < (P::OFF_T1 - P::OFF_P2T) / 4; i += 256)
@@ -296,35 +314,67 @@ __global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
     gather_x(v_cur, q_cur, j_cur);
     load_ids(tile + 2 * (int64_t)gridDim.x, v_nxt, q_nxt, j_nxt);
 
-    float s1 = 0.f, s2 = 0.f;
+    // LayerNorm 1 statistics over the four waves with one exchange: wave w sends the mean m_w of its n_w true channels,
+    // q_w = sum (v - m_w)^2 and r_w = sum (v - m_w) over them; the header comment has the merge.
+    const int nw1 = true_channels(a.hid_t, w);
+    {
+      float s1 = 0.f;
 #pragma unroll
-    for (int t = 0; t < HB; ++t) {
-      const float* t1 = tab + (w * HB + t) * 96 + h * 16;
+      for (int t = 0; t < HB; ++t) {
+        const float* t1 = tab + (w * HB + t) * 96 + h * 16;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        acc1[t][r] += t1[r];
-        s1 += acc1[t][r];
-        s2 += acc1[t][r] * acc1[t][r];
+        for (int r = 0; r < 16; ++r) {
+          acc1[t][r] += t1[r];
+          s1 += acc1[t][r];
+        }
       }
-    }
-    s1 += half_swap(s1);
-    s2 += half_swap(s2);
-    if (h == 0) {
-      st[(w * 32 + e) * 2 + 0] = s1;
-      st[(w * 32 + e) * 2 + 1] = s2;
+      s1 += half_swap(s1);
+      const float mw = nw1 > 0 ? s1 / (float)nw1 : 0.f;
+      const int lim = a.hid_t - 32 * HB * w - 4 * h;  // channel 32 (w HB + t) + sigma(r, h) is a true one: 32 t + sigma(r, 0) < lim
+      float qw = 0.f, rw = 0.f;
+      if (full1) {  // no padded channel (a uniform branch): every register counts
+#pragma unroll
+        for (int t = 0; t < HB; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float d = acc1[t][r] - mw;
+            rw += d;
+            qw = fmaf(d, d, qw);
+          }
+      } else {
+#pragma unroll
+        for (int t = 0; t < HB; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float d = (32 * t + sigma(r, 0) < lim) ? acc1[t][r] - mw : 0.f;
+            rw += d;
+            qw = fmaf(d, d, qw);
+          }
+      }
+      qw += half_swap(qw);
+      rw += half_swap(rw);
+      if (h == 0) {
+        st[(w * 32 + e) * 3 + 0] = mw;
+        st[(w * 32 + e) * 3 + 1] = qw;
+        st[(w * 32 + e) * 3 + 2] = rw;
+      }
     }
     __syncthreads();  // 1: tX, st[0], (jt, dout)
 
     float mu1, rstd1;
     {
-      float S1 = 0.f, S2 = 0.f;
+      float S1 = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < kPcWaves; ++ww)
+        S1 += (float)true_channels(a.hid_t, ww) * st[(ww * 32 + e) * 3 + 0] + st[(ww * 32 + e) * 3 + 2];
+      mu1 = S1 * inv_hid;
+      float M2 = 0.f;
 #pragma unroll
       for (int ww = 0; ww < kPcWaves; ++ww) {
-        S1 += st[(ww * 32 + e) * 2 + 0];
-        S2 += st[(ww * 32 + e) * 2 + 1];
+        const float dm = st[(ww * 32 + e) * 3 + 0] - mu1;
+        M2 += st[(ww * 32 + e) * 3 + 1] + dm * (2.f * st[(ww * 32 + e) * 3 + 2] + (float)true_channels(a.hid_t, ww) * dm);
       }
-      mu1 = S1 * inv_hid;
-      rstd1 = rsqrtf(fmaxf(S2 * inv_hid - mu1 * mu1, 0.f) + a.eps1);
+      rstd1 = rsqrtf(fmaxf(M2, 0.f) * inv_hid + a.eps1);
     }
     float xh1[HB][16], H[HB][16];
 #pragma unroll
@@ -362,7 +412,7 @@ __global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
     float xh2[NB2][16];  // normalised GEMM2 output
     float mu2, rstd2;
     {
-      float s1b = 0.f, s2b = 0.f;
+      float s1b = 0.f;
 #pragma unroll
       for (int b = 0; b < NB2; ++b) {
         const float* t2 = tab + (P::NB1 + b) * 96 + h * 16;
@@ -377,14 +427,29 @@ __global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
             const float ov = v[d] + t2[r];
             xh2[b][r] = ov;
             s1b += ov;
-            s2b += ov * ov;
           }
         }
       }
       s1b += half_swap(s1b);
-      s2b += half_swap(s2b);
       mu2 = s1b * inv_co;
-      rstd2 = rsqrtf(fmaxf(s2b * inv_co - mu2 * mu2, 0.f) + a.eps2);
+      const int lim = a.co_t - 4 * h;  // channel 32 b + sigma(r, h) is a true one: 32 b + sigma(r, 0) < lim
+      float s2b = 0.f;  // squared deviations of the true channels (the padded ones hold 0, not the mean)
+      if (full2) {
+#pragma unroll
+        for (int b = 0; b < NB2; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s2b = fmaf(xh2[b][r] - mu2, xh2[b][r] - mu2, s2b);
+      } else {
+#pragma unroll
+        for (int b = 0; b < NB2; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float d = (32 * b + sigma(r, 0) < lim) ? xh2[b][r] - mu2 : 0.f;
+            s2b = fmaf(d, d, s2b);
+          }
+      }
+      s2b += half_swap(s2b);
+      rstd2 = rsqrtf(s2b * inv_co + a.eps2);
 #pragma unroll
       for (int b = 0; b < NB2; ++b)
 #pragma unroll
@@ -456,8 +521,8 @@ __global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
       p1 += half_swap(p1);
       p2 += half_swap(p2);
       if (h == 0) {
-        st[256 + (w * 32 + e) * 2 + 0] = p1;
-        st[256 + (w * 32 + e) * 2 + 1] = p2;
+        st[P::ST_LN1 + (w * 32 + e) * 2 + 0] = p1;
+        st[P::ST_LN1 + (w * 32 + e) * 2 + 1] = p2;
       }
     }
     __syncthreads();  // 3: st[1], tB
@@ -467,8 +532,8 @@ __global__ __launch_bounds__(256, 1) void pointconv_bwd_kernel(const PcArgs a) {
       float m1 = 0.f, m2 = 0.f;
 #pragma unroll
       for (int ww = 0; ww < kPcWaves; ++ww) {
-        m1 += st[256 + (ww * 32 + e) * 2 + 0];
-        m2 += st[256 + (ww * 32 + e) * 2 + 1];
+        m1 += st[P::ST_LN1 + (ww * 32 + e) * 2 + 0];
+        m2 += st[P::ST_LN1 + (ww * 32 + e) * 2 + 1];
       }
       m1 *= inv_hid;
       m2 *= inv_hid;
@@ -723,6 +788,7 @@ __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs
   const int64_t n_edges = RAG ? a.n_edges : (a.n_query << a.log2k);
   const int64_t ntiles = (n_edges + 31) >> 5;
   const float inv_hid = 1.f / (float)a.hid_t, inv_co = 1.f / (float)a.co_t;
+  const bool full1 = a.hid_t == HID, full2 = a.co_t == CO;  // no padded channels: the LayerNorm sums take every register
   const int64_t nwaves = (int64_t)gridDim.x * 8;
   int64_t tile = (int64_t)blockIdx.x * 8 + (tid >> 6);
   // neighbour id of the first tile; the next tile's id is requested while the current tile is computed
@@ -778,7 +844,7 @@ __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs
     }
     // ---- GEMM1 (all hidden blocks) + LayerNorm1 + ReLU ----
     f32x16 hb[NB1];
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f;
 #pragma unroll
     for (int blk = 0; blk < NB1; ++blk) {
 #pragma unroll
@@ -794,12 +860,28 @@ __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs
       for (int r = 0; r < 16; ++r) {
         hb[blk][r] += t1[r];
         s1 += hb[blk][r];
-        s2 += hb[blk][r] * hb[blk][r];
       }
     }
     s1 += half_swap(s1);
+    const float mu1 = s1 * inv_hid;
+    const int lim1 = a.hid_t - 4 * h;  // channel 32 blk + sigma(r, h) is a true one: 32 blk + sigma(r, 0) < lim1
+    float s2 = 0.f;  // squared deviations of the true channels (the padded ones hold 0, not the mean)
+    if (full1) {  // no padded channel (a uniform branch): every register counts
+#pragma unroll
+      for (int blk = 0; blk < NB1; ++blk)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s2 = fmaf(hb[blk][r] - mu1, hb[blk][r] - mu1, s2);
+    } else {
+#pragma unroll
+      for (int blk = 0; blk < NB1; ++blk)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float d = (32 * blk + sigma(r, 0) < lim1) ? hb[blk][r] - mu1 : 0.f;
+          s2 = fmaf(d, d, s2);
+        }
+    }
     s2 += half_swap(s2);
-    const float mu1 = s1 * inv_hid, rstd1 = rsqrtf(fmaxf(s2 * inv_hid - mu1 * mu1, 0.f) + a.eps1);
+    const float rstd1 = rsqrtf(s2 * inv_hid + a.eps1);
 #pragma unroll
     for (int blk = 0; blk < NB1; ++blk) {
       const float* t1 = sTabL + blk * 96 + h * 16;
@@ -808,7 +890,7 @@ __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs
     }
     // ---- GEMM2 + LayerNorm2 + shortcut ----
     f32x16 o[NB2];
-    float u1 = 0.f, u2 = 0.f;
+    float u1 = 0.f;
 #pragma unroll
     for (int b = 0; b < NB2; ++b) {
 #pragma unroll
@@ -826,12 +908,28 @@ __global__ __launch_bounds__(512, 1) void pointconv_fwd_wave_kernel(const PcArgs
       for (int r = 0; r < 16; ++r) {
         o[b][r] += t2[r];
         u1 += o[b][r];
-        u2 += o[b][r] * o[b][r];
       }
     }
     u1 += half_swap(u1);
+    const float mu2 = u1 * inv_co;
+    const int lim2 = a.co_t - 4 * h;
+    float u2 = 0.f;
+    if (full2) {
+#pragma unroll
+      for (int b = 0; b < NB2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u2 = fmaf(o[b][r] - mu2, o[b][r] - mu2, u2);
+    } else {
+#pragma unroll
+      for (int b = 0; b < NB2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float d = (32 * b + sigma(r, 0) < lim2) ? o[b][r] - mu2 : 0.f;
+          u2 = fmaf(d, d, u2);
+        }
+    }
     u2 += half_swap(u2);
-    const float mu2 = u1 * inv_co, rstd2 = rsqrtf(fmaxf(u2 * inv_co - mu2 * mu2, 0.f) + a.eps2);
+    const float rstd2 = rsqrtf(u2 * inv_co + a.eps2);
 #pragma unroll
     for (int b = 0; b < NB2; ++b) {
       const float* t2 = sTabL + (NB1 + b) * 96 + h * 16;
@@ -1009,7 +1107,7 @@ int log2_exact(int k) {
 }
 int bwd_grid(int64_t n_query, int k) {
   const int64_t tiles = (n_query * k + 31) / 32;
-  return (int)(tiles < 256 ? tiles : 256);  // one persistent workgroup per CU
+  return (int)(tiles < kPcMaxGrid ? tiles : kPcMaxGrid);  // one persistent workgroup per CU
 }
 
 // The two runtime flags of a launch as template flags: f(bool_constant<LIN>, bool_constant<RAG>).
@@ -1041,7 +1139,7 @@ int launch_fwd_wave(const PcArgs& a, hipStream_t s) {
   const int64_t edges = a.edge_q ? a.n_edges : (a.n_query << a.log2k);
   const int64_t tiles = (edges + 31) / 32;
   const int64_t wgs = (tiles + 7) / 8;
-  const int grid = (int)(wgs < 256 ? wgs : 256);  // one persistent 8-wave workgroup per CU
+  const int grid = (int)(wgs < kPcMaxGrid ? wgs : kPcMaxGrid);  // one persistent 8-wave workgroup per CU
   const auto kernel_of = [](auto lin, auto rag) {
     return pointconv_fwd_wave_kernel<P::EIN, P::HID, P::CO, decltype(lin)::value, decltype(rag)::value>;
   };
