@@ -1212,6 +1212,50 @@ int wcn_fdg_emit(const int32_t* nbr, int32_t pitch, const uint8_t* flags, const 
                  int32_t lerp_dtype, float voxel_size, const float lo[3], const void* workspace, size_t workspace_bytes,
                  int64_t capacity, float* verts, int32_t* quads, int32_t* faces, wcn_stream_t stream);
 
+/* ---- ragged row repack: cat <-> pad <-> patch (csrc/pad.hip; additions only, wcn_abi_version() stays 18) -------------------
+ * A batch of num_segs segments, segment b of cu[b + 1] - cu[b] rows (`cu` int32 [num_segs + 1] on the device, never read on
+ * the host).  A layout says where a segment's first row is: `starts` int32 [num_segs + 1] on the device (cat: cu itself;
+ * patch: the patch offsets), or NULL with `pitch` = M for the padded [num_segs, M, c] tensor (rows must equal num_segs *
+ * pitch).  Rows are `row_bytes` bytes of elements of `elem_bytes` (1, 2, 4 or 8) bytes: a byte copy, any dtype.
+ *   wcn_pad_repack   every destination row is written exactly once: row j of its segment gets the segment's source row j if
+ *                    j < len_b, else the fill element (the low elem_bytes bytes of `fill_bits`) in every element; so do rows
+ *                    past the last segment and rows whose source row lies outside [0, src_rows).  src NULL = fill only: rows
+ *                    with j < len_b are left as they are (clear_padding).  One launch, no atomics, no prior zero fill;
+ *                    16-B pieces where row_bytes and both pointers allow, else 8, 4, 2 or 1 (never below elem_bytes).
+ *   wcn_pad_max_grid / wcn_pad_block_threads   the grid cap (the kernel strides beyond it) and the threads of a workgroup;
+ *                    a thread moves one piece.
+ * WCN_ERROR_INVALID_PARAMETERS, before any launch: negative sizes, sizes above INT32_MAX, row_bytes not a multiple of
+ * elem_bytes, a pitch layout whose rows are not num_segs * pitch, a missing or misaligned pointer, rows without a segment.
+ * WCN_ERROR_UNSUPPORTED_CONFIG: another elem_bytes.  dst_rows == 0: success without a launch. */
+int32_t wcn_pad_max_grid(void);
+int32_t wcn_pad_block_threads(void);
+int wcn_pad_repack(const void* src, void* dst, const int32_t* cu, int64_t num_segs, const int32_t* src_starts,
+                   int64_t src_pitch, int64_t src_rows, const int32_t* dst_starts, int64_t dst_pitch, int64_t dst_rows,
+                   int64_t row_bytes, int32_t elem_bytes, uint64_t fill_bits, wcn_stream_t stream);
+
+/* ---- per-segment GEMM over contiguous rows (csrc/seg_bmm.hip; additions only) --------------------------------------------------
+ * x [rows, .] in `dtype` (f32 / f16 / bf16), W [num_segs, cin, cout] in the same dtype, `cu` as above.  fp32 accumulation, one
+ * rounding; fp32 operands stay fp32 (v_mfma_f32_16x16x4_f32), the half types use v_mfma_f32_16x16x32.  1 <= cin, cout <=
+ * wcn_seg_bmm_max_channels() (256).  No float atomics; no host read; two calls agree bit for bit.
+ *   wcn_seg_bmm        transpose_w == 0: y [rows, cout] = x [rows, cin] @ W[seg(r)]; else y [rows, cin] = x [rows, cout] @
+ *                      W[seg(r)]^T (the data gradient).  A row's result depends bit for bit on that row and its weight alone.
+ *                      Two launches (the tile plan, the tiles of wcn_seg_bmm_tile_rows() rows).
+ *   wcn_seg_bmm_wgrad  dw [num_segs, cin, cout] in `dtype` = X_b^T dY_b: chunks of wcn_seg_bmm_chunk_rows() rows counted from
+ *                      the segment's own first row, fp32 partial sums added in chunk order, rounded once.  dw[b] depends bit for
+ *                      bit on segment b alone; a segment without rows gives exact zeros.  Three launches.
+ *   wcn_seg_bmm_workspace_bytes  host-only; wgrad != 0 for wcn_seg_bmm_wgrad.  16-B aligned workspace.
+ * WCN_ERROR_INVALID_PARAMETERS: negative sizes, channels < 1, rows above INT32_MAX, num_segs above 65535, a missing or
+ * misaligned pointer, a short workspace.  WCN_ERROR_UNSUPPORTED_CONFIG: an unknown dtype, channels above the cap.  Checked
+ * before any launch.  rows == 0 or num_segs == 0: success without a launch (dw zero-filled). */
+int32_t wcn_seg_bmm_max_channels(void);
+int32_t wcn_seg_bmm_tile_rows(void);
+int32_t wcn_seg_bmm_chunk_rows(void);
+size_t wcn_seg_bmm_workspace_bytes(int64_t rows, int64_t num_segs, int32_t cin, int32_t cout, int32_t wgrad);
+int wcn_seg_bmm(const void* x, const void* w, const int32_t* cu, int64_t num_segs, int64_t rows, int32_t cin, int32_t cout,
+                int32_t transpose_w, int32_t dtype, void* y, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_seg_bmm_wgrad(const void* x, const void* dy, const int32_t* cu, int64_t num_segs, int64_t rows, int32_t cin,
+                      int32_t cout, int32_t dtype, void* dw, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -395,6 +395,18 @@ SIGNATURES = {
     "wcn_fdg_emit": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                              c_int32, ctypes.c_float, ctypes.c_float * 3, c_void_p, c_size_t, c_int64, c_void_p, c_void_p,
                              c_void_p, c_void_p]),
+    "wcn_pad_max_grid": (c_int32, []),
+    "wcn_pad_block_threads": (c_int32, []),
+    "wcn_pad_repack": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                               c_int64, c_int32, ctypes.c_uint64, c_void_p]),
+    "wcn_seg_bmm_max_channels": (c_int32, []),
+    "wcn_seg_bmm_tile_rows": (c_int32, []),
+    "wcn_seg_bmm_chunk_rows": (c_int32, []),
+    "wcn_seg_bmm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    "wcn_seg_bmm": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                            c_void_p, c_size_t, c_void_p]),
+    "wcn_seg_bmm_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

@@ -121,7 +121,7 @@ class Geometry:
     # ---- functional updates -------------------------------------------------------------------
     def replace(self, batched_coordinates: Optional[Coords] = None, batched_features=None, **kwargs) -> "Geometry":
         if (batched_coordinates is None and not kwargs and isinstance(batched_features, Tensor) and batched_features.ndim == 2
-                and batched_features.shape[0] == self.batched_features.batched_tensor.shape[0]
+                and self.batched_features.batched_tensor.ndim == 2 and batched_features.shape[0] == self.batched_features.batched_tensor.shape[0]
                 and batched_features.device == self.batched_features.batched_tensor.device):
             # the per-layer case (a module swaps the feature tensor): same coordinates, same offsets, same attributes - the
             # constructor's host-side validation has nothing new to look at (~15 us per call, ~80 calls per MinkUNet forward)
@@ -168,8 +168,26 @@ class Geometry:
     def double(self):
         return self._apply_feature_transform(lambda x: x.double())
 
+    @property
+    def padded_features(self):
+        """The features as `PadFeatures` [B, M, C], converted if they are concatenated."""
+        if self.batched_features.is_pad:
+            return self.batched_features
+        if self.batched_features.is_cat:
+            return self.batched_features.to_pad()
+        raise ValueError(f"Unsupported features type: {type(self.batched_features)}")
+
+    def to_pad(self, pad_multiple: Optional[int] = None) -> "Geometry":
+        """The same geometry with padded features [B, M, C], M a multiple of ``pad_multiple``."""
+        if self.batched_features.is_pad and self.batched_features.pad_multiple == pad_multiple:
+            return self
+        return self.replace(batched_features=self.batched_features.to_pad(pad_multiple))
+
     def to_cat(self) -> "Geometry":
-        return self
+        """The same geometry with concatenated features [N, C]."""
+        if self.batched_features.is_cat:
+            return self
+        return self.replace(batched_features=self.batched_features.to_cat())
 
     # ---- arithmetic on features -----------------------------------------------------------------
     def equal_shape(self, value) -> bool:

@@ -1,11 +1,10 @@
 """Concatenated features [N, C] (reference `geometry/features/cat.py:11-33`).
 
-Padded features (`PadFeatures`) belong to the dense-grid / FIGConv families and are out of scope
-(SURVEY.md §2a P5).
+The padded layout [B, M, C] is `features/pad.py`, the per-patch padded one `features/patch.py`; `features/ops/convert.py`
+moves rows between them.
 """
 from typing import Optional
 
-import torch
 from torch import Tensor
 
 from warpconvnet_amd.geometry.base.features import Features
@@ -19,6 +18,14 @@ class CatFeatures(Features):
             f"Offsets {self.offsets.tolist()} do not match tensor {tuple(self.batched_tensor.shape)}"
         )
 
+    def to_pad(self, pad_multiple: Optional[int] = None, backend: Optional[str] = None) -> "PadFeatures":  # noqa: F821
+        from warpconvnet_amd.geometry.features.ops.convert import cat_to_pad
+
+        return cat_to_pad(self, pad_multiple=pad_multiple, backend=backend)
+
+    def to_cat(self) -> "CatFeatures":
+        return self
+
     def equal_shape(self, value: object) -> bool:
         return (
             isinstance(value, CatFeatures)
@@ -27,9 +34,8 @@ class CatFeatures(Features):
         )
 
 
-def to_batched_features(features, offsets: Tensor, device: Optional[str] = None) -> CatFeatures:
-    """Wrap a raw [N, C] tensor (or pass an existing Features through)."""
-    if isinstance(features, Features):
-        return features if device is None else features.to(device)
-    assert isinstance(features, Tensor) and features.ndim == 2, "features must be [N, C]"
-    return CatFeatures(features, offsets, device=device)
+def to_batched_features(features, offsets: Tensor, device: Optional[str] = None) -> Features:
+    """Wrap a raw [N, C] (cat) or [B, M, C] (pad) tensor, or pass existing features through."""
+    from warpconvnet_amd.geometry.features.ops.convert import to_batched_features as convert
+
+    return convert(features, offsets, device=device)

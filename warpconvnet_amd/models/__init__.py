@@ -1,10 +1,11 @@
-"""Model definitions the hot path's configurations exercise (reference `warpconvnet/models/`: the MinkUNet family and the Volt
-volume transformer)."""
+"""Model definitions the hot path's configurations exercise (reference `warpconvnet/models/`: the MinkUNet family, the Volt
+volume transformer and PointNet)."""
 from .mink_unet import (BasicBlock, BottleneckBlock, ConvBlock, ConvTrBlock, MinkUNet14, MinkUNet18, MinkUNet34, MinkUNet50,
                         MinkUNet101, MinkUNetBase)
+from .pointnet import PointNet, STNkd
 from .volt import (Block, ConvBlockTokenizer, Decoder, Detokenizer, DropPath, LayerScale, Mlp, RoPE, RoPEAttention, SparseResBlock,
                    TokenConv, Tokenizer, Volt)
 
 __all__ = ["BasicBlock", "BottleneckBlock", "ConvBlock", "ConvTrBlock", "MinkUNet14", "MinkUNet18", "MinkUNet34", "MinkUNet50",
            "MinkUNet101", "MinkUNetBase", "Block", "ConvBlockTokenizer", "Decoder", "Detokenizer", "DropPath", "LayerScale", "Mlp",
-           "RoPE", "RoPEAttention", "SparseResBlock", "TokenConv", "Tokenizer", "Volt"]
+           "PointNet", "STNkd", "RoPE", "RoPEAttention", "SparseResBlock", "TokenConv", "Tokenizer", "Volt"]

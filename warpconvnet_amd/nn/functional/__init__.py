@@ -1,5 +1,5 @@
-"""Functional layer.  The segmented operations are exported here by name; they are resolved on first use, so importing a
-submodule of this package stays as cheap as it was."""
+"""Functional layer.  The segmented operations and the ragged ``segment_bmm`` are exported here by name; they are resolved on
+first use, so importing a submodule of this package stays as cheap as it was."""
 import importlib
 
 _EXPORTS = {
@@ -10,6 +10,7 @@ _EXPORTS = {
     "segmented_norm": "normalizations",
     "segmented_layer_norm": "normalizations",
     "segmented_range_norm": "normalizations",
+    "segment_bmm": "bmm",  # (bmm the function shares its name with that submodule: import it from there)
     "global_scale": "global_pool",  # (global_pool the function shares its name with that submodule: import it from there)
 }
 

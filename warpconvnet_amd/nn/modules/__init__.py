@@ -1,7 +1,8 @@
-from .attention import BatchedLinear, FeedForward, LayerNorm, PatchAttention, TransformerBlock
+from .attention import (Attention, BatchedLinear, FeedForward, GeometryToPaddedBatch, LayerNorm, PaddedBatchToGeometry,
+                        PatchAttention, SpatialFeatureAttention, TransformerBlock, ZeroOutPoints)
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
-from .activations import DropPath
+from .activations import DropPath, ReLU
 from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool,
                           FactorGridProjection, FactorGridToPoint, FactorGridTransform, PointToFactorGrid)
 from .grid_conv import GridConv
@@ -36,7 +37,8 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "SparseMultiHeadCrossAttention", "ModulatedSparseTransformerCrossBlock",
            "SparseConvNeXtBlock3d", "SparseChannelToSpatialResBlock3d", "SparseSpatialToChannelResBlock3d",
            "SparseUNetDecoderStages", "SparseUNetEncoderStages",
-           "DropPath", "Linear", "SpaceAttention", "AllAttention", "STR2ATTN", "SpaCeFormerBlockBase", "PreNormBlock",
+           "DropPath", "ReLU", "Attention", "SpatialFeatureAttention", "GeometryToPaddedBatch", "PaddedBatchToGeometry",
+           "ZeroOutPoints", "Linear", "SpaceAttention", "AllAttention", "STR2ATTN", "SpaCeFormerBlockBase", "PreNormBlock",
            "PostNormBlock", "StreamNormBlock", "BLOCK_REGISTRY", "block_factory",
            "PermutohedralFilter", "PermutohedralFilterCached", "BilateralPermutohedralFilter",
            "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",

@@ -1,12 +1,12 @@
-"""Stochastic depth over ``Geometry`` features (reference `nn/modules/activations.py:113-166`)."""
+"""ReLU and stochastic depth over ``Geometry`` features (reference `nn/modules/activations.py:36-53, 113-166`)."""
 from typing import Union
 
-from torch import Tensor
+from torch import Tensor, nn
 
 from warpconvnet_amd.geometry.base.geometry import Geometry
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 
-__all__ = ["DropPath", "drop_path"]
+__all__ = ["ReLU", "DropPath", "drop_path"]
 
 
 def drop_path(x: Tensor, drop_prob: float = 0.0, training: bool = False, scale_by_keep: bool = True) -> Tensor:
@@ -34,3 +34,19 @@ class DropPath(BaseSpatialModule):
 
     def extra_repr(self):
         return f"drop_prob={round(self.drop_prob, 3): 0.3f}"
+
+
+class ReLU(BaseSpatialModule):
+    """``nn.ReLU`` over ``Geometry`` features."""
+
+    def __init__(self, inplace: bool = False):
+        super().__init__()
+        self.relu = nn.ReLU(inplace=inplace)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(inplace={self.relu.inplace})"
+
+    def forward(self, input: Union[Geometry, Tensor]):
+        if isinstance(input, Geometry):
+            return input.replace(batched_features=self.relu(input.feature_tensor))
+        return self.relu(input)
