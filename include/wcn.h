@@ -1256,6 +1256,62 @@ int wcn_seg_bmm(const void* x, const void* w, const int32_t* cu, int64_t num_seg
 int wcn_seg_bmm_wgrad(const void* x, const void* dy, const int32_t* cu, int64_t num_segs, int64_t rows, int32_t cin,
                       int32_t cout, int32_t dtype, void* dw, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
 
+/* ---- EdgeConv without an edge tensor (csrc/edgeconv.hip; additions only, wcn_abi_version() stays 18) -------------------------
+ * out[i] = max over the list of i of leaky_relu(a z_e + s), z[e = (i <- j)] = P[j] + Q[i]: the edge pre-activation of
+ * Linear(cat(x_j, x_i)) split into the per-point products P [num_inputs, channels] (row pitch ld_p floats) and Q
+ * [num_queries, channels] (row pitch ld_q), which the caller makes with a library GEMM.  fp32; 1 <= channels <=
+ * wcn_edgeconv_max_channels() (512), 16-B pieces when channels % 4 == 0 and the pitches and pointers allow, else single
+ * channels.  Lists: nbr int32 [num_edges] rows of P, and either row_splits int64 [num_queries + 1] (ragged, empty lists
+ * allowed) or NULL with the uniform length k (k * num_queries == num_edges).  Everything on the device, nothing read on the
+ * host; spans are clamped to the edges there are and a neighbour outside [0, num_inputs) is skipped.  No float atomics: every
+ * sum has a fixed order and two calls agree bit for bit.  a, s [channels]: gamma * rstd and beta - a * mean (training: batch
+ * statistics, eval: running ones, no BatchNorm: 1 and 0).
+ *   wcn_edgeconv_stats           mean / biased variance [channels] of z over all edges, one pass: sums of (z - p) and (z - p)^2
+ *                                around the pivot p = P[nbr[0]] + Q[0], wcn_edgeconv_sum_blocks() workgroup partials merged in
+ *                                fp64 in workgroup order.  The count is num_edges.
+ *   wcn_edgeconv_forward         out [num_queries, channels] and, if arg != NULL, the slot (position in its list) of the FIRST
+ *                                maximum as arg_bytes-wide integers (1, 2 or 4; wcn_edgeconv_arg_bytes(longest list) is the
+ *                                narrowest that holds it).  An empty list: out = 0, arg = -1.
+ *   wcn_edgeconv_backward_sums   dbeta = sum g, dgamma = sum g (z - mu) rstd over the arg-max entries, g = grad_out * (u > 0 ? 1 :
+ *                                slope); mu / rstd NULL = 0 / 1.
+ *   wcn_edgeconv_backward_query  dq[i] (pitch ld_q) = sum over the list of i, in list order, of dz_e = a (t_e - k0 - zhat_e k1),
+ *                                t_e = g at the arg-max edge and 0 elsewhere.  k0 = dbeta / E and k1 = dgamma / E (training) or
+ *                                both NULL (eval, no BatchNorm: dz_e = a t_e).
+ *   wcn_edgeconv_backward_input  dp[j] (pitch ld_p) = the same dz_e summed over the incoming edges of j in incoming order: perm
+ *                                int32 [num_edges] = the edges sorted by neighbour, ties ascending; offsets int64 [num_inputs +
+ *                                1]; edge_query int32 [num_edges] the query of every edge (ragged lists; uniform: e / k).  A row
+ *                                of more than wcn_csr_chunk_rows() incoming edges is cut into chunks added in chunk order.
+ * WCN_ERROR_INVALID_PARAMETERS, before any launch: negative sizes, sizes above INT32_MAX, a pitch below channels, k * num_queries
+ * != num_edges, a missing or misaligned pointer (arg and the input workspace: 16 B / 256 B), another arg_bytes, a short
+ * workspace, statistics of no edge.  WCN_ERROR_UNSUPPORTED_CONFIG: channels above the cap. */
+int32_t wcn_edgeconv_max_channels(void);
+int32_t wcn_edgeconv_sum_blocks(void);
+int32_t wcn_edgeconv_arg_bytes(int64_t longest_list);
+size_t wcn_edgeconv_sums_workspace_bytes(int32_t channels);
+size_t wcn_edgeconv_backward_input_workspace_bytes(int64_t num_edges, int32_t channels);
+int wcn_edgeconv_stats(const float* P, int64_t ld_p, const float* Q, int64_t ld_q, const int32_t* nbr, const int64_t* row_splits,
+                       int32_t k, int64_t num_edges, int64_t num_queries, int64_t num_inputs, int32_t channels, float* mean,
+                       float* var, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_edgeconv_forward(const float* P, int64_t ld_p, const float* Q, int64_t ld_q, const int32_t* nbr, const int64_t* row_splits,
+                         int32_t k, int64_t num_edges, int64_t num_queries, int64_t num_inputs, int32_t channels, const float* a,
+                         const float* s, float slope, float* out, void* arg, int32_t arg_bytes, wcn_stream_t stream);
+int wcn_edgeconv_backward_sums(const float* P, int64_t ld_p, const float* Q, int64_t ld_q, const int32_t* nbr,
+                               const int64_t* row_splits, int32_t k, int64_t num_edges, int64_t num_queries, int64_t num_inputs,
+                               int32_t channels, const float* a, const float* s, const float* mu, const float* rstd, float slope,
+                               const float* grad_out, const void* arg, int32_t arg_bytes, float* dbeta, float* dgamma,
+                               void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_edgeconv_backward_query(const float* P, int64_t ld_p, const float* Q, int64_t ld_q, const int32_t* nbr,
+                                const int64_t* row_splits, int32_t k, int64_t num_edges, int64_t num_queries, int64_t num_inputs,
+                                int32_t channels, const float* a, const float* s, const float* mu, const float* rstd,
+                                const float* k0, const float* k1, float slope, const float* grad_out, const void* arg,
+                                int32_t arg_bytes, float* dq, wcn_stream_t stream);
+int wcn_edgeconv_backward_input(const float* P, int64_t ld_p, const float* Q, int64_t ld_q, const int32_t* nbr,
+                                const int64_t* row_splits, int32_t k, int64_t num_edges, int64_t num_queries, int64_t num_inputs,
+                                int32_t channels, const int32_t* perm, const int64_t* offsets, const int32_t* edge_query,
+                                const float* a, const float* s, const float* mu, const float* rstd, const float* k0,
+                                const float* k1, float slope, const float* grad_out, const void* arg, int32_t arg_bytes, float* dp,
+                                void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ WCN_ATTN_AUTO, WCN_ATTN_ONE_WAVE, WCN_ATTN_SHARED = 0, 1, 2  # variant of wcn_at
 
 _I32P = c_void_p  # all pointers travel as void*
 _3I = c_int32 * 3
+_EC_LISTS = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int32]
 
 # name -> (restype, argtypes); one line per declaration in include/wcn.h
 SIGNATURES = {
@@ -407,6 +408,20 @@ SIGNATURES = {
                             c_void_p, c_size_t, c_void_p]),
     "wcn_seg_bmm_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),
+    "wcn_edgeconv_max_channels": (c_int32, []),
+    "wcn_edgeconv_sum_blocks": (c_int32, []),
+    "wcn_edgeconv_arg_bytes": (c_int32, [c_int64]),
+    "wcn_edgeconv_sums_workspace_bytes": (c_size_t, [c_int32]),
+    "wcn_edgeconv_backward_input_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    # every entry starts with the lists: P, ld_p, Q, ld_q, nbr, row_splits, k, num_edges, num_queries, num_inputs, channels
+    "wcn_edgeconv_stats": (c_int, _EC_LISTS + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wcn_edgeconv_forward": (c_int, _EC_LISTS + [c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_int32, c_void_p]),
+    "wcn_edgeconv_backward_sums": (c_int, _EC_LISTS + [c_void_p] * 4 + [ctypes.c_float, c_void_p, c_void_p, c_int32, c_void_p,
+                                                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wcn_edgeconv_backward_query": (c_int, _EC_LISTS + [c_void_p] * 6 + [ctypes.c_float, c_void_p, c_void_p, c_int32, c_void_p,
+                                                                         c_void_p]),
+    "wcn_edgeconv_backward_input": (c_int, _EC_LISTS + [c_void_p] * 3 + [c_void_p] * 6 +
+                                    [ctypes.c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

@@ -39,11 +39,27 @@ class RealSearchResult:
         else:
             raise ValueError("RealSearchResult takes (indices, row_splits) or a single [M, k] tensor")
         self.neighbor_distances = None
+        self._transposed = None  # (num_inputs, view): see transposed()
 
     def to(self, device):
         self.neighbor_indices = self.neighbor_indices.to(device)
         self.neighbor_row_splits = self.neighbor_row_splits.to(device)
+        self._transposed = None
         return self
+
+    def transposed(self, num_inputs: int):
+        """The incoming-edge view of the lists, ``(perm, offsets [num_inputs + 1], edge_query or None)`` of
+        `nn/functional/edge_conv.py:transposed_lists`: built once per result (every layer that shares this neighbour result
+        shares the view) and without a host read."""
+        if self._transposed is None or self._transposed[0] != int(num_inputs):
+            import importlib
+
+            edge_conv = importlib.import_module("warpconvnet_amd.nn.functional.edge_conv")
+            uniform = self.neighbor_indices.ndim == 2
+            view = edge_conv.transposed_lists(self.neighbor_indices, int(num_inputs),
+                                              None if uniform else self.neighbor_row_splits)
+            self._transposed = (int(num_inputs), view)
+        return self._transposed[1]
 
     def __repr__(self):
         return (

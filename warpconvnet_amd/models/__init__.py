@@ -1,5 +1,6 @@
 """Model definitions the hot path's configurations exercise (reference `warpconvnet/models/`: the MinkUNet family, the Volt
-volume transformer and PointNet)."""
+volume transformer, PointNet and DGCNN)."""
+from .dgcnn import DGCNN, DGCNNEncoder, PointConvBlock
 from .mink_unet import (BasicBlock, BottleneckBlock, ConvBlock, ConvTrBlock, MinkUNet14, MinkUNet18, MinkUNet34, MinkUNet50,
                         MinkUNet101, MinkUNetBase)
 from .pointnet import PointNet, STNkd
@@ -7,5 +8,6 @@ from .volt import (Block, ConvBlockTokenizer, Decoder, Detokenizer, DropPath, La
                    TokenConv, Tokenizer, Volt)
 
 __all__ = ["BasicBlock", "BottleneckBlock", "ConvBlock", "ConvTrBlock", "MinkUNet14", "MinkUNet18", "MinkUNet34", "MinkUNet50",
-           "MinkUNet101", "MinkUNetBase", "Block", "ConvBlockTokenizer", "Decoder", "Detokenizer", "DropPath", "LayerScale", "Mlp",
+           "MinkUNet101", "MinkUNetBase", "DGCNN", "DGCNNEncoder", "PointConvBlock", "Block", "ConvBlockTokenizer", "Decoder",
+           "Detokenizer", "DropPath", "LayerScale", "Mlp",
            "PointNet", "STNkd", "RoPE", "RoPEAttention", "SparseResBlock", "TokenConv", "Tokenizer", "Volt"]

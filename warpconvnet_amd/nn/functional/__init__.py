@@ -11,6 +11,12 @@ _EXPORTS = {
     "segmented_layer_norm": "normalizations",
     "segmented_range_norm": "normalizations",
     "segment_bmm": "bmm",  # (bmm the function shares its name with that submodule: import it from there)
+    "edge_conv_supported": "edge_conv",  # (edge_conv the function shares its name with that submodule: import it from there)
+    "transposed_lists": "edge_conv",
+    "apply_feature_transform": "transforms",
+    "create_activation_function": "transforms",
+    "create_norm_function": "transforms",
+    "cat": "transforms",
     "global_scale": "global_pool",  # (global_pool the function shares its name with that submodule: import it from there)
 }
 

@@ -3,8 +3,9 @@
 Constructor and checks of the reference (`warpconvnet/nn/modules/point_conv.py:36-282`).  What is native here: the neighbour
 search (``wcn_knn_grid``, exact grid kNN instead of O(M*N) cdist + topk), and for the default configuration the whole edge
 pipeline - gather, edge MLP, reduction over the neighbours - as one HIP kernel per direction (``csrc/pointconv.hip``), so no
-``[M*k, C]`` edge tensor exists.  Other configurations (custom edge MLPs, max / several reductions, ragged radius lists,
-sinusoidal encodings) compose the same result from ``wcn_segment_reduce`` and library GEMMs.
+``[M*k, C]`` edge tensor exists.  The DGCNN block (``Sequential(Linear, [BatchNorm1d], LeakyReLU | ReLU)`` under one ``max``)
+is two per-point GEMMs and the gather-add-max kernels of ``csrc/edgeconv.hip``.  Other configurations (other custom edge MLPs,
+several reductions, sinusoidal encodings) compose the same result from ``wcn_segment_reduce`` and library GEMMs.
 """
 import warnings
 from typing import List, Literal, Optional
@@ -16,6 +17,7 @@ from warpconvnet_amd.geometry.base.coords import Coords
 from warpconvnet_amd.geometry.coords.search.search_configs import RealSearchConfig, RealSearchMode
 from warpconvnet_amd.geometry.types.points import Points
 from warpconvnet_amd.nn.encodings import SinusoidalEncoding
+from warpconvnet_amd.nn.functional.edge_conv import edge_conv_block, edge_conv_supported
 from warpconvnet_amd.nn.functional.point_conv import fused_edge_supported, fused_point_conv_edge
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 from warpconvnet_amd.nn.modules.mlp import MLPBlock
@@ -134,7 +136,7 @@ class PointConv(BaseSpatialModule):
         if nrel and (in_pc.coordinate_tensor.requires_grad or query_pc.coordinate_tensor.requires_grad):
             return None  # the kernel has no coordinate gradient: the composed path differentiates the relative positions
         if not fused_edge_supported(self.edge_transform_mlp, fin, fq, nrel, k, self.reductions[0]):
-            return None
+            return self._edge_conv(in_pc, query_pc, neighbors, fin, fq)
         if nidx.ndim == 2:
             counts = in_pc.offsets[1:] - in_pc.offsets[:-1]
             if int(counts.min()) < nidx.shape[1]:  # lists padded with -1 (fewer than k points in a batch element): composed path
@@ -142,6 +144,23 @@ class PointConv(BaseSpatialModule):
         xyz = (in_pc.coordinate_tensor.view(-1, 3), query_pc.coordinate_tensor.view(-1, 3)) if nrel else (None, None)
         splits = None if uniform else neighbors.neighbor_row_splits
         return fused_point_conv_edge(self.edge_transform_mlp, fin, fq, nidx, k, self.reductions[0], *xyz, row_splits=splits)
+
+    def _edge_conv(self, in_pc: Points, query_pc: Points, neighbors, fin, fq):
+        """The DGCNN block - ``Sequential(Linear, [BatchNorm1d], LeakyReLU | ReLU)`` under one ``max`` - as two per-point GEMMs
+        and the gather-add-max kernels of `nn/functional/edge_conv.py`; None = the composed path."""
+        nidx = neighbors.neighbor_indices
+        padded = False
+        if nidx.ndim == 2:
+            counts = in_pc.offsets[1:] - in_pc.offsets[:-1]
+            padded = int(counts.min()) < nidx.shape[1]  # lists padded with -1 (fewer than k points in a batch element)
+        if not edge_conv_supported(self.edge_transform_mlp, fin, fq, self.reductions, nidx.numel(), self.use_rel_pos, padded):
+            return None
+        uniform = nidx.ndim == 2
+        num_in = fin.shape[0]
+        return edge_conv_block(self.edge_transform_mlp, fin, fin if query_pc is in_pc else fq, nidx,
+                               k=nidx.shape[1] if uniform else None,
+                               row_splits=None if uniform else neighbors.neighbor_row_splits,
+                               transposed=lambda: neighbors.transposed(num_in))
 
     def forward(self, in_pc: Points, query_pc: Optional[Points] = None) -> Points:
         if self.out_point_feature_type == "provided":
