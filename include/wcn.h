@@ -505,6 +505,18 @@ int wcn_pointconv_edge_backward_ragged(const float* in_feats, const float* q_fea
  * (warpconvnet/nn/functional/sparse_pool.py:84-110). */
 int wcn_pool_gather(const void* in, const int32_t* tbl, int64_t n_in, int64_t n_out, int32_t channels, int32_t num_offsets,
                     int32_t dtype, int32_t op, void* out, int32_t* arg, int32_t* count, wcn_stream_t stream);
+/* The same over in[r][c] * scale[r]: `scale` fp32 [n_in], one factor per SOURCE row (NULL = wcn_pool_gather).  The
+ * backward of the mean runs it over the reverse table with scale = 1 / count: the terms dy[r] / count[r] are formed and
+ * summed in fp32 and the sum is rounded once.  Both entry points take the 16-B row pieces only when `in` and `out` are
+ * 16-B aligned (and channels is a whole number of pieces) and one element at a time otherwise; wcn_pool_select does the
+ * same for `dy` and `dx`.  Pointers must be aligned to their element. */
+int wcn_pool_gather_scaled(const void* in, const int32_t* tbl, const float* scale, int64_t n_in, int64_t n_out,
+                           int32_t channels, int32_t num_offsets, int32_t dtype, int32_t op, void* out, int32_t* arg,
+                           int32_t* count, wcn_stream_t stream);
+/* Host only: elements per memory access the pooling kernels use for feature pointers `src` and `dst` (nothing is
+ * dereferenced): 16 / element size, or 1 when channels is no whole number of 16-B pieces or a pointer is not 16-B aligned;
+ * 0 for a bad dtype or channels < 1. */
+int wcn_pool_row_vec(const void* src, const void* dst, int32_t channels, int32_t dtype);
 /* Gradient of max / min pooling, output-stationary and deterministic: dx[n][c] = sum over the present k of
  * dy[r][c] where r = tbl[n][k] and arg[r][c] == n.  `tbl` is the REVERSE table [n_in][pitch] (pooled rows per input
  * row), `arg` the forward pass's [n_out][channels]. */

@@ -86,6 +86,9 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     "wcn_pool_gather": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
+    "wcn_pool_gather_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "wcn_pool_row_vec": (c_int, [c_void_p, c_void_p, c_int32, c_int32]),
     "wcn_pool_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "wcn_morton_code": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wcn_kmap_counts_bytes": (c_size_t, [c_int64, c_int32]),

@@ -20,24 +20,23 @@ from warpconvnet_amd.geometry.coords.real import RealCoords
 from warpconvnet_amd.geometry.coords.sample import farthest_sample_per_batch, random_sample_per_batch
 from warpconvnet_amd.geometry.coords.search.knn import batched_knn_search
 from warpconvnet_amd.geometry.coords.search.search_results import RealSearchResult
-from warpconvnet_amd.ops.csr_rows import csr_pool
-from warpconvnet_amd.ops.reductions import REDUCTION_TYPES_STR, REDUCTIONS
+from warpconvnet_amd.ops.csr_rows import csr_pool, csr_unpool
+from warpconvnet_amd.ops.reductions import REDUCTION_TYPES_STR, REDUCTIONS, two_pass_var
 from warpconvnet_amd.utils.unique import ToUnique, UniqueInfo
 
 __all__ = ["point_pool", "point_pool_by_code", "pool_features"]
 
 
 def pool_features(features: Tensor, to_unique: ToUnique, reduction: Union[REDUCTIONS, REDUCTION_TYPES_STR], eps: float = 1e-6):
-    """``features`` [N, C] reduced over the groups of ``to_unique``; ``var`` / ``std`` compose two means like
-    ``ops.reductions.row_reduction``."""
+    """``features`` [N, C] reduced over the groups of ``to_unique``; ``var`` / ``std`` are the two passes of
+    ``ops.reductions.two_pass_var`` (the mean is spread back to the points with ``wcn_row_spread``)."""
     if isinstance(reduction, str):
         reduction = REDUCTIONS(reduction)
     if reduction in (REDUCTIONS.SUM, REDUCTIONS.MEAN, REDUCTIONS.MAX, REDUCTIONS.MIN):
         return csr_pool(features, to_unique, reduction.value)
     if reduction in (REDUCTIONS.VAR, REDUCTIONS.STD):
-        mean = csr_pool(features, to_unique, "mean")
-        var = csr_pool(features**2, to_unique, "mean") - mean**2
-        return var if reduction == REDUCTIONS.VAR else torch.sqrt(var + eps)
+        return two_pass_var(features, lambda t: csr_pool(t, to_unique, "mean"), lambda y: csr_unpool(y, to_unique),
+                            std=reduction == REDUCTIONS.STD, eps=eps)
     raise ValueError(f"Invalid reduction for pooling: {reduction}")
 
 

@@ -6,7 +6,9 @@ the map into CSR with a device sort, gathers ``features[in_maps]`` into a tempor
 ``torch_scatter.segment_csr``; here the forward is ONE kernel over the map's row-major neighbour table
 (`wcn_pool_gather`, csrc/pool.hip) and the backward is output-stationary over the reverse table (sum / mean: the
 same kernel on the pre-scaled gradient; max / min: `wcn_pool_select` on the saved arg rows) - no atomics, so both
-directions are deterministic.  The map is cached under the same key as a strided convolution's
+directions are deterministic.  The mean's backward hands the kernel the 16-bit gradient and the fp32 factors
+``1 / count`` per pooled row (`wcn_pool_gather_scaled`): the terms of overlapping windows are scaled and summed in fp32
+and rounded once, with no scaled copy of the gradient in memory.  The map is cached under the same key as a strided convolution's
 (`IntSearchCacheKey`, STRIDE_ONLY), so ``sparse_unpool`` and a following transposed convolution find it.
 """
 from typing import Optional, Tuple, Union
@@ -31,15 +33,19 @@ from warpconvnet_amd.utils.ntuple import ntuple
 _OP = {"sum": 0, "mean": 1, "max": 2, "min": 3}
 
 
-def _pool_gather(x: Tensor, tbl: Tensor, n_out: int, K: int, op: int, want_arg: bool, want_count: bool):
+def _pool_gather(x: Tensor, tbl: Tensor, n_out: int, K: int, op: int, want_arg: bool, want_count: bool,
+                 scale: Optional[Tensor] = None):
+    """``scale`` fp32 [rows of x]: the kernel reduces ``x[r] * scale[r]`` instead of ``x[r]``."""
     c = x.shape[1]
+    assert scale is None or (scale.dtype == torch.float32 and scale.shape == (x.shape[0],) and scale.is_contiguous())
     out = torch.empty((n_out, c), dtype=x.dtype, device=x.device)
     arg = torch.empty((n_out, c), dtype=torch.int32, device=x.device) if want_arg else None
     cnt = torch.empty(n_out, dtype=torch.int32, device=x.device) if want_count else None
     _lib.check(
-        _lib.lib().wcn_pool_gather(_lib.ptr(x), _lib.ptr(tbl), x.shape[0], n_out, c, K, _lib.dtype_code(x.dtype), op,
-                                   _lib.ptr(out), _lib.ptr(arg), _lib.ptr(cnt), _lib.stream_handle(x.device)),
-        "wcn_pool_gather",
+        _lib.lib().wcn_pool_gather_scaled(_lib.ptr(x), _lib.ptr(tbl), _lib.ptr(scale), x.shape[0], n_out, c, K,
+                                          _lib.dtype_code(x.dtype), op, _lib.ptr(out), _lib.ptr(arg), _lib.ptr(cnt),
+                                          _lib.stream_handle(x.device)),
+        "wcn_pool_gather_scaled",
     )
     return out, arg, cnt
 
@@ -75,10 +81,11 @@ class _SparsePoolFunction(Function):
                 "wcn_pool_select",
             )
         else:
+            scale = None
             if op == 1:
                 (cnt,) = ctx.saved_tensors
-                g = (g.float() / cnt.clamp_min(1).unsqueeze(1)).to(g.dtype)
-            dx, _, _ = _pool_gather(g, rev_tbl, n_in, K, 0, False, False)
+                scale = 1.0 / cnt.clamp_min(1).float()
+            dx, _, _ = _pool_gather(g, rev_tbl, n_in, K, 0, False, False, scale=scale)
         ctx.kernel_map = None
         return dx, None, None, None
 

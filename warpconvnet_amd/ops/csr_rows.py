@@ -16,7 +16,7 @@ from torch import Tensor
 from torch.autograd import Function
 
 from warpconvnet_amd import _lib
-from warpconvnet_amd.ops.reductions import _OP, _segment_cpu
+from warpconvnet_amd.ops.reductions import _OP, _segment_cpu, _wide
 
 SPREAD_PLAIN, SPREAD_INV_COUNT, SPREAD_ARG_MATCH = 0, 1, 2
 
@@ -93,7 +93,7 @@ class _CsrPool(Function):
         else:
             g = grad_out[to_orig]
             if mode == SPREAD_INV_COUNT:
-                g = g / (csr_offsets[1:] - csr_offsets[:-1])[to_orig].to(g.dtype).unsqueeze(1)
+                g = (_wide(g) / (csr_offsets[1:] - csr_offsets[:-1])[to_orig].unsqueeze(1)).to(g.dtype)
             elif mode == SPREAD_ARG_MATCH:
                 g = g * (arg[to_orig] == torch.arange(ctx.n).unsqueeze(1)).to(g.dtype)
         return g, None, None, None, None, None
