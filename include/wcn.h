@@ -1324,6 +1324,55 @@ int wcn_edgeconv_backward_input(const float* P, int64_t ld_p, const float* Q, in
                                 const float* k1, float slope, const float* grad_out, const void* arg, int32_t arg_bytes, float* dp,
                                 void* workspace, size_t workspace_bytes, wcn_stream_t stream);
 
+/* ---- split-key attention: few queries against a long context (additions only; wcn_abi_version() stays 18) -----------------------
+ * The forward and the dQ kernel give one wave or workgroup per (sequence, query block, head), which sweeps every key of the
+ * sequence serially; a few learned queries per scene against 10^4 .. 10^5 points (MaskFormer's decoder) then launch a handful
+ * of work items that each walk thousands of key tiles.  With k_splits = S > 1 a work item is (sequence, query block, split,
+ * head): with nb = ceil(len_k / 32) and per = ceil(nb / S), split j sweeps the 32-key blocks [j per, min((j + 1) per, nb)) of
+ * its sequence (read from cu_k on the device; trailing shares may be empty; the same shares under both variants) and writes
+ * fp32 partials to the workspace:
+ *   forward  o [S, total_q, heads, head_dim] the unnormalised accumulator, then ml [S, total_q, heads, 2] the share's running
+ *            maximum (exp2 domain) and sum; an empty share writes (-inf, 0) and o = 0.  A combine kernel forms, per (query,
+ *            head) and with j = 0 .. S - 1 in that order, M = max_j m_j, L = sum_j exp2(m_j - M) l_j,
+ *            out = sum_j exp2(m_j - M) o_j / L, lse = (M + log2 L) ln 2; no key at all: out = 0, lse = -inf.
+ *   dQ       dq_j [S, total_q, heads, head_dim] unscaled (P comes from the final lse: nothing to renormalise); a reduce kernel
+ *            adds them in the order 0 .. S - 1, scales, casts, stores.  dK/dV keeps its q_splits and is otherwise unchanged.
+ * Every partial a later kernel reads is written first, so the workspace's previous contents never matter; no float atomics;
+ * one-wave and shared give the same bits for every S; S = 1 launches the unsplit kernels (the bits of the entry points above).
+ *   wcn_attn_varlen_k_splits                host-only: the count the library chooses for k_splits = 0 (direction 0 = forward,
+ *                                           1 = backward; one rule for both).  1 when the unsplit launch already has 4096
+ *                                           work items, counted in 128-query blocks: num_seqs * ceil(max_seqlen_q / 128) *
+ *                                           heads; otherwise enough splits to reach 4096, at most ceil(max_seqlen_k / 32) / 17
+ *                                           (a split sweeps at least 17 key blocks), at most what keeps the partials of
+ *                                           num_seqs * max_seqlen_q rows at head_dim 64 under 256 MiB, at most 64.  Non-
+ *                                           increasing in num_seqs and max_seqlen_q.  The count is in 128-query blocks whatever
+ *                                           variant the call names (a sweep long enough to split is one WCN_ATTN_AUTO gives to the
+ *                                           shared kernels): a forced WCN_ATTN_ONE_WAVE launches four times the work items the
+ *                                           target means, which costs nothing but is not what was measured.  `direction` is
+ *                                           accepted and ignored.  Constants: docs/OPTIMISATION_LOG.md section AN.
+ *   wcn_attn_varlen_ksplit_workspace_bytes  host-only: direction 0: k_splits > 1 ? 4 k_splits total_q heads (head_dim + 2) : 0;
+ *                                           direction 1: wcn_attn_varlen_kv_workspace_bytes(.., q_splits) plus, when
+ *                                           k_splits > 1, 4 k_splits total_q heads head_dim (k_splits as resolved, not 0).
+ *   wcn_attn_varlen_kv_fwd_s / _kv_bwd_s    the _v entry points with k_splits (0: the rule, 1: no split, < 0 ->
+ *                                           WCN_ERROR_INVALID_PARAMETERS) and, for the forward, a workspace.  A needed workspace
+ *                                           that is NULL, not 16-byte aligned or smaller than the function above reports ->
+ *                                           WCN_ERROR_INVALID_PARAMETERS, nothing launched.  Every other entry point stays at
+ *                                           one split. */
+int32_t wcn_attn_varlen_k_splits(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads, int32_t direction);
+size_t wcn_attn_varlen_ksplit_workspace_bytes(int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
+                                              int32_t q_splits, int32_t k_splits, int32_t direction);
+int wcn_attn_varlen_kv_fwd_s(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                             int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                             int32_t dtype, void* out, float* lse, int32_t variant, int32_t k_splits, void* workspace,
+                             size_t workspace_bytes, wcn_stream_t stream);
+int wcn_attn_varlen_kv_bwd_s(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                             int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                             int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                             void* dv, int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace,
+                             size_t workspace_bytes, int32_t variant, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

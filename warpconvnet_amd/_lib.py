@@ -284,6 +284,19 @@ SIGNATURES = {
          c_int64, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
          c_int32, c_void_p, c_size_t, c_int32, c_void_p],
     ),
+    "wcn_attn_varlen_k_splits": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "wcn_attn_varlen_ksplit_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "wcn_attn_varlen_kv_fwd_s": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
+         c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p],
+    ),
+    "wcn_attn_varlen_kv_bwd_s": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+         c_int64, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+         c_int32, c_int32, c_void_p, c_size_t, c_int32, c_void_p],
+    ),
     "wcn_rope_table": (c_int, [c_void_p, c_int32, c_int64, c_void_p, ctypes.c_float, c_void_p, c_int32, c_void_p, c_void_p]),
     "wcn_rope_table_axes": (c_int, [c_void_p, c_int32, c_int64, c_void_p, ctypes.c_float, c_void_p, _3I, c_void_p, c_void_p]),
     "wcn_qk_prologue_supported": (c_int, [c_int32, c_int32, c_int32]),

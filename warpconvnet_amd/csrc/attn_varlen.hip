@@ -44,6 +44,22 @@
 // (32 waves) per CU by LDS, 3 per SIMD by registers (116 VGPRs); dQ K rows + V rows + K^T = 13 824 B, 27 KiB -> 5 workgroups,
 // 2 per SIMD by registers (138 VGPRs); dK/dV Q rows + dO rows + Q^T + dO^T + lse + delta = 18 688 B, 36.5 KiB -> 4
 // workgroups, 2 per SIMD by registers (161 VGPRs).  Of the 160 KiB of a CU none of them is bound by LDS.
+// Split-key sweep (KSPLIT instantiations of the forward and dQ kernels, one-wave and shared).  The mirror case of the split
+// dK/dV sweep: a handful of queries per sequence against 10^4 .. 10^5 keys (a query decoder over a whole scene) gives the
+// forward and dQ num_seqs * ceil(Lq / 128) * H work items that each walk thousands of key tiles.  With k_splits = S > 1 an
+// item is (sequence, query block, split, head); split j sweeps the 32-key blocks [j per, min((j + 1) per, nb)) of its
+// sequence, nb = ceil(len_k / 32), per = ceil(nb / S) (attn_key_share: from cu_k on the device, the same keys under both
+// variants, trailing shares possibly empty), with the unsplit tile loop.  The forward writes the share's unnormalised
+// accumulator o_j [S, Tq, H, D] and (m_j, l_j) [S, Tq, H, 2] in fp32 - an empty share leaves (-inf, 0) and zeros - and
+// attn_fwd_combine_kernel forms M = max_j m_j, L = sum_j exp2(m_j - M) l_j, out = sum_j exp2(m_j - M) o_j / L,
+// lse = (M + log2 L) ln 2 with j = 0 .. S - 1 in that order.  dQ writes unscaled fp32 dq_j [S, Tq, H, D] (P comes from the
+// final LSE: nothing to renormalise) and attn_dq_reduce_kernel adds them in the same order.  Every partial read was written
+// by the launch before it: the workspace's earlier contents never matter, and there is no float atomic.  S = 1 launches the
+// KSPLIT = false instantiations, whose loop bounds are the constants they always were.
+// Resources of the split instantiations at D = 64 (hipcc -Rpass-analysis=kernel-resource-usage): forward one-wave 111 VGPRs,
+// 4.5 KiB LDS, shared 114 VGPRs, 18 KiB - 3 waves per SIMD both, as unsplit; dQ one-wave 126 VGPRs, 4.5 KiB, shared 132
+// VGPRs, 27 KiB - 3 per SIMD (the unsplit shared dQ: 138 VGPRs, 2 per SIMD); combine 28 VGPRs, reduce 24, no LDS.  None
+// spills; none is bound by LDS.
 // D in {16, 32, 64}: D / 16 k-steps per score product, one (D <= 32) or two 32-row halves of d per output product
 // (D = 16 computes 16 rows it drops; the bound at that size is the exp and the softmax VALU work, not the MFMA).
 #include "wcn_common.h"
@@ -200,10 +216,29 @@ __device__ __forceinline__ void store_dcol_f32(float* __restrict__ dst, const a_
     }
 }
 
+// The keys [beg, end) that split `split` of `splits` sweeps: its contiguous share of the sequence's 32-key blocks, the same
+// for the one-wave and the shared kernels.  Trailing shares may be empty (beg == end).
+__device__ __forceinline__ void attn_key_share(int len_k, int splits, int split, int& beg, int& end) {
+  const int64_t nb = (len_k + kAttnBlock - 1) / kAttnBlock, per = (nb + splits - 1) / splits;
+  const int64_t lo = split * per * kAttnBlock, hi = (split + 1) * per * kAttnBlock;
+  beg = (int)(lo < len_k ? lo : len_k);
+  end = (int)(hi < len_k ? hi : len_k);
+}
+
+// The partials of a split-key sweep (forward and dQ), all fp32 in the caller's workspace.
+//   o  [k_splits, total_q, H, D]   forward: the unnormalised accumulator of a share; dQ: its unscaled dq
+//   ml [k_splits, total_q, H, 2]   forward only: the share's running maximum (exp2 domain) and sum; (-inf, 0) when empty
+struct AttnKSplit {
+  int k_splits;
+  int64_t total_q;
+  float *o, *ml;
+};
+
 // ---- forward --------------------------------------------------------------------------------------------------------
-template <typename T, int D>
+// KSPLIT: item ids are (sequence, query block, split, head); the wave sweeps its share of the keys and writes partials.
+template <typename T, int D, bool KSPLIT>
 __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnOperands<T> a, int64_t items, int nblk, float c2,
-                                                      T* __restrict__ out, float* __restrict__ lse) {
+                                                      T* __restrict__ out, float* __restrict__ lse, const AttnKSplit ks) {
   typedef typename AFrag<T>::type frag;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
   __shared__ __attribute__((aligned(16))) T vt[NMB * 32 * kAttnPitch];
@@ -212,8 +247,17 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnOperands<T> a, i
   const int64_t qp = a.q_stride, kp = a.kv_stride;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    int split = 0, k_beg = 0;
+    if (KSPLIT) {
+      const int64_t t = id / heads;
+      split = (int)(t % ks.k_splits);
+      attn_item((t / ks.k_splits) * heads + id % heads, nblk, heads, a.cu_q, a.cu_k, w);
+    } else {
+      attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    }
     if (w.b0 >= w.len_q) continue;
+    int k_end = w.len_k;
+    if (KSPLIT) attn_key_share(w.len_k, ks.k_splits, split, k_beg, k_end);
     const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
     const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
     const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
@@ -226,7 +270,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnOperands<T> a, i
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[mb][i] = 0.f;
     float m = -INFINITY, l = 0.f;
-    for (int k0 = 0; k0 < w.len_k; k0 += kAttnBlock) {
+    for (int k0 = k_beg; k0 < k_end; k0 += kAttnBlock) {
       a_f32x16 st;
 #pragma unroll
       for (int i = 0; i < 16; ++i) st[i] = 0.f;
@@ -266,7 +310,14 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnOperands<T> a, i
       }
     }
     const int row = w.b0 + r;
-    if (row < w.len_q) {
+    if (KSPLIT) {
+      // the share's state as it stands: an empty share leaves m = -inf, l = 0 and a zero accumulator
+      if (row < w.len_q) {
+        const int64_t idx = ((int64_t)split * ks.total_q + w.beg_q + row) * heads + w.hd;
+        store_dcol_f32<D>(ks.o + idx * D, acc, h);
+        if (h == 0) *reinterpret_cast<float2*>(ks.ml + 2 * idx) = make_float2(m, l);
+      }
+    } else if (row < w.len_q) {
       // l > 0 whenever the sequence has a key (the row maximum contributes exp2(0) = 1).  No key: the accumulator is
       // still zero and is stored as exact zeros, lse = -inf.
       const bool any = w.len_k > 0;
@@ -446,12 +497,13 @@ __global__ __launch_bounds__(256) void attn_dkdv_reduce_kernel(const float* __re
   }
 }
 
-// dQ of one (sequence, 32-query block, head).
-template <typename T, int D>
+// dQ of one (sequence, 32-query block, head) - or, with KSPLIT, of one share of that item's keys (the forward's shares):
+// P is recomputed from the final LSE, so the unscaled fp32 partials in ks.o only need adding (attn_dq_reduce_kernel).
+template <typename T, int D, bool KSPLIT>
 __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const AttnOperands<T> a, const T* __restrict__ dout,
                                                          const float* __restrict__ lse, const float* __restrict__ delta,
                                                          int64_t items, int nblk, float c2, float scale, T* __restrict__ dq_out,
-                                                         int64_t dq_stride) {
+                                                         int64_t dq_stride, const AttnKSplit ks) {
   typedef typename AFrag<T>::type frag;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
   __shared__ __attribute__((aligned(16))) T kt[NMB * 32 * kAttnPitch];
@@ -460,8 +512,17 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const AttnOperands<T> a
   const int64_t qp = a.q_stride, kp = a.kv_stride, opitch = (int64_t)heads * D;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    int split = 0, k_beg = 0;
+    if (KSPLIT) {
+      const int64_t t = id / heads;
+      split = (int)(t % ks.k_splits);
+      attn_item((t / ks.k_splits) * heads + id % heads, nblk, heads, a.cu_q, a.cu_k, w);
+    } else {
+      attn_item(id, nblk, heads, a.cu_q, a.cu_k, w);
+    }
     if (w.b0 >= w.len_q) continue;
+    int k_end = w.len_k;
+    if (KSPLIT) attn_key_share(w.len_k, ks.k_splits, split, k_beg, k_end);
     const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
     const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
     const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
@@ -484,7 +545,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const AttnOperands<T> a
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) dq[mb][i] = 0.f;
-    for (int k0 = 0; k0 < w.len_k; k0 += kAttnBlock) {
+    for (int k0 = k_beg; k0 < k_end; k0 += kAttnBlock) {
       a_f32x16 st, dpt;
       frag kf[NS];
 #pragma unroll
@@ -512,7 +573,72 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const AttnOperands<T> a
         for (int mb = 0; mb < NMB; ++mb) dq[mb] = AFrag<T>::mfma(read_tr<T>(kt, mb, s, r, h), dsf, dq[mb]);
       }
     }
-    if (ok) store_dcol<T, D>(dq_out + (w.beg_q + row) * dq_stride + (int64_t)w.hd * D, dq, scale, h);
+    if (KSPLIT) {
+      if (ok) store_dcol_f32<D>(ks.o + (((int64_t)split * ks.total_q + w.beg_q + row) * heads + w.hd) * D, dq, h);
+    } else if (ok) {
+      store_dcol<T, D>(dq_out + (w.beg_q + row) * dq_stride + (int64_t)w.hd * D, dq, scale, h);
+    }
+  }
+}
+
+// out, lse from the partials of a split-key forward, one thread per 4 consecutive d of a (query row, head); j runs
+// 0 .. k_splits - 1 in that order:  M = max_j m_j,  L = sum_j exp2(m_j - M) l_j,  out = sum_j exp2(m_j - M) o_j / L,
+// lse = (M + log2 L) ln 2.  No share saw a key (M = -inf): out = 0, lse = -inf.  Rows outside [cu_q[0], cu_q[num_seqs])
+// belong to no sequence: not written.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_fwd_combine_kernel(const AttnKSplit ks, const int32_t* __restrict__ cu_q,
+                                                               int64_t num_seqs, int heads, T* __restrict__ out,
+                                                               float* __restrict__ lse) {
+  typedef typename AFrag<T>::half_type half;
+  const int64_t slab = ks.total_q * heads, n = slab * (D / 4);
+  const int64_t first = cu_q[0], last = cu_q[num_seqs];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % (D / 4));
+    const int64_t th = i / (D / 4), row = th / heads;
+    if (row < first || row >= last) continue;
+    float M = -INFINITY;
+    for (int j = 0; j < ks.k_splits; ++j) M = fmaxf(M, ks.ml[2 * (j * slab + th)]);
+    const bool any = M > -INFINITY;
+    float L = 0.f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (any)
+      for (int j = 0; j < ks.k_splits; ++j) {
+        const float2 ml = *reinterpret_cast<const float2*>(ks.ml + 2 * (j * slab + th));
+        const float wj = __builtin_amdgcn_exp2f(ml.x - M);  // an empty share: exp2(-inf) = 0 against l = 0, o = 0
+        const float4 x = *reinterpret_cast<const float4*>(ks.o + (j * slab + th) * D + 4 * c);
+        L += wj * ml.y;
+        acc.x += wj * x.x, acc.y += wj * x.y, acc.z += wj * x.z, acc.w += wj * x.w;
+      }
+    const float inv = any ? 1.f / L : 0.f;
+    half o;
+    o[0] = (T)(acc.x * inv), o[1] = (T)(acc.y * inv), o[2] = (T)(acc.z * inv), o[3] = (T)(acc.w * inv);
+    *reinterpret_cast<half*>(out + th * D + 4 * c) = o;
+    if (c == 0) lse[th] = any ? (M + __log2f(L)) * kLn2 : -INFINITY;
+  }
+}
+
+// dq rows from the partials of a split-key dQ sweep: splits summed in the order 0 .. k_splits - 1, scaled, cast.  The
+// walk of attn_dkdv_reduce_kernel over [k_splits, total_q, H, D].
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_dq_reduce_kernel(const AttnKSplit ks, const int32_t* __restrict__ cu_q,
+                                                             int64_t num_seqs, int heads, float scale, T* __restrict__ dq_out,
+                                                             int64_t dq_stride) {
+  typedef typename AFrag<T>::half_type half;
+  const int64_t slab = ks.total_q * heads, n = slab * (D / 4);
+  const int64_t first = cu_q[0], last = cu_q[num_seqs];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % (D / 4));
+    const int64_t th = i / (D / 4), row = th / heads;
+    const int hd = (int)(th % heads);
+    if (row < first || row >= last) continue;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < ks.k_splits; ++j) {
+      const float4 x = *reinterpret_cast<const float4*>(ks.o + (j * slab + th) * D + 4 * c);
+      acc.x += x.x, acc.y += x.y, acc.z += x.z, acc.w += x.w;
+    }
+    half o;
+    o[0] = (T)(acc.x * scale), o[1] = (T)(acc.y * scale), o[2] = (T)(acc.z * scale), o[3] = (T)(acc.w * scale);
+    *reinterpret_cast<half*>(dq_out + row * dq_stride + (int64_t)hd * D + 4 * c) = o;
   }
 }
 
@@ -544,9 +670,10 @@ __device__ __forceinline__ typename AFrag<T>::type get_row(const T* __restrict__
   return *reinterpret_cast<const typename AFrag<T>::type*>(rows + r * SharedTile<D>::kRowPitch + 16 * s + 8 * h);
 }
 
-template <typename T, int D>
+template <typename T, int D, bool KSPLIT>
 __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(const AttnOperands<T> a, int64_t items, int nblk, float c2,
-                                                              T* __restrict__ out, float* __restrict__ lse) {
+                                                              T* __restrict__ out, float* __restrict__ lse,
+                                                              const AttnKSplit ks) {
   typedef typename AFrag<T>::type frag;
   typedef SharedTile<D> Tile;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
@@ -559,8 +686,17 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(const AttnOperands
   const int64_t qp = a.q_stride, kp = a.kv_stride;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    int split = 0, k_beg = 0;
+    if (KSPLIT) {
+      const int64_t t = id / heads;
+      split = (int)(t % ks.k_splits);
+      attn_item((t / ks.k_splits) * heads + id % heads, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    } else {
+      attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    }
     if (w.b0 >= w.len_q) continue;  // (the same for every wave of the workgroup)
+    int k_end = w.len_k;
+    if (KSPLIT) attn_key_share(w.len_k, ks.k_splits, split, k_beg, k_end);
     const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
     const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
     const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
@@ -575,13 +711,13 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(const AttnOperands
       for (int i = 0; i < 16; ++i) acc[mb][i] = 0.f;
     float m = -INFINITY, l = 0.f;
     frag kreg, vreg;
-    if (stager && w.len_k > 0) {
-      put_rows<T, D>(kr[0], load8<T>(k, kp, srow, w.len_k, 8 * sdch), srow, sdch);
-      put_tr<T>(vt[0], load8<T>(v, kp, srow, w.len_k, 8 * sdch), srow, sdch);
+    if (stager && k_beg < k_end) {
+      put_rows<T, D>(kr[0], load8<T>(k, kp, k_beg + srow, w.len_k, 8 * sdch), srow, sdch);
+      put_tr<T>(vt[0], load8<T>(v, kp, k_beg + srow, w.len_k, 8 * sdch), srow, sdch);
     }
     __syncthreads();
-    for (int k0 = 0, cur = 0; k0 < w.len_k; k0 += kAttnBlock, cur ^= 1) {
-      const bool more = stager && k0 + kAttnBlock < w.len_k;
+    for (int k0 = k_beg, cur = 0; k0 < k_end; k0 += kAttnBlock, cur ^= 1) {
+      const bool more = stager && k0 + kAttnBlock < k_end;
       if (more) {  // the next tile's loads are in flight during this tile's MFMAs
         kreg = load8<T>(k, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
         vreg = load8<T>(v, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
@@ -627,7 +763,13 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(const AttnOperands
       __syncthreads();  // the next tile is staged, and this tile's reads are done before its buffer is written again
     }
     const int row = rb + r;
-    if (row < w.len_q) {
+    if (KSPLIT) {
+      if (row < w.len_q) {
+        const int64_t idx = ((int64_t)split * ks.total_q + w.beg_q + row) * heads + w.hd;
+        store_dcol_f32<D>(ks.o + idx * D, acc, h);
+        if (h == 0) *reinterpret_cast<float2*>(ks.ml + 2 * idx) = make_float2(m, l);
+      }
+    } else if (row < w.len_q) {
       const bool any = w.len_k > 0;
       const int64_t t = w.beg_q + row;
       store_dcol<T, D>(out + (t * heads + w.hd) * D, acc, any ? 1.f / l : 0.f, h);
@@ -636,12 +778,14 @@ __global__ __launch_bounds__(256) void attn_fwd_shared_kernel(const AttnOperands
   }
 }
 
-// dQ of one (sequence, 128-query block, head): K and V rows and the K^T image staged once per key tile.
-template <typename T, int D>
+// dQ of one (sequence, 128-query block, [split,] head): K and V rows and the K^T image staged once per key tile.  KSPLIT as
+// in attn_bwd_dq_kernel (same shares, same partial layout).
+template <typename T, int D, bool KSPLIT>
 __global__ __launch_bounds__(256) void attn_bwd_dq_shared_kernel(const AttnOperands<T> a, const T* __restrict__ dout,
                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
                                                                  int64_t items, int nblk, float c2, float scale,
-                                                                 T* __restrict__ dq_out, int64_t dq_stride) {
+                                                                 T* __restrict__ dq_out, int64_t dq_stride,
+                                                                 const AttnKSplit ks) {
   typedef typename AFrag<T>::type frag;
   typedef SharedTile<D> Tile;
   constexpr int NS = D / 16, NMB = (D + 31) / 32;
@@ -655,8 +799,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_shared_kernel(const AttnOpera
   const int64_t qp = a.q_stride, kp = a.kv_stride, opitch = (int64_t)heads * D;
   for (int64_t id = blockIdx.x; id < items; id += gridDim.x) {
     AttnItem w;
-    attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    int split = 0, k_beg = 0;
+    if (KSPLIT) {
+      const int64_t t = id / heads;
+      split = (int)(t % ks.k_splits);
+      attn_item((t / ks.k_splits) * heads + id % heads, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    } else {
+      attn_item(id, nblk, heads, a.cu_q, a.cu_k, w, kAttnWgRows);
+    }
     if (w.b0 >= w.len_q) continue;
+    int k_end = w.len_k;
+    if (KSPLIT) attn_key_share(w.len_k, ks.k_splits, split, k_beg, k_end);
     const T* q = a.q + w.beg_q * qp + (int64_t)w.hd * D;
     const T* k = a.k + w.beg_k * kp + (int64_t)w.hd * D;
     const T* v = a.v + w.beg_k * kp + (int64_t)w.hd * D;
@@ -678,15 +831,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_shared_kernel(const AttnOpera
 #pragma unroll
       for (int i = 0; i < 16; ++i) dq[mb][i] = 0.f;
     frag kreg, vreg;
-    if (stager && w.len_k > 0) {
-      kreg = load8<T>(k, kp, srow, w.len_k, 8 * sdch);
+    if (stager && k_beg < k_end) {
+      kreg = load8<T>(k, kp, k_beg + srow, w.len_k, 8 * sdch);
       put_rows<T, D>(kr[0], kreg, srow, sdch);
       put_tr<T>(kt[0], kreg, srow, sdch);
-      put_rows<T, D>(vr[0], load8<T>(v, kp, srow, w.len_k, 8 * sdch), srow, sdch);
+      put_rows<T, D>(vr[0], load8<T>(v, kp, k_beg + srow, w.len_k, 8 * sdch), srow, sdch);
     }
     __syncthreads();
-    for (int k0 = 0, cur = 0; k0 < w.len_k; k0 += kAttnBlock, cur ^= 1) {
-      const bool more = stager && k0 + kAttnBlock < w.len_k;
+    for (int k0 = k_beg, cur = 0; k0 < k_end; k0 += kAttnBlock, cur ^= 1) {
+      const bool more = stager && k0 + kAttnBlock < k_end;
       if (more) {
         kreg = load8<T>(k, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
         vreg = load8<T>(v, kp, k0 + kAttnBlock + srow, w.len_k, 8 * sdch);
@@ -718,7 +871,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_shared_kernel(const AttnOpera
       }
       __syncthreads();
     }
-    if (ok) store_dcol<T, D>(dq_out + (w.beg_q + row) * dq_stride + (int64_t)w.hd * D, dq, scale, h);
+    if (KSPLIT) {
+      if (ok) store_dcol_f32<D>(ks.o + (((int64_t)split * ks.total_q + w.beg_q + row) * heads + w.hd) * D, dq, h);
+    } else if (ok) {
+      store_dcol<T, D>(dq_out + (w.beg_q + row) * dq_stride + (int64_t)w.hd * D, dq, scale, h);
+    }
   }
 }
 
@@ -901,28 +1058,39 @@ static int attn_variant(const AttnCall& c, int variant, int direction) {
   return wcn_attn_varlen_variant(c.num_seqs, c.max_q, c.max_k, c.heads, direction);
 }
 
+// k_splits > 1: the split-key kernels into the partials `ks`, then the combine; 1: the unsplit kernels, as ever.
 template <typename T, int D>
-static int attn_fwd_t(const AttnCall& c, void* out, float* lse, int variant, hipStream_t s) {
-  if (attn_variant(c, variant, 0) == WCN_ATTN_SHARED) {
-    const int nblk = attn_wg_blocks(c.max_q);
-    const int64_t items = c.num_seqs * nblk * c.heads;
-    if (items > 0)
-      hipLaunchKernelGGL((attn_fwd_shared_kernel<T, D>), dim3(attn_grid(items)), dim3(64 * kAttnWaves), 0, s, attn_operands<T>(c),
-                         items, nblk, c.scale * kLog2e, (T*)out, lse);
-    return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
+static int attn_fwd_t(const AttnCall& c, void* out, float* lse, int variant, const AttnKSplit& ks, hipStream_t s) {
+  const bool shared = attn_variant(c, variant, 0) == WCN_ATTN_SHARED;
+  const int nblk = shared ? attn_wg_blocks(c.max_q) : attn_blocks(c.max_q);
+  const dim3 wg(shared ? 64 * kAttnWaves : 64);
+  const int64_t items = c.num_seqs * nblk * c.heads * ks.k_splits;
+  const AttnOperands<T> a = attn_operands<T>(c);
+  const float c2 = c.scale * kLog2e;
+  if (items > 0) {
+    if (ks.k_splits > 1) {
+      if (shared)
+        hipLaunchKernelGGL((attn_fwd_shared_kernel<T, D, true>), dim3(attn_grid(items)), wg, 0, s, a, items, nblk, c2, (T*)out,
+                           lse, ks);
+      else
+        hipLaunchKernelGGL((attn_fwd_kernel<T, D, true>), dim3(attn_grid(items)), wg, 0, s, a, items, nblk, c2, (T*)out, lse, ks);
+      const int64_t n = c.total_q * c.heads * (D / 4);
+      hipLaunchKernelGGL((attn_fwd_combine_kernel<T, D>), dim3(attn_grid((n + 255) / 256)), dim3(256), 0, s, ks, c.cu_q,
+                         c.num_seqs, c.heads, (T*)out, lse);
+    } else if (shared) {
+      hipLaunchKernelGGL((attn_fwd_shared_kernel<T, D, false>), dim3(attn_grid(items)), wg, 0, s, a, items, nblk, c2, (T*)out,
+                         lse, ks);
+    } else {
+      hipLaunchKernelGGL((attn_fwd_kernel<T, D, false>), dim3(attn_grid(items)), wg, 0, s, a, items, nblk, c2, (T*)out, lse, ks);
+    }
   }
-  const int nblk = attn_blocks(c.max_q);
-  const int64_t items = c.num_seqs * nblk * c.heads;
-  if (items > 0)
-    hipLaunchKernelGGL((attn_fwd_kernel<T, D>), dim3(attn_grid(items)), dim3(64), 0, s, attn_operands<T>(c), items, nblk,
-                       c.scale * kLog2e, (T*)out, lse);
   return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
 }
 
 template <typename T, int D>
 static int attn_bwd_t(const AttnCall& c, const void* dout, const void* out, const float* lse, void* dq, int64_t dq_stride,
                       void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part, float* delta, int variant,
-                      hipStream_t s) {
+                      const AttnKSplit& ks, hipStream_t s) {
   const AttnOperands<T> a = attn_operands<T>(c);
   const float c2 = c.scale * kLog2e;
   const int64_t rows = c.total_q * c.heads;
@@ -959,36 +1127,51 @@ static int attn_bwd_t(const AttnCall& c, const void* dout, const void* out, cons
     }
   }
   if (items_q > 0 && c.total_q > 0) {
-    if (shared)
-      hipLaunchKernelGGL((attn_bwd_dq_shared_kernel<T, D>), dim3(attn_grid(items_q)), wg, 0, s, a, (const T*)dout, lse,
-                         (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride);
-    else
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), dim3(attn_grid(items_q)), wg, 0, s, a, (const T*)dout, lse,
-                         (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride);
+    if (ks.k_splits > 1) {
+      const int64_t items = items_q * ks.k_splits;
+      if (shared)
+        hipLaunchKernelGGL((attn_bwd_dq_shared_kernel<T, D, true>), dim3(attn_grid(items)), wg, 0, s, a, (const T*)dout, lse,
+                           (const float*)delta, items, nblk_q, c2, c.scale, (T*)dq, dq_stride, ks);
+      else
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, true>), dim3(attn_grid(items)), wg, 0, s, a, (const T*)dout, lse,
+                           (const float*)delta, items, nblk_q, c2, c.scale, (T*)dq, dq_stride, ks);
+      const int64_t n = c.total_q * c.heads * (D / 4);
+      hipLaunchKernelGGL((attn_dq_reduce_kernel<T, D>), dim3(attn_grid((n + 255) / 256)), dim3(256), 0, s, ks, c.cu_q,
+                         c.num_seqs, c.heads, c.scale, (T*)dq, dq_stride);
+    } else if (shared) {
+      hipLaunchKernelGGL((attn_bwd_dq_shared_kernel<T, D, false>), dim3(attn_grid(items_q)), wg, 0, s, a, (const T*)dout, lse,
+                         (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride, ks);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, false>), dim3(attn_grid(items_q)), wg, 0, s, a, (const T*)dout, lse,
+                         (const float*)delta, items_q, nblk_q, c2, c.scale, (T*)dq, dq_stride, ks);
+    }
   }
   return hipGetLastError() == hipSuccess ? WCN_SUCCESS : WCN_ERROR_KERNEL_EXECUTION;
 }
 
-static int attn_fwd_dispatch(const AttnCall& c, int head_dim, int dtype, void* out, float* lse, int variant, hipStream_t s) {
+static const AttnKSplit kAttnNoKSplit{1, 0, nullptr, nullptr};
+
+static int attn_fwd_dispatch(const AttnCall& c, int head_dim, int dtype, void* out, float* lse, int variant, hipStream_t s,
+                             const AttnKSplit& ks = kAttnNoKSplit) {
   return with_dtype16(dtype, [&](auto t) {
     using T = decltype(t);
     switch (head_dim) {
-      case 16: return attn_fwd_t<T, 16>(c, out, lse, variant, s);
-      case 32: return attn_fwd_t<T, 32>(c, out, lse, variant, s);
-      default: return attn_fwd_t<T, 64>(c, out, lse, variant, s);
+      case 16: return attn_fwd_t<T, 16>(c, out, lse, variant, ks, s);
+      case 32: return attn_fwd_t<T, 32>(c, out, lse, variant, ks, s);
+      default: return attn_fwd_t<T, 64>(c, out, lse, variant, ks, s);
     }
   });
 }
 
 static int attn_bwd_dispatch(const AttnCall& c, int head_dim, int dtype, const void* dout, const void* out, const float* lse,
                              void* dq, int64_t dq_stride, void* dk, void* dv, int64_t dkv_stride, int q_splits, float* part,
-                             float* delta, int variant, hipStream_t s) {
+                             float* delta, int variant, hipStream_t s, const AttnKSplit& ks = kAttnNoKSplit) {
   return with_dtype16(dtype, [&](auto t) {
     using T = decltype(t);
     switch (head_dim) {
-      case 16: return attn_bwd_t<T, 16>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, s);
-      case 32: return attn_bwd_t<T, 32>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, s);
-      default: return attn_bwd_t<T, 64>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, s);
+      case 16: return attn_bwd_t<T, 16>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, ks, s);
+      case 32: return attn_bwd_t<T, 32>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, ks, s);
+      default: return attn_bwd_t<T, 64>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, variant, ks, s);
     }
   });
 }
@@ -1038,6 +1221,15 @@ constexpr int64_t kAttnSplitTargetWaves = 4096;          // (sequence, key block
 constexpr int kAttnSplitMinBlocks = 16;                  // query blocks a split sweeps at the least
 constexpr int kAttnSplitMax = 16;
 constexpr int64_t kAttnSplitPartCap = 256LL << 20;       // bytes of partials the rule may ask for (at head_dim 64)
+
+// The split rule of the key sweep of the forward and of dQ (see wcn.h).  Measured on an MI355X: docs/OPTIMISATION_LOG.md.
+constexpr int64_t kAttnKSplitTargetItems = 4096;         // (sequence, 128-query block, split, head) workgroups worth launching
+// 32-key blocks a split sweeps at the least.  Set by a constraint, not by the table: 17 is the least value that leaves the
+// 1 025-key shapes of the existing tests at one split (tests/test_attention_ksplit_api.py); the measured best at 2 000 keys
+// is 4 - 8 splits, 8 - 16 blocks each.
+constexpr int kAttnKSplitMinBlocks = 17;
+constexpr int kAttnKSplitMax = 64;
+constexpr int64_t kAttnKSplitPartCap = 256LL << 20;      // bytes of partials the rule may ask for (at head_dim 64)
 
 }  // namespace wcn
 
@@ -1118,15 +1310,56 @@ int wcn_attn_varlen_kv_fwd_v(const void* q, int64_t q_stride, const void* k, con
                              const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
                              int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
                              int32_t dtype, void* out, float* lse, int32_t variant, wcn_stream_t stream) {
-  if (!attn_variant_ok(variant)) return WCN_ERROR_INVALID_PARAMETERS;
+  return wcn_attn_varlen_kv_fwd_s(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
+                                  max_seqlen_q, max_seqlen_k, softmax_scale, dtype, out, lse, variant, 1, nullptr, 0, stream);
+}
+
+int32_t wcn_attn_varlen_k_splits(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads,
+                                 int32_t direction) {
+  (void)direction;  // the forward and dQ sweep the same keys from the same work items: one rule for both
+  if (num_seqs < 1 || max_seqlen_q < 1 || max_seqlen_k < 1 || heads < 1) return 1;
+  // A sweep long enough to split (2 * kAttnKSplitMinBlocks blocks >= kAttnSharedMinSweep keys) runs the shared kernels
+  // under WCN_ATTN_AUTO, so the unsplit launch is counted in their 128-query work items whatever variant is forced.
+  const int64_t base = num_seqs * attn_wg_blocks(max_seqlen_q) * heads;
+  int64_t s = (kAttnKSplitTargetItems + base - 1) / base;
+  const int64_t by_blocks = attn_blocks(max_seqlen_k) / kAttnKSplitMinBlocks;
+  const int64_t by_bytes = kAttnKSplitPartCap / (num_seqs * max_seqlen_q * heads * (64 + 2) * (int64_t)sizeof(float));
+  if (s > by_blocks) s = by_blocks;
+  if (s > by_bytes) s = by_bytes;
+  if (s > kAttnKSplitMax) s = kAttnKSplitMax;
+  return s < 1 ? 1 : (int32_t)s;
+}
+
+size_t wcn_attn_varlen_ksplit_workspace_bytes(int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
+                                              int32_t q_splits, int32_t k_splits, int32_t direction) {
+  if (total_q < 0 || total_k < 0 || heads < 0 || head_dim < 0) return 0;
+  const size_t rows = (size_t)total_q * (size_t)heads;
+  const size_t ks = k_splits > 1 ? (size_t)k_splits : 0;
+  if (direction == 0) return ks * rows * ((size_t)head_dim + 2) * sizeof(float);
+  return wcn_attn_varlen_kv_workspace_bytes(total_q, total_k, heads, head_dim, q_splits) +
+         ks * rows * (size_t)head_dim * sizeof(float);
+}
+
+int wcn_attn_varlen_kv_fwd_s(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                             int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                             int32_t dtype, void* out, float* lse, int32_t variant, int32_t k_splits, void* workspace,
+                             size_t workspace_bytes, wcn_stream_t stream) {
+  if (!attn_variant_ok(variant) || k_splits < 0) return WCN_ERROR_INVALID_PARAMETERS;
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
   if (st != WCN_SUCCESS) return st;
   if (total_q > 0 && (!out || !lse || !aligned_to(out, 16))) return WCN_ERROR_INVALID_PARAMETERS;
+  if (k_splits == 0) k_splits = wcn_attn_varlen_k_splits(num_seqs, max_seqlen_q, max_seqlen_k, heads, 0);
+  const size_t need = wcn_attn_varlen_ksplit_workspace_bytes(total_q, total_k, heads, head_dim, 1, k_splits, 0);
+  if (need > 0 && (!workspace || workspace_bytes < need || !aligned_to(workspace, 16))) return WCN_ERROR_INVALID_PARAMETERS;
   if (num_seqs == 0 || total_q == 0 || max_seqlen_q == 0) return WCN_SUCCESS;
   const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
                    softmax_scale};
-  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, variant, (hipStream_t)stream);
+  // o [k_splits, total_q, heads, head_dim] first (a multiple of 64 bytes), ml [k_splits, total_q, heads, 2] after it
+  float* o = (float*)workspace;
+  const AttnKSplit ks{k_splits, total_q, o, o + (size_t)k_splits * (size_t)total_q * (size_t)heads * (size_t)head_dim};
+  return attn_fwd_dispatch(c, head_dim, dtype, out, lse, variant, (hipStream_t)stream, ks);
 }
 
 int wcn_attn_varlen_kv_bwd(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
@@ -1146,7 +1379,18 @@ int wcn_attn_varlen_kv_bwd_v(const void* dout, const void* q, int64_t q_stride, 
                              int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
                              void* dv, int64_t dkv_stride, int32_t q_splits, void* workspace, size_t workspace_bytes,
                              int32_t variant, wcn_stream_t stream) {
-  if (!attn_variant_ok(variant)) return WCN_ERROR_INVALID_PARAMETERS;
+  return wcn_attn_varlen_kv_bwd_s(dout, q, q_stride, k, v, kv_stride, out, lse, cu_q, cu_k, num_seqs, total_q, total_k, heads,
+                                  head_dim, max_seqlen_q, max_seqlen_k, softmax_scale, dtype, dq, dq_stride, dk, dv, dkv_stride,
+                                  q_splits, 1, workspace, workspace_bytes, variant, stream);
+}
+
+int wcn_attn_varlen_kv_bwd_s(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                             int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                             int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                             void* dv, int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace,
+                             size_t workspace_bytes, int32_t variant, wcn_stream_t stream) {
+  if (!attn_variant_ok(variant) || k_splits < 0) return WCN_ERROR_INVALID_PARAMETERS;
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, dtype);
   if (st != WCN_SUCCESS) return st;
@@ -1158,14 +1402,19 @@ int wcn_attn_varlen_kv_bwd_v(const void* dout, const void* q, int64_t q_stride, 
       !aligned_to(workspace, 16))
     return WCN_ERROR_INVALID_PARAMETERS;
   if (q_splits == 0) q_splits = wcn_attn_varlen_kv_splits(num_seqs, max_seqlen_q, max_seqlen_k, heads);
-  const size_t need = wcn_attn_varlen_kv_workspace_bytes(total_q, total_k, heads, head_dim, q_splits);
+  if (k_splits == 0) k_splits = wcn_attn_varlen_k_splits(num_seqs, max_seqlen_q, max_seqlen_k, heads, 1);
+  const size_t need = wcn_attn_varlen_ksplit_workspace_bytes(total_q, total_k, heads, head_dim, q_splits, k_splits, 1);
   if (workspace_bytes < need || (need > 0 && !workspace)) return WCN_ERROR_INVALID_PARAMETERS;
   if (num_seqs == 0 || (total_q == 0 && total_k == 0)) return WCN_SUCCESS;
-  // the partials come first (their size is a multiple of 16 bytes), delta [total_q, heads] after them
+  // the dK/dV partials come first, the dQ partials [k_splits, total_q, heads, head_dim] after them (both sizes are
+  // multiples of 16 bytes, either may be empty), delta [total_q, heads] last
+  const size_t dq_bytes = k_splits > 1 ? (size_t)k_splits * (size_t)total_q * (size_t)heads * (size_t)head_dim * sizeof(float) : 0;
+  const size_t delta_bytes = (size_t)total_q * (size_t)heads * sizeof(float);
   float* part = (float*)workspace;
-  float* delta = (float*)((char*)workspace + (need - (size_t)total_q * (size_t)heads * sizeof(float)));
+  float* delta = (float*)((char*)workspace + (need - delta_bytes));
+  const AttnKSplit ks{k_splits, total_q, (float*)((char*)workspace + (need - delta_bytes - dq_bytes)), nullptr};
   const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
                    softmax_scale};
   return attn_bwd_dispatch(c, head_dim, dtype, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta,
-                           variant, (hipStream_t)stream);
+                           variant, (hipStream_t)stream, ks);
 }

@@ -255,22 +255,36 @@ class _CrossVarlenAttention(Function):
 
     @staticmethod
     def forward(ctx, q: Tensor, k: Tensor, v: Optional[Tensor], cu_q: Tensor, cu_k: Tensor, max_q: int, max_k: int,
-                scale: float, q_splits: int, variant: int = 0) -> Tensor:
+                scale: float, q_splits: int, variant: int = 0, k_splits: int = 1) -> Tensor:
         packed = v is None
         kk, vv = (k[:, 0], k[:, 1]) if packed else (k, v)
         tq, h, d = q.shape
         dev = q.device
         out = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
         lse = torch.empty(tq, h, dtype=torch.float32, device=dev)
-        _lib.check(
-            _lib.lib().wcn_attn_varlen_kv_fwd_v(_lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
-                                                _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, kk.shape[0], h, d, max_q,
-                                                max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(out), _lib.ptr(lse), variant,
-                                                _lib.stream_handle(dev)),
-            "wcn_attn_varlen_kv_fwd",
-        )
+        L = _lib.lib()
+        if k_splits == 0:  # the library's rule, resolved once: the backward's dQ sweep uses the same count
+            k_splits = L.wcn_attn_varlen_k_splits(cu_q.numel() - 1, max_q, max_k, h, 0)
+        if k_splits == 1:
+            _lib.check(
+                L.wcn_attn_varlen_kv_fwd_v(_lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk), _lib.ptr(cu_q),
+                                           _lib.ptr(cu_k), cu_q.numel() - 1, tq, kk.shape[0], h, d, max_q, max_k, scale,
+                                           _lib.dtype_code(q.dtype), _lib.ptr(out), _lib.ptr(lse), variant, _lib.stream_handle(dev)),
+                "wcn_attn_varlen_kv_fwd",
+            )
+        else:
+            ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, kk.shape[0], h, d, 1, k_splits, 0), dtype=torch.uint8,
+                             device=dev)
+            _lib.check(
+                L.wcn_attn_varlen_kv_fwd_s(_lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk), _lib.ptr(cu_q),
+                                           _lib.ptr(cu_k), cu_q.numel() - 1, tq, kk.shape[0], h, d, max_q, max_k, scale,
+                                           _lib.dtype_code(q.dtype), _lib.ptr(out), _lib.ptr(lse), variant, k_splits, _lib.ptr(ws),
+                                           ws.numel(), _lib.stream_handle(dev)),
+                "wcn_attn_varlen_kv_fwd_s",
+            )
         ctx.save_for_backward(q, k, v, cu_q, cu_k, out, lse)
         ctx.args = (max_q, max_k, scale, q_splits)
+        ctx.k_splits = k_splits
         ctx.variant = variant
         return out
 
@@ -292,25 +306,39 @@ class _CrossVarlenAttention(Function):
             dk, dv = torch.empty(tk, h, d, dtype=q.dtype, device=dev), torch.empty(tk, h, d, dtype=q.dtype, device=dev)
         L = _lib.lib()
         splits = q_splits if q_splits > 0 else L.wcn_attn_varlen_kv_splits(cu_q.numel() - 1, max_q, max_k, h)
-        ws = torch.empty(L.wcn_attn_varlen_kv_workspace_bytes(tq, tk, h, d, splits), dtype=torch.uint8, device=dev)
-        _lib.check(
-            L.wcn_attn_varlen_kv_bwd_v(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
-                                       _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h,
-                                       d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(dq), h * d, _lib.ptr(dk),
-                                       _lib.ptr(dv), (2 if packed else 1) * h * d, splits, _lib.ptr(ws), ws.numel(), ctx.variant,
-                                       _lib.stream_handle(dev)),
-            "wcn_attn_varlen_kv_bwd",
-        )
+        if ctx.k_splits == 1:
+            ws = torch.empty(L.wcn_attn_varlen_kv_workspace_bytes(tq, tk, h, d, splits), dtype=torch.uint8, device=dev)
+            _lib.check(
+                L.wcn_attn_varlen_kv_bwd_v(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
+                                           _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h,
+                                           d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(dq), h * d, _lib.ptr(dk),
+                                           _lib.ptr(dv), (2 if packed else 1) * h * d, splits, _lib.ptr(ws), ws.numel(), ctx.variant,
+                                           _lib.stream_handle(dev)),
+                "wcn_attn_varlen_kv_bwd",
+            )
+        else:
+            ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, tk, h, d, splits, ctx.k_splits, 1), dtype=torch.uint8,
+                             device=dev)
+            _lib.check(
+                L.wcn_attn_varlen_kv_bwd_s(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
+                                           _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h,
+                                           d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(dq), h * d, _lib.ptr(dk),
+                                           _lib.ptr(dv), (2 if packed else 1) * h * d, splits, ctx.k_splits, _lib.ptr(ws),
+                                           ws.numel(), ctx.variant, _lib.stream_handle(dev)),
+                "wcn_attn_varlen_kv_bwd_s",
+            )
         if packed:
-            return dq, dkv, None, None, None, None, None, None, None, None
-        return dq, dk, dv, None, None, None, None, None, None, None
+            return dq, dkv, None, None, None, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
 def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                   max_seqlen_k: int, dropout_p: float, softmax_scale: Optional[float], kv: Optional[Tensor],
-                  q_splits: int, variant="auto") -> Tensor:
+                  q_splits: int, variant="auto", k_splits: int = 1) -> Tensor:
     """The checks of both public forms; ``k`` / ``v`` are the slots of ``kv`` when that is given."""
     variant = _variant_code(variant)
+    if not isinstance(k_splits, int) or isinstance(k_splits, bool) or k_splits < 0:
+        raise ValueError(f"k_splits must be an int >= 0 (0: the library's rule, 1: no split), got {k_splits!r}")
     if dropout_p > 0.0:
         raise NotImplementedError(f"{name}: dropout is not implemented (dropout_p must be 0)")
     if q.ndim != 3:
@@ -349,33 +377,36 @@ def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tens
         q = q.contiguous()
     if kv is not None:
         return _CrossVarlenAttention.apply(q, kv.contiguous(), None, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), scale,
-                                           int(q_splits), variant)
+                                           int(q_splits), variant, k_splits)
     if not (_kernel_rows(k) and _kernel_rows(v) and _row_stride(k) == _row_stride(v)):
         k, v = k.contiguous(), v.contiguous()
-    return _CrossVarlenAttention.apply(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), scale, int(q_splits), variant)
+    return _CrossVarlenAttention.apply(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), scale, int(q_splits), variant,
+                                       k_splits)
 
 
 @eager_unless_compiling
 def flash_attn_varlen_func(q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                            max_seqlen_k: int, dropout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                           q_splits: int = 0, variant="auto") -> Tensor:
+                           q_splits: int = 0, variant="auto", k_splits: int = 1) -> Tensor:
     """Attention of the queries of sequence s, rows [cu_q[s], cu_q[s+1]) of ``q`` [Tq, H, D], over its keys, rows
     [cu_k[s], cu_k[s+1]) of ``k`` / ``v`` [Tk, H, D] -> [Tq, H, D]; fp16 / bf16 on the GPU.  The call the reference makes
     into the flash_attn package, minus dropout; differentiable in q, k and v (deterministic backward).  Host boundaries are
     checked and copied, device ones trusted (no host sync).  A query with no key gets zeros.  ``q_splits`` forces the
     split count of the backward's dK/dV sweep (0: the library's rule), ``variant`` names the kernels as in
-    ``flash_attn_varlen_qkvpacked``."""
+    ``flash_attn_varlen_qkvpacked``.  ``k_splits`` cuts the key sweep of the forward and of dQ into that many shares whose
+    fp32 partials a second kernel combines in a fixed order - for a few queries against a very long context (1, the default:
+    no split; 0: the library's rule, ``wcn_attn_varlen_k_splits``); the backward uses the forward's count."""
     return _cross_varlen("flash_attn_varlen_func", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
-                         dropout_p, softmax_scale, None, q_splits, variant)
+                         dropout_p, softmax_scale, None, q_splits, variant, k_splits)
 
 
 @eager_unless_compiling
 def flash_attn_varlen_kvpacked_func(q: Tensor, kv: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                                     max_seqlen_k: int, dropout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                                    q_splits: int = 0, variant="auto") -> Tensor:
+                                    q_splits: int = 0, variant="auto", k_splits: int = 1) -> Tensor:
     """``flash_attn_varlen_func`` with keys and values as the two slots of ``kv`` [Tk, 2, H, D].  The kernels read the
     slots through their strides, and write the gradient of ``kv`` as one [Tk, 2, H, D] tensor the same way (no ``cat``)."""
     if kv.ndim != 4 or kv.shape[1] != 2:
         raise ValueError(f"kv must be [Tk, 2, H, D], got {tuple(kv.shape)}")
     return _cross_varlen("flash_attn_varlen_kvpacked_func", q, kv[:, 0], kv[:, 1], cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
-                         max_seqlen_k, dropout_p, softmax_scale, kv, q_splits, variant)
+                         max_seqlen_k, dropout_p, softmax_scale, kv, q_splits, variant, k_splits)
