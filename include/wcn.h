@@ -97,6 +97,11 @@ int32_t wcn_kmap_mask_words(int32_t num_offsets);
  * aligned); the counts buffer holds wcn_kmap_counts_bytes(m, K) bytes: K rows of tile counts, K totals, a ticket word */
 int64_t wcn_kmap_num_blocks(int64_t m);
 size_t wcn_kmap_counts_bytes(int64_t m, int32_t num_offsets);
+/* ... and, behind those, the SLAB BOUNDS the scan writes for the weight gradient's team sweep: int32 [17][K] at element
+ * wcn_kmap_slab_bounds_offset(m, K) of the counts buffer.  bounds[t][k] = pairs of bucket k whose output row lies in front of
+ * row slab t (16 equal slabs of ceil(num_blocks / 16) tiles; bounds[0][k] = 0, bounds[16][k] = the bucket's size).  They
+ * describe pair lists in OUTPUT-ROW order inside each bucket - what wcn_kmap_scatter writes from the same counts. */
+int64_t wcn_kmap_slab_bounds_offset(int64_t m, int32_t num_offsets);
 
 /* reference: _C.cuhash.packed_kernel_map_size + packed_kernel_map_offset (cuhash_kernel_map.cu:68-134)
  * fused with build_pair_mask (mask_data_kernels.cu:23-44).
@@ -390,6 +395,23 @@ int wcn_conv_wgrad_bias(const void* x, const void* dy, float* dw, const int32_t*
                         int32_t num_offsets, int32_t dtype, int32_t self_offset, float* bias_grad, void* workspace,
                         size_t workspace_bytes, wcn_stream_t stream);
 
+/* The MFMA weight gradient (wcn_conv_wgrad, algo = WCN_ALGO_MFMA; with `bias_grad` non-NULL: wcn_conv_wgrad_bias) of a map
+ * whose pair lists come with SLAB BOUNDS (wcn_kmap_slab_bounds_offset; device pointer, NULL = none).  Where the rule of
+ * csrc/wgrad_plan.h holds - K = 27, one (cin, cout) tile, >= 512 x 512 pairs, the largest off-centre bucket <= 1.10 x their
+ * mean, no (slab, offset) range longer than the level the centre pieces fill every workgroup up to - the device sweeps the lists in row-slab TEAMS (the 26 off-centre offsets of a slab side by side on one XCD, so that
+ * the repeated gathers of a dY row meet in L2) instead of 512 equal ranges; the decision is made on the device from
+ * offsets[] and the bounds, every other launch runs exactly as without them.  Deterministic either way; the two sweeps add
+ * the fp32 partial tiles in different orders.  WARPCONVNET_AMD_WGRAD_TEAMS = 0 | auto (default) | force (the size and
+ * balance conditions dropped; tests, A/B runs), read per call.  workspace: wcn_conv_wgrad_workspace(..., WCN_ALGO_MFMA).
+ * wcn_wgrad_plan_host (host only, host pointers): the segments {bucket, begin, end} x (1 or 2) workgroup g of `grid`
+ * sweeps under the team plan; 0 = the rule refuses; `mode` 0 / 1 / 2 = off / auto / force. */
+int wcn_conv_wgrad_teams(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
+                         const int32_t* offsets, const int32_t* slab_bounds, int64_t n_in, int64_t n_out, int32_t cin,
+                         int32_t cout, int32_t num_offsets, int32_t dtype, int32_t self_offset, float* bias_grad,
+                         void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_wgrad_plan_host(const int32_t* offsets, const int32_t* slab_bounds, int32_t num_offsets, int32_t grid, int32_t tiles,
+                        int32_t mode, int32_t g, int64_t* out);
+
 /* ---- depthwise sparse convolution (weight [K, C], same dtype as the features) ----------------------------------------
  * reference semantics: warpconvnet/nn/functional/sparse_conv_depth.py:227-306 (explicit depthwise forward/backward);
  * replaces _C.fma.implicit_fma / _C.fma.implicit_reduction (call sites sparse_conv_depth.py:309-421).
@@ -618,6 +640,17 @@ int wcn_conv_bn_backward_ld(const void* grad_out, int64_t grad_out_ld, const voi
                             float* dw, void* wgrad_workspace, size_t wgrad_workspace_bytes, int64_t n_in, int64_t n_out,
                             int32_t cin, int32_t cout, int32_t num_offsets, int32_t dtype, void* bn_workspace,
                             size_t bn_workspace_bytes, wcn_stream_t stream);
+
+/* ... with the map's slab bounds (wcn_kmap_slab_bounds_offset; NULL = none) for the weight gradient: the sweep of
+ * wcn_conv_wgrad_teams on the same operands, so a layer computes the same bits through this entry and through the passes one by one. */
+int wcn_conv_bn_backward_teams(const void* grad_out, int64_t grad_out_ld, const void* x, const void* y, const void* z, int32_t relu,
+                               const float* stats, const float* gamma, int32_t training, float* sums, void* dy_conv, void* dres,
+                               const void* w_packed_dgrad, const int32_t* rev_nbr, const uint32_t* rev_mask,
+                               const int32_t* rev_perm, int32_t flip, void* dx, const int32_t* in_maps, const int32_t* out_maps,
+                               const int32_t* offsets, const int32_t* slab_bounds, float* dw, void* wgrad_workspace,
+                               size_t wgrad_workspace_bytes, int64_t n_in, int64_t n_out, int32_t cin, int32_t cout,
+                               int32_t num_offsets, int32_t dtype, void* bn_workspace, size_t bn_workspace_bytes,
+                               wcn_stream_t stream);
 
 /* ---- block-diagonal ("varlen") multi-head attention over a packed qkv tensor ----------------------------------------------
  * The attention core of PatchAttention (reference nn/modules/attention.py:496 calls flash_attn_varlen_qkvpacked_func through

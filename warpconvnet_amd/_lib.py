@@ -80,6 +80,10 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32,
                                         c_void_p, c_size_t, c_void_p]),
+    "wcn_conv_bn_backward_teams": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                           c_int32, c_void_p, c_size_t, c_void_p]),
     "wcn_conv_bn_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p,
@@ -92,6 +96,7 @@ SIGNATURES = {
     "wcn_pool_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "wcn_morton_code": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wcn_kmap_counts_bytes": (c_size_t, [c_int64, c_int32]),
+    "wcn_kmap_slab_bounds_offset": (c_int64, [c_int64, c_int32]),
     "wcn_kmap_binned_workspace": (c_size_t, [c_int64, c_int64]),
     "wcn_kmap_binned_supported": (c_int, [_3I, _3I]),
     "wcn_kmap_build_binned": (
@@ -360,6 +365,12 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
          c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "wcn_conv_wgrad_teams": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+         c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "wcn_wgrad_plan_host": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "wcn_lattice_chunk_rows": (c_int32, []),
     "wcn_hash128_insert": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "wcn_hash128_search": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
@@ -479,7 +490,7 @@ def _single_gpu() -> bool:
         return False
 
 
-_HOST_ONLY = {"wcn_status_string"}
+_HOST_ONLY = {"wcn_status_string", "wcn_wgrad_plan_host"}
 _CALL_DEVICE = threading.local()  # .dev = device index of the stream this THREAD asked for last (evaluated per call)
 
 

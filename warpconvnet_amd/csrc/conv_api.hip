@@ -1,5 +1,6 @@
 // conv_api.hip - C-ABI entry points of the sparse-conv GEMMs (include/wcn.h); dispatch only.
 #include "gather_gemm.h"  // the gather-GEMM families: family decision, launchers, weight packer
+#include "wgrad_plan.h"   // wcn_wgrad_plan_host
 
 namespace wcn {
 // conv_ref.hip
@@ -15,7 +16,7 @@ size_t wgrad_mfma_workspace(int K, int cin, int cout);
 bool mfma_wgrad_bias_supported(int cin, int cout, int dtype);
 int conv_wgrad_mfma(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                     const int32_t* offsets, int cin, int cout, int K, int dtype, void* workspace, size_t workspace_bytes,
-                    int cs_k, float* bias_grad, int64_t pair_bound, hipStream_t s);
+                    int cs_k, float* bias_grad, int64_t pair_bound, const int32_t* bounds, hipStream_t s);
 // dwconv.hip
 int dwconv_gather(const void* in, const void* w, void* out, const int32_t* tbl, const float* bias, int64_t n_out, int C,
                   int K, int dtype, int k_flip, hipStream_t s);
@@ -205,7 +206,7 @@ int wcn_conv_wgrad(const void* x, const void* dy, float* dw, const int32_t* in_m
       return conv_wgrad_ref(x, dy, dw, in_maps, out_maps, offsets, cin, cout, num_offsets, dtype, s);
     case WCN_ALGO_MFMA:
       return conv_wgrad_mfma(x, dy, dw, in_maps, out_maps, offsets, cin, cout, num_offsets, dtype, workspace,
-                             workspace_bytes, -1, nullptr, (int64_t)num_offsets * (n_in < n_out ? n_in : n_out), s);
+                             workspace_bytes, -1, nullptr, (int64_t)num_offsets * (n_in < n_out ? n_in : n_out), nullptr, s);
     default:
       return WCN_ERROR_INVALID_PARAMETERS;
   }
@@ -231,6 +232,22 @@ int wcn_conv_bn_backward_ld(const void* grad_out, int64_t grad_out_ld, const voi
                             float* dw, void* wgrad_workspace, size_t wgrad_workspace_bytes, int64_t n_in, int64_t n_out,
                             int32_t cin, int32_t cout, int32_t num_offsets, int32_t dtype, void* bn_workspace,
                             size_t bn_workspace_bytes, wcn_stream_t stream) {
+  return wcn_conv_bn_backward_teams(grad_out, grad_out_ld, x, y, z, relu, stats, gamma, training, sums, dy_conv, dres, w_packed_dgrad,
+                                    rev_nbr, rev_mask, rev_perm, flip, dx, in_maps, out_maps, offsets, nullptr, dw, wgrad_workspace,
+                                    wgrad_workspace_bytes, n_in, n_out, cin, cout, num_offsets, dtype, bn_workspace,
+                                    bn_workspace_bytes, stream);
+}
+
+// ... with the map's slab bounds (NULL: none): the weight gradient of the layer entry takes the same sweep as wcn_conv_wgrad_teams
+// on the same operands, so a layer computes the same bits through either entry.
+int wcn_conv_bn_backward_teams(const void* grad_out, int64_t grad_out_ld, const void* x, const void* y, const void* z, int32_t relu,
+                               const float* stats, const float* gamma, int32_t training, float* sums, void* dy_conv, void* dres,
+                               const void* w_packed_dgrad, const int32_t* rev_nbr, const uint32_t* rev_mask,
+                               const int32_t* rev_perm, int32_t flip, void* dx, const int32_t* in_maps, const int32_t* out_maps,
+                               const int32_t* offsets, const int32_t* slab_bounds, float* dw, void* wgrad_workspace,
+                               size_t wgrad_workspace_bytes, int64_t n_in, int64_t n_out, int32_t cin, int32_t cout,
+                               int32_t num_offsets, int32_t dtype, void* bn_workspace, size_t bn_workspace_bytes,
+                               wcn_stream_t stream) {
   if (!dy_conv || (dtype != WCN_F16 && dtype != WCN_BF16)) return WCN_ERROR_INVALID_PARAMETERS;
   int rc = wcn_bn_train_backward_ld(grad_out, grad_out_ld, y, z, relu, n_out, cout, dtype, stats, gamma, training, sums, dy_conv, dres,
                                     bn_workspace, bn_workspace_bytes, stream);
@@ -242,8 +259,8 @@ int wcn_conv_bn_backward_ld(const void* grad_out, int64_t grad_out_ld, const voi
     if (rc != WCN_SUCCESS) return rc;
   }
   if (dw)
-    rc = wcn_conv_wgrad(x, dy_conv, dw, in_maps, out_maps, offsets, n_in, n_out, cin, cout, num_offsets, dtype, WCN_ALGO_MFMA,
-                        wgrad_workspace, wgrad_workspace_bytes, stream);
+    rc = wcn_conv_wgrad_teams(x, dy_conv, dw, in_maps, out_maps, offsets, slab_bounds, n_in, n_out, cin, cout, num_offsets, dtype, -1,
+                              nullptr, wgrad_workspace, wgrad_workspace_bytes, stream);
   return rc;
 }
 
@@ -259,7 +276,39 @@ int wcn_conv_wgrad_bias(const void* x, const void* dy, float* dw, const int32_t*
     return WCN_ERROR_INVALID_PARAMETERS;
   if (self_offset < 0 || self_offset >= num_offsets) return WCN_ERROR_INVALID_PARAMETERS;
   return conv_wgrad_mfma(x, dy, dw, in_maps, out_maps, offsets, cin, cout, num_offsets, dtype, workspace, workspace_bytes,
-                         self_offset, bias_grad, (int64_t)num_offsets * (n_in < n_out ? n_in : n_out), (hipStream_t)stream);
+                         self_offset, bias_grad, (int64_t)num_offsets * (n_in < n_out ? n_in : n_out), nullptr,
+                         (hipStream_t)stream);
+}
+
+// The MFMA weight gradient of a map that carries the scan's slab bounds (wcn_kmap_slab_bounds_offset): the device takes
+// the team sweep of wgrad_plan.h where its rule holds.  bias_grad NULL: no bias gradient (self_offset ignored).
+int wcn_conv_wgrad_teams(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
+                         const int32_t* offsets, const int32_t* slab_bounds, int64_t n_in, int64_t n_out, int32_t cin,
+                         int32_t cout, int32_t num_offsets, int32_t dtype, int32_t self_offset, float* bias_grad,
+                         void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
+  if (n_in < 0 || n_out < 0 || cin < 1 || cout < 1 || num_offsets < 1 || !dtype_ok(dtype) || !dw || !offsets)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (bias_grad && (self_offset < 0 || self_offset >= num_offsets)) return WCN_ERROR_INVALID_PARAMETERS;
+  return conv_wgrad_mfma(x, dy, dw, in_maps, out_maps, offsets, cin, cout, num_offsets, dtype, workspace, workspace_bytes,
+                         bias_grad ? self_offset : -1, bias_grad, (int64_t)num_offsets * (n_in < n_out ? n_in : n_out),
+                         slab_bounds, (hipStream_t)stream);
+}
+
+// Host only: the segments workgroup g of a G-workgroup launch sweeps under the team plan, from HOST copies of the tables.
+// -> 0: the rule refuses (range sweep, `out` untouched); else the number of segments n (1 or 2) and out[3 s + 0 .. 2] =
+// {bucket, begin, end} of segment s.  `mode`: 0 off, 1 auto, 2 force (WARPCONVNET_AMD_WGRAD_TEAMS).
+int wcn_wgrad_plan_host(const int32_t* offsets, const int32_t* slab_bounds, int32_t num_offsets, int32_t grid, int32_t tiles,
+                        int32_t mode, int32_t g, int64_t* out) {
+  if (!offsets || !out || num_offsets < 1 || g < 0 || g >= grid) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!wgrad_team_rule_all(offsets, slab_bounds, num_offsets, grid, tiles, mode)) return 0;
+  WgradSeg seg[2];
+  const int n = wgrad_team_plan(offsets, slab_bounds, num_offsets, grid, g, seg);
+  for (int i = 0; i < n; ++i) {
+    out[3 * i] = seg[i].k;
+    out[3 * i + 1] = seg[i].begin;
+    out[3 * i + 2] = seg[i].end;
+  }
+  return n;
 }
 
 int wcn_dwconv_gather(const void* in, const void* w, void* out, const int32_t* nbr, const float* bias, int64_t n_in,

@@ -15,12 +15,14 @@
 // with atomic cursors), mask_data_kernels.cu:23-124.
 #include "kmap_cells.h"
 #include "mask_sort.h"
+#include "wgrad_plan.h"  // kPlanSlabs: the row slabs whose pair positions the scan keeps for the weight gradient
 
 namespace wcn {
 
 constexpr int kTileRows = 256;  // rows per bucket tile = 4 waves x 64
 constexpr int kBkThreads = 256;
 constexpr int kTallyThreads = (kRsTile / kTileRows) * 64;  // one wave per tile, one workgroup per sort tile
+constexpr int kBoundsGap = 64;  // ints between the totals and the slab bounds in the counts buffer (ticket word + slack)
 constexpr int kStageCap = 3072;  // pairs staged in LDS per (tile, mask word); denser tiles store directly
 
 static_assert(kRsTile % kTileRows == 0, "a sort tile is a whole number of bucket tiles");
@@ -129,6 +131,14 @@ __global__ __launch_bounds__(kBkThreads) void kmap_scan_kernel(int32_t* __restri
   // 4096 counts per trip (a 1 M-row map is one trip = one memory round trip), 16-B accesses: the rows are 16-B aligned and
   // ntile is a multiple of 4 (wcn_kmap_num_blocks)
   const int total = scan_counts_in_place<kBkThreads, 16>(counts + (int64_t)blockIdx.x * ntile, ntile, s_wave);
+  if (tid <= kPlanSlabs) {
+    // slab bounds [kPlanSlabs + 1][K] behind the ticket word (wcn_kmap_slab_bounds_offset): the scanned count at the first
+    // tile of each of 16 equal row slabs = the bucket's pairs in front of that slab (buckets are written in row order)
+    const int64_t tile = tid * ((ntile + kPlanSlabs - 1) / kPlanSlabs);
+    int32_t* bounds = counts + (int64_t)K * (ntile + 1) + kBoundsGap;
+    bounds[tid * K + blockIdx.x] =
+        tile < ntile ? __hip_atomic_load(&counts[(int64_t)blockIdx.x * ntile + tile], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : total;
+  }
   if (tid == 0) {
     // device-scope store + fence + ticket: the workgroup that draws the last ticket sees every total
     __hip_atomic_store(&totals[blockIdx.x], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -501,8 +511,12 @@ extern "C" {
 int64_t wcn_kmap_num_blocks(int64_t m) { return (ceil_div(m > 0 ? m : 0, kTileRows) + 3) & ~(int64_t)3; }
 
 size_t wcn_kmap_counts_bytes(int64_t m, int32_t num_offsets) {
-  // K rows of counts + K totals + the ticket word (+ slack)
-  return ((size_t)num_offsets * (size_t)(wcn_kmap_num_blocks(m) + 1) + 64) * 4;
+  // K rows of counts + K totals + the ticket word (+ slack) + the slab bounds [kPlanSlabs + 1][K]
+  return ((size_t)num_offsets * (size_t)(wcn_kmap_num_blocks(m) + 1) + kBoundsGap + (size_t)(kPlanSlabs + 1) * num_offsets) * 4;
+}
+
+int64_t wcn_kmap_slab_bounds_offset(int64_t m, int32_t num_offsets) {
+  return (int64_t)num_offsets * (wcn_kmap_num_blocks(m) + 1) + kBoundsGap;
 }
 
 static void launch_tally(uint32_t* mask, int32_t* nbr, int64_t m, int K, int32_t* counts, bool hist, int nblk_sort,

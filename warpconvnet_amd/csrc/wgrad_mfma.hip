@@ -11,11 +11,19 @@
 //     workgroup flushes its fp32 partial tile to workspace slab (g + k) whenever the offset changes.
 //     Slab ids are unique, so a second tiny kernel reduces the slabs of each offset in ascending g:
 //     deterministic, no fp32 atomics.
+//   * team sweep (wgrad_plan.h; headline-like launches of a 3 x 3 x 3 map that carries the scan's slab bounds): the same
+//     pipeline over other segments - one (row slab, offset) range per workgroup, then a piece of the centre bucket - so
+//     that the 26 gathers of a dY row by the off-centre offsets happen close together in time on one XCD.  Slab ids are
+//     2g and 2g + 1 there.  Which sweep a launch takes is decided on the device, from offsets[] and bounds[].
 //   * grid.y tiles the (Cin, Cout) plane in CIT x COT blocks; 4 waves = 2 x 2 sub-tiles.
 //
 // Reference semantics: warpconvnet/nn/functional/sparse_conv/detail/explicit.py:93-97; role of
 // _C.mask_gemm.wgrad (warpconvnet/csrc/bindings/mask_gemm_bindings.cu:2103-2116, split-K atomics there).
 #include "wcn_common.h"
+#include "wgrad_plan.h"
+
+#include <cstdlib>
+#include <cstring>
 
 namespace wcn {
 
@@ -27,7 +35,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kWgradGrid = 512;   // G: pair ranges (2 workgroups per CU) - the upper bound, see wgrad_ranges()
 constexpr int kPairs = 64;        // pairs per pipeline step
-constexpr int kZeroPage = 1024;   // bytes reserved at the start of the workspace (kept for layout compatibility)
+constexpr int kZeroPage = 1024;   // bytes in front of the slabs in the workspace; word 0: which sweep the launch took
 __device__ uint4 g_wgrad_zero_page[64];  // 1 KiB of zeros: source rows of padded pairs (no per-call memset)
 
 template <typename T> struct WFrag;
@@ -104,6 +112,27 @@ struct Wgrad {
   static_assert(X_UNITS % 4 == 0 && Y_UNITS % 4 == 0, "every wave must issue the same number of DMA instructions");
 };
 
+// The rule of the team sweep (wgrad_plan.h), both parts, by a whole workgroup of 256 threads - every workgroup of
+// wgrad_mfma_kernel calls this on the same operands, the reduce kernel reads what they found.  Thread t evaluates the own ranges of the plan's workgroups t and t + 256 (`o0`, `o1`: their
+// steps; `own_total`: the steps of all own ranges); the level condition is one vote.  `s_wave`: 4 ints of LDS.
+__device__ __forceinline__ bool wgrad_team_rule_block(const int32_t* __restrict__ offsets, const int32_t* __restrict__ bounds,
+                                                      int K, int G, int tiles, int mode, int* s_wave, int& o0, int& o1,
+                                                      int& own_total) {
+  static_assert(kPlanGrid == 2 * 256, "two workgroups of the plan per thread");
+  o0 = o1 = own_total = 0;
+  if (!wgrad_team_rule(offsets, bounds, K, G, tiles, mode)) return false;  // (uniform)
+  const int tid = threadIdx.x;
+  const int64_t centre = (int64_t)offsets[K / 2 + 1] - offsets[K / 2];
+  o0 = (int)wgrad_own_steps(offsets, bounds, K, tid);
+  o1 = (int)wgrad_own_steps(offsets, bounds, K, tid + 256);
+  block_excl_scan<256>(o0 + o1, s_wave, &own_total);
+  own_total = __builtin_amdgcn_readfirstlane(own_total);  // (the same in every lane: keep the plan in scalar registers)
+  __syncthreads();
+  if (mode == kTeamsForce) return true;
+  const bool ok = wgrad_level_holds(centre, own_total, o0, G, tid) && wgrad_level_holds(centre, own_total, o1, G, tid + 256);
+  return __syncthreads_and(ok) != 0;
+}
+
 // Pipeline (per 64-pair step i of a segment; every wave issues the same instruction counts so the counted
 // vmcnt below means the same thing in all waves):
 //   A  index DMA for step i+3   (2 instructions: 16 in-rows + 16 out-rows per wave, 4 B per lane)
@@ -120,7 +149,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const T* __restrict_
                                                          const int32_t* __restrict__ out_maps,
                                                          const int32_t* __restrict__ offsets, int K, int cin, int cout,
                                                          const char* __restrict__ zero_page, float* __restrict__ slabs,
-                                                         float* __restrict__ cs_slabs, int cs_k) {
+                                                         float* __restrict__ cs_slabs, int cs_k,
+                                                         const int32_t* __restrict__ bounds, int teams_mode,
+                                                         int32_t* __restrict__ sweep_word) {
   typedef Wgrad<T, CIT, COT> W;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* s_idx = smem + (size_t)kStages * W::STAGE_BYTES;  // [kIdxSlots][2][64] int32
@@ -129,15 +160,39 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const T* __restrict_
   const int tiles_co = cout / COT;
   const int ci0 = (blockIdx.y / tiles_co) * CIT, co0 = (blockIdx.y % tiles_co) * COT;
 
-  const int64_t L = offsets[K];
-  int64_t Q = (L + G - 1) / G;
-  Q = ((Q + kPairs - 1) / kPairs) * kPairs;
-  const int64_t r_begin = (int64_t)g * Q;
-  const int64_t r_end = (r_begin + Q < L) ? (r_begin + Q) : L;
-  if (r_begin >= r_end) return;
-
-  int k = 0;  // first bucket containing r_begin
-  {
+  // team sweep: up to two segments from the plan (wgrad_plan.h), the sums over all workgroups by block reduction
+  int o0, o1, own_total;
+  const bool team = wgrad_team_rule_block(offsets, bounds, K, G, (int)gridDim.y, teams_mode, reinterpret_cast<int*>(s_idx), o0, o1,
+                                          own_total);  // (the index ring is idle until the first segment's prologue)
+  // the launch's decision, for the reduce kernel behind this one (every workgroup here arrives at the same value; 3 584 reduce
+  // workgroups each loading the rule's 108 words cost 12 us where one word costs nothing)
+  if (g == 0 && blockIdx.y == 0 && tid == 0) *sweep_word = team ? 1 : 0;
+  WgradSeg own, centre_piece;  // (two scalars-only structs, never indexed: an array would live in scratch)
+  int ti = 2;                  // segment of the team sweep: 0 = own range (members), 1 = centre piece
+  int64_t r_begin = 0, r_end = 0;
+  int k = 0;
+  if (team) {
+    static_assert(kPlanStep == kPairs, "the plan counts in pipeline steps");
+    int* s_wave = reinterpret_cast<int*>(s_idx);
+    const int64_t centre = (int64_t)offsets[K / 2 + 1] - offsets[K / 2];
+    int before;
+    const int c0 = tid < g ? (int)wgrad_centre_steps(centre, own_total, o0, G, tid) : 0;
+    const int c1 = tid + 256 < g ? (int)wgrad_centre_steps(centre, own_total, o1, G, tid + 256) : 0;
+    block_excl_scan<256>(c0 + c1, s_wave, &before);
+    before = __builtin_amdgcn_readfirstlane(before);
+    __syncthreads();
+    const bool member = wgrad_own_range(offsets, bounds, K, g, &own);
+    wgrad_centre_piece(offsets, K, before, wgrad_centre_steps(centre, own_total, wgrad_steps(own.end - own.begin), G, g),
+                       &centre_piece);
+    ti = member ? 0 : 1;
+  } else {
+    const int64_t L = offsets[K];
+    int64_t Q = (L + G - 1) / G;
+    Q = ((Q + kPairs - 1) / kPairs) * kPairs;
+    r_begin = (int64_t)g * Q;
+    r_end = (r_begin + Q < L) ? (r_begin + Q) : L;
+    if (r_begin >= r_end) return;
+    // first bucket containing r_begin
     int lo = 0, hi = K;
     while (hi - lo > 1) {
       const int mid = (lo + hi) >> 1;
@@ -163,8 +218,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const T* __restrict_
   };
   const bool cs_tile = CS && (blockIdx.y / tiles_co) == 0;  // one ci tile is enough: the sums do not depend on ci
   const s16x8 ones = ones_row_frag<T>(lane);
-  auto flush = [&](int kk) {
-    float* slab = slabs + (int64_t)(g + kk) * cin * cout;
+  auto flush = [&](int slab_id) {
+    float* slab = slabs + (int64_t)slab_id * cin * cout;
     const int h = lane >> 5, n = lane & 31;
 #pragma unroll
     for (int j = 0; j < W::PER_WAVE; ++j) {
@@ -260,40 +315,53 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const T* __restrict_
   };
 
   int64_t pos = r_begin;
-  while (pos < r_end) {
-    while ((int64_t)offsets[k + 1] <= pos) ++k;  // skip empty buckets
-    const int64_t seg_end = ((int64_t)offsets[k + 1] < r_end) ? (int64_t)offsets[k + 1] : r_end;
+  while (team ? ti < 2 : pos < r_end) {
+    int64_t seg_end;
+    int slab_id;
+    if (team) {  // (an empty segment runs no step and flushes a zero tile: the reduce reads every slab of the plan)
+      k = ti == 0 ? own.k : centre_piece.k;
+      pos = ti == 0 ? own.begin : centre_piece.begin;
+      seg_end = ti == 0 ? own.end : centre_piece.end;
+      slab_id = 2 * g + ti;
+      ++ti;
+    } else {
+      while ((int64_t)offsets[k + 1] <= pos) ++k;  // skip empty buckets
+      seg_end = ((int64_t)offsets[k + 1] < r_end) ? (int64_t)offsets[k + 1] : r_end;
+      slab_id = g + k;
+    }
     const int nsteps = (int)((seg_end - pos + kPairs - 1) / kPairs);
     const bool do_cs = cs_tile && k == cs_k;
     zero_acc();
-    // ---- prologue: indices of steps 0..2, data of steps 0..1 ----
-    dma_idx(0, pos, seg_end);
-    if (nsteps > 1) dma_idx(1, pos, seg_end);
-    if (nsteps > 2) dma_idx(2, pos, seg_end);
-    wait_vmcnt<0>();
-    barrier();
-    dma_data(0, pos, seg_end);
-    if (nsteps > 1) {
-      dma_data(1, pos, seg_end);
-      wait_vmcnt<W::DATA_OPS>();
-    } else {
+    if (nsteps > 0) {
+      // ---- prologue: indices of steps 0..2, data of steps 0..1 ----
+      dma_idx(0, pos, seg_end);
+      if (nsteps > 1) dma_idx(1, pos, seg_end);
+      if (nsteps > 2) dma_idx(2, pos, seg_end);
       wait_vmcnt<0>();
-    }
-    barrier();
-    // ---- steady state ----
-    for (int i = 0; i < nsteps; ++i) {
-      if (i + 3 < nsteps) dma_idx(i + 3, pos, seg_end);
-      const bool more = i + 2 < nsteps;
-      if (more) dma_data(i + 2, pos, seg_end);
-      compute(i, do_cs);
-      if (more) {
+      barrier();
+      dma_data(0, pos, seg_end);
+      if (nsteps > 1) {
+        dma_data(1, pos, seg_end);
         wait_vmcnt<W::DATA_OPS>();
       } else {
         wait_vmcnt<0>();
       }
       barrier();
+      // ---- steady state ----
+      for (int i = 0; i < nsteps; ++i) {
+        if (i + 3 < nsteps) dma_idx(i + 3, pos, seg_end);
+        const bool more = i + 2 < nsteps;
+        if (more) dma_data(i + 2, pos, seg_end);
+        compute(i, do_cs);
+        if (more) {
+          wait_vmcnt<W::DATA_OPS>();
+        } else {
+          wait_vmcnt<0>();
+        }
+        barrier();
+      }
     }
-    flush(k);
+    flush(slab_id);
     if (CS && do_cs && (wave >> 1) == 0 && lane < 32) {  // row 0 of the ones-row product: lanes 0..31, register 0
 #pragma unroll
       for (int b = 0; b < W::NB; ++b)
@@ -309,7 +377,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const T* __restrict_
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slabs,
                                                            const int32_t* __restrict__ offsets, int K, int64_t ce, int G,
                                                            float* __restrict__ dw, const float* __restrict__ cs_slabs,
-                                                           int cs_k, int cout, float* __restrict__ bias_grad) {
+                                                           int cs_k, int cout, float* __restrict__ bias_grad,
+                                                           const int32_t* __restrict__ sweep_word) {
   __shared__ float4 s_part[16][16];
   const int part = threadIdx.x >> 4, el = threadIdx.x & 15;
   const int64_t e = (int64_t)blockIdx.x * 64 + el * 4;
@@ -317,6 +386,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   const int64_t L = offsets[K];
   int64_t Q = (L + G - 1) / G;
   Q = ((Q + kPairs - 1) / kPairs) * kPairs;
+  // team sweep (the word wgrad_mfma_kernel left in front of the slabs: its evaluation of the rule): slab 2g of member g = (t, k)
+  // for an off-centre bucket in ascending t, slab 2g + 1 of every workgroup in ascending g for the centre bucket - all written
+  const bool team = *sweep_word != 0;
   if (k == K) {
     // extra grid row (bias-gradient launches only): bias_grad[co] = sum over the ranges g that intersect bucket cs_k
     // (ascending) of cs_slabs[g][co]; one wavefront per channel - same launch instead of a ~5 us kernel of its own
@@ -324,7 +396,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     if (co >= cout) return;
     const int64_t b = offsets[cs_k], en = offsets[cs_k + 1];
     float s = 0.f;
-    if (en > b && Q > 0) {
+    if (team) {
+      for (int g = lane; g < G; g += 64) s += cs_slabs[(int64_t)g * cout + co];
+    } else if (en > b && Q > 0) {
       const int g_lo = (int)(b / Q), g_hi = (int)((en - 1) / Q);
       for (int g = g_lo + lane; g <= g_hi; g += 64) s += cs_slabs[(int64_t)g * cout + co];
     }
@@ -335,7 +409,27 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
   const int64_t b = offsets[k], en = offsets[k + 1];
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (e < ce && en > b && Q > 0) {
+  if (team) {
+    if (e < ce) {
+      if (k == K / 2) {
+        // 32 slabs per thread where a bucket of the range sweep has one or two: eight loads in flight, then added in order (sixteen measured no better)
+        constexpr int kBatch = 8;
+        for (int g0 = part; g0 < G; g0 += 16 * kBatch) {
+          float4 v[kBatch];
+#pragma unroll
+          for (int j = 0; j < kBatch; ++j) {
+            const int g = g0 + 16 * j;
+            v[j] = g < G ? *reinterpret_cast<const float4*>(slabs + (int64_t)(2 * g + 1) * ce + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+#pragma unroll
+          for (int j = 0; j < kBatch; ++j) { s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w; }
+        }
+      } else {
+        static_assert(kPlanSlabs == 16, "one team per part");
+        s = *reinterpret_cast<const float4*>(slabs + (int64_t)(2 * wgrad_member_g(part, k < K / 2 ? k : k - 1)) * ce + e);
+      }
+    }
+  } else if (e < ce && en > b && Q > 0) {
     const int g_lo = (int)(b / Q), g_hi = (int)((en - 1) / Q);
     for (int g = g_lo + part; g <= g_hi; g += 16) {
       const float4 v = *reinterpret_cast<const float4*>(slabs + (int64_t)(g + k) * ce + e);
@@ -373,9 +467,29 @@ bool mfma_wgrad_bias_supported(int cin, int cout, int dtype) {
   return (wgrad_tile(cin) / 32) % 2 == 0 && (wgrad_tile(cout) / 32) % 2 == 0;  // 2 x 2 wave layout (Wgrad::GRID)
 }
 
+// slabs of a launch: g + k < G + K for the range sweep, 2g + s < 2G for the team sweep
+// (2G only where a launch can take the team sweep - 3 x 3 x 3 and ONE (cin, cout) tile, i.e. at most 128 x 128 floats a slab:
+// 32 MB for 64 -> 128; the wide layers, whose slabs are large, keep G + K)
+static bool wgrad_one_tile(int cin, int cout) {
+  const int cit = wgrad_tile(cin) == 128 ? 64 : wgrad_tile(cin);  // (dispatch_wgrad: 128 input channels run as two 64-wide tiles)
+  return cit == cin && wgrad_tile(cout) == cout;
+}
+static size_t wgrad_slab_count(int K, int cin, int cout) {
+  return (size_t)(K == kPlanK && wgrad_one_tile(cin, cout) ? 2 * kWgradGrid : kWgradGrid + K);
+}
+
 size_t wgrad_mfma_workspace(int K, int cin, int cout) {
   // zero page + weight-gradient slabs + bias-gradient partials
-  return (size_t)kZeroPage + (size_t)(kWgradGrid + K) * cin * cout * sizeof(float) + (size_t)kWgradGrid * cout * sizeof(float);
+  return (size_t)kZeroPage + wgrad_slab_count(K, cin, cout) * cin * cout * sizeof(float) + (size_t)kWgradGrid * cout * sizeof(float);
+}
+
+// WARPCONVNET_AMD_WGRAD_TEAMS = 0 | auto | force: the team sweep never / where the rule of wgrad_plan.h holds / wherever it
+// is defined (tests, A/B runs: the size and balance conditions dropped).  Read at every call: a process may flip it.
+static int wgrad_teams_mode() {
+  const char* e = getenv("WARPCONVNET_AMD_WGRAD_TEAMS");
+  if (!e || !*e || !strcmp(e, "auto")) return kTeamsAuto;
+  if (!strcmp(e, "force")) return kTeamsForce;
+  return kTeamsOff;
 }
 
 // Pair ranges of a launch.  Every range flushes one fp32 [CIT, COT] tile per bucket it touches, and the reduce kernel reads them
@@ -398,7 +512,7 @@ static int wgrad_ranges(int64_t pair_bound, int tiles) {
 template <typename T, int CIT, int COT>
 static int launch_wgrad(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                         const int32_t* offsets, int cin, int cout, int K, void* workspace, int cs_k, float* bias_grad,
-                        int64_t pair_bound, hipStream_t s) {
+                        int64_t pair_bound, const int32_t* bounds, hipStream_t s) {
   typedef Wgrad<T, CIT, COT> W;
   static unsigned long long attr_done = 0ull;  // per device (wcn_common.h)
   const int rc = once_per_device(attr_done, [] {
@@ -424,46 +538,50 @@ static int launch_wgrad(const void* x, const void* dy, float* dw, const int32_t*
     if (dev >= 0 && dev < 64) __atomic_store_n(&zero_pages[dev], zero_page, __ATOMIC_RELAXED);
   }
   float* slabs = (float*)((char*)workspace + kZeroPage);
-  float* cs_slabs = slabs + (size_t)(kWgradGrid + K) * cin * cout;
-  const int G = wgrad_ranges(pair_bound, (cin / CIT) * (cout / COT));
+  float* cs_slabs = slabs + wgrad_slab_count(K, cin, cout) * cin * cout;
+  const int tiles = (cin / CIT) * (cout / COT);
+  // (the fused bias gradient of a team launch rides on the centre pieces: only the centre bucket may be the self bucket)
+  const int teams = (bounds && !(bias_grad && cs_k != K / 2)) ? wgrad_teams_mode() : kTeamsOff;
+  const int G = wgrad_ranges(pair_bound, tiles);  // (one tile: always kWgradGrid, the grid of the team sweep)
   const dim3 grid(G, (cin / CIT) * (cout / COT));
   if (bias_grad) {
     if constexpr (W::GRID) {
       hipLaunchKernelGGL((wgrad_mfma_kernel<T, CIT, COT, true>), grid, dim3(256), W::LDS_BYTES, s, (const T*)x,
                          (const T*)dy, in_maps, out_maps, offsets, K, cin, cout, (const char*)zero_page, slabs, cs_slabs,
-                         cs_k);
+                         cs_k, bounds, teams, (int32_t*)workspace);
     } else {
       return WCN_ERROR_UNSUPPORTED_CONFIG;
     }
   } else {
     hipLaunchKernelGGL((wgrad_mfma_kernel<T, CIT, COT, false>), grid, dim3(256), W::LDS_BYTES, s, (const T*)x,
-                       (const T*)dy, in_maps, out_maps, offsets, K, cin, cout, (const char*)zero_page, slabs, nullptr, -1);
+                       (const T*)dy, in_maps, out_maps, offsets, K, cin, cout, (const char*)zero_page, slabs, nullptr, -1,
+                       bounds, teams, (int32_t*)workspace);
   }
   const int64_t ce = (int64_t)cin * cout;
   // (the row K of the grid, present with a bias gradient, reduces the column-sum partials: 4 channels per workgroup)
   const unsigned gx = (unsigned)ceil_div(ce, 64);
   if (bias_grad && (int64_t)gx * 4 < cout) return WCN_ERROR_UNSUPPORTED_CONFIG;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(gx, bias_grad ? K + 1 : K), dim3(256), 0, s, (const float*)slabs, offsets, K, ce,
-                     G, dw, (const float*)cs_slabs, cs_k, cout, bias_grad);
+                     G, dw, (const float*)cs_slabs, cs_k, cout, bias_grad, (const int32_t*)workspace);
   return launch_status();
 }
 
 template <typename T, int CIT>
 static int dispatch_wgrad_co(int cot, const void* x, const void* dy, float* dw, const int32_t* in_maps,
                              const int32_t* out_maps, const int32_t* offsets, int cin, int cout, int K, void* workspace,
-                             int cs_k, float* bias_grad, int64_t pair_bound, hipStream_t s) {
+                             int cs_k, float* bias_grad, int64_t pair_bound, const int32_t* bounds, hipStream_t s) {
   switch (cot) {
-    case 32: return launch_wgrad<T, CIT, 32>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-    case 64: return launch_wgrad<T, CIT, 64>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-    case 96: return launch_wgrad<T, CIT, 96>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-    default: return launch_wgrad<T, CIT, 128>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
+    case 32: return launch_wgrad<T, CIT, 32>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
+    case 64: return launch_wgrad<T, CIT, 64>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
+    case 96: return launch_wgrad<T, CIT, 96>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
+    default: return launch_wgrad<T, CIT, 128>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
   }
 }
 
 template <typename T>
 static int dispatch_wgrad(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                           const int32_t* offsets, int cin, int cout, int K, void* workspace, int cs_k, float* bias_grad,
-                          int64_t pair_bound, hipStream_t s) {
+                          int64_t pair_bound, const int32_t* bounds, hipStream_t s) {
   const int cot = wgrad_tile(cout);
   int cit = wgrad_tile(cin);
   // 128 input channels: two 64-wide tiles instead of one 128-wide.  dY is then streamed twice (+43 % algorithmic traffic at
@@ -472,22 +590,22 @@ static int dispatch_wgrad(const void* x, const void* dy, float* dw, const int32_
   // 128 -> 128: 50 -> 31 us.
   if (cit == 128) cit = 64;
   switch (cit) {
-    case 32: return dispatch_wgrad_co<T, 32>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-    case 64: return dispatch_wgrad_co<T, 64>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-    case 96: return dispatch_wgrad_co<T, 96>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
-    default: return dispatch_wgrad_co<T, 128>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, s);
+    case 32: return dispatch_wgrad_co<T, 32>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
+    case 64: return dispatch_wgrad_co<T, 64>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
+    case 96: return dispatch_wgrad_co<T, 96>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
+    default: return dispatch_wgrad_co<T, 128>(cot, x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound, bounds, s);
   }
 }
 
 int conv_wgrad_mfma(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                     const int32_t* offsets, int cin, int cout, int K, int dtype, void* workspace, size_t workspace_bytes,
-                    int cs_k, float* bias_grad, int64_t pair_bound, hipStream_t s) {
+                    int cs_k, float* bias_grad, int64_t pair_bound, const int32_t* bounds, hipStream_t s) {
   if (!mfma_wgrad_supported(cin, cout, dtype)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (bias_grad && (!mfma_wgrad_bias_supported(cin, cout, dtype) || cs_k < 0 || cs_k >= K)) return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (!workspace || workspace_bytes < wgrad_mfma_workspace(K, cin, cout)) return WCN_ERROR_INVALID_PARAMETERS;
   return with_dtype16(dtype, [&](auto t) {
     return dispatch_wgrad<decltype(t)>(x, dy, dw, in_maps, out_maps, offsets, cin, cout, K, workspace, cs_k, bias_grad, pair_bound,
-                                       s);
+                                       bounds, s);
   });
 }
 

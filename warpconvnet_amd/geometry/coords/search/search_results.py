@@ -102,6 +102,9 @@ class IntSearchResult:
         self._mask: Optional[Tensor] = None
         self._perm: Optional[Tensor] = None
         self._offsets_dev: Optional[Tensor] = None
+        # int32 [17, K] on the device, submanifold builder only: positions of 16 row slabs inside each (row-ordered) bucket,
+        # kept from the scan of the pair counts - the weight gradient's team sweep (`csrc/wgrad_plan.h`); None = range sweep
+        self._wgrad_bounds: Optional[Tensor] = None
         self._symmetric: bool = False
         self._self_exact: bool = False  # symmetric AND no duplicate coordinates: nbr[r][K//2] == r for every row
         self._has_duplicates: bool = False  # submanifold map over repeated coordinates: dgrad goes through the pair lists

@@ -474,6 +474,9 @@ def generate_kernel_map(
         else:
             result._nbr = b["nbr"]
         result._offsets_dev = b["meta"][: K + 1]
+        # slab bounds of the weight gradient's team sweep: the scan left them behind the counts this build's scatter reads
+        bo = L.wcn_kmap_slab_bounds_offset(M, K) if use_binned else 0
+        result._wgrad_bounds = b["block_counts"][bo : bo + 17 * K] if use_binned else None
         result._hashtable = b["table"]
         result._keepalive = b  # (workspaces the queued kernels still read)
 

@@ -134,12 +134,18 @@ class _ConvBnAct(Function):
             ws_bytes = hip_gemm._wgrad_workspace(K, cin, cout, _lib.WCN_ALGO_MFMA)
             wws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         bws = bn_workspace(cout, dev)
-        _lib.check(L.wcn_conv_bn_backward_ld(
-            _lib.ptr(g), g_ld, _lib.ptr(x), _lib.ptr(y), _lib.ptr(z) if masked else None, int(plan.relu), stats.data_ptr(), _lib.ptr(gamma),
-            int(plan.bn[0]), sums.data_ptr(), _lib.ptr(dyc), _lib.ptr(dres), _lib.ptr(wpd), _lib.ptr(tbl), _lib.ptr(msk),
-            _lib.ptr(perm), int(flip), _lib.ptr(dx), _lib.ptr(km.in_maps_device) if need_dw else None,
-            _lib.ptr(km.out_maps_device) if need_dw else None, _lib.ptr(km._offsets_dev) if need_dw else None, _lib.ptr(dw),
-            _lib.ptr(wws), ws_bytes, plan.num_in, M, cin, cout, K, code, _lib.ptr(bws), bws.numel(), stream), "wcn_conv_bn_backward_ld")
+        # (a map that may take the weight gradient's team sweep hands its slab bounds over, as `hip_gemm.hip_wgrad` does: the
+        # layer computes the same bits through this call and through the passes one by one)
+        bounds = hip_gemm._team_bounds(km, K) if need_dw else None
+        head = (_lib.ptr(g), g_ld, _lib.ptr(x), _lib.ptr(y), _lib.ptr(z) if masked else None, int(plan.relu), stats.data_ptr(),
+                _lib.ptr(gamma), int(plan.bn[0]), sums.data_ptr(), _lib.ptr(dyc), _lib.ptr(dres), _lib.ptr(wpd), _lib.ptr(tbl),
+                _lib.ptr(msk), _lib.ptr(perm), int(flip), _lib.ptr(dx), _lib.ptr(km.in_maps_device) if need_dw else None,
+                _lib.ptr(km.out_maps_device) if need_dw else None, _lib.ptr(km._offsets_dev) if need_dw else None)
+        tail = (_lib.ptr(dw), _lib.ptr(wws), ws_bytes, plan.num_in, M, cin, cout, K, code, _lib.ptr(bws), bws.numel(), stream)
+        if bounds is not None:
+            _lib.check(L.wcn_conv_bn_backward_teams(*head, _lib.ptr(bounds), *tail), "wcn_conv_bn_backward_teams")
+        else:
+            _lib.check(L.wcn_conv_bn_backward_ld(*head, *tail), "wcn_conv_bn_backward_ld")
         if need_dres and not masked:
             dres = g
         if dw is not None and dw.dtype != w.dtype:

@@ -15,6 +15,7 @@ Role of the reference's `_mask_gemm_forward_logic` / `_mask_gemm_backward_logic`
 (`warpconvnet/nn/functional/sparse_conv/detail/mask_gemm.py:661-745, 818-963`).
 """
 import functools
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -486,6 +487,23 @@ def hip_wgrad(in_features: Tensor, grad_output: Tensor, kernel_map: IntSearchRes
     return (dw, db) if want_bias_grad else dw
 
 
+def _team_bounds(kernel_map: IntSearchResult, K: int) -> Optional[Tensor]:
+    """The map's slab bounds where a weight-gradient launch may take the team sweep, else None (the entry points without
+    bounds).  Only what the host knows for free is looked at here - the kernel volume, the pair count, the switch
+    ``WARPCONVNET_AMD_WGRAD_TEAMS`` (0 | auto | force) - the decision itself is the device's (`csrc/wgrad_plan.h`)."""
+    bounds = kernel_map._wgrad_bounds
+    if bounds is None or K != 27:
+        return None
+    # (the library reads the switch itself, with exactly these three spellings; here it only decides whether a small map is
+    # worth the entry point that carries the bounds)
+    mode = os.environ.get("WARPCONVNET_AMD_WGRAD_TEAMS") or "auto"
+    if mode == "force":
+        return bounds
+    if mode != "auto" or int(kernel_map.offsets[-1]) < 512 * 512:
+        return None
+    return bounds
+
+
 def _wgrad_launch(x: Tensor, dy: Tensor, kernel_map: IntSearchResult, K: int, cin: int, cout: int, code: int,
                   out: Optional[Tensor], want_bias_grad: bool):
     """-> (dw fp32 [K, cin, cout], written into ``out`` when given; the fp32 column sums of ``dy`` from the same kernel or None)."""
@@ -499,6 +517,18 @@ def _wgrad_launch(x: Tensor, dy: Tensor, kernel_map: IntSearchResult, K: int, ci
     fuse = (want_bias_grad and code == _lib.WCN_ALGO_MFMA and kernel_map._self_exact
             and x.shape[0] == dy.shape[0] and dy.shape[0] > 0
             and _wgrad_bias_ok(cin, cout, _lib.dtype_code(x.dtype)))
+    bounds = _team_bounds(kernel_map, K) if code == _lib.WCN_ALGO_MFMA else None
+    if bounds is not None:
+        # the map carries the scan's slab bounds: same kernels, and the device may take the team sweep (csrc/wgrad_plan.h)
+        db = torch.empty(cout, dtype=torch.float32, device=dev) if fuse else None
+        _lib.check(
+            L.wcn_conv_wgrad_teams(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(kernel_map.in_maps_device),
+                                   _lib.ptr(kernel_map.out_maps_device), _lib.ptr(kernel_map._offsets_dev), _lib.ptr(bounds),
+                                   x.shape[0], dy.shape[0], cin, cout, K, _lib.dtype_code(x.dtype), K // 2, _lib.ptr(db),
+                                   _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev)),
+            "wcn_conv_wgrad_teams",
+        )
+        return dw, db
     if fuse:
         db = torch.empty(cout, dtype=torch.float32, device=dev)
         _lib.check(
