@@ -892,6 +892,34 @@ int wcn_channel_spread(const void* x, const void* h, int64_t rows, int32_t cx, i
 int wcn_channel_fold(const void* x, const void* h, int64_t rows, int32_t cout, int32_t g, float alpha, int32_t dtype,
                      void* out, wcn_stream_t stream);
 
+/* ---- permuted rows: the attention sub-layer of a serialized-attention block (additions only, ABI unchanged) ----------------
+ * x + drop_path(attn(norm1(x)[perm])[inverse_perm]) around the attention itself, as two row passes (csrc/ln_act.hip).  Rows
+ * are [rows, channels] contiguous in `dtype`, widths and dtypes those of wcn_ln_act_supported; `index` / `inverse` are int64
+ * [rows], a permutation of 0..rows-1 and its inverse.
+ *   wcn_ln_permute_fwd   y[i] = LN(x[index[i]]) * weight + bias (the pair optional, fp32), the arithmetic of wcn_ln_act_fwd
+ *                        with act = 0; stats [rows, 2] fp32 = (mean, rstd) of SOURCE row j = index[i].
+ *   wcn_ln_permute_bwd   dy in output order: for every source row j, i = inverse[j], g = dy[i] * weight,
+ *                        dx[j] = rstd (g - mean_c(g) - xhat mean_c(g xhat)), written once; dweight = sum_j dy[inverse[j]] xhat[j],
+ *                        dbias = sum_j dy[inverse[j]] through the partial slots of wcn_ln_act_bwd (workspace of
+ *                        wcn_ln_act_workspace_bytes; NULL / 0 without weight): no float atomics, bit-identical reruns.
+ *   wcn_permute_add      out[t] = residual[t] + scale[s] * y[index[t]] with s = t, or s = index[t] when `scale_at_source`;
+ *                        `residual` (rows of `dtype`) and `scale` (fp32 [rows]) may each be NULL.  Without scale: one fp32 add
+ *                        per element, rounded once.  The gradient of y is the same call with the inverse index, no residual and
+ *                        scale_at_source = 1; the gradient of residual is dout itself.
+ * Every index is compared as unsigned with `rows` before it forms an address: an entry outside 0..rows-1 gives a row of zeros
+ * (in wcn_ln_permute_bwd: dx[j] = 0 and no contribution to dweight / dbias; in the forward the stats of a source row that no
+ * entry names stay unwritten) and never an out-of-bounds access.
+ * Checks before any launch, as above: width / dtype -> WCN_ERROR_UNSUPPORTED_CONFIG; rows < 0 or > INT32_MAX, weight without
+ * bias, a missing or misaligned pointer, a short workspace, a bad eps, scale_at_source other than 0 / 1 ->
+ * WCN_ERROR_INVALID_PARAMETERS; rows == 0 -> WCN_SUCCESS without a launch. */
+int wcn_ln_permute_fwd(const void* x, const int64_t* index, const float* weight, const float* bias, int64_t rows,
+                       int32_t channels, float eps, int32_t dtype, void* y, float* stats, wcn_stream_t stream);
+int wcn_ln_permute_bwd(const void* dy, const void* x, const int64_t* inverse, const float* weight, const float* stats,
+                       int64_t rows, int32_t channels, int32_t dtype, void* dx, float* dweight, float* dbias, void* workspace,
+                       size_t workspace_bytes, wcn_stream_t stream);
+int wcn_permute_add(const void* y, const int64_t* index, const void* residual, const float* scale, int32_t scale_at_source,
+                    int64_t rows, int32_t channels, int32_t dtype, void* out, wcn_stream_t stream);
+
 /* ---- window grouping of voxels: a deterministic counting sort by 3-D window (ABI 11, additions only) ------------------------
  * The step that turns coordinates into the attention sequences of SpaceAttention (reference: voxel_encode(...,
  * encoding_method="counting_sort"), nn/functional/voxel_encode.py:237-316, on the two kernels of

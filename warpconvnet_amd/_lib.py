@@ -333,6 +333,9 @@ SIGNATURES = {
     "wcn_ln_act_fwd": (c_int, [c_void_p] * 3 + [c_int64, c_int32, ctypes.c_float, c_int32, c_int32, c_void_p, c_void_p,
                                                  c_void_p]),
     "wcn_ln_act_bwd": (c_int, [c_void_p] * 5 + [c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "wcn_ln_permute_fwd": (c_int, [c_void_p] * 4 + [c_int64, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p, c_void_p]),
+    "wcn_ln_permute_bwd": (c_int, [c_void_p] * 5 + [c_int64, c_int32, c_int32] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "wcn_permute_add": (c_int, [c_void_p] * 4 + [c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "wcn_channel_spread": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p,
                                    c_void_p]),
     "wcn_channel_fold": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p, c_void_p]),

@@ -14,6 +14,17 @@
 //     One lane per 8-element piece of an output row, 16-B accesses, where the narrow side's channel count is a multiple of
 //     8 and r / g is 1, 2, 4 or 8 (what halving / doubling widths around a factor-2 resample give; every index into the
 //     lane's registers is then a compile-time constant, so nothing goes to scratch); one lane per output element otherwise.
+//   permuted rows   the attention sub-layer of a serialized-attention block, x + drop_path(attn(norm1(x)[perm])[inverse]), around
+//                   the attention itself: two row passes instead of LayerNorm, two gathers, a mask multiply and an add.
+//     LN + permute  y[i] = LN(x[index[i]]) * weight + bias: the LN forward above with the row read through `index`; stats are
+//                   kept per SOURCE row j = index[i].  The backward is a gather too: lane group u owns the source rows of chunk
+//                   u, reads dy at i = inverse[j], and writes dx[j] once; dweight / dbias go through the same partial slots
+//                   and ln_act_final_kernel.  No float atomics, no zero-filled workspace.
+//     permute + add out[t] = residual[t] + scale * y[index[t]]; `scale` the fp32 per-row stochastic-depth factor, read at t
+//                   (forward) or at index[t] (the backward, which is the same kernel with the inverse index and no residual).
+//     Index guard: an index is an int64 read from memory and compared as unsigned with `rows` before any address is formed
+//     from it ((uint64_t)j < (uint64_t)rows: negative values fail too).  A row whose index fails is written as zeros (in the
+//     LN backward: dx[j] = 0 and nothing is added to the column sums); no load or store ever uses the failed value.
 #include <limits.h>
 
 #include <cmath>
@@ -183,6 +194,200 @@ __global__ __launch_bounds__(kAdaThreads) void ln_act_bwd_kernel(const T* __rest
   }
 }
 
+// ---- LN + permute ---------------------------------------------------------------------------------------------------------
+// y[t] = LN(x[index[t]]) (* weight + bias); stats[index[t]] = (mean, rstd).  The row loop of ln_act_fwd_kernel; `act` is the
+// index guard as well: a lane group whose row has no valid source walks the butterflies on zeros and writes a zero row.
+template <typename T, int NCH, bool AFFINE>
+__global__ __launch_bounds__(kAdaThreads) void ln_permute_fwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ index,
+                                                                     const float* __restrict__ weight,
+                                                                     const float* __restrict__ bias, T* __restrict__ y,
+                                                                     float* __restrict__ stats, const LnGeom g) {
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
+  const float fc = (float)C;
+
+  for (int64_t t0 = 0; t0 < g.rows; t0 += g.units) {
+    const int64_t t = t0 + l.unit;
+    const bool live = t < g.rows;
+    const int64_t j = live ? index[t] : -1;  // the same in every lane of the group
+    const bool act = (uint64_t)j < (uint64_t)g.rows;
+    float f[NCH][8];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
+        ld_vec(x + j * C + c * 8, f[k]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += f[k][e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[k][e] = 0.f;
+      }
+    }
+    const float mean = row_mean(s, g.glog, fc);
+    float sd = 0.f, ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const bool m = act && l.gl + k * l.G < l.nvec;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) row_dev(&f[k][e], m, mean, sd, ss);
+    }
+    const RowStats st = row_stats(mean, sd, ss, g.glog, fc, g.eps);
+    if (act && l.gl == 0) row_stats_st(stats, j, st);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = l.gl + k * l.G;
+      if (live && c < l.nvec) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f[k][e] - st.delta) * st.rstd;
+        if constexpr (AFFINE) {
+          float w[8], b[8];
+          ld_vec(weight + c * 8, w);
+          ld_vec(bias + c * 8, b);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = o[e] * w[e] + b[e];
+        }
+        if (!act) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = 0.f;
+        }
+        st_vec(y + t * C + c * 8, o);
+      }
+    }
+  }
+}
+
+// Lane group u owns the source rows j of chunk u: dy is read at i = inverse[j], x and stats at j, dx[j] written once.
+// partial [units][2][C] as in ln_act_bwd_kernel.
+template <typename T, int NCH, bool AFFINE>
+__global__ __launch_bounds__(kAdaThreads) void ln_permute_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                     const int64_t* __restrict__ inverse,
+                                                                     const float* __restrict__ weight,
+                                                                     const float* __restrict__ stats, T* __restrict__ dx,
+                                                                     float* __restrict__ partial, const LnGeom g) {
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
+  const float inv_c = 1.0f / (float)C;
+  const bool live = l.unit < g.units;
+
+  float a_w[AFFINE ? NCH : 1][8], a_b[AFFINE ? NCH : 1][8];
+  if constexpr (AFFINE) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { a_w[k][e] = 0.f; a_b[k][e] = 0.f; }
+  }
+
+#pragma unroll 1
+  for (int r = 0; r < kAdaChunk; ++r) {
+    const int64_t j = l.unit * kAdaChunk + r;
+    const bool row = live && j < g.rows;
+    const int64_t i = row ? inverse[j] : -1;
+    const bool act = (uint64_t)i < (uint64_t)g.rows;
+    float gd[NCH][8], xh[NCH][8];  // g * weight; xhat
+    float mean = 0.f, rstd = 0.f, s1 = 0.f, s2 = 0.f;
+    if (act) row_stats_ld(stats, j, mean, rstd);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = l.gl + k * l.G;
+      if (act && c < l.nvec) {
+        float xv[8], w[8];
+        ld_vec(dy + i * C + c * 8, gd[k]);
+        ld_vec(x + j * C + c * 8, xv);
+        if constexpr (AFFINE) ld_vec(weight + c * 8, w);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float d = gd[k][e];
+          xh[k][e] = row_xhat(xv[e], mean, rstd);
+          if constexpr (AFFINE) {
+            a_b[k][e] += d;
+            a_w[k][e] += d * xh[k][e];
+            d *= w[e];
+          }
+          gd[k][e] = d;
+          s1 += d;
+          s2 += d * xh[k][e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { gd[k][e] = 0.f; xh[k][e] = 0.f; }
+      }
+    }
+    s1 = row_mean_rcp(s1, g.glog, inv_c);
+    s2 = row_mean_rcp(s2, g.glog, inv_c);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = l.gl + k * l.G;
+      if (row && c < l.nvec) {  // without a valid i: gd = xh = 0 and rstd = 0, a row of zeros
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = row_dx(rstd, gd[k][e], xh[k][e], s1, s2);
+        st_vec(dx + j * C + c * 8, o);
+      }
+    }
+  }
+  if constexpr (AFFINE) {
+    if (live) {
+      float* p = partial + l.unit * 2 * (int64_t)C;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        const int c = l.gl + k * l.G;
+        if (c < l.nvec) {
+          st_vec(p + c * 8, a_w[k]);
+          st_vec(p + C + c * 8, a_b[k]);
+        }
+      }
+    }
+  }
+}
+
+// ---- permute + add --------------------------------------------------------------------------------------------------------
+// out[t] = residual[t] + scale * y[index[t]]: one lane per 8-element piece, G lanes side by side on a row.  `residual` may be
+// NULL; SCALED = false is one fp32 add per element.  scale is read at t, or at index[t] with scale_at_source.
+struct PermGeom {
+  int64_t rows;
+  int64_t units;
+  int channels, glog;
+  int scale_at_source;
+};
+
+template <typename T, bool SCALED>
+__global__ __launch_bounds__(kAdaThreads) void permute_add_kernel(const T* __restrict__ y, const int64_t* __restrict__ index,
+                                                                  const T* __restrict__ residual,
+                                                                  const float* __restrict__ scale, T* __restrict__ out,
+                                                                  const PermGeom g) {
+  const RowLane l = row_lane(g.glog, g.channels);
+  const int C = g.channels;
+  for (int64_t t = l.unit; t < g.rows; t += g.units) {
+    const int64_t i = index[t];
+    const bool ok = (uint64_t)i < (uint64_t)g.rows;
+    float sc = 1.f;
+    if constexpr (SCALED) sc = ok ? scale[g.scale_at_source ? i : t] : 0.f;
+    for (int p = l.gl; p < l.nvec; p += l.G) {
+      float o[8];
+      if (ok) {
+        ld_vec(y + i * C + p * 8, o);
+        if constexpr (SCALED) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] *= sc;
+        }
+        if (residual != nullptr) {  // the same in every lane
+          float rv[8];
+          ld_vec(residual + t * C + p * 8, rv);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = rv[e] + o[e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = 0.f;
+      }
+      st_vec(out + t * C + p * 8, o);
+    }
+  }
+}
+
 // second level of the column sums: 32 columns x 32 slot slices per workgroup, one of the two sums each; both levels in a
 // fixed order
 constexpr int kLnFinalSlices = 32;
@@ -330,6 +535,41 @@ static int ln_bwd_t(const void* dy, const void* x, const float* weight, const fl
   return launch_status();
 }
 
+template <typename T, bool AFFINE>
+static int ln_perm_fwd_t(const void* x, const int64_t* index, const float* weight, const float* bias, void* y, float* stats,
+                         LnGeom g, hipStream_t s) {
+  const unsigned blocks = row_fwd_grid(g.rows, g.glog, &g.units);
+  row_with_nch(g.channels, g.glog, [&](auto nch) {
+    hipLaunchKernelGGL((ln_permute_fwd_kernel<T, nch(), AFFINE>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)x, index,
+                       weight, bias, (T*)y, stats, g);
+  });
+  return launch_status();
+}
+
+template <typename T, bool AFFINE>
+static int ln_perm_bwd_t(const void* dy, const void* x, const int64_t* inverse, const float* weight, const float* stats,
+                         void* dx, float* partial, LnGeom g, hipStream_t s) {
+  const unsigned blocks = row_bwd_grid(g.rows, g.glog, &g.units);
+  row_with_nch(g.channels, g.glog, [&](auto nch) {
+    hipLaunchKernelGGL((ln_permute_bwd_kernel<T, nch(), AFFINE>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)dy,
+                       (const T*)x, inverse, weight, stats, (T*)dx, partial, g);
+  });
+  return launch_status();
+}
+
+template <typename T>
+static int permute_add_t(const void* y, const int64_t* index, const void* residual, const float* scale, void* out, PermGeom g,
+                         hipStream_t s) {
+  const unsigned blocks = row_fwd_grid(g.rows, g.glog, &g.units);
+  if (scale != nullptr)
+    hipLaunchKernelGGL((permute_add_kernel<T, true>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)y, index,
+                       (const T*)residual, scale, (T*)out, g);
+  else
+    hipLaunchKernelGGL((permute_add_kernel<T, false>), dim3(blocks), dim3(kAdaThreads), 0, s, (const T*)y, index,
+                       (const T*)residual, scale, (T*)out, g);
+  return launch_status();
+}
+
 // the four uses of one dtype
 #define WCN_LN_USES(FN, T, ...)                                                                \
   (affine ? (act ? FN<T, true, true>(__VA_ARGS__) : FN<T, true, false>(__VA_ARGS__))           \
@@ -438,6 +678,77 @@ int wcn_ln_act_bwd(const void* dy, const void* x, const float* weight, const flo
   hipLaunchKernelGGL(ln_act_final_kernel, dim3((unsigned)ceil_div(channels, 32), 2), dim3(32 * kLnFinalSlices), 0, s,
                      (const float*)partial, ceil_div(rows, kAdaChunk), channels, dweight, dbias);
   return launch_status();
+}
+
+int wcn_ln_permute_fwd(const void* x, const int64_t* index, const float* weight, const float* bias, int64_t rows,
+                       int32_t channels, float eps, int32_t dtype, void* y, float* stats, wcn_stream_t stream) {
+  int st = ln_check(rows, channels, dtype, 0, weight, bias);
+  if ((st == WCN_SUCCESS || st == 1) && !(eps >= 0.f && std::isfinite(eps))) st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!x || !index || !y || !stats) st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!aligned_to(x, 16) || !aligned_to(index, 8) || !aligned_to(weight, 16) || !aligned_to(bias, 16) ||
+             !aligned_to(y, 16) || !aligned_to(stats, 8))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
+  const LnGeom g = ln_geom(rows, channels, eps);
+  return with_dtype(dtype, [&](auto el) {
+    using T = decltype(el);
+    return weight != nullptr ? ln_perm_fwd_t<T, true>(x, index, weight, bias, y, stats, g, (hipStream_t)stream)
+                             : ln_perm_fwd_t<T, false>(x, index, weight, bias, y, stats, g, (hipStream_t)stream);
+  });
+}
+
+int wcn_ln_permute_bwd(const void* dy, const void* x, const int64_t* inverse, const float* weight, const float* stats,
+                       int64_t rows, int32_t channels, int32_t dtype, void* dx, float* dweight, float* dbias, void* workspace,
+                       size_t workspace_bytes, wcn_stream_t stream) {
+  const bool affine = weight != nullptr;
+  int st = ln_check(rows, channels, dtype, 0, weight, weight);
+  if ((st == WCN_SUCCESS || st == 1) && affine && workspace_bytes < wcn_ln_act_workspace_bytes(rows, channels))
+    st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!dy || !x || !inverse || !stats || !dx || (affine && (!dweight || !dbias || !workspace)))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!aligned_to(dy, 16) || !aligned_to(x, 16) || !aligned_to(inverse, 8) || !aligned_to(weight, 16) ||
+             !aligned_to(stats, 8) || !aligned_to(dx, 16) || !aligned_to(dweight, 4) || !aligned_to(dbias, 4) ||
+             (affine && !aligned_to(workspace, 16)))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
+  hipStream_t s = (hipStream_t)stream;
+  const LnGeom g = ln_geom(rows, channels, 0.f);
+  float* partial = affine ? (float*)workspace : nullptr;
+  st = with_dtype(dtype, [&](auto el) {
+    using T = decltype(el);
+    return affine ? ln_perm_bwd_t<T, true>(dy, x, inverse, weight, stats, dx, partial, g, s)
+                  : ln_perm_bwd_t<T, false>(dy, x, inverse, weight, stats, dx, partial, g, s);
+  });
+  if (st != WCN_SUCCESS || !affine) return st;
+  hipLaunchKernelGGL(ln_act_final_kernel, dim3((unsigned)ceil_div(channels, 32), 2), dim3(32 * kLnFinalSlices), 0, s,
+                     (const float*)partial, ceil_div(rows, kAdaChunk), channels, dweight, dbias);
+  return launch_status();
+}
+
+int wcn_permute_add(const void* y, const int64_t* index, const void* residual, const float* scale, int32_t scale_at_source,
+                    int64_t rows, int32_t channels, int32_t dtype, void* out, wcn_stream_t stream) {
+  int st = ln_check(rows, channels, dtype, 0, nullptr, nullptr);
+  if ((st == WCN_SUCCESS || st == 1) && scale_at_source != 0 && scale_at_source != 1) st = WCN_ERROR_INVALID_PARAMETERS;
+  if (st == WCN_SUCCESS) {
+    if (!y || !index || !out) st = WCN_ERROR_INVALID_PARAMETERS;
+    else if (!aligned_to(y, 16) || !aligned_to(index, 8) || !aligned_to(residual, 16) || !aligned_to(scale, 4) ||
+             !aligned_to(out, 16))
+      st = WCN_ERROR_INVALID_PARAMETERS;
+  }
+  if (st != WCN_SUCCESS) return st == 1 ? WCN_SUCCESS : st;
+  PermGeom g;
+  g.rows = rows;
+  g.units = 0;
+  g.channels = channels;
+  g.glog = row_glog(channels / 8);
+  g.scale_at_source = scale_at_source;
+  return with_dtype(dtype, [&](auto el) {
+    return permute_add_t<decltype(el)>(y, index, residual, scale, out, g, (hipStream_t)stream);
+  });
 }
 
 int wcn_channel_spread(const void* x, const void* h, int64_t rows, int32_t cx, int32_t r, float alpha, int32_t dtype,

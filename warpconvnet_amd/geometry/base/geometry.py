@@ -136,7 +136,12 @@ class Geometry:
         feats = batched_features if batched_features is not None else self.batched_features
         if isinstance(feats, Tensor):
             feats = to_batched_features(feats, coords.offsets)
-        return self.__class__(coords, feats, **{**self._extra_attributes, **kwargs})
+        extra = self._extra_attributes
+        if batched_coordinates is not None and batched_coordinates is not self.batched_coordinates:
+            # other coordinates (pooling, pruning, resampling): what the spatial cache holds - window groupings, curve
+            # serializations - describes the rows of the old ones
+            extra = {k: v for k, v in extra.items() if k != "_spatial_cache"}
+        return self.__class__(coords, feats, **{**extra, **kwargs})
 
     def replace_features(self, new_features) -> "Geometry":
         return self.replace(batched_features=new_features)

@@ -79,7 +79,9 @@ class Voxels(Geometry):
         idx, offsets = voxel_downsample_random_indices(self.coordinate_tensor, self.offsets)
         coords = IntCoords(self.coordinate_tensor[idx], offsets, tensor_stride=self.tensor_stride)
         feats = CatFeatures(self.batched_features.batched_tensor[idx], offsets)
-        return self.__class__(coords, feats, **self.extra_attributes)
+        kwargs = self.extra_attributes
+        kwargs.pop("_spatial_cache", None)  # groupings and serializations of the rows before de-duplication
+        return self.__class__(coords, feats, **kwargs)
 
     def sort(self, ordering="morton_xyz") -> "Voxels":
         """Rows of every batch element in space-filling-curve order (reference `types/voxels.py:248-269`); the

@@ -2,7 +2,7 @@ from .attention import (Attention, BatchedLinear, FeedForward, GeometryToPaddedB
                         PatchAttention, SpatialFeatureAttention, TransformerBlock, ZeroOutPoints)
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
-from .activations import DropPath, ReLU
+from .activations import GELU, DropPath, ReLU
 from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool,
                           FactorGridProjection, FactorGridToPoint, FactorGridTransform, PointToFactorGrid)
 from .grid_conv import GridConv
@@ -14,7 +14,7 @@ from .permutohedral import (BilateralPermutohedralFilter, BilateralPermutohedral
 from .point_conv import PointConv
 from .prune import SparsePrune
 from .rope import VoxelRotaryPositionalEmbeddings, suggest_voxel_rope_base
-from .sequential import Sequential
+from .sequential import Sequential, TupleSequential
 from .sparse_attention import SparseMultiHeadAttention, SparseMultiHeadCrossAttention, SparseRotaryPositionEmbedder
 from .sparse_dit import ModulatedSparseTransformerBlock, ModulatedSparseTransformerCrossBlock, SparseFeedForwardNet
 from .sparse_convnext import SparseConvNeXtBlock3d
@@ -44,4 +44,5 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",
            "FastBilateralSolver",
            "FactorGridCat", "FactorGridIntraCommunication", "FactorGridPadToMatch", "FactorGridPool", "FactorGridToPoint",
-           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "GridConv", "SegmentedLayerNorm"]
+           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "GridConv", "SegmentedLayerNorm", "GELU",
+           "TupleSequential"]

@@ -1,4 +1,4 @@
-"""ReLU and stochastic depth over ``Geometry`` features (reference `nn/modules/activations.py:36-53, 113-166`)."""
+"""ReLU, GELU and stochastic depth over ``Geometry`` features (reference `nn/modules/activations.py:36-53, 113-166`)."""
 from typing import Union
 
 from torch import Tensor, nn
@@ -6,7 +6,7 @@ from torch import Tensor, nn
 from warpconvnet_amd.geometry.base.geometry import Geometry
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 
-__all__ = ["ReLU", "DropPath", "drop_path"]
+__all__ = ["ReLU", "GELU", "DropPath", "drop_path"]
 
 
 def drop_path(x: Tensor, drop_prob: float = 0.0, training: bool = False, scale_by_keep: bool = True) -> Tensor:
@@ -50,3 +50,16 @@ class ReLU(BaseSpatialModule):
         if isinstance(input, Geometry):
             return input.replace(batched_features=self.relu(input.feature_tensor))
         return self.relu(input)
+
+
+class GELU(BaseSpatialModule):
+    """``nn.GELU`` over ``Geometry`` features."""
+
+    def __init__(self, approximate: str = "none"):
+        super().__init__()
+        self.gelu = nn.GELU(approximate=approximate)
+
+    def forward(self, input: Union[Geometry, Tensor]):
+        if isinstance(input, Geometry):
+            return input.replace(batched_features=self.gelu(input.feature_tensor))
+        return self.gelu(input)

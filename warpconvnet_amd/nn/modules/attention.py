@@ -21,7 +21,8 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from warpconvnet_amd.geometry.base.geometry import Geometry
-from warpconvnet_amd.geometry.coords.ops.serialization import POINT_ORDERING, encode, to_point_ordering
+from warpconvnet_amd.geometry.coords.ops.serialization import (POINT_ORDERING, SerializationResult, encode,
+                                                                to_point_ordering)
 from warpconvnet_amd.geometry.features.ops.convert import cat_to_pad_tensor, pad_to_cat_tensor
 from warpconvnet_amd.nn.encodings import SinusoidalEncoding
 from warpconvnet_amd.nn.functional.attention import (flash_attn_varlen_qkvpacked, patch_cu_seqlens,
@@ -98,33 +99,50 @@ class PatchAttention(BaseSpatialModule):
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop)
 
+    def serialization(self, x: Geometry, order: POINT_ORDERING) -> Optional[SerializationResult]:
+        """The permutation that puts the rows of ``x`` in ``order`` (and its inverse); None where ``x`` is in that order
+        already.  It depends on the coordinates alone, so it is kept in the geometry's spatial cache, which every geometry
+        made from ``x`` with ``replace`` shares: the blocks of a level encode once per order.  ``RANDOM`` draws a new
+        permutation every time and is never cached."""
+        if getattr(x, "ordering", None) == order:
+            return None
+        cache = getattr(x, "spatial_cache", None)
+        if cache is None or order == POINT_ORDERING.RANDOM:
+            return encode(x.coordinate_tensor, batch_offsets=x.offsets, order=order, return_perm=True, return_inverse=True)
+        key = ("serialization", order.value)
+        res = cache.get(key)
+        if res is None:
+            res = cache[key] = encode(x.coordinate_tensor, batch_offsets=x.offsets, order=order, return_perm=True,
+                                      return_inverse=True)
+        return res
+
+    def forward_ordered(self, feats: Tensor, offsets: Tensor) -> Tensor:
+        """qkv, the attention inside patches of consecutive rows, and the projection on rows [M, C] that are in curve order
+        already (batch element b = rows ``offsets[b] : offsets[b + 1]``); the result is in the same order."""
+        m, c = feats.shape[:2]
+        qkv = self.qkv(feats).reshape(m, 3, self.num_heads, c // self.num_heads)
+        cu = patch_cu_seqlens(offsets, self.patch_size).to(torch.int32)
+        if not qkv.is_cuda:  # CPU tensors: the per-sequence torch reference in the features' precision (no fp16 cast)
+            out, _ = varlen_attention_reference(qkv, cu, self.scale,
+                                                dtype=torch.float64 if qkv.dtype == torch.float64 else torch.float32)
+            return self.proj_drop(self.proj(out.reshape(m, c).to(feats.dtype)))
+        if qkv.dtype not in (torch.float16, torch.bfloat16):
+            qkv = qkv.to(torch.float16)
+        out = flash_attn_varlen_qkvpacked(qkv, cu, max_seqlen=self.patch_size, dropout_p=0.0, softmax_scale=self.scale)
+        out = self.proj(out.reshape(m, c).to(feats.dtype))
+        return self.proj_drop(out)
+
     def forward(self, x: Geometry, order: Optional[POINT_ORDERING] = None) -> Geometry:
         if self.training and self.attn_drop_p > 0.0:
             raise NotImplementedError("PatchAttention: attention dropout (attn_drop > 0 while training) is not implemented")
         order = to_point_ordering(order or self.order)
         feats = x.feature_tensor
-        m, c = feats.shape[:2]
-        inverse_perm = None
-        if getattr(x, "ordering", None) != order:
-            res = encode(x.coordinate_tensor, batch_offsets=x.offsets, order=order, return_perm=True, return_inverse=True)
+        res = self.serialization(x, order)
+        if res is not None:
             feats = feats[res.perm]
-            inverse_perm = res.inverse_perm
-        qkv = self.qkv(feats).reshape(m, 3, self.num_heads, c // self.num_heads)
-        cu = patch_cu_seqlens(x.offsets, self.patch_size).to(torch.int32)
-        if not qkv.is_cuda:  # CPU tensors: the per-sequence torch reference in the features' precision (no fp16 cast)
-            out, _ = varlen_attention_reference(qkv, cu, self.scale,
-                                                dtype=torch.float64 if qkv.dtype == torch.float64 else torch.float32)
-            out = self.proj_drop(self.proj(out.reshape(m, c).to(feats.dtype)))
-            if inverse_perm is not None:
-                out = out[inverse_perm]
-            return x.replace(batched_features=out.to(feats.dtype))
-        if qkv.dtype not in (torch.float16, torch.bfloat16):
-            qkv = qkv.to(torch.float16)
-        out = flash_attn_varlen_qkvpacked(qkv, cu, max_seqlen=self.patch_size, dropout_p=0.0, softmax_scale=self.scale)
-        out = self.proj(out.reshape(m, c).to(feats.dtype))
-        out = self.proj_drop(out)
-        if inverse_perm is not None:
-            out = out[inverse_perm]
+        out = self.forward_ordered(feats, x.offsets)
+        if res is not None:
+            out = out[res.inverse_perm]
         return x.replace(batched_features=out.to(feats.dtype))
 
 

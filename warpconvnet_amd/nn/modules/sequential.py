@@ -2,7 +2,10 @@
 
 Reference: `warpconvnet/nn/modules/sequential.py:14-62`: a plain ``nn.Module`` receives the feature tensor,
 a spatial module receives the geometry; consecutive plain layers do not rebuild the geometry in between.
+``TupleSequential`` (reference `:67-91`) hands the further inputs of its call to the one layer ``tuple_layer`` names.
 """
+from typing import Sequence
+
 import torch
 import torch.nn as nn
 
@@ -65,6 +68,36 @@ class Sequential(nn.Sequential, BaseSpatialModule):
                     carrier, x = x, module(x.feature_tensor)
             else:
                 x = module(carrier.replace(batched_features=x)) if spatial else module(x)
+        if isinstance(x, torch.Tensor):
+            x = carrier.replace(batched_features=x)
+        return x
+
+
+class TupleSequential(Sequential):
+    """``Sequential`` called with several inputs: the first one runs through the layers, the others go, behind it, to layer
+    number ``tuple_layer`` alone (an unpooling layer that needs the skip geometry).  The layers run one by one through
+    ``module(...)``: none of the fused pairs of ``Sequential``."""
+
+    def __init__(self, *args, tuple_layer: int):
+        if len(args) == 1 and isinstance(args[0], Sequence):
+            super().__init__(*args[0])
+        else:
+            super().__init__(*args)
+        self.tuple_layer = tuple_layer
+
+    def forward(self, *xs):
+        x = carrier = xs[0]
+        assert isinstance(x, Geometry), f"Expected a Geometry, got {type(x)}"
+        for i, module in enumerate(self):
+            rest = xs[1:] if i == self.tuple_layer else ()
+            spatial = isinstance(module, BaseSpatialModule)
+            if isinstance(x, Geometry):
+                if spatial:
+                    x = module(x, *rest)
+                else:
+                    carrier, x = x, module(x.feature_tensor, *rest)
+            else:
+                x = module(carrier.replace(batched_features=x), *rest) if spatial else module(x, *rest)
         if isinstance(x, torch.Tensor):
             x = carrier.replace(batched_features=x)
         return x
