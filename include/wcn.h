@@ -1434,6 +1434,39 @@ int wcn_attn_varlen_kv_bwd_s(const void* dout, const void* q, int64_t q_stride, 
                              void* dv, int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace,
                              size_t workspace_bytes, int32_t variant, wcn_stream_t stream);
 
+/* ---- dense 3-D brick convolution (csrc/dense_conv3d.hip; additions only, wcn_abi_version() stays 18) ------------------------
+ * nn.Conv3d with kernel `ks` = 3 (padding 1) or 1, stride 1, on channels-last cubes: x [batch, D, H, W, cin], y
+ * [batch, D, H, W, cout], all tensors of one `dtype` (f32 / f16 / bf16), fp32 accumulation, no float atomics (the same call
+ * gives the same bits).  `w` / `dw` have nn.Conv3d's layout [cout, cin, ks, ks, ks], `bias` / `dbias` [cout].
+ *   wcn_dense_conv3d_supported    host-only: ks in {1, 3}, a dtype above, 1 <= cin, cout <= 8192.
+ *   wcn_dense_conv3d_packed_bytes host-only: size of the weight image (0 for an unsupported shape).
+ *   wcn_dense_conv3d_pack         w -> image.  dgrad = 0: the forward's.  dgrad = 1: offsets reversed, channels transposed -
+ *                                 the image with which wcn_dense_conv3d(dy, ..., cin = cout, cout = cin) is the input gradient.
+ *   wcn_dense_conv3d              y = conv(x) + bias + residual, formed exactly and rounded once to fp32 and once to `dtype`;
+ *                                 `bias`, `residual` (the shape of y, not aliasing it) may be NULL.  pixel_shuffle = 2 (cout a
+ *                                 multiple of 8): channel c * 8 + (sd * 4 + sh * 2 + sw) of voxel (d, h, w) is stored as
+ *                                 channel c of voxel (2d + sd, 2h + sh, 2w + sw) of y [batch, 2D, 2H, 2W, cout / 8]; 1: none.
+ *   wcn_dense_conv3d_wgrad_slabs  host-only: the slab count `slabs` = 0 stands for - a function of the shape alone.
+ *   wcn_dense_conv3d_wgrad_workspace  host-only: bytes for `slabs` (as resolved, >= 1) slabs.
+ *   wcn_dense_conv3d_wgrad        dw[co, ci, delta] = sum_v x[v + delta - pad, ci] * dy[v, co] (x zero outside the volume) and,
+ *                                 with `dbias`, dbias[co] = sum_v dy[v, co]: fp32 partials per slab of voxels, added in slab
+ *                                 order, rounded once to `dtype`.  slabs in 0..256; `workspace` 256-B aligned.
+ * A call without voxels (batch, D, H or W zero) launches nothing and writes nothing.  Bad arguments come back before any launch:
+ * sizes below the above, a pixel_shuffle other than 1 / 2, missing or misaligned pointers, short buffers ->
+ * WCN_ERROR_INVALID_PARAMETERS; another ks, dtype or channel count -> WCN_ERROR_UNSUPPORTED_CONFIG. */
+int wcn_dense_conv3d_supported(int32_t cin, int32_t cout, int32_t ks, int32_t dtype);
+size_t wcn_dense_conv3d_packed_bytes(int32_t cin, int32_t cout, int32_t ks, int32_t dtype, int32_t dgrad);
+int wcn_dense_conv3d_pack(const void* w, int32_t cin, int32_t cout, int32_t ks, int32_t dtype, int32_t dgrad, void* packed,
+                          size_t packed_bytes, wcn_stream_t stream);
+int wcn_dense_conv3d(const void* x, const void* packed, const void* bias, const void* residual, void* y, int64_t batch,
+                     int32_t D, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t ks, int32_t pixel_shuffle,
+                     int32_t dtype, wcn_stream_t stream);
+int32_t wcn_dense_conv3d_wgrad_slabs(int64_t voxels, int32_t cin, int32_t cout, int32_t ks, int32_t dtype);
+size_t wcn_dense_conv3d_wgrad_workspace(int32_t cin, int32_t cout, int32_t ks, int32_t slabs);
+int wcn_dense_conv3d_wgrad(const void* x, const void* dy, int64_t batch, int32_t D, int32_t H, int32_t W, int32_t cin,
+                           int32_t cout, int32_t ks, int32_t dtype, int32_t slabs, void* dw, void* dbias, void* workspace,
+                           size_t workspace_bytes, wcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -452,6 +452,13 @@ SIGNATURES = {
                                                                          c_void_p]),
     "wcn_edgeconv_backward_input": (c_int, _EC_LISTS + [c_void_p] * 3 + [c_void_p] * 6 +
                                     [ctypes.c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wcn_dense_conv3d_supported": (c_int, [c_int32] * 4),
+    "wcn_dense_conv3d_packed_bytes": (c_size_t, [c_int32] * 5),
+    "wcn_dense_conv3d_pack": (c_int, [c_void_p] + [c_int32] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "wcn_dense_conv3d": (c_int, [c_void_p] * 5 + [c_int64] + [c_int32] * 8 + [c_void_p]),
+    "wcn_dense_conv3d_wgrad_slabs": (c_int32, [c_int64] + [c_int32] * 4),
+    "wcn_dense_conv3d_wgrad_workspace": (c_size_t, [c_int32] * 4),
+    "wcn_dense_conv3d_wgrad": (c_int, [c_void_p, c_void_p, c_int64] + [c_int32] * 8 + [c_void_p] * 3 + [c_size_t, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

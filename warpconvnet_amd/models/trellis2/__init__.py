@@ -4,7 +4,8 @@ from .mesh_extract import MeshOut, extract_meshes
 from .shape_vae import (FlexiDualGridVaeDecoder, FlexiDualGridVaeEncoder, SparseResBlockC2S3d, SparseResBlockS2C3d,
                         SparseUnetVaeDecoder, SparseUnetVaeEncoder, convert_trellis2_shape_vae_state_dict)
 from .sparse_conv_blocks import SparseConv3d, SparseConvNeXtBlock3d
+from .sparse_structure_vae import SparseStructureDecoder, SparseStructureEncoder
 
 __all__ = ["FlexiDualGridVaeDecoder", "FlexiDualGridVaeEncoder", "MeshOut", "SparseConv3d", "SparseConvNeXtBlock3d",
-           "SparseResBlockC2S3d", "SparseResBlockS2C3d", "SparseUnetVaeDecoder", "SparseUnetVaeEncoder",
-           "convert_trellis2_shape_vae_state_dict", "extract_meshes"]
+           "SparseResBlockC2S3d", "SparseResBlockS2C3d", "SparseStructureDecoder", "SparseStructureEncoder",
+           "SparseUnetVaeDecoder", "SparseUnetVaeEncoder", "convert_trellis2_shape_vae_state_dict", "extract_meshes"]

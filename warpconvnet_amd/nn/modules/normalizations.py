@@ -1,5 +1,5 @@
 """Normalisation modules over ``Geometry`` features (reference `nn/modules/normalizations.py:30-68`)."""
-from typing import Union
+from typing import Optional, Union
 
 import torch
 import torch.nn as nn
@@ -84,3 +84,33 @@ class LayerNorm32(nn.LayerNorm):
 
     def forward(self, x: Tensor) -> Tensor:
         return super().forward(x.float()).to(x.dtype)
+
+
+class GroupNorm32(nn.GroupNorm):
+    """``torch.nn.GroupNorm`` that always computes in fp32, then casts back (reference `nn/modules/normalizations.py:204-209`).
+    Plain torch: it is not the default norm of the dense blocks."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        return super().forward(x.float()).to(x.dtype)
+
+
+class ChannelLayerNorm32(LayerNorm32):
+    """LayerNorm over the channel axis of a ``(B, C, *spatial)`` tensor in fp32 (reference
+    `nn/modules/normalizations.py:212-219`, which permutes to channels-last, copies, normalises, permutes and copies back).
+    A GPU tensor that is channels-last in memory already IS ``[B * D * H * W, C]`` rows: those go through ``layer_norm_act``
+    (`csrc/ln_act.hip`) without a transpose.  A plain call returns the reference's contiguous tensor; a caller that stays
+    channels-last names ``act`` ("none", or "silu" to fold the activation the dense blocks apply next into the same pass) and
+    gets the result in the input's memory format.  Same values and shape either way."""
+
+    def forward(self, x: Tensor, act: Optional[str] = None) -> Tensor:
+        from warpconvnet_amd.nn.functional.ln_act import hip_ln_act_supported, layer_norm_act
+
+        nd = x.dim()
+        rows = x.permute(0, *range(2, nd), 1)
+        if (x.is_cuda and nd >= 3 and rows.is_contiguous() and self.elementwise_affine and self.bias is not None
+                and hip_ln_act_supported(x.shape[1], x.dtype)):
+            y = layer_norm_act(rows.reshape(-1, x.shape[1]), self.weight, self.bias, eps=self.eps, act=act or "none")
+            y = y.view(rows.shape).permute(0, nd - 1, *range(1, nd - 1))
+            return y.contiguous() if act is None else y
+        y = super().forward(rows.contiguous()).permute(0, nd - 1, *range(1, nd - 1)).contiguous()
+        return nn.functional.silu(y) if act == "silu" else y
