@@ -272,9 +272,10 @@ int wcn_mask_tile_order(const uint32_t* mask, int32_t mask_words, int32_t num_of
  * `algo`: 1 = hip_ref (any channel count / dtype), 2 = hip_mfma (bf16/f16; forward/dgrad: Cin%16==0,
  * Cout in {32,64,96,128,192,256}, K<=32; wgrad: Cin%32==0, Cout%32==0; WCN_ERROR_UNSUPPORTED_CONFIG
  * otherwise).  0 (auto) is resolved by the caller with wcn_mfma_*_supported because the two algorithms
- * take different weight images.  Accumulation is always fp32.
+ * take different weight images.  Accumulation is always fp32.  3 = hip_mfma_f32: fp32 operands on the fp32 MFMA, the plain
+ * weight tensor (section "sparse convolution on true fp32 operands" at the end of this header).
  */
-enum wcn_algo { WCN_ALGO_AUTO = 0, WCN_ALGO_REF = 1, WCN_ALGO_MFMA = 2 };
+enum wcn_algo { WCN_ALGO_AUTO = 0, WCN_ALGO_REF = 1, WCN_ALGO_MFMA = 2, WCN_ALGO_MFMA_F32 = 3 };
 
 /* 1 if the MFMA kernels cover the shape (so the caller can resolve "auto" without a trial launch). */
 int wcn_mfma_gather_supported(int32_t cin, int32_t cout, int32_t num_offsets, int32_t dtype);
@@ -1466,6 +1467,21 @@ size_t wcn_dense_conv3d_wgrad_workspace(int32_t cin, int32_t cout, int32_t ks, i
 int wcn_dense_conv3d_wgrad(const void* x, const void* dy, int64_t batch, int32_t D, int32_t H, int32_t W, int32_t cin,
                            int32_t cout, int32_t ks, int32_t dtype, int32_t slabs, void* dw, void* dbias, void* workspace,
                            size_t workspace_bytes, wcn_stream_t stream);
+
+/* ---- sparse convolution on true fp32 operands (csrc/conv_mfma_f32.hip; additions only, wcn_abi_version() stays 18) ------------
+ * algo = WCN_ALGO_MFMA_F32 (3) of wcn_conv_gather_gemm, wcn_conv_wgrad and wcn_conv_wgrad_workspace: fp32 operands on
+ * v_mfma_f32_32x32x2_f32, fp32 accumulation, fp32 results, no float atomics (the same call gives the same bits).
+ *   wcn_mfma_f32_gather_supported  host-only: cin % 16 == 0, cout % 32 == 0, 1 <= num_offsets <= 4096 (cin = the width the
+ *                                  product reduces over, cout the width it produces: exchanged for an input gradient).
+ *   wcn_mfma_f32_wgrad_supported   host-only: cin % 16 == 0, cout % 32 == 0, cin * cout <= 2^24.
+ *   wcn_conv_gather_gemm           `in`, `out`, `bias` fp32; `w` the plain fp32 [K, cin, cout] tensor, or [K, cout', cin'] with
+ *                                  w_transposed = 1 - read as stored, there is no packed image; k_flip as for WCN_ALGO_REF;
+ *                                  `nbr` the dense table with its `mask` (compact tables are not taken), `perm` or NULL.
+ *   wcn_conv_wgrad                 x, dy fp32; workspace: wcn_conv_wgrad_workspace(num_offsets, cin, cout, 3) bytes, 16-B aligned.
+ * Another dtype or a shape outside the probes -> WCN_ERROR_UNSUPPORTED_CONFIG; missing or misaligned pointers, a short
+ * workspace -> WCN_ERROR_INVALID_PARAMETERS; both before any launch. */
+int wcn_mfma_f32_gather_supported(int32_t cin, int32_t cout, int32_t num_offsets);
+int wcn_mfma_f32_wgrad_supported(int32_t cin, int32_t cout);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("WARPCONVNET_AMD_LIB") or os.path.join(_CSRC, "libwcn_hip.so")
 
 WCN_F32, WCN_F16, WCN_BF16 = 0, 1, 2
-WCN_ALGO_AUTO, WCN_ALGO_REF, WCN_ALGO_MFMA = 0, 1, 2
+WCN_ALGO_AUTO, WCN_ALGO_REF, WCN_ALGO_MFMA, WCN_ALGO_MFMA_F32 = 0, 1, 2, 3
 WCN_FLAG_TABLE_FULL, WCN_FLAG_COORD_RANGE, WCN_FLAG_PAIR_OVERFLOW, WCN_FLAG_DUPLICATE_COORD = 1, 2, 4, 8
 WCN_FLAG_NEED_STRICT = 16
 WCN_FLAG_ROW_OVERFLOW = 32
@@ -141,6 +141,8 @@ SIGNATURES = {
     "wcn_mask_tile_order": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wcn_mfma_gather_supported": (c_int, [c_int32, c_int32, c_int32, c_int32]),
     "wcn_mfma_wgrad_supported": (c_int, [c_int32, c_int32, c_int32]),
+    "wcn_mfma_f32_gather_supported": (c_int, [c_int32, c_int32, c_int32]),
+    "wcn_mfma_f32_wgrad_supported": (c_int, [c_int32, c_int32]),
     "wcn_conv_identity_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_dense_rows_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_dense_rows": (

@@ -5,13 +5,14 @@ Mirrors the three algorithm knobs of the reference (`warpconvnet/constants.py:11
 
 * ``auto``          - static choice: the fused HIP kernels (no run-time sweep, so ranks never diverge)
 * ``hip_mfma``      - fused gather->MFMA->store kernels (bf16/fp16/fp32), gfx950
+* ``hip_mfma_f32``  - the same three products on true fp32 operands (fp32 MFMA); the compute dtype must be float32
 * ``hip_ref``       - simple one-thread-per-output HIP kernels (any channel count; slow, for bring-up)
 * ``explicit_gemm`` - gather / torch.matmul / index_add on the tensor's device (reference `explicit.py` semantics)
 """
 import os
 from typing import List, Optional
 
-VALID_ALGOS = ["auto", "hip_mfma", "hip_ref", "explicit_gemm"]
+VALID_ALGOS = ["auto", "hip_mfma", "hip_mfma_f32", "hip_ref", "explicit_gemm"]
 
 
 def _env_choice(name: str, default: str, valid: Optional[List[str]] = None) -> str:

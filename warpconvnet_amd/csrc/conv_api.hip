@@ -17,6 +17,11 @@ bool mfma_wgrad_bias_supported(int cin, int cout, int dtype);
 int conv_wgrad_mfma(const void* x, const void* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
                     const int32_t* offsets, int cin, int cout, int K, int dtype, void* workspace, size_t workspace_bytes,
                     int cs_k, float* bias_grad, int64_t pair_bound, const int32_t* bounds, hipStream_t s);
+// conv_mfma_f32.hip
+bool mfma_f32_wgrad_supported(int cin, int cout);
+size_t wgrad_f32_workspace(int K, int cin, int cout);
+int conv_wgrad_f32(const float* x, const float* dy, float* dw, const int32_t* in_maps, const int32_t* out_maps,
+                   const int32_t* offsets, int cin, int cout, int K, void* workspace, size_t workspace_bytes, hipStream_t s);
 // dwconv.hip
 int dwconv_gather(const void* in, const void* w, void* out, const int32_t* tbl, const float* bias, int64_t n_out, int C,
                   int K, int dtype, int k_flip, hipStream_t s);
@@ -50,6 +55,11 @@ int wcn_conv_identity_supported(int32_t cin, int32_t cout, int32_t dtype) {
 int wcn_mfma_wgrad_supported(int32_t cin, int32_t cout, int32_t dtype) {
   return mfma_wgrad_supported(cin, cout, dtype) ? 1 : 0;
 }
+
+int wcn_mfma_f32_gather_supported(int32_t cin, int32_t cout, int32_t num_offsets) {
+  return mfma_f32_gather_supported(cin, cout, num_offsets) ? 1 : 0;
+}
+int wcn_mfma_f32_wgrad_supported(int32_t cin, int32_t cout) { return mfma_f32_wgrad_supported(cin, cout) ? 1 : 0; }
 
 size_t wcn_packed_weight_bytes(int32_t num_offsets, int32_t cin, int32_t cout, int32_t dtype, int32_t transpose) {
   (void)transpose;  // cin / cout are the kernel-side roles already (reduce over cin, produce cout)
@@ -104,6 +114,9 @@ int wcn_conv_gather_gemm(const void* in, const void* w, void* out, const int32_t
                          int32_t k_flip, wcn_stream_t stream) {
   if (n_in < 0 || n_out < 0 || cin < 1 || cout < 1 || num_offsets < 1 || !dtype_ok(dtype))
     return WCN_ERROR_INVALID_PARAMETERS;
+  // the fp32 kernels take fp32 operands and their own shapes only - said before the empty-launch shortcut and before any launch
+  if (algo == WCN_ALGO_MFMA_F32 && (dtype != WCN_F32 || !mfma_f32_gather_supported(cin, cout, num_offsets)))
+    return WCN_ERROR_UNSUPPORTED_CONFIG;
   if (n_out == 0) return WCN_SUCCESS;
   // nbr == mask == NULL with one offset: the identity map (row r pairs with row r) - the dense product of a 1 x 1 x 1
   // convolution streamed through the channel-split gather kernel (shapes of wcn_conv_identity_supported)
@@ -122,6 +135,11 @@ int wcn_conv_gather_gemm(const void* in, const void* w, void* out, const int32_t
         epi.bias = bias;
         return conv_gather_gemm_mfma(in, w, out, nbr, mask, perm, epi, n_out, cin, cout, num_offsets, dtype, nullptr, s);
       }
+    case WCN_ALGO_MFMA_F32:
+      // `w` is the plain fp32 tensor: the kernel reads it as stored, in either orientation
+      if (!mask) return WCN_ERROR_INVALID_PARAMETERS;
+      return conv_gather_gemm_f32((const float*)in, (const float*)w, (float*)out, nbr, mask, perm, bias, n_out, cin, cout,
+                                  num_offsets, w_transposed, k_flip, s);
     default:
       // AUTO cannot be resolved here because the two algorithms take different weight images.
       return WCN_ERROR_INVALID_PARAMETERS;
@@ -192,6 +210,7 @@ int wcn_colsum(const void* in, int64_t n, int32_t channels, int32_t dtype, float
 
 size_t wcn_conv_wgrad_workspace(int32_t num_offsets, int32_t cin, int32_t cout, int32_t algo) {
   if (algo == WCN_ALGO_MFMA) return wgrad_mfma_workspace(num_offsets, cin, cout);
+  if (algo == WCN_ALGO_MFMA_F32) return (num_offsets > 0 && cin > 0 && cout > 0) ? wgrad_f32_workspace(num_offsets, cin, cout) : 0;
   return 256;
 }
 
@@ -207,6 +226,10 @@ int wcn_conv_wgrad(const void* x, const void* dy, float* dw, const int32_t* in_m
     case WCN_ALGO_MFMA:
       return conv_wgrad_mfma(x, dy, dw, in_maps, out_maps, offsets, cin, cout, num_offsets, dtype, workspace,
                              workspace_bytes, -1, nullptr, (int64_t)num_offsets * (n_in < n_out ? n_in : n_out), nullptr, s);
+    case WCN_ALGO_MFMA_F32:
+      if (dtype != WCN_F32) return WCN_ERROR_UNSUPPORTED_CONFIG;
+      return conv_wgrad_f32((const float*)x, (const float*)dy, dw, in_maps, out_maps, offsets, cin, cout, num_offsets, workspace,
+                            workspace_bytes, s);
     default:
       return WCN_ERROR_INVALID_PARAMETERS;
   }

@@ -2,6 +2,7 @@
 //   conv_mfma.hip     32x32x16, rows gathered into registers, weights by LDS-DMA (also groups, K > 32)
 //   conv_mfma16.hip   16x16x32, same structure, the channel counts the others do not take
 //   conv_mfma_cs.hip  channel-split, rows staged through LDS (the headline shapes)
+//   conv_mfma_f32.hip 32x32x2 on fp32 operands, rows and the weight as stored staged through LDS
 // Every piece here is used as it is by at least two of them; what one family alone needs stays in its file.  The
 // prototypes at the end are the only declarations of the functions these files and conv_api.hip call across
 // translation units.
@@ -185,6 +186,12 @@ int conv_gather_gemm16(const void* in, const void* wp, void* out, const int32_t*
 int conv_gather_gemm_grouped(const void* in, const void* wp, void* out, const int32_t* nbr, const uint32_t* mask,
                              const int32_t* perm, const ConvEpilogue& epi, int64_t n_out, int cin, int cout, int groups,
                              int K, int dtype, hipStream_t s);
+
+// true-fp32 operands on v_mfma_f32_32x32x2_f32 (conv_mfma_f32.hip): `w` is the weight as stored, no packed image
+bool mfma_f32_gather_supported(int cin, int cout, int K);
+int conv_gather_gemm_f32(const float* in, const float* w, float* out, const int32_t* nbr, const uint32_t* mask,
+                         const int32_t* perm, const float* bias, int64_t n_out, int cin, int cout, int K, int w_transposed,
+                         int k_flip, hipStream_t s);
 
 // weight packer (conv_mfma.hip); `w` fp32 (w_is_f32) or already in the 16-bit storage dtype
 int pack_weight_mfma(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,

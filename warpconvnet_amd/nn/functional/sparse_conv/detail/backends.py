@@ -4,7 +4,7 @@ Same plug-in interface as the reference (`warpconvnet/nn/functional/sparse_conv/
 443-510`): ``FORWARD_BACKENDS[name](FwdCtx) -> Tensor | int``, ``BACKWARD_BACKENDS[name](BwdCtx) ->
 (Tensor | int | None, Tensor | None)``; a non-zero int status becomes a ``RuntimeError`` in
 ``run_forward`` / ``run_backward``.  Registered names: ``explicit_gemm``, ``hip_ref``, ``hip_mfma``,
-``auto`` (static shape-class choice between the two HIP paths).
+``hip_mfma_f32`` (true fp32 operands; the compute dtype must be float32), ``auto`` (static shape-class choice between the two HIP paths).
 """
 import dataclasses
 import functools
@@ -104,7 +104,7 @@ def _hip_bwd(algo: str, ctx: BwdCtx):
     return dx, dw
 
 
-_HIP_ALGOS = ("hip_ref", "hip_mfma", "auto")
+_HIP_ALGOS = ("hip_ref", "hip_mfma", "hip_mfma_f32", "auto")
 FORWARD_BACKENDS: Dict[str, FwdFn] = {"explicit_gemm": _fwd_explicit, **{a: functools.partial(_hip_fwd, a) for a in _HIP_ALGOS}}
 BACKWARD_BACKENDS: Dict[str, BwdFn] = {"explicit_gemm": _bwd_explicit, **{a: functools.partial(_hip_bwd, a) for a in _HIP_ALGOS}}
 

@@ -1,6 +1,8 @@
 """HIP backends of the three sparse-conv GEMMs (through the C-ABI in ``include/wcn.h``).
 
 * ``hip_mfma`` - fused gather -> MFMA -> store kernels (`csrc/conv_mfma.hip`, `csrc/wgrad_mfma.hip`)
+* ``hip_mfma_f32`` - the three products on true fp32 operands, `v_mfma_f32_32x32x2_f32` (`csrc/conv_mfma_f32.hip`); the weight
+  is read as stored (no packed image); float32 only, any other dtype raises
 * ``hip_ref``  - simple kernels for any channel count / fp32 (`csrc/conv_ref.hip`)
 * ``auto``     - ``hip_mfma`` when the shape is covered, else ``hip_ref``; a pure function of
   (C_in, C_out, K, dtype), so every rank of a data-parallel job takes the same path.
@@ -9,7 +11,7 @@ fp32 feature tensors under ``auto`` / ``hip_mfma`` follow the reference's produc
 (`mask_gemm.py:72-103, 696-745, 818-963`): operands are cast to fp16 - rescaled by an exact power of two, in both directions
 (`fp16_safe_cast`: unlike the reference's, which leaves small tensors to the fp16 subnormals), computed on the device, no host
 sync - the matrix cores accumulate in fp32, the fused kernels write fp32 results and the product of the operand scales is
-multiplied back.  ``hip_ref`` / ``explicit_gemm`` keep full fp32 operands.
+multiplied back.  ``hip_mfma_f32`` / ``hip_ref`` / ``explicit_gemm`` keep full fp32 operands.
 
 Role of the reference's `_mask_gemm_forward_logic` / `_mask_gemm_backward_logic`
 (`warpconvnet/nn/functional/sparse_conv/detail/mask_gemm.py:661-745, 818-963`).
@@ -104,7 +106,9 @@ def _via_fp16(a: Tensor, b: Tensor, launch) -> Tensor:
 # `warpgemm_a_loader_precomputed.cuh:176-224`).  Here the operands are padded with zero channels to the next shape the MFMA
 # kernels take and the result is cut back: zeros contribute nothing to any of the three products, so the values are those of the
 # unpadded problem (same fp32 accumulation), at the cost of one padded copy of the operands.
-_NATIVE, _REF, _VIA_FP16, _PADDED = "native", "ref", "via_fp16", "padded"
+# ``native_f32``: fp32 operands as they are on the fp32 MFMA kernels (``hip_mfma_f32``), channels zero-padded to their shapes.
+_NATIVE, _REF, _VIA_FP16, _PADDED, _NATIVE_F32 = "native", "ref", "via_fp16", "padded", "native_f32"
+_F32_ALGO = "hip_mfma_f32"
 _MFMA_COUTS = (16, 32, 48, 64, 96, 128, 160, 192, 256, 384, 512)
 
 
@@ -119,10 +123,23 @@ def _resolve(algo: str, ok: bool, what: str, shape: str):
     return (_NATIVE, _lib.WCN_ALGO_MFMA) if ok and algo != "hip_ref" else (_REF, _lib.WCN_ALGO_REF)
 
 
+def _f32_plan(what: str, kin: int, kout: int, dtype: torch.dtype, ok):
+    """The ``hip_mfma_f32`` treatment: fp32 only (no silent route for another dtype), kin padded to 16, kout to 32."""
+    if dtype != torch.float32:
+        raise RuntimeError(f"{_F32_ALGO} {what}: the compute dtype must be float32, got {dtype} (float32 features without "
+                           f"autocast, or compute_dtype=torch.float32)")
+    kin_p, kout_p = max(16, (kin + 15) // 16 * 16), max(32, (kout + 31) // 32 * 32)
+    if not ok(kin_p, kout_p):
+        raise RuntimeError(f"{_F32_ALGO} {what}: {_lib.status_string(-4)} (cin={kin}, cout={kout})")
+    return _NATIVE_F32, _lib.WCN_ALGO_MFMA_F32, kin_p, kout_p
+
+
 @functools.lru_cache(maxsize=None)
 def _gather_plan(algo: str, kin: int, kout: int, K: int, dtype: torch.dtype, on_gpu: bool):
     """``(treatment, algorithm code, kin, kout as launched)`` of a forward (kin = Cin) or dgrad (kin = Cout: it reduces over Cout
     and produces Cin) product.  A pure function of its arguments, memoised: asked on every call of every layer."""
+    if algo == _F32_ALGO:
+        return _f32_plan("gather", kin, kout, dtype, lambda a, b: bool(_lib.lib().wcn_mfma_f32_gather_supported(a, b, K)))
     if algo == "auto" and on_gpu and not _gather_ok(kin, kout, K, _code16(dtype)) and dtype in (torch.float16, torch.bfloat16):
         # the smallest MFMA shape that contains kin x kout (fp32 features keep full fp32 operands on such shapes instead)
         kin_p = max(32, (kin + 31) // 32 * 32)
@@ -139,6 +156,8 @@ def _gather_plan(algo: str, kin: int, kout: int, K: int, dtype: torch.dtype, on_
 def _wgrad_plan(algo: str, cin: int, cout: int, dtype: torch.dtype, on_gpu: bool):
     """The same for the weight gradient: its own probe, and both channel counts padded to a multiple of 32 (the padded rows /
     columns of dw are zero)."""
+    if algo == _F32_ALGO:
+        return _f32_plan("wgrad", cin, cout, dtype, lambda a, b: bool(_lib.lib().wcn_mfma_f32_wgrad_supported(a, b)))
     if algo == "auto" and on_gpu and not _wgrad_ok(cin, cout, _code16(dtype)) and dtype != torch.float32:
         cin_p, cout_p = (cin + 31) // 32 * 32, (cout + 31) // 32 * 32
         if _wgrad_ok(cin_p, cout_p, _lib.dtype_code(dtype)):
@@ -354,7 +373,8 @@ def hip_forward(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult
     K, cin, cout = w.shape
     assert K == len(kernel_map) and cin == x.shape[1]
     how, code, cin_p, cout_p = _gather_plan(algo, cin, cout, K, x.dtype, x.is_cuda)
-    if how == _PADDED:  # zero-padded channels on the MFMA kernels instead of one thread per output element
+    padded = (cin_p, cout_p) != (cin, cout)  # (`padded` and, for widths outside its shapes, `native_f32`)
+    if padded:  # zero-padded channels on the MFMA kernels instead of one thread per output element
         x, w, bias = _fit(x, cin_p), _fit(w, cin_p, cout_p), _fit(bias, cout_p)
     attach_tables_from_csr(kernel_map, x.shape[0], num_out_coords)
 
@@ -374,7 +394,7 @@ def hip_forward(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult
     y = launch()
     if kernel_map.validate():
         y = launch()
-    return _fit(y, cout) if how == _PADDED else y
+    return _fit(y, cout) if padded else y
 
 
 def hip_colsum(t: Tensor) -> Tensor:
@@ -444,7 +464,8 @@ def hip_dgrad(grad_output: Tensor, weight: Tensor, kernel_map: IntSearchResult, 
             return _dgrad_duplicates(dy, w, kernel_map, num_in_coords, algo)
         return _dgrad_pair_lists(dy, w, kernel_map, num_in_coords)
     how, code, cout_p, cin_p = _gather_plan(algo, cout, cin, K, dy.dtype, dy.is_cuda)  # kernel-side roles: reduce over cout
-    if how == _PADDED:
+    padded = (cin_p, cout_p) != (cin, cout)
+    if padded:
         dy, w = _fit(dy, cout_p), _fit(w, cin_p, cout_p)
     attach_tables_from_csr(kernel_map, num_in_coords, dy.shape[0])
     tbl, mask, perm, flip = dgrad_tables(kernel_map, num_in_coords, cout_p, cin_p, K,
@@ -453,7 +474,7 @@ def hip_dgrad(grad_output: Tensor, weight: Tensor, kernel_map: IntSearchResult, 
         return _via_fp16(dy, w, lambda g16, w16: _gather_gemm(g16, w16, tbl, mask, perm, num_in_coords, cout, cin, K, code,
                                                               transposed=True, flip=flip, f32_out=True))
     dx = _gather_gemm(dy, w, tbl, mask, perm, num_in_coords, cout_p, cin_p, K, code, transposed=True, flip=flip)
-    return _fit(dx, cin) if how == _PADDED else dx
+    return _fit(dx, cin) if padded else dx
 
 
 def hip_wgrad(in_features: Tensor, grad_output: Tensor, kernel_map: IntSearchResult, weight_shape, algo: str = "auto",
@@ -472,17 +493,18 @@ def hip_wgrad(in_features: Tensor, grad_output: Tensor, kernel_map: IntSearchRes
         raise RuntimeError(f"hip wgrad error: {_lib.status_string(-6)} ({x.dtype} vs {dy.dtype})")
     K, cin, cout = weight_shape
     how, code, cin_p, cout_p = _wgrad_plan(algo, cin, cout, x.dtype, x.is_cuda)
-    if how == _PADDED:
+    padded = (cin_p, cout_p) != (cin, cout)
+    if padded:
         x, dy = _fit(x, cin_p), _fit(dy, cout_p)
     kernel_map.validate()
     if how == _VIA_FP16:  # (no bias gradient from this kernel then: it stays an exact fp32 column sum, the caller's)
         dw = _via_fp16(x, dy, lambda x16, g16: _wgrad_launch(x16, g16, kernel_map, K, cin, cout, code, None, False)[0])
         return (dw, None) if want_bias_grad else dw
-    if out is not None and (how == _PADDED or out.shape != (K, cin, cout) or out.dtype != torch.float32
+    if out is not None and (padded or out.shape != (K, cin, cout) or out.dtype != torch.float32
                             or not out.is_contiguous() or out.device != x.device):
         out = None
     dw, db = _wgrad_launch(x, dy, kernel_map, K, cin_p, cout_p, code, out, want_bias_grad)
-    if how == _PADDED:
+    if padded:
         dw, db = _fit(dw, cin, cout), _fit(db, cout)
     return (dw, db) if want_bias_grad else dw
 

@@ -25,6 +25,7 @@ class SPARSE_CONV_AB_ALGO_MODE(Enum):
     EXPLICIT_GEMM = "explicit_gemm"
     HIP_REF = "hip_ref"
     HIP_MFMA = "hip_mfma"
+    HIP_MFMA_F32 = "hip_mfma_f32"
     AUTO = "auto"
 
 
@@ -32,6 +33,7 @@ class SPARSE_CONV_ATB_ALGO_MODE(Enum):
     EXPLICIT_GEMM = "explicit_gemm"
     HIP_REF = "hip_ref"
     HIP_MFMA = "hip_mfma"
+    HIP_MFMA_F32 = "hip_mfma_f32"
     AUTO = "auto"
 
 
