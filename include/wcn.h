@@ -1435,6 +1435,30 @@ int wcn_attn_varlen_kv_bwd_s(const void* dout, const void* q, int64_t q_stride, 
                              void* dv, int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace,
                              size_t workspace_bytes, int32_t variant, wcn_stream_t stream);
 
+/* ---- varlen attention at head size 128 (csrc/attn_varlen_d128.hip; additions only, wcn_abi_version() stays 18) ----------------
+ * The separate-operand attention above for head_dim = 128, fp16 / bf16: a work item (sequence, 32-row block, head) is run by
+ * two waves, each on 64 columns of the head, which exchange their partial 32 x 32 score tiles through LDS.  Operands,
+ * boundaries, strides, outputs, the empty-side conventions and determinism are those of wcn_attn_varlen_kv_fwd_s / _kv_bwd_s,
+ * whose arguments these take minus `variant` (there is no shared-tile variant at this size); a packed [T, 3, H, 128] tensor is
+ * the same call with q_stride = kv_stride = 3 * heads * 128 and cu_q = cu_k.  k_splits / q_splits: 0 = the rules
+ * wcn_attn_varlen_k_splits / wcn_attn_varlen_kv_splits, 1 = no split; the workspace is what
+ * wcn_attn_varlen_ksplit_workspace_bytes(total_q, total_k, heads, 128, q_splits, k_splits, direction) reports (splits as
+ * resolved), 16-byte aligned - the forward needs none at k_splits = 1.
+ *   wcn_attn_d128_supported   host-only: 1 for head_dim 128 with WCN_F16 / WCN_BF16, 0 otherwise.
+ * Before any launch: missing pointers, negative sizes or splits, a NaN scale, bad strides or alignment, a short workspace ->
+ * WCN_ERROR_INVALID_PARAMETERS; another head size or dtype -> WCN_ERROR_UNSUPPORTED_CONFIG; nothing to compute -> success. */
+int wcn_attn_d128_supported(int32_t head_dim, int32_t dtype);
+int wcn_attn_d128_fwd(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* cu_q,
+                      const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
+                      int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* out, float* lse,
+                      int32_t k_splits, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_attn_d128_bwd(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                      const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                      int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                      int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk, void* dv,
+                      int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace, size_t workspace_bytes,
+                      wcn_stream_t stream);
+
 /* ---- dense 3-D brick convolution (csrc/dense_conv3d.hip; additions only, wcn_abi_version() stays 18) ------------------------
  * nn.Conv3d with kernel `ks` = 3 (padding 1) or 1, stride 1, on channels-last cubes: x [batch, D, H, W, cin], y
  * [batch, D, H, W, cout], all tensors of one `dtype` (f32 / f16 / bf16), fp32 accumulation, no float atomics (the same call

@@ -3,9 +3,10 @@ tensor (self-attention inside patches or batch elements) and with separate query
 
 The reference's PatchAttention (`nn/modules/attention.py:496`) runs ``flash_attn.flash_attn_varlen_qkvpacked_func``
 (wrapped in `nn/functional/flash_attn_utils.py:15-82`), a CUDA-only package.  ``flash_attn_varlen_qkvpacked`` is the
-same call on gfx950: fp16 / bf16, head_dim 16 / 32 / 64, no dropout; anything else raises (there is no fallback to eager
-attention).  ``varlen_attention_reference`` is a plain per-sequence torch implementation in fp32 / fp64 for CPU tensors
-that ask for it and for the tests.
+same call on gfx950: fp16 / bf16, head_dim 16 / 32 / 64 - and 128 on the wave-pair kernels of
+`csrc/attn_varlen_d128.hip` - no dropout; anything else raises (there is no fallback to eager attention).
+``varlen_attention_reference`` is a plain per-sequence torch implementation in fp32 / fp64 for CPU tensors that ask for it
+and for the tests.
 
 The reference's sparse cross-attention (`nn/modules/sparse_dit_attention.py:265-315`) calls
 ``flash_attn.flash_attn_varlen_func`` and ``flash_attn.flash_attn_varlen_kvpacked_func``; the functions of those names here
@@ -23,7 +24,8 @@ from warpconvnet_amd import _lib
 from warpconvnet_amd.utils.compile_guard import eager_unless_compiling
 
 __all__ = ["flash_attn_varlen_qkvpacked", "patch_cu_seqlens", "varlen_attention_reference", "hip_attn_varlen_supported",
-           "flash_attn_varlen_func", "flash_attn_varlen_kvpacked_func", "cross_attention_reference"]
+           "flash_attn_varlen_func", "flash_attn_varlen_kvpacked_func", "cross_attention_reference",
+           "hip_attn_d128_supported"]
 
 
 def hip_attn_varlen_supported(head_dim: int, dtype: torch.dtype) -> bool:
@@ -31,6 +33,13 @@ def hip_attn_varlen_supported(head_dim: int, dtype: torch.dtype) -> bool:
     if dtype not in (torch.float16, torch.bfloat16):
         return False
     return bool(_lib.lib().wcn_attn_varlen_supported(int(head_dim), _lib.dtype_code(dtype)))
+
+
+def hip_attn_d128_supported(head_dim: int, dtype: torch.dtype) -> bool:
+    """Whether the wave-pair kernels of the wide head serve this head size and dtype (``wcn_attn_d128_supported``)."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        return False
+    return bool(_lib.lib().wcn_attn_d128_supported(int(head_dim), _lib.dtype_code(dtype)))
 
 
 def patch_cu_seqlens(offsets: Tensor, patch_size: int) -> Tensor:
@@ -113,11 +122,70 @@ def _variant_code(variant) -> int:
     raise ValueError(f"variant must be one of {sorted(_VARIANTS)}, got {variant!r}")
 
 
+def _check_head(name: str, t: Tensor, variant: int) -> None:
+    """Raises unless a kernel family serves the head size of ``t`` [.., H, D]: 16 / 32 / 64 anywhere, 128 on a GPU tensor
+    (the wave-pair kernels, which have no shared-tile variant)."""
+    d = t.shape[-1]
+    if hip_attn_d128_supported(d, t.dtype):
+        if variant == _lib.WCN_ATTN_SHARED:
+            raise NotImplementedError(f"{name}: head_dim {d} runs on the wave-pair kernels, which have no shared-tile variant "
+                                      "(variant must be 'auto' or 'one_wave')")
+        if t.is_cuda:
+            return
+    if not hip_attn_varlen_supported(d, t.dtype):
+        raise NotImplementedError(f"{name}: head_dim {d} is not supported (16, 32 or 64)")
+
+
+def _d128_fwd(q: Tensor, k: Tensor, v: Tensor, cu_q: Tensor, cu_k: Tensor, max_q: int, max_k: int, scale: float,
+              k_splits: int) -> Tuple[Tensor, Tensor, int]:
+    """``wcn_attn_d128_fwd`` on [T, H, 128] row views (``k`` and ``v`` with one common row stride) -> out, lse and the
+    split count as resolved (0: the library's rule), which the backward's dQ sweep uses too."""
+    tq, h, d = q.shape
+    dev = q.device
+    L = _lib.lib()
+    if k_splits == 0:
+        k_splits = L.wcn_attn_varlen_k_splits(cu_q.numel() - 1, max_q, max_k, h, 0)
+    out = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
+    lse = torch.empty(tq, h, dtype=torch.float32, device=dev)
+    ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, k.shape[0], h, d, 1, k_splits, 0), dtype=torch.uint8, device=dev)
+    _lib.check(
+        L.wcn_attn_d128_fwd(_lib.ptr(q), _row_stride(q), _lib.ptr(k), _lib.ptr(v), _row_stride(k), _lib.ptr(cu_q), _lib.ptr(cu_k),
+                            cu_q.numel() - 1, tq, k.shape[0], h, d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(out),
+                            _lib.ptr(lse), k_splits, _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
+        "wcn_attn_d128_fwd",
+    )
+    return out, lse, k_splits
+
+
+def _d128_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, cu_q: Tensor, cu_k: Tensor, max_q: int,
+              max_k: int, scale: float, dq: Tensor, dk: Tensor, dv: Tensor, q_splits: int, k_splits: int) -> None:
+    """``wcn_attn_d128_bwd`` into the [T, H, 128] row views ``dq``, ``dk``, ``dv`` (``dk`` and ``dv`` with one row stride)."""
+    tq, h, d = q.shape
+    tk = k.shape[0]
+    dev = q.device
+    L = _lib.lib()
+    if q_splits == 0:
+        q_splits = L.wcn_attn_varlen_kv_splits(cu_q.numel() - 1, max_q, max_k, h)
+    ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, tk, h, d, q_splits, k_splits, 1), dtype=torch.uint8, device=dev)
+    _lib.check(
+        L.wcn_attn_d128_bwd(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(k), _lib.ptr(v), _row_stride(k), _lib.ptr(out),
+                            _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h, d, max_q, max_k, scale,
+                            _lib.dtype_code(q.dtype), _lib.ptr(dq), _row_stride(dq), _lib.ptr(dk), _lib.ptr(dv), _row_stride(dk),
+                            q_splits, k_splits, _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
+        "wcn_attn_d128_bwd",
+    )
+
+
 class _VarlenAttention(Function):
     @staticmethod
     def forward(ctx, qkv: Tensor, cu: Tensor, max_seqlen: int, scale: float, variant: int = 0) -> Tensor:
         t, _, h, d = qkv.shape
         dev = qkv.device
+        ctx.max_seqlen, ctx.scale, ctx.variant = int(max_seqlen), float(scale), variant
+        if d == 128:  # the wave-pair kernels, the three slots as separate operands
+            out, lse, _ = _d128_fwd(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu, cu, ctx.max_seqlen, ctx.max_seqlen, ctx.scale, 1)
+            ctx.save_for_backward(qkv, cu, out, lse)
+            return out
         out = torch.empty(t, h, d, dtype=qkv.dtype, device=dev)
         lse = torch.empty(t, h, dtype=torch.float32, device=dev)
         if variant == _lib.WCN_ATTN_AUTO:
@@ -135,7 +203,6 @@ class _VarlenAttention(Function):
                 "wcn_attn_varlen_kv_fwd_v",
             )
         ctx.save_for_backward(qkv, cu, out, lse)
-        ctx.max_seqlen, ctx.scale, ctx.variant = int(max_seqlen), float(scale), variant
         return out
 
     @staticmethod
@@ -145,6 +212,10 @@ class _VarlenAttention(Function):
         dev = qkv.device
         dout = dout.to(qkv.dtype).contiguous()
         dqkv = torch.empty_like(qkv)
+        if d == 128:
+            _d128_bwd(dout, qkv[:, 0], qkv[:, 1], qkv[:, 2], out, lse, cu, cu, ctx.max_seqlen, ctx.max_seqlen, ctx.scale,
+                      dqkv[:, 0], dqkv[:, 1], dqkv[:, 2], 1, 1)
+            return dqkv, None, None, None, None
         L = _lib.lib()
         ws = torch.empty(L.wcn_attn_varlen_workspace_bytes(t, h), dtype=torch.uint8, device=dev)
         if ctx.variant == _lib.WCN_ATTN_AUTO:
@@ -184,8 +255,7 @@ def flash_attn_varlen_qkvpacked(qkv: Tensor, cu_seqlens: Tensor, max_seqlen: int
     if qkv.dtype not in (torch.float16, torch.bfloat16):
         raise TypeError(f"flash_attn_varlen_qkvpacked: qkv must be float16 or bfloat16, got {qkv.dtype} (cast it first; "
                         "there is no fp32 kernel)")
-    if not hip_attn_varlen_supported(d, qkv.dtype):
-        raise NotImplementedError(f"flash_attn_varlen_qkvpacked: head_dim {d} is not supported (16, 32 or 64)")
+    _check_head("flash_attn_varlen_qkvpacked", qkv, variant)
     if max_seqlen < 0:
         raise ValueError(f"max_seqlen must be >= 0, got {max_seqlen}")
     if not cu_seqlens.is_cuda:
@@ -260,6 +330,12 @@ class _CrossVarlenAttention(Function):
         kk, vv = (k[:, 0], k[:, 1]) if packed else (k, v)
         tq, h, d = q.shape
         dev = q.device
+        ctx.args = (max_q, max_k, scale, q_splits)
+        ctx.variant = variant
+        if d == 128:  # the wave-pair kernels
+            out, lse, ctx.k_splits = _d128_fwd(q, kk, vv, cu_q, cu_k, max_q, max_k, scale, k_splits)
+            ctx.save_for_backward(q, k, v, cu_q, cu_k, out, lse)
+            return out
         out = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
         lse = torch.empty(tq, h, dtype=torch.float32, device=dev)
         L = _lib.lib()
@@ -283,9 +359,7 @@ class _CrossVarlenAttention(Function):
                 "wcn_attn_varlen_kv_fwd_s",
             )
         ctx.save_for_backward(q, k, v, cu_q, cu_k, out, lse)
-        ctx.args = (max_q, max_k, scale, q_splits)
         ctx.k_splits = k_splits
-        ctx.variant = variant
         return out
 
     @staticmethod
@@ -306,7 +380,9 @@ class _CrossVarlenAttention(Function):
             dk, dv = torch.empty(tk, h, d, dtype=q.dtype, device=dev), torch.empty(tk, h, d, dtype=q.dtype, device=dev)
         L = _lib.lib()
         splits = q_splits if q_splits > 0 else L.wcn_attn_varlen_kv_splits(cu_q.numel() - 1, max_q, max_k, h)
-        if ctx.k_splits == 1:
+        if d == 128:
+            _d128_bwd(dout, q, kk, vv, out, lse, cu_q, cu_k, max_q, max_k, scale, dq, dk, dv, splits, ctx.k_splits)
+        elif ctx.k_splits == 1:
             ws = torch.empty(L.wcn_attn_varlen_kv_workspace_bytes(tq, tk, h, d, splits), dtype=torch.uint8, device=dev)
             _lib.check(
                 L.wcn_attn_varlen_kv_bwd_v(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
@@ -354,8 +430,7 @@ def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tens
                             "kernel)")
     if k.dtype != q.dtype or v.dtype != q.dtype:
         raise TypeError(f"{name}: q, k and v must share one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
-    if not hip_attn_varlen_supported(d, q.dtype):
-        raise NotImplementedError(f"{name}: head_dim {d} is not supported (16, 32 or 64)")
+    _check_head(name, q, variant)
     if max_seqlen_q < 0 or max_seqlen_k < 0:
         raise ValueError(f"max_seqlen_q and max_seqlen_k must be >= 0, got {max_seqlen_q} and {max_seqlen_k}")
     if cu_seqlens_q.numel() != cu_seqlens_k.numel():
