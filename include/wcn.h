@@ -275,7 +275,9 @@ int wcn_mask_tile_order(const uint32_t* mask, int32_t mask_words, int32_t num_of
  * take different weight images.  Accumulation is always fp32.  3 = hip_mfma_f32: fp32 operands on the fp32 MFMA, the plain
  * weight tensor (section "sparse convolution on true fp32 operands" at the end of this header).
  */
-enum wcn_algo { WCN_ALGO_AUTO = 0, WCN_ALGO_REF = 1, WCN_ALGO_MFMA = 2, WCN_ALGO_MFMA_F32 = 3 };
+enum wcn_algo { WCN_ALGO_AUTO = 0, WCN_ALGO_REF = 1, WCN_ALGO_MFMA = 2, WCN_ALGO_MFMA_F32 = 3, WCN_ALGO_MFMA_FP8 = 4 };
+/* 4 = hip_mfma_fp8 names the FP8 inference forward; it has entry points of its own (wcn_conv_gather_gemm_fp8, at the end of this
+ * header) because its operands, scales and output dtype do not fit wcn_conv_gather_gemm, which refuses it like any unknown code. */
 
 /* 1 if the MFMA kernels cover the shape (so the caller can resolve "auto" without a trial launch). */
 int wcn_mfma_gather_supported(int32_t cin, int32_t cout, int32_t num_offsets, int32_t dtype);
@@ -1506,6 +1508,42 @@ int wcn_dense_conv3d_wgrad(const void* x, const void* dy, int64_t batch, int32_t
  * workspace -> WCN_ERROR_INVALID_PARAMETERS; both before any launch. */
 int wcn_mfma_f32_gather_supported(int32_t cin, int32_t cout, int32_t num_offsets);
 int wcn_mfma_f32_wgrad_supported(int32_t cin, int32_t cout);
+
+/* ---- FP8 (OCP E4M3) inference sparse convolution, forward only (csrc/conv_mfma_fp8.hip; additions only, wcn_abi_version() stays
+ * 18) ----
+ *   y[m, c] = (s_x * s_w[c]) * sum_k sum_ci Xq[nbr[m][k], ci] * Wq[k, ci, c] (+ bias[c]) on v_mfma_f32_32x32x64_f8f6f4: E4M3
+ *   operands, fp32 accumulation, fp32 epilogue, one rounding to out_dtype.  No float atomics: the same call gives the same bits.
+ *   wcn_conv_fp8_supported       host-only: cin % 64 == 0 (64 .. 2^20), cout % 32 == 0 (cout / 32 <= 65535), 1 <= num_offsets <= 4096
+ *                                - the widths AFTER zero padding.
+ *   wcn_fp8_packed_weight_bytes  host-only: num_offsets * cin * cout for a shape of the probe, 0 otherwise.
+ *   wcn_fp8_amax_workspace       host-only: bytes of the reduction's workspace.  Its LAST 4-byte word must be zero before the first
+ *                                call; every call leaves it zero.  Calls that share a workspace must be ordered (one stream).
+ *   wcn_fp8_amax_scale           *scale = max|x| / 448 over `count` elements (IEEE division; 1 for all zeros or count = 0): one
+ *                                launch, per-workgroup partials reduced in index order by the last workgroup, no float atomics.
+ *   wcn_fp8_quantize_rows        out[r][c] = rne_e4m3(x[r][c] / *scale) (IEEE division), zero bytes for channels <= c < out_pitch;
+ *                                x [n][channels] (dtype f32 / f16 / bf16, 16-B aligned), out rows of out_pitch bytes (% 16 == 0).
+ *   wcn_fp8_pack_weight          w the plain [num_offsets][cin][cout] tensor -> w_scale[cout_padded] (max|w[:, :, c]| / 448; 1 for
+ *                                an all-zero or padded channel) and the fragment-ordered image of the padded E4M3 weight: one
+ *                                2-KiB fragment per (offset k, 64-channel chunk q, 32-column block cb), in that order, each
+ *                                [j = 0, 1][lane = 32 h + n][16 bytes b] = Wq[k][64 q + 32 h + 16 j + b][32 cb + n].  Two launches.
+ *   wcn_conv_gather_gemm_fp8     xq rows of cin bytes, *x_scale a device scalar, w_image / w_scale as packed above, `nbr` the
+ *                                dense table with its `mask`, `perm` or NULL, bias fp32 [cout] or NULL, out [n_out][cout] of
+ *                                out_dtype.
+ * Negative sizes, missing or misaligned pointers, a short buffer -> WCN_ERROR_INVALID_PARAMETERS; a shape outside the probe ->
+ * WCN_ERROR_UNSUPPORTED_CONFIG; both before any launch.  Nothing to compute (n = 0, n_out = 0) -> WCN_SUCCESS. */
+int wcn_conv_fp8_supported(int32_t cin, int32_t cout, int32_t num_offsets);
+size_t wcn_fp8_packed_weight_bytes(int32_t num_offsets, int32_t cin, int32_t cout);
+size_t wcn_fp8_amax_workspace(void);
+int wcn_fp8_amax_scale(const void* x, int64_t count, int32_t dtype, void* workspace, size_t workspace_bytes, float* scale,
+                       wcn_stream_t stream);
+int wcn_fp8_quantize_rows(const void* x, int64_t n, int32_t channels, int32_t dtype, const float* scale, void* out,
+                          int32_t out_pitch, wcn_stream_t stream);
+int wcn_fp8_pack_weight(const void* w, int32_t num_offsets, int32_t cin, int32_t cout, int32_t dtype, int32_t cin_padded,
+                        int32_t cout_padded, void* image, size_t image_bytes, float* w_scale, wcn_stream_t stream);
+int wcn_conv_gather_gemm_fp8(const void* xq, const float* x_scale, const void* w_image, const float* w_scale, void* out,
+                             const int32_t* nbr, const uint32_t* mask, const int32_t* perm, const float* bias, int64_t n_in,
+                             int64_t n_out, int32_t cin, int32_t cout, int32_t num_offsets, int32_t out_dtype,
+                             wcn_stream_t stream);
 
 #ifdef __cplusplus
 }

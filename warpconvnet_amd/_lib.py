@@ -19,7 +19,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("WARPCONVNET_AMD_LIB") or os.path.join(_CSRC, "libwcn_hip.so")
 
 WCN_F32, WCN_F16, WCN_BF16 = 0, 1, 2
-WCN_ALGO_AUTO, WCN_ALGO_REF, WCN_ALGO_MFMA, WCN_ALGO_MFMA_F32 = 0, 1, 2, 3
+WCN_ALGO_AUTO, WCN_ALGO_REF, WCN_ALGO_MFMA, WCN_ALGO_MFMA_F32, WCN_ALGO_MFMA_FP8 = 0, 1, 2, 3, 4
 WCN_FLAG_TABLE_FULL, WCN_FLAG_COORD_RANGE, WCN_FLAG_PAIR_OVERFLOW, WCN_FLAG_DUPLICATE_COORD = 1, 2, 4, 8
 WCN_FLAG_NEED_STRICT = 16
 WCN_FLAG_ROW_OVERFLOW = 32
@@ -143,6 +143,15 @@ SIGNATURES = {
     "wcn_mfma_wgrad_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_mfma_f32_gather_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_mfma_f32_wgrad_supported": (c_int, [c_int32, c_int32]),
+    "wcn_conv_fp8_supported": (c_int, [c_int32, c_int32, c_int32]),
+    "wcn_fp8_packed_weight_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "wcn_fp8_amax_workspace": (c_size_t, []),
+    "wcn_fp8_amax_scale": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "wcn_fp8_quantize_rows": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "wcn_fp8_pack_weight": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p,
+                                    c_void_p]),
+    "wcn_conv_gather_gemm_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "wcn_conv_identity_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_dense_rows_supported": (c_int, [c_int32, c_int32, c_int32]),
     "wcn_dense_rows": (

@@ -6,13 +6,16 @@ Mirrors the three algorithm knobs of the reference (`warpconvnet/constants.py:11
 * ``auto``          - static choice: the fused HIP kernels (no run-time sweep, so ranks never diverge)
 * ``hip_mfma``      - fused gather->MFMA->store kernels (bf16/fp16/fp32), gfx950
 * ``hip_mfma_f32``  - the same three products on true fp32 operands (fp32 MFMA); the compute dtype must be float32
+* ``hip_mfma_fp8``  - FP8 (E4M3) inference forward on the fp8 MFMA, dynamic per-tensor feature scale, per-channel weight scales;
+  a forward algorithm only (``WARPCONVNET_FWD_ALGO_MODE``)
 * ``hip_ref``       - simple one-thread-per-output HIP kernels (any channel count; slow, for bring-up)
 * ``explicit_gemm`` - gather / torch.matmul / index_add on the tensor's device (reference `explicit.py` semantics)
 """
 import os
 from typing import List, Optional
 
-VALID_ALGOS = ["auto", "hip_mfma", "hip_mfma_f32", "hip_ref", "explicit_gemm"]
+VALID_ALGOS = ["auto", "hip_mfma", "hip_mfma_f32", "hip_mfma_fp8", "hip_ref", "explicit_gemm"]
+VALID_BWD_ALGOS = [a for a in VALID_ALGOS if a != "hip_mfma_fp8"]
 
 
 def _env_choice(name: str, default: str, valid: Optional[List[str]] = None) -> str:
@@ -36,8 +39,8 @@ def _env_bool(name: str, default: bool) -> bool:
 
 
 WARPCONVNET_FWD_ALGO_MODE = _env_choice("WARPCONVNET_FWD_ALGO_MODE", "auto", VALID_ALGOS)
-WARPCONVNET_DGRAD_ALGO_MODE = _env_choice("WARPCONVNET_DGRAD_ALGO_MODE", "auto", VALID_ALGOS)
-WARPCONVNET_WGRAD_ALGO_MODE = _env_choice("WARPCONVNET_WGRAD_ALGO_MODE", "auto", VALID_ALGOS)
+WARPCONVNET_DGRAD_ALGO_MODE = _env_choice("WARPCONVNET_DGRAD_ALGO_MODE", "auto", VALID_BWD_ALGOS)
+WARPCONVNET_WGRAD_ALGO_MODE = _env_choice("WARPCONVNET_WGRAD_ALGO_MODE", "auto", VALID_BWD_ALGOS)
 
 # MFMA on CDNA4 always accumulates in fp32; the flag exists for API parity
 # (reference `constants.py:214, 251-271`) and is ignored by the kernels.

@@ -61,6 +61,54 @@ int wcn_mfma_f32_gather_supported(int32_t cin, int32_t cout, int32_t num_offsets
 }
 int wcn_mfma_f32_wgrad_supported(int32_t cin, int32_t cout) { return mfma_f32_wgrad_supported(cin, cout) ? 1 : 0; }
 
+// ---- FP8 (E4M3) inference forward (conv_mfma_fp8.hip): every refusal before any launch -----------------------------------------
+int wcn_conv_fp8_supported(int32_t cin, int32_t cout, int32_t num_offsets) {
+  return conv_fp8_supported(cin, cout, num_offsets) ? 1 : 0;
+}
+size_t wcn_fp8_packed_weight_bytes(int32_t num_offsets, int32_t cin, int32_t cout) {
+  return conv_fp8_supported(cin, cout, num_offsets) ? fp8_packed_weight_bytes(num_offsets, cin, cout) : 0;
+}
+size_t wcn_fp8_amax_workspace(void) { return fp8_amax_workspace(); }
+
+int wcn_fp8_amax_scale(const void* x, int64_t count, int32_t dtype, void* workspace, size_t workspace_bytes, float* scale,
+                       wcn_stream_t stream) {
+  if (count < 0 || !dtype_ok(dtype) || !scale || !workspace || workspace_bytes < fp8_amax_workspace() || !aligned_to(workspace, 4) ||
+      (count > 0 && !x))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  return fp8_amax_scale(x, count, dtype, workspace, scale, (hipStream_t)stream);  // (count = 0: scale 1)
+}
+
+int wcn_fp8_quantize_rows(const void* x, int64_t n, int32_t channels, int32_t dtype, const float* scale, void* out,
+                          int32_t out_pitch, wcn_stream_t stream) {
+  if (n < 0 || channels < 1 || !dtype_ok(dtype) || out_pitch < channels || out_pitch % 16 != 0) return WCN_ERROR_INVALID_PARAMETERS;
+  if (n == 0) return WCN_SUCCESS;
+  if (!x || !scale || !out || !aligned_to(x, 16) || !aligned_to(out, 16)) return WCN_ERROR_INVALID_PARAMETERS;
+  return fp8_quantize_rows(x, n, channels, dtype, scale, out, out_pitch, (hipStream_t)stream);
+}
+
+int wcn_fp8_pack_weight(const void* w, int32_t num_offsets, int32_t cin, int32_t cout, int32_t dtype, int32_t cin_padded,
+                        int32_t cout_padded, void* image, size_t image_bytes, float* w_scale, wcn_stream_t stream) {
+  if (num_offsets < 1 || cin < 1 || cout < 1 || !dtype_ok(dtype) || cin_padded < cin || cout_padded < cout)
+    return WCN_ERROR_INVALID_PARAMETERS;
+  if (!conv_fp8_supported(cin_padded, cout_padded, num_offsets)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (!w || !image || !w_scale || !aligned_to(image, 16) || image_bytes < fp8_packed_weight_bytes(num_offsets, cin_padded, cout_padded))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  return fp8_pack_weight(w, num_offsets, cin, cout, dtype, cin_padded, cout_padded, image, w_scale, (hipStream_t)stream);
+}
+
+int wcn_conv_gather_gemm_fp8(const void* xq, const float* x_scale, const void* w_image, const float* w_scale, void* out,
+                             const int32_t* nbr, const uint32_t* mask, const int32_t* perm, const float* bias, int64_t n_in,
+                             int64_t n_out, int32_t cin, int32_t cout, int32_t num_offsets, int32_t out_dtype,
+                             wcn_stream_t stream) {
+  if (n_in < 0 || n_out < 0 || cin < 1 || cout < 1 || num_offsets < 1 || !dtype_ok(out_dtype)) return WCN_ERROR_INVALID_PARAMETERS;
+  if (!conv_fp8_supported(cin, cout, num_offsets)) return WCN_ERROR_UNSUPPORTED_CONFIG;
+  if (n_out == 0) return WCN_SUCCESS;
+  if (!xq || !x_scale || !w_image || !w_scale || !out || !nbr || !mask || !aligned_to(xq, 16) || !aligned_to(w_image, 16))
+    return WCN_ERROR_INVALID_PARAMETERS;
+  return conv_gather_gemm_fp8(xq, x_scale, w_image, w_scale, out, nbr, mask, perm, bias, n_out, cin, cout, num_offsets, out_dtype,
+                              (hipStream_t)stream);
+}
+
 size_t wcn_packed_weight_bytes(int32_t num_offsets, int32_t cin, int32_t cout, int32_t dtype, int32_t transpose) {
   (void)transpose;  // cin / cout are the kernel-side roles already (reduce over cin, produce cout)
   if (num_offsets < 1 || cin < 1 || cout < 1 || !dtype_ok(dtype)) return 0;

@@ -3,6 +3,7 @@
 //   conv_mfma16.hip   16x16x32, same structure, the channel counts the others do not take
 //   conv_mfma_cs.hip  channel-split, rows staged through LDS (the headline shapes)
 //   conv_mfma_f32.hip 32x32x2 on fp32 operands, rows and the weight as stored staged through LDS
+//   conv_mfma_fp8.hip 32x32x64 on E4M3 operands (forward only), rows staged through LDS, weight fragments L2 -> VGPR
 // Every piece here is used as it is by at least two of them; what one family alone needs stays in its file.  The
 // prototypes at the end are the only declarations of the functions these files and conv_api.hip call across
 // translation units.
@@ -192,6 +193,19 @@ bool mfma_f32_gather_supported(int cin, int cout, int K);
 int conv_gather_gemm_f32(const float* in, const float* w, float* out, const int32_t* nbr, const uint32_t* mask,
                          const int32_t* perm, const float* bias, int64_t n_out, int cin, int cout, int K, int w_transposed,
                          int k_flip, hipStream_t s);
+
+// FP8 (E4M3) inference forward on v_mfma_f32_32x32x64_f8f6f4 (conv_mfma_fp8.hip): quantiser, weight image + scales, gather GEMM.
+// The callers (conv_api.hip) have checked pointers, sizes and the probe.
+bool conv_fp8_supported(int cin, int cout, int K);
+size_t fp8_packed_weight_bytes(int K, int cin, int cout);
+size_t fp8_amax_workspace();
+int fp8_amax_scale(const void* x, int64_t count, int dtype, void* workspace, float* scale, hipStream_t s);
+int fp8_quantize_rows(const void* x, int64_t n, int c, int dtype, const float* scale, void* out, int c_pad, hipStream_t s);
+int fp8_pack_weight(const void* w, int K, int cin, int cout, int dtype, int cin_p, int cout_p, void* image, float* w_scale,
+                    hipStream_t s);
+int conv_gather_gemm_fp8(const void* xq, const float* x_scale, const void* wq, const float* w_scale, void* out, const int32_t* nbr,
+                         const uint32_t* mask, const int32_t* perm, const float* bias, int64_t n_out, int cin, int cout, int K,
+                         int out_dtype, hipStream_t s);
 
 // weight packer (conv_mfma.hip); `w` fp32 (w_is_f32) or already in the 16-bit storage dtype
 int pack_weight_mfma(const void* w, int w_is_f32, int K, int cin, int cout, int dtype, int transpose, int flip, void* packed,

@@ -4,7 +4,7 @@ Same plug-in interface as the reference (`warpconvnet/nn/functional/sparse_conv/
 443-510`): ``FORWARD_BACKENDS[name](FwdCtx) -> Tensor | int``, ``BACKWARD_BACKENDS[name](BwdCtx) ->
 (Tensor | int | None, Tensor | None)``; a non-zero int status becomes a ``RuntimeError`` in
 ``run_forward`` / ``run_backward``.  Registered names: ``explicit_gemm``, ``hip_ref``, ``hip_mfma``,
-``hip_mfma_f32`` (true fp32 operands; the compute dtype must be float32), ``auto`` (static shape-class choice between the two HIP paths).
+``hip_mfma_f32`` (true fp32 operands; the compute dtype must be float32), ``hip_mfma_fp8`` (FP8 inference, forward only), ``auto`` (static shape-class choice between the two HIP paths).
 """
 import dataclasses
 import functools
@@ -104,9 +104,18 @@ def _hip_bwd(algo: str, ctx: BwdCtx):
     return dx, dw
 
 
-_HIP_ALGOS = ("hip_ref", "hip_mfma", "hip_mfma_f32", "auto")
-FORWARD_BACKENDS: Dict[str, FwdFn] = {"explicit_gemm": _fwd_explicit, **{a: functools.partial(_hip_fwd, a) for a in _HIP_ALGOS}}
-BACKWARD_BACKENDS: Dict[str, BwdFn] = {"explicit_gemm": _bwd_explicit, **{a: functools.partial(_hip_bwd, a) for a in _HIP_ALGOS}}
+def _fp8_fwd(ctx: FwdCtx):
+    # the weight goes in as it is: it is quantised from its own precision, and its image is cached on the parameter
+    dt = ctx.compute_dtype or ctx.in_features.dtype
+    out = hip_gemm.hip_forward(ctx.in_features.to(dt), ctx.weight, ctx.kernel_map, ctx.num_out_coords, "hip_mfma_fp8", bias=ctx.bias)
+    return out.to(ctx.in_features.dtype) if ctx.compute_dtype is not None else out
+
+
+_HIP_ALGOS = ("hip_ref", "hip_mfma", "hip_mfma_f32", "hip_mfma_fp8", "auto")
+_HIP_BWD_ALGOS = tuple(a for a in _HIP_ALGOS if a != "hip_mfma_fp8")  # FP8 is a forward (inference) algorithm only
+FORWARD_BACKENDS: Dict[str, FwdFn] = {"explicit_gemm": _fwd_explicit, **{a: functools.partial(_hip_fwd, a) for a in _HIP_ALGOS},
+                                      "hip_mfma_fp8": _fp8_fwd}
+BACKWARD_BACKENDS: Dict[str, BwdFn] = {"explicit_gemm": _bwd_explicit, **{a: functools.partial(_hip_bwd, a) for a in _HIP_BWD_ALGOS}}
 
 
 def _hip_algo(algo: str, t: Tensor) -> bool:

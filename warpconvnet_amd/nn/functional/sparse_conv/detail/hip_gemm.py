@@ -3,6 +3,8 @@
 * ``hip_mfma`` - fused gather -> MFMA -> store kernels (`csrc/conv_mfma.hip`, `csrc/wgrad_mfma.hip`)
 * ``hip_mfma_f32`` - the three products on true fp32 operands, `v_mfma_f32_32x32x2_f32` (`csrc/conv_mfma_f32.hip`); the weight
   is read as stored (no packed image); float32 only, any other dtype raises
+* ``hip_mfma_fp8`` - inference forward on FP8 (E4M3) operands, `v_mfma_f32_32x32x64_f8f6f4` (`csrc/conv_mfma_fp8.hip`): the features
+  are quantised per call with one scale per tensor, the weight once with one scale per output channel; forward only
 * ``hip_ref``  - simple kernels for any channel count / fp32 (`csrc/conv_ref.hip`)
 * ``auto``     - ``hip_mfma`` when the shape is covered, else ``hip_ref``; a pure function of
   (C_in, C_out, K, dtype), so every rank of a data-parallel job takes the same path.
@@ -107,8 +109,10 @@ def _via_fp16(a: Tensor, b: Tensor, launch) -> Tensor:
 # kernels take and the result is cut back: zeros contribute nothing to any of the three products, so the values are those of the
 # unpadded problem (same fp32 accumulation), at the cost of one padded copy of the operands.
 # ``native_f32``: fp32 operands as they are on the fp32 MFMA kernels (``hip_mfma_f32``), channels zero-padded to their shapes.
-_NATIVE, _REF, _VIA_FP16, _PADDED, _NATIVE_F32 = "native", "ref", "via_fp16", "padded", "native_f32"
+# ``fp8``: E4M3 operands on the fp8 MFMA kernel (``hip_mfma_fp8``, forward only), Cin zero-padded to 64, Cout to 32.
+_NATIVE, _REF, _VIA_FP16, _PADDED, _NATIVE_F32, _FP8 = "native", "ref", "via_fp16", "padded", "native_f32", "fp8"
 _F32_ALGO = "hip_mfma_f32"
+_FP8_ALGO = "hip_mfma_fp8"
 _MFMA_COUTS = (16, 32, 48, 64, 96, 128, 160, 192, 256, 384, 512)
 
 
@@ -134,12 +138,32 @@ def _f32_plan(what: str, kin: int, kout: int, dtype: torch.dtype, ok):
     return _NATIVE_F32, _lib.WCN_ALGO_MFMA_F32, kin_p, kout_p
 
 
+def _fp8_plan(kin: int, kout: int, K: int, dtype: torch.dtype):
+    """The ``hip_mfma_fp8`` treatment: kin padded to 64, kout to 32; features fp16 / bf16 / fp32."""
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise RuntimeError(f"{_FP8_ALGO} forward: features must be float16, bfloat16 or float32, got {dtype}")
+    kin_p, kout_p = (kin + 63) // 64 * 64, (kout + 31) // 32 * 32
+    if not _lib.lib().wcn_conv_fp8_supported(kin_p, kout_p, K):
+        raise RuntimeError(f"{_FP8_ALGO} forward: {_lib.status_string(-4)} (cin={kin}, cout={kout}, K={K})")
+    return _FP8, _lib.WCN_ALGO_MFMA_FP8, kin_p, kout_p
+
+
+def refuse_fp8_grad(*tensors: Optional[Tensor]) -> None:
+    """``hip_mfma_fp8`` is forward only: with autograd recording and an operand that requires grad it raises rather than return
+    a result whose gradient is silently absent."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{_FP8_ALGO} is an inference (forward-only) algorithm: run it under torch.no_grad() or on operands "
+                           f"that do not require grad")
+
+
 @functools.lru_cache(maxsize=None)
 def _gather_plan(algo: str, kin: int, kout: int, K: int, dtype: torch.dtype, on_gpu: bool):
     """``(treatment, algorithm code, kin, kout as launched)`` of a forward (kin = Cin) or dgrad (kin = Cout: it reduces over Cout
     and produces Cin) product.  A pure function of its arguments, memoised: asked on every call of every layer."""
     if algo == _F32_ALGO:
         return _f32_plan("gather", kin, kout, dtype, lambda a, b: bool(_lib.lib().wcn_mfma_f32_gather_supported(a, b, K)))
+    if algo == _FP8_ALGO:
+        return _fp8_plan(kin, kout, K, dtype)
     if algo == "auto" and on_gpu and not _gather_ok(kin, kout, K, _code16(dtype)) and dtype in (torch.float16, torch.bfloat16):
         # the smallest MFMA shape that contains kin x kout (fp32 features keep full fp32 operands on such shapes instead)
         kin_p = max(32, (kin + 31) // 32 * 32)
@@ -362,12 +386,18 @@ def hip_forward(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult
                 algo: str = "auto", bias: Optional[Tensor] = None, want_dgrad_image: bool = False) -> Tensor:
     """y[m] = sum_k x[nbr[m][k]] @ w[k] (+ bias, fused into the epilogue in fp32).  ``want_dgrad_image``: a backward with an input
     gradient follows (the autograd Function says so) - the dgrad weight image is packed in the forward image's launch."""
+    if algo == _FP8_ALGO:
+        refuse_fp8_grad(in_features, weight, bias)
+        if not in_features.is_cuda:
+            raise RuntimeError(f"{_FP8_ALGO}: in_features must live on a GPU (got {in_features.device}); there is no CPU fallback")
     if bias is not None:
         bias = bias.detach()
         if bias.dtype != torch.float32:
             bias = bias.float()
         bias = _prep(bias, "bias")
     x, w = _prep(in_features, "in_features"), _prep(weight, "weight")
+    if algo == _FP8_ALGO:
+        return _forward_fp8_dynamic(x, w, weight, kernel_map, num_out_coords, bias)
     if x.dtype != w.dtype and not master_weight_ok(x.dtype, w, algo, False):
         raise RuntimeError(f"hip forward error: {_lib.status_string(-6)} ({x.dtype} vs {w.dtype})")
     K, cin, cout = w.shape
@@ -395,6 +425,58 @@ def hip_forward(in_features: Tensor, weight: Tensor, kernel_map: IntSearchResult
     if kernel_map.validate():
         y = launch()
     return _fit(y, cout) if padded else y
+
+
+def hip_forward_fp8(xq: Tensor, x_scale: Tensor, wq_image: Tensor, w_scale: Tensor, kernel_map: IntSearchResult, num_out: int,
+                    bias: Optional[Tensor] = None, out_dtype: torch.dtype = torch.float16) -> Tensor:
+    """The FP8 forward on pre-quantised operands: ``y[m, c] = x_scale * w_scale[c] * sum_k xq[nbr[m][k]] . wq[k][:, c] (+ bias[c])``
+    in ``out_dtype``.  ``xq``: E4M3 rows [N_in, Cin_p] (uint8 or float8_e4m3fn storage, Cin_p % 64 == 0); ``x_scale``: fp32 device
+    scalar; ``wq_image`` / ``w_scale``: `fp8_utils.pack_weight_e4m3` ([K, Cin_p, Cout_p] bytes in fragment order, fp32 [Cout_p]);
+    ``bias``: fp32 [Cout_p] or None.  Returns [num_out, Cout_p]."""
+    xq, wq_image = _prep(xq, "xq"), _prep(wq_image, "wq_image")
+    x_scale, w_scale = _prep(x_scale, "x_scale"), _prep(w_scale, "w_scale")
+    K, cin_p, cout_p = wq_image.shape
+    if xq.element_size() != 1 or wq_image.element_size() != 1 or x_scale.dtype != torch.float32 or w_scale.dtype != torch.float32:
+        raise RuntimeError(f"{_FP8_ALGO}: operands are one-byte E4M3 values, scales float32")
+    if xq.shape[1] != cin_p or w_scale.numel() != cout_p or x_scale.numel() != 1 or K != len(kernel_map):
+        raise RuntimeError(f"{_FP8_ALGO}: operand shapes do not match (xq {tuple(xq.shape)}, image {tuple(wq_image.shape)})")
+    if bias is not None:
+        bias = _prep(bias.detach().float(), "bias")
+        if bias.numel() != cout_p:
+            raise RuntimeError(f"{_FP8_ALGO}: bias has {bias.numel()} entries, the image {cout_p} columns")
+    attach_tables_from_csr(kernel_map, xq.shape[0], num_out)
+
+    def launch():
+        tb, mk = own_tables(kernel_map, cin_p, cout_p, K, out_dtype, mfma=False)  # the dense table and its mask
+        out = torch.empty((num_out, cout_p), dtype=out_dtype, device=xq.device)
+        _lib.check(
+            _lib.lib().wcn_conv_gather_gemm_fp8(
+                _lib.ptr(xq), _lib.ptr(x_scale), _lib.ptr(wq_image), _lib.ptr(w_scale), _lib.ptr(out), _lib.ptr(tb), _lib.ptr(mk),
+                _lib.ptr(kernel_map._perm), _lib.ptr(bias), xq.shape[0], num_out, cin_p, cout_p, K, _lib.dtype_code(out_dtype),
+                _lib.stream_handle(xq.device)),
+            "wcn_conv_gather_gemm_fp8",
+        )
+        return out
+
+    y = launch()
+    if kernel_map.validate():  # (an optimistic map whose build had to be redone: as in `hip_forward`)
+        y = launch()
+    return y
+
+
+def _forward_fp8_dynamic(x: Tensor, w: Tensor, weight: Tensor, kernel_map: IntSearchResult, num_out: int,
+                         bias: Optional[Tensor]) -> Tensor:
+    """``hip_mfma_fp8`` on unquantised operands: the features are quantised for this call (two launches, no host read), the weight
+    image and its scales are cached on the weight's version like the packed 16-bit images."""
+    from warpconvnet_amd.nn.functional.fp8_utils import pack_weight_e4m3, quantize_rows_e4m3
+
+    K, cin, cout = w.shape
+    assert K == len(kernel_map) and cin == x.shape[1]
+    _, _, cin_p, cout_p = _gather_plan(_FP8_ALGO, cin, cout, K, x.dtype, True)
+    image, w_scale = _cached_image(weight, _FP8, lambda keep: {_FP8: pack_weight_e4m3(w)})
+    xq, x_scale = quantize_rows_e4m3(x, cin_p)
+    y = hip_forward_fp8(xq, x_scale, image, w_scale, kernel_map, num_out, _fit(bias, cout_p), out_dtype=x.dtype)
+    return _fit(y, cout) if cout_p != cout else y
 
 
 def hip_colsum(t: Tensor) -> Tensor:

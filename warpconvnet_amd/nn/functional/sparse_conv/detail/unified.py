@@ -26,6 +26,7 @@ class SPARSE_CONV_AB_ALGO_MODE(Enum):
     HIP_REF = "hip_ref"
     HIP_MFMA = "hip_mfma"
     HIP_MFMA_F32 = "hip_mfma_f32"
+    HIP_MFMA_FP8 = "hip_mfma_fp8"  # FP8 (E4M3) inference: a forward algorithm only
     AUTO = "auto"
 
 
@@ -79,7 +80,12 @@ class UnifiedSpatiallySparseConvFunction(Function):
         ctx.dgrad_algo = _algo_name(dgrad_algo, on_gpu)
         ctx.wgrad_algo = _algo_name(wgrad_algo, on_gpu)
         ctx.weight_dtype = weight.dtype
-        if compute_dtype is not None and weight.dtype != compute_dtype and weight.is_floating_point():
+        # FP8 is an inference algorithm: `spatially_sparse_conv` refuses operands that require grad (the caller's grad mode is not
+        # visible in here); a backward that is reached all the same raises instead of differentiating another function
+        fp8 = ctx.fwd_fp8 = _algo_name(fwd_algo, on_gpu) == "hip_mfma_fp8"
+        if fp8:
+            pass  # the weight is quantised from its own precision (and its image cached on the parameter): no cast
+        elif compute_dtype is not None and weight.dtype != compute_dtype and weight.is_floating_point():
             from .hip_gemm import master_weight_ok
 
             fa, da = _algo_name(fwd_algo, on_gpu), ctx.dgrad_algo
@@ -101,6 +107,8 @@ class UnifiedSpatiallySparseConvFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_output: Tensor):
+        if ctx.fwd_fp8:
+            raise RuntimeError("hip_mfma_fp8 is an inference (forward-only) algorithm: it has no backward")
         in_features, weight = ctx.saved_tensors  # read exactly once (activation-checkpointing contract)
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_db = ctx.has_bias and len(ctx.needs_input_grad) > 14 and ctx.needs_input_grad[14]

@@ -198,6 +198,11 @@ def spatially_sparse_conv(
                 out = out + bias.to(out.dtype)
         return input_sparse_tensor.replace(batched_features=out)
 
+    if str(getattr(fwd_algo, "value", fwd_algo)).lower() == "hip_mfma_fp8":  # forward only: no silently missing gradient
+        from warpconvnet_amd.nn.functional.sparse_conv.detail.hip_gemm import refuse_fp8_grad
+
+        refuse_fp8_grad(input_sparse_tensor.feature_tensor, weight, bias)
+
     in_tensor_stride = input_sparse_tensor.tensor_stride or ntuple(1, ndim=nd)
     if transposed and not generative:
         assert output_spatially_sparse_tensor is not None, (
