@@ -1441,15 +1441,36 @@ int wcn_attn_varlen_kv_bwd_s(const void* dout, const void* q, int64_t q_stride, 
  * The separate-operand attention above for head_dim = 128, fp16 / bf16: a work item (sequence, 32-row block, head) is run by
  * two waves, each on 64 columns of the head, which exchange their partial 32 x 32 score tiles through LDS.  Operands,
  * boundaries, strides, outputs, the empty-side conventions and determinism are those of wcn_attn_varlen_kv_fwd_s / _kv_bwd_s,
- * whose arguments these take minus `variant` (there is no shared-tile variant at this size); a packed [T, 3, H, 128] tensor is
+ * whose arguments these take minus `variant` (they run under WCN_ATTN_AUTO); a packed [T, 3, H, 128] tensor is
  * the same call with q_stride = kv_stride = 3 * heads * 128 and cu_q = cu_k.  k_splits / q_splits: 0 = the rules
  * wcn_attn_varlen_k_splits / wcn_attn_varlen_kv_splits, 1 = no split; the workspace is what
  * wcn_attn_varlen_ksplit_workspace_bytes(total_q, total_k, heads, 128, q_splits, k_splits, direction) reports (splits as
  * resolved), 16-byte aligned - the forward needs none at k_splits = 1.
  *   wcn_attn_d128_supported   host-only: 1 for head_dim 128 with WCN_F16 / WCN_BF16, 0 otherwise.
+ *   wcn_attn_d128_fwd_v / _bwd_v   the same calls with `variant` (enum wcn_attn_variant) before `stream`.  WCN_ATTN_ONE_WAVE:
+ *                             the wave-pair kernels above.  WCN_ATTN_SHARED: workgroups of four wave pairs on a work item
+ *                             (sequence, 128-row block, head [, split share]) that stage every 32-row tile of the swept side
+ *                             once in LDS for all their pairs; each wave issues the pair kernels' arithmetic on its rows and
+ *                             columns, so out, lse, dq, dk and dv carry the same bits under either variant, with the same
+ *                             splits and workspace.  Another value -> WCN_ERROR_INVALID_PARAMETERS.
+ *   wcn_attn_d128_variant     host-only: what WCN_ATTN_AUTO resolves to at this head size for `direction` (0 = forward, 1 =
+ *                             backward), a pure function of these numbers over the longest swept side, as
+ *                             wcn_attn_varlen_variant: the measured rule of DESIGN.md 4.37 (WCN_ATTN_ONE_WAVE for an empty
+ *                             call).
  * Before any launch: missing pointers, negative sizes or splits, a NaN scale, bad strides or alignment, a short workspace ->
  * WCN_ERROR_INVALID_PARAMETERS; another head size or dtype -> WCN_ERROR_UNSUPPORTED_CONFIG; nothing to compute -> success. */
 int wcn_attn_d128_supported(int32_t head_dim, int32_t dtype);
+int32_t wcn_attn_d128_variant(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads, int32_t direction);
+int wcn_attn_d128_fwd_v(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* cu_q,
+                        const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
+                        int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* out, float* lse,
+                        int32_t k_splits, void* workspace, size_t workspace_bytes, int32_t variant, wcn_stream_t stream);
+int wcn_attn_d128_bwd_v(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                        const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                        int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                        int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk, void* dv,
+                        int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace, size_t workspace_bytes,
+                        int32_t variant, wcn_stream_t stream);
 int wcn_attn_d128_fwd(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* cu_q,
                       const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
                       int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* out, float* lse,

@@ -27,7 +27,8 @@
 // side's end exits for both waves together.  The transposed images are private to a wave: its LDS accesses complete in
 // program order, and the barrier of every tile orders them as well.
 // Split sweeps: q_splits (dK/dV) and k_splits (forward, dQ) with the shares, the fp32 partial layouts and the combine /
-// reduce kernels of attn_varlen.h, instantiated at 128.  There is no four-wave shared-tile variant at this head size.
+// reduce kernels of attn_varlen.h, instantiated at 128.  The shared-tile variant (WCN_ATTN_SHARED) is attn_varlen_d128_shared.hip;
+// the entry points below choose between the two (wcn_attn_d128_variant).
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage --offload-arch=gfx950; bf16 and f16 alike; VGPRs + AGPRs, LDS
 // per workgroup, waves per SIMD by registers, workgroups per CU by the 160 KiB of LDS):
 //   forward          112 + 32   25 600 B   3 per SIMD   6 workgroups = 12 waves per CU: both limits agree
@@ -39,33 +40,9 @@
 //   delta 17, combine 28, reduce 22 VGPRs at D = 128, no LDS.
 // None spills to scratch (ScratchSize 0, no VGPR or SGPR spill).  fp32 arithmetic of this file stays scalar (no packed
 // fp32 instructions: see the Makefile).
-#include "attn_varlen.h"
+#include "attn_varlen_d128.h"
 
 namespace wcn {
-
-constexpr int kPairThreads = 128;                     // two waves
-constexpr int kPairCols = 64;                         // columns of the head one wave owns
-constexpr int kPairTr = kPairCols * kAttnPitch;       // elements of a wave's transposed image of its columns
-constexpr int kPairTile = kAttnTile * kAttnTile;      // floats of an exchanged score tile
-constexpr int64_t kAttnPairMaxGrid = 1 << 22;         // workgroups of one grid; the kernels stride beyond it
-
-// A wave's partial score tile into its exchange slot: piece g of lane l at float 4 (64 g + l).
-__device__ __forceinline__ void put_tile(float* __restrict__ slot, const a_f32x16& t, int lane) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-    *reinterpret_cast<float4*>(slot + 4 * (64 * g + lane)) = make_float4(t[4 * g], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3]);
-}
-// own + partner, element by element (the same bits in both waves).
-__device__ __forceinline__ void add_tile(a_f32x16& t, const float* __restrict__ slot, int lane) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4 x = *reinterpret_cast<const float4*>(slot + 4 * (64 * g + lane));
-    t[4 * g] = t[4 * g] + x.x;
-    t[4 * g + 1] = t[4 * g + 1] + x.y;
-    t[4 * g + 2] = t[4 * g + 2] + x.z;
-    t[4 * g + 3] = t[4 * g + 3] + x.w;
-  }
-}
 
 // ---- forward --------------------------------------------------------------------------------------------------------
 template <typename T, bool KSPLIT>
@@ -387,7 +364,6 @@ __global__ __launch_bounds__(kPairThreads) void attn_pair_dq_kernel(const AttnOp
 
 // ---- host -----------------------------------------------------------------------------------------------------------
 static inline int pair_blocks(int max_seqlen) { return (max_seqlen + kAttnTile - 1) / kAttnTile; }
-static inline unsigned pair_grid(int64_t items) { return (unsigned)(items < kAttnPairMaxGrid ? items : kAttnPairMaxGrid); }
 
 // k_splits > 1: the split-key kernel into the partials `ks`, then the combine; 1: the unsplit kernel.
 template <typename T>
@@ -463,11 +439,32 @@ int wcn_attn_d128_supported(int32_t head_dim, int32_t dtype) {
   return head_dim == 128 && (dtype == WCN_F16 || dtype == WCN_BF16) ? 1 : 0;
 }
 
+// What WCN_ATTN_AUTO resolves to at this head size: the shared-tile kernels from the shortest measured swept length at which
+// they were ahead of the pair kernels in both directions by more than the spread of the rounds (8 192 rows;
+// at 2 048 the forward + backward lead of 2 % is inside the spread), the pair kernels below it.
+constexpr int32_t kD128SharedMinSweep = 8192;
+static bool d128_variant_ok(int32_t v) { return v == WCN_ATTN_AUTO || v == WCN_ATTN_ONE_WAVE || v == WCN_ATTN_SHARED; }
+
+int32_t wcn_attn_d128_variant(int64_t num_seqs, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t heads, int32_t direction) {
+  if (num_seqs < 1 || max_seqlen_q < 1 || max_seqlen_k < 1 || heads < 1) return WCN_ATTN_ONE_WAVE;
+  const int32_t sweep = direction == 0 ? max_seqlen_k : (max_seqlen_q > max_seqlen_k ? max_seqlen_q : max_seqlen_k);
+  return sweep >= kD128SharedMinSweep ? WCN_ATTN_SHARED : WCN_ATTN_ONE_WAVE;
+}
+
 int wcn_attn_d128_fwd(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* cu_q,
                       const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
                       int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* out, float* lse,
                       int32_t k_splits, void* workspace, size_t workspace_bytes, wcn_stream_t stream) {
-  if (k_splits < 0) return WCN_ERROR_INVALID_PARAMETERS;
+  return wcn_attn_d128_fwd_v(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim, max_seqlen_q,
+                             max_seqlen_k, softmax_scale, dtype, out, lse, k_splits, workspace, workspace_bytes, WCN_ATTN_AUTO,
+                             stream);
+}
+
+int wcn_attn_d128_fwd_v(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* cu_q,
+                        const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim,
+                        int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* out, float* lse,
+                        int32_t k_splits, void* workspace, size_t workspace_bytes, int32_t variant, wcn_stream_t stream) {
+  if (!d128_variant_ok(variant) || k_splits < 0) return WCN_ERROR_INVALID_PARAMETERS;
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, wcn_attn_d128_supported(head_dim, dtype));
   if (st != WCN_SUCCESS) return st;
@@ -481,6 +478,8 @@ int wcn_attn_d128_fwd(const void* q, int64_t q_stride, const void* k, const void
   // o [k_splits, total_q, heads, 128] first, ml [k_splits, total_q, heads, 2] after it (the layout of the narrower heads)
   float* o = (float*)workspace;
   const AttnKSplit ks{k_splits, total_q, o, o + (size_t)k_splits * (size_t)total_q * (size_t)heads * (size_t)head_dim};
+  if (variant == WCN_ATTN_AUTO) variant = wcn_attn_d128_variant(num_seqs, max_seqlen_q, max_seqlen_k, heads, 0);
+  if (variant == WCN_ATTN_SHARED) return attn_wg_fwd(dtype, c, out, lse, ks, (hipStream_t)stream);
   return with_dtype16(dtype, [&](auto t) { return attn_pair_fwd_t<decltype(t)>(c, out, lse, ks, (hipStream_t)stream); });
 }
 
@@ -490,7 +489,18 @@ int wcn_attn_d128_bwd(const void* dout, const void* q, int64_t q_stride, const v
                       int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk, void* dv,
                       int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace, size_t workspace_bytes,
                       wcn_stream_t stream) {
-  if (k_splits < 0 || q_splits < 0) return WCN_ERROR_INVALID_PARAMETERS;
+  return wcn_attn_d128_bwd_v(dout, q, q_stride, k, v, kv_stride, out, lse, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
+                             max_seqlen_q, max_seqlen_k, softmax_scale, dtype, dq, dq_stride, dk, dv, dkv_stride, q_splits, k_splits,
+                             workspace, workspace_bytes, WCN_ATTN_AUTO, stream);
+}
+
+int wcn_attn_d128_bwd_v(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                        const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                        int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                        int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk, void* dv,
+                        int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace, size_t workspace_bytes,
+                        int32_t variant, wcn_stream_t stream) {
+  if (!d128_variant_ok(variant) || k_splits < 0 || q_splits < 0) return WCN_ERROR_INVALID_PARAMETERS;
   const int st = attn_kv_check(q, q_stride, k, v, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, head_dim,
                                max_seqlen_q, max_seqlen_k, softmax_scale, wcn_attn_d128_supported(head_dim, dtype));
   if (st != WCN_SUCCESS) return st;
@@ -515,6 +525,9 @@ int wcn_attn_d128_bwd(const void* dout, const void* q, int64_t q_stride, const v
   const AttnKSplit ks{k_splits, total_q, (float*)((char*)workspace + (need - delta_bytes - dq_bytes)), nullptr};
   const AttnCall c{q, k, v, q_stride, kv_stride, cu_q, cu_k, num_seqs, total_q, total_k, heads, max_seqlen_q, max_seqlen_k,
                    softmax_scale};
+  if (variant == WCN_ATTN_AUTO) variant = wcn_attn_d128_variant(num_seqs, max_seqlen_q, max_seqlen_k, heads, 1);
+  if (variant == WCN_ATTN_SHARED)
+    return attn_wg_bwd(dtype, c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, ks, (hipStream_t)stream);
   return with_dtype16(dtype, [&](auto t) {
     return attn_pair_bwd_t<decltype(t)>(c, dout, out, lse, dq, dq_stride, dk, dv, dkv_stride, q_splits, part, delta, ks,
                                         (hipStream_t)stream);

@@ -3,8 +3,8 @@ tensor (self-attention inside patches or batch elements) and with separate query
 
 The reference's PatchAttention (`nn/modules/attention.py:496`) runs ``flash_attn.flash_attn_varlen_qkvpacked_func``
 (wrapped in `nn/functional/flash_attn_utils.py:15-82`), a CUDA-only package.  ``flash_attn_varlen_qkvpacked`` is the
-same call on gfx950: fp16 / bf16, head_dim 16 / 32 / 64 - and 128 on the wave-pair kernels of
-`csrc/attn_varlen_d128.hip` - no dropout; anything else raises (there is no fallback to eager attention).
+same call on gfx950: fp16 / bf16, head_dim 16 / 32 / 64 - and 128 on the kernels of
+`csrc/attn_varlen_d128.hip` and `csrc/attn_varlen_d128_shared.hip` - no dropout; anything else raises (there is no fallback to eager attention).
 ``varlen_attention_reference`` is a plain per-sequence torch implementation in fp32 / fp64 for CPU tensors that ask for it
 and for the tests.
 
@@ -124,21 +124,17 @@ def _variant_code(variant) -> int:
 
 def _check_head(name: str, t: Tensor, variant: int) -> None:
     """Raises unless a kernel family serves the head size of ``t`` [.., H, D]: 16 / 32 / 64 anywhere, 128 on a GPU tensor
-    (the wave-pair kernels, which have no shared-tile variant)."""
+    (the wave-pair kernels as ``"one_wave"``, workgroups of wave pairs on staged tiles as ``"shared"``)."""
     d = t.shape[-1]
-    if hip_attn_d128_supported(d, t.dtype):
-        if variant == _lib.WCN_ATTN_SHARED:
-            raise NotImplementedError(f"{name}: head_dim {d} runs on the wave-pair kernels, which have no shared-tile variant "
-                                      "(variant must be 'auto' or 'one_wave')")
-        if t.is_cuda:
-            return
+    if hip_attn_d128_supported(d, t.dtype) and t.is_cuda:
+        return
     if not hip_attn_varlen_supported(d, t.dtype):
         raise NotImplementedError(f"{name}: head_dim {d} is not supported (16, 32 or 64)")
 
 
 def _d128_fwd(q: Tensor, k: Tensor, v: Tensor, cu_q: Tensor, cu_k: Tensor, max_q: int, max_k: int, scale: float,
-              k_splits: int) -> Tuple[Tensor, Tensor, int]:
-    """``wcn_attn_d128_fwd`` on [T, H, 128] row views (``k`` and ``v`` with one common row stride) -> out, lse and the
+              k_splits: int, variant: int = _lib.WCN_ATTN_AUTO) -> Tuple[Tensor, Tensor, int]:
+    """``wcn_attn_d128_fwd_v`` on [T, H, 128] row views (``k`` and ``v`` with one common row stride) -> out, lse and the
     split count as resolved (0: the library's rule), which the backward's dQ sweep uses too."""
     tq, h, d = q.shape
     dev = q.device
@@ -149,17 +145,18 @@ def _d128_fwd(q: Tensor, k: Tensor, v: Tensor, cu_q: Tensor, cu_k: Tensor, max_q
     lse = torch.empty(tq, h, dtype=torch.float32, device=dev)
     ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, k.shape[0], h, d, 1, k_splits, 0), dtype=torch.uint8, device=dev)
     _lib.check(
-        L.wcn_attn_d128_fwd(_lib.ptr(q), _row_stride(q), _lib.ptr(k), _lib.ptr(v), _row_stride(k), _lib.ptr(cu_q), _lib.ptr(cu_k),
-                            cu_q.numel() - 1, tq, k.shape[0], h, d, max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(out),
-                            _lib.ptr(lse), k_splits, _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
-        "wcn_attn_d128_fwd",
+        L.wcn_attn_d128_fwd_v(_lib.ptr(q), _row_stride(q), _lib.ptr(k), _lib.ptr(v), _row_stride(k), _lib.ptr(cu_q),
+                              _lib.ptr(cu_k), cu_q.numel() - 1, tq, k.shape[0], h, d, max_q, max_k, scale, _lib.dtype_code(q.dtype),
+                              _lib.ptr(out), _lib.ptr(lse), k_splits, _lib.ptr(ws), ws.numel(), variant, _lib.stream_handle(dev)),
+        "wcn_attn_d128_fwd_v",
     )
     return out, lse, k_splits
 
 
 def _d128_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, cu_q: Tensor, cu_k: Tensor, max_q: int,
-              max_k: int, scale: float, dq: Tensor, dk: Tensor, dv: Tensor, q_splits: int, k_splits: int) -> None:
-    """``wcn_attn_d128_bwd`` into the [T, H, 128] row views ``dq``, ``dk``, ``dv`` (``dk`` and ``dv`` with one row stride)."""
+              max_k: int, scale: float, dq: Tensor, dk: Tensor, dv: Tensor, q_splits: int, k_splits: int,
+              variant: int = _lib.WCN_ATTN_AUTO) -> None:
+    """``wcn_attn_d128_bwd_v`` into the [T, H, 128] row views ``dq``, ``dk``, ``dv`` (``dk`` and ``dv`` with one row stride)."""
     tq, h, d = q.shape
     tk = k.shape[0]
     dev = q.device
@@ -168,11 +165,11 @@ def _d128_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: T
         q_splits = L.wcn_attn_varlen_kv_splits(cu_q.numel() - 1, max_q, max_k, h)
     ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, tk, h, d, q_splits, k_splits, 1), dtype=torch.uint8, device=dev)
     _lib.check(
-        L.wcn_attn_d128_bwd(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(k), _lib.ptr(v), _row_stride(k), _lib.ptr(out),
-                            _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h, d, max_q, max_k, scale,
-                            _lib.dtype_code(q.dtype), _lib.ptr(dq), _row_stride(dq), _lib.ptr(dk), _lib.ptr(dv), _row_stride(dk),
-                            q_splits, k_splits, _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev)),
-        "wcn_attn_d128_bwd",
+        L.wcn_attn_d128_bwd_v(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(k), _lib.ptr(v), _row_stride(k), _lib.ptr(out),
+                              _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h, d, max_q, max_k, scale,
+                              _lib.dtype_code(q.dtype), _lib.ptr(dq), _row_stride(dq), _lib.ptr(dk), _lib.ptr(dv), _row_stride(dk),
+                              q_splits, k_splits, _lib.ptr(ws), ws.numel(), variant, _lib.stream_handle(dev)),
+        "wcn_attn_d128_bwd_v",
     )
 
 
@@ -182,8 +179,8 @@ class _VarlenAttention(Function):
         t, _, h, d = qkv.shape
         dev = qkv.device
         ctx.max_seqlen, ctx.scale, ctx.variant = int(max_seqlen), float(scale), variant
-        if d == 128:  # the wave-pair kernels, the three slots as separate operands
-            out, lse, _ = _d128_fwd(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu, cu, ctx.max_seqlen, ctx.max_seqlen, ctx.scale, 1)
+        if d == 128:  # the head-size-128 kernels, the three slots as separate operands
+            out, lse, _ = _d128_fwd(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu, cu, ctx.max_seqlen, ctx.max_seqlen, ctx.scale, 1, variant)
             ctx.save_for_backward(qkv, cu, out, lse)
             return out
         out = torch.empty(t, h, d, dtype=qkv.dtype, device=dev)
@@ -214,7 +211,7 @@ class _VarlenAttention(Function):
         dqkv = torch.empty_like(qkv)
         if d == 128:
             _d128_bwd(dout, qkv[:, 0], qkv[:, 1], qkv[:, 2], out, lse, cu, cu, ctx.max_seqlen, ctx.max_seqlen, ctx.scale,
-                      dqkv[:, 0], dqkv[:, 1], dqkv[:, 2], 1, 1)
+                      dqkv[:, 0], dqkv[:, 1], dqkv[:, 2], 1, 1, ctx.variant)
             return dqkv, None, None, None, None
         L = _lib.lib()
         ws = torch.empty(L.wcn_attn_varlen_workspace_bytes(t, h), dtype=torch.uint8, device=dev)
@@ -332,8 +329,8 @@ class _CrossVarlenAttention(Function):
         dev = q.device
         ctx.args = (max_q, max_k, scale, q_splits)
         ctx.variant = variant
-        if d == 128:  # the wave-pair kernels
-            out, lse, ctx.k_splits = _d128_fwd(q, kk, vv, cu_q, cu_k, max_q, max_k, scale, k_splits)
+        if d == 128:  # the head-size-128 kernels
+            out, lse, ctx.k_splits = _d128_fwd(q, kk, vv, cu_q, cu_k, max_q, max_k, scale, k_splits, variant)
             ctx.save_for_backward(q, k, v, cu_q, cu_k, out, lse)
             return out
         out = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
@@ -381,7 +378,8 @@ class _CrossVarlenAttention(Function):
         L = _lib.lib()
         splits = q_splits if q_splits > 0 else L.wcn_attn_varlen_kv_splits(cu_q.numel() - 1, max_q, max_k, h)
         if d == 128:
-            _d128_bwd(dout, q, kk, vv, out, lse, cu_q, cu_k, max_q, max_k, scale, dq, dk, dv, splits, ctx.k_splits)
+            _d128_bwd(dout, q, kk, vv, out, lse, cu_q, cu_k, max_q, max_k, scale, dq, dk, dv, splits, ctx.k_splits,
+                      ctx.variant)
         elif ctx.k_splits == 1:
             ws = torch.empty(L.wcn_attn_varlen_kv_workspace_bytes(tq, tk, h, d, splits), dtype=torch.uint8, device=dev)
             _lib.check(
