@@ -1515,6 +1515,51 @@ int wcn_dense_conv3d_wgrad(const void* x, const void* dy, int64_t batch, int32_t
                            int32_t cout, int32_t ks, int32_t dtype, int32_t slabs, void* dw, void* dbias, void* workspace,
                            size_t workspace_bytes, wcn_stream_t stream);
 
+/* ---- dense 2-D tile convolution (csrc/dense_conv2d.hip; additions only, wcn_abi_version() stays 18) --------------------------
+ * nn.Conv2d with kernel `ks` in {1, 3, 5}, padding (ks - 1) / 2, `stride` 1 or 2, and nn.ConvTranspose2d with stride 2 and the
+ * same padding, on channels-last images: x [batch, H, W, cin], y [batch, Ho, Wo, cout], all tensors of one `dtype` (f32 / f16 /
+ * bf16), fp32 accumulation, no float atomics (the same call gives the same bits).  `w` / `dw` have nn.Conv2d's layout
+ * [cout, cin, ks, ks] (a ConvTranspose2d weight [Cin, Cout, ks, ks] is the weight of the convolution it transposes: pass
+ * cout = Cin, cin = Cout).  In the two image launches `cin` is the channel count of `x` and `cout` that of `y`.
+ *   wcn_dense_conv2d_supported    host-only: ks in {1, 3, 5}, stride in {1, 2}, a dtype above, 1 <= cin, cout <= 8192.
+ *   wcn_dense_conv2d_packed_bytes host-only: size of the weight image (0 for an unsupported shape or mode).
+ *   wcn_dense_conv2d_pack         w -> image.  mode 0: the convolution's forward (reduces over cin).  mode 1: offsets reversed,
+ *                                 channels transposed - with it wcn_dense_conv2d(dy, stride 1, cin = cout, cout = cin) is the
+ *                                 input gradient of the stride-1 convolution.  mode 2: channels transposed, offsets as they are -
+ *                                 the image of wcn_dense_conv2d_frac.
+ *   wcn_dense_conv2d              y[o] = sum_delta x[stride * o + delta - pad] W[delta] + bias, Ho = (H - 1) / stride + 1 (Wo
+ *                                 likewise), acc + bias one fp32 add, rounded once to `dtype`; `bias` may be NULL.  With the
+ *                                 mode-0 image of a transposed convolution's weight and stride 2: that module's input gradient.
+ *   wcn_dense_conv2d_frac         y[2 i + delta - pad] += x[i] W[delta] over the coarse image x [batch, Hc, Wc, cin], + bias, for
+ *                                 every pixel of y [batch, Ho, Wo, cout] (Ho, Wo are arguments; pixels no tap reaches are bias or
+ *                                 an exact 0): the forward of ConvTranspose2d (Ho = 2 Hc - 1) and the input gradient of the
+ *                                 stride-2 convolution (Ho = that convolution's input size).  No product is issued for a tap
+ *                                 the parity of an output pixel rules out.
+ *   wcn_dense_conv2d_wgrad_slabs  host-only: the slab count `slabs` = 0 stands for, over `pixels` = batch * Ho * Wo.
+ *   wcn_dense_conv2d_wgrad_workspace  host-only: bytes for `slabs` (as resolved, >= 1) slabs.
+ *   wcn_dense_conv2d_wgrad        dw[co, ci, delta] = sum_o x[stride * o + delta - pad, ci] * dy[o, co] (x [batch, H, W, cin] zero
+ *                                 outside the image, dy [batch, Ho, Wo, cout]) and, with `dbias`, the column sums of dy
+ *                                 (dbias [cout]) or, with dbias_from_x = 1, of x (dbias [cin]: the transposed module, whose
+ *                                 input is this call's dy and whose output gradient is this call's x).  fp32 partials per slab
+ *                                 of output pixels, added in slab order, rounded once to `dtype`.  slabs in 0..256; `workspace`
+ *                                 256-B aligned.
+ * A call without pixels launches nothing and writes nothing.  Bad arguments come back before any launch: negative sizes, a mode
+ * outside 0..2, missing or misaligned pointers, short buffers -> WCN_ERROR_INVALID_PARAMETERS; another ks, stride, dtype or
+ * channel count -> WCN_ERROR_UNSUPPORTED_CONFIG. */
+int wcn_dense_conv2d_supported(int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t dtype);
+size_t wcn_dense_conv2d_packed_bytes(int32_t cin, int32_t cout, int32_t ks, int32_t dtype, int32_t mode);
+int wcn_dense_conv2d_pack(const void* w, int32_t cin, int32_t cout, int32_t ks, int32_t dtype, int32_t mode, void* packed,
+                          size_t packed_bytes, wcn_stream_t stream);
+int wcn_dense_conv2d(const void* x, const void* packed, const void* bias, void* y, int64_t batch, int32_t H, int32_t W,
+                     int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t dtype, wcn_stream_t stream);
+int wcn_dense_conv2d_frac(const void* x, const void* packed, const void* bias, void* y, int64_t batch, int32_t Hc, int32_t Wc,
+                          int32_t Ho, int32_t Wo, int32_t cin, int32_t cout, int32_t ks, int32_t dtype, wcn_stream_t stream);
+int32_t wcn_dense_conv2d_wgrad_slabs(int64_t pixels, int32_t cin, int32_t cout, int32_t ks, int32_t dtype);
+size_t wcn_dense_conv2d_wgrad_workspace(int32_t cin, int32_t cout, int32_t ks, int32_t slabs);
+int wcn_dense_conv2d_wgrad(const void* x, const void* dy, int64_t batch, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                           int32_t ks, int32_t stride, int32_t dtype, int32_t slabs, int32_t dbias_from_x, void* dw, void* dbias,
+                           void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 /* ---- sparse convolution on true fp32 operands (csrc/conv_mfma_f32.hip; additions only, wcn_abi_version() stays 18) ------------
  * algo = WCN_ALGO_MFMA_F32 (3) of wcn_conv_gather_gemm, wcn_conv_wgrad and wcn_conv_wgrad_workspace: fp32 operands on
  * v_mfma_f32_32x32x2_f32, fp32 accumulation, fp32 results, no float atomics (the same call gives the same bits).

@@ -494,6 +494,14 @@ SIGNATURES = {
     "wcn_dense_conv3d_wgrad_slabs": (c_int32, [c_int64] + [c_int32] * 4),
     "wcn_dense_conv3d_wgrad_workspace": (c_size_t, [c_int32] * 4),
     "wcn_dense_conv3d_wgrad": (c_int, [c_void_p, c_void_p, c_int64] + [c_int32] * 8 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "wcn_dense_conv2d_supported": (c_int, [c_int32] * 5),
+    "wcn_dense_conv2d_packed_bytes": (c_size_t, [c_int32] * 5),
+    "wcn_dense_conv2d_pack": (c_int, [c_void_p] + [c_int32] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "wcn_dense_conv2d": (c_int, [c_void_p] * 4 + [c_int64] + [c_int32] * 7 + [c_void_p]),
+    "wcn_dense_conv2d_frac": (c_int, [c_void_p] * 4 + [c_int64] + [c_int32] * 8 + [c_void_p]),
+    "wcn_dense_conv2d_wgrad_slabs": (c_int32, [c_int64] + [c_int32] * 4),
+    "wcn_dense_conv2d_wgrad_workspace": (c_size_t, [c_int32] * 4),
+    "wcn_dense_conv2d_wgrad": (c_int, [c_void_p, c_void_p, c_int64] + [c_int32] * 9 + [c_void_p] * 3 + [c_size_t, c_void_p]),
 }
 
 _LIB = None  # _GuardedLib

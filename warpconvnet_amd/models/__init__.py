@@ -1,6 +1,7 @@
 """Model definitions the hot path's configurations exercise (reference `warpconvnet/models/`: the MinkUNet family, the Volt
-volume transformer, PointNet, DGCNN, MaskFormer, Point Transformer V3 and SpaCeFormer).  ``Block``, ``Mlp`` and ``DropPath`` are
+volume transformer, PointNet, DGCNN, MaskFormer, Point Transformer V3, SpaCeFormer and FIGConvNet).  ``Block``, ``Mlp`` and ``DropPath`` are
 Volt's; Point Transformer V3's own ``MLP`` and ``PatchAttentionBlock`` are exported under their names."""
+from .figconv import FIGConvNet, FIGConvNetDrivAer
 from .dgcnn import DGCNN, DGCNNEncoder, PointConvBlock
 from .maskformer import (CrossAttention, FFNLayer, GeometryToPaddedBatchNoMask, MaskFormer, MaskInnerProduct, MaskTransformer,
                          SpatialFeatureCrossAttention, TransformerDecoderBlock)
@@ -12,7 +13,7 @@ from .spaceformer import SpaCeFormer
 from .volt import (Block, ConvBlockTokenizer, Decoder, Detokenizer, DropPath, LayerScale, Mlp, RoPE, RoPEAttention, SparseResBlock,
                    TokenConv, Tokenizer, Volt)
 
-__all__ = ["BasicBlock", "BottleneckBlock", "ConvBlock", "ConvTrBlock", "MinkUNet14", "MinkUNet18", "MinkUNet34", "MinkUNet50",
+__all__ = ["FIGConvNet", "FIGConvNetDrivAer", "BasicBlock", "BottleneckBlock", "ConvBlock", "ConvTrBlock", "MinkUNet14", "MinkUNet18", "MinkUNet34", "MinkUNet50",
            "MinkUNet101", "MinkUNetBase", "DGCNN", "DGCNNEncoder", "PointConvBlock", "Block", "ConvBlockTokenizer", "Decoder",
            "Detokenizer", "DropPath", "LayerScale", "Mlp", "CrossAttention", "FFNLayer", "GeometryToPaddedBatchNoMask",
            "MaskFormer", "MaskInnerProduct", "MaskTransformer", "SpatialFeatureCrossAttention", "TransformerDecoderBlock",

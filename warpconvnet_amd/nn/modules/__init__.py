@@ -3,10 +3,10 @@ from .attention import (Attention, BatchedLinear, FeedForward, GeometryToPaddedB
 from .base_module import BaseSpatialModel, BaseSpatialModule
 from .fused_block import FusedSparseConvBlock
 from .activations import GELU, DropPath, ReLU
-from .factor_grid import (FactorGridCat, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool,
+from .factor_grid import (FactorGridCat, FactorGridGlobalConv, FactorGridIntraCommunication, FactorGridPadToMatch, FactorGridPool,
                           FactorGridProjection, FactorGridToPoint, FactorGridTransform, PointToFactorGrid)
 from .grid_conv import GridConv
-from .mlp import Linear, MLPBlock
+from .mlp import FeatureMLPBlock, Linear, MLPBlock
 from .normalizations import BatchNorm, LayerNorm32, MultiHeadRMSNorm, NormalizationBase, SegmentedLayerNorm
 from .bilateral import BilateralFilter, BilateralFilterGrid, BilateralFilterGridCached, FastBilateralSolver
 from .permutohedral import (BilateralPermutohedralFilter, BilateralPermutohedralFilterCached, PermutohedralFilter,
@@ -44,5 +44,5 @@ __all__ = ["BaseSpatialModel", "BaseSpatialModule", "MLPBlock", "PointConv", "Se
            "BilateralPermutohedralFilterCached", "BilateralFilterGrid", "BilateralFilterGridCached", "BilateralFilter",
            "FastBilateralSolver",
            "FactorGridCat", "FactorGridIntraCommunication", "FactorGridPadToMatch", "FactorGridPool", "FactorGridToPoint",
-           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "GridConv", "SegmentedLayerNorm", "GELU",
+           "FactorGridTransform", "PointToFactorGrid", "FactorGridProjection", "FactorGridGlobalConv", "FeatureMLPBlock", "GridConv", "SegmentedLayerNorm", "GELU",
            "TupleSequential"]

@@ -10,8 +10,14 @@ joined with the point features and the position relative to the box centre (raw 
 over the folded 2-D image, channel dim ``C * compressed_dim`` (the framework's convolution).  Two defects of the reference
 are not copied: its ``forward`` hands a ``Grid`` to an ``nn.Sequential`` of tensor ops and raises - here the block runs on the
 feature tensor and the grid is rebuilt; and with image sizes that ``stride`` does not divide it would build a ``Grid`` whose
-shape disagrees with its features - here that raises a ``ValueError`` naming the shapes.  ``FactorGridGlobalConv`` and the
-model are not part of this module.
+shape disagrees with its features - here that raises a ``ValueError`` naming the shapes.
+
+``FactorGridGlobalConv`` is the block of FIGConvNet's U-Net: per grid one ``_FactorGridConvNormAct`` (``Conv2d`` of stride 1 / 2
+or ``ConvTranspose2d`` of ``up_stride`` 2, norm, activation), then the intra-communication and, with two communication types,
+a 1 x 1 ``FactorGridProjection``.  Every convolution goes through `nn/functional/dense_conv2d.py` on the module's own
+``nn.Conv2d`` / ``nn.ConvTranspose2d`` parameters (``backend``: ``"hip"`` the tile kernels of csrc/dense_conv2d.hip, ``"torch"``
+the framework, ``None`` by the measured table); where the kernels run the features become channels-last once at the block's
+entry and the norm and activation run on that layout.  The same two departures hold for these blocks.
 """
 from typing import List, Literal, Optional, Tuple, Type
 
@@ -23,6 +29,7 @@ from torch import Tensor
 from warpconvnet_amd.geometry.features.grid import COMPRESSED_FORMATS, FORMAT_TO_AXIS, GridMemoryFormat, as_memory_format
 from warpconvnet_amd.geometry.types.factor_grid import FactorGrid
 from warpconvnet_amd.geometry.types.points import Points
+from warpconvnet_amd.nn.functional.dense_conv2d import dense_conv2d, dense_conv_transpose2d, takes_hip
 from warpconvnet_amd.nn.functional.encodings import get_freqs, sinusoidal_encoding
 from warpconvnet_amd.nn.functional.factor_grid import (factor_grid_cat, factor_grid_intra_communication, factor_grid_pool,
                                                        factor_grid_transform)
@@ -30,7 +37,7 @@ from warpconvnet_amd.nn.functional.grid_sample import grid_sample_points
 from warpconvnet_amd.nn.modules.base_module import BaseSpatialModule
 
 __all__ = ["FactorGridTransform", "FactorGridCat", "FactorGridPool", "FactorGridIntraCommunication", "FactorGridPadToMatch",
-           "FactorGridToPoint", "PointToFactorGrid", "FactorGridProjection"]
+           "FactorGridToPoint", "PointToFactorGrid", "FactorGridProjection", "FactorGridGlobalConv"]
 
 
 class FactorGridTransform(BaseSpatialModule):
@@ -208,14 +215,29 @@ def _rebuilt(grid, features: Tensor, grid_shape: Tuple[int, int, int]):
     return Grid(coords, features, memory_format=grid.memory_format, grid_shape=tuple(grid_shape))
 
 
+def _conv_norm_act(layers: nn.Sequential, feats: Tensor, backend: Optional[str]) -> Tensor:
+    """``layers`` = (``Conv2d`` | ``ConvTranspose2d``, norm, activation) on ``feats``: the convolution through the dense 2-D
+    functional on the layer's own parameters, the rest as framework ops on whatever layout the convolution left."""
+    conv = layers[0]
+    transposed = isinstance(conv, nn.ConvTranspose2d)
+    if takes_hip(feats, conv.weight, conv.bias, conv.stride[0], transposed, backend):
+        feats = feats.contiguous(memory_format=torch.channels_last)  # once, at the block's entry
+    fn = dense_conv_transpose2d if transposed else dense_conv2d
+    feats = fn(feats, conv.weight, conv.bias, stride=conv.stride[0], backend=backend)
+    for layer in list(layers)[1:]:
+        feats = layer(feats)
+    return feats
+
+
 class FactorGridProjection(BaseSpatialModule):
     """One ``Conv2d - norm - activation`` per grid over the folded channels (``convs``)."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int, compressed_spatial_dims: Tuple[int, ...],
                  compressed_memory_formats: Tuple[GridMemoryFormat, ...], stride: int = 1,
-                 norm: Type[nn.Module] = nn.BatchNorm2d, activation: Type[nn.Module] = nn.GELU):
+                 norm: Type[nn.Module] = nn.BatchNorm2d, activation: Type[nn.Module] = nn.GELU, backend: Optional[str] = None):
         super().__init__()
         self.stride = stride
+        self.backend = backend
         self.convs = nn.ModuleList()
         for dim, _ in zip(compressed_spatial_dims, compressed_memory_formats):
             self.convs.append(nn.Sequential(
@@ -226,7 +248,7 @@ class FactorGridProjection(BaseSpatialModule):
         assert len(grid) == len(self.convs), f"Expected {len(self.convs)} grids, got {len(grid)}"
         out = []
         for g, conv in zip(grid, self.convs):
-            feats = conv(g.grid_features.batched_tensor)
+            feats = _conv_norm_act(conv, g.grid_features.batched_tensor, self.backend)
             axes, shape = _image_axes(g.memory_format), list(g.grid_shape)
             shape[axes[0]], shape[axes[1]] = int(feats.shape[2]), int(feats.shape[3])
             if self.stride != 1 and any(g.grid_shape[a] % self.stride for a in axes):
@@ -234,3 +256,70 @@ class FactorGridProjection(BaseSpatialModule):
                                  f"({g.memory_format.name}); the convolution gives features of shape {tuple(feats.shape)}")
             out.append(_rebuilt(g, feats, tuple(shape)))
         return FactorGrid(out)
+
+
+class _FactorGridConvNormAct(BaseSpatialModule):
+    """``Conv2d`` (stride 1 / 2) or ``ConvTranspose2d`` (``up_stride``), norm and activation on one grid's folded image
+    (``conv_norm_layers``).  A stride divides the image axes (ValueError otherwise); after the transposed convolution the image
+    (``2 H - 1``) is padded, replicating its border, to ``up_stride * H``."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int, compressed_spatial_dim: int,
+                 compressed_memory_format: GridMemoryFormat, stride: int = 1, up_stride: Optional[int] = None,
+                 norm: Type[nn.Module] = nn.BatchNorm2d, activation: Type[nn.Module] = nn.GELU, backend: Optional[str] = None):
+        super().__init__()
+        compressed_memory_format = as_memory_format(compressed_memory_format)
+        assert compressed_memory_format in COMPRESSED_FORMATS, f"not a compressed format: {compressed_memory_format}"
+        self.stride, self.up_stride, self.backend = stride, up_stride, backend
+        self.compressed_spatial_dim = compressed_spatial_dim
+        self.compressed_memory_format = compressed_memory_format
+        cin, cout, pad = in_channels * compressed_spatial_dim, out_channels * compressed_spatial_dim, (kernel_size - 1) // 2
+        self.conv_norm_layers = nn.Sequential(
+            nn.Conv2d(cin, cout, kernel_size, stride, pad, bias=True) if up_stride is None
+            else nn.ConvTranspose2d(cin, cout, kernel_size, stride=up_stride, padding=pad, bias=True),
+            norm(cout) if norm is not None else nn.Identity(),
+            activation() if activation is not None else nn.Identity())
+
+    def forward(self, grid):
+        feats = _conv_norm_act(self.conv_norm_layers, grid.grid_features.batched_tensor, self.backend)
+        if self.up_stride is None and self.stride == 1:
+            return grid.replace(batched_features=feats)
+        axes, shape = _image_axes(grid.memory_format), list(grid.grid_shape)
+        if self.up_stride is not None:
+            for a in axes:
+                shape[a] = grid.grid_shape[a] * self.up_stride
+            pad_h, pad_w = max(0, shape[axes[0]] - feats.shape[2]), max(0, shape[axes[1]] - feats.shape[3])
+            feats = F.pad(feats, (0, pad_w, 0, pad_h), mode="replicate")
+        else:
+            if any(grid.grid_shape[a] % self.stride for a in axes):
+                raise ValueError(f"stride {self.stride} does not divide the image axes of grid shape {tuple(grid.grid_shape)} "
+                                 f"({grid.memory_format.name}); the convolution gives features of shape {tuple(feats.shape)}")
+            for a in axes:
+                shape[a] = grid.grid_shape[a] // self.stride
+        return _rebuilt(grid, feats, tuple(shape))
+
+
+class FactorGridGlobalConv(BaseSpatialModule):
+    """Per grid a ``_FactorGridConvNormAct`` (``conv_blocks``), then ``intra_communications`` and, with two communication types,
+    the 1 x 1 projection ``proj`` back to ``out_channels``."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int, compressed_spatial_dims: Tuple[int, ...],
+                 compressed_memory_formats: Tuple[GridMemoryFormat, ...], stride: int = 1, up_stride: Optional[int] = None,
+                 communication_types: List[Literal["sum", "mul"]] = ["sum"], norm: Type[nn.Module] = nn.BatchNorm2d,
+                 activation: Type[nn.Module] = nn.GELU, backend: Optional[str] = None):
+        super().__init__()
+        assert len(compressed_spatial_dims) == len(compressed_memory_formats), "one compressed dimension per memory format"
+        self.conv_blocks = nn.ModuleList([
+            _FactorGridConvNormAct(in_channels, out_channels, kernel_size, dim, fmt, stride=stride, up_stride=up_stride, norm=norm,
+                                   activation=activation, backend=backend)
+            for dim, fmt in zip(compressed_spatial_dims, compressed_memory_formats)])
+        self.intra_communications = FactorGridIntraCommunication(communication_types=communication_types)
+        if len(communication_types) > 1:
+            self.proj = FactorGridProjection(out_channels * len(communication_types), out_channels, 1, compressed_spatial_dims,
+                                             compressed_memory_formats, stride=1, backend=backend)
+        else:
+            self.proj = nn.Identity()
+
+    def forward(self, factor_grid: FactorGrid) -> FactorGrid:
+        assert len(factor_grid) == len(self.conv_blocks), f"Expected {len(self.conv_blocks)} grids, got {len(factor_grid)}"
+        convolved = FactorGrid([block(g) for g, block in zip(factor_grid, self.conv_blocks)])
+        return self.proj(self.intra_communications(convolved))

@@ -48,3 +48,19 @@ class MLPBlock(BaseSpatialModule):
         if isinstance(x, Geometry):
             return x.replace(batched_features=self._forward_feature(x.feature_tensor))
         return self._forward_feature(x)
+
+
+class FeatureMLPBlock(nn.Module):
+    """``Linear - LayerNorm - activation`` per entry of ``hidden_channels``, then a last ``Linear`` to ``out_channels``; on plain
+    feature tensors (``block``, parameter names as in the reference)."""
+
+    def __init__(self, in_channels: int, out_channels: int, hidden_channels=(), activation=nn.GELU, bias: bool = True):
+        super().__init__()
+        widths = [in_channels, *hidden_channels]
+        layers = []
+        for a, b in zip(widths[:-1], widths[1:]):
+            layers += [nn.Linear(a, b, bias=bias), nn.LayerNorm(b), activation()]
+        self.block = nn.Sequential(*layers, nn.Linear(widths[-1], out_channels, bias=bias))
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.block(x)
