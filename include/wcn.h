@@ -521,6 +521,34 @@ int wcn_pointconv_edge_backward_ragged(const float* in_feats, const float* q_fea
                                        const float* grad_out, float* d_in, float* d_q, float* d_params, void* workspace,
                                        size_t workspace_bytes, wcn_stream_t stream);
 
+/* The same edge pipeline under autocast (csrc/pointconv16.hip): `dtype` WCN_F16 / WCN_BF16 = T.  Feature rows are stored in
+ * T, the relative position is formed in fp32 and rounded to T, W1 / W2 / Ws are rounded to T once by wcn_pointconv16_pack
+ * (fp32 parameters in; image of wcn_pointconv16_packed_bytes bytes, 16-B aligned, biases and LayerNorm vectors stay fp32);
+ * the GEMMs run on v_mfma_f32_32x32x16_{f16,bf16} with fp32 accumulators, the hidden activation is rounded to T once,
+ * everything else (bias, LayerNorm, ReLU, shortcut add, reduction, scale) is fp32; `out` is fp32.  Uniform lists only,
+ * k in {1, 2, 4, 8, 16, 32}; a neighbour id of -1 is an edge that contributes nothing (mean divides by k).
+ * wcn_pointconv16_edge_backward: `grad_out` fp32; `d_in` fp32 [n_in][cin] ZERO-FILLED by the caller (hardware fp32
+ * atomics); `d_q` fp32 [n_query][cq], every row stored once; `d_params` fp32 in the layout of wcn_pointconv_edge_backward,
+ * per-workgroup partials summed in fixed order (bitwise repeatable). */
+int wcn_pointconv16_supported(int32_t cin, int32_t cq, int32_t nrel, int32_t hidden, int32_t cout, int32_t k,
+                              int32_t linear_shortcut, int32_t dtype);
+int64_t wcn_pointconv16_packed_bytes(int32_t ein, int32_t hidden, int32_t cout);
+int64_t wcn_pointconv16_grad_floats(int32_t ein, int32_t hidden, int32_t cout, int32_t linear_shortcut);
+size_t wcn_pointconv16_backward_workspace(int64_t n_query, int32_t k, int32_t ein, int32_t hidden, int32_t cout,
+                                          int32_t linear_shortcut);
+int wcn_pointconv16_pack(const float* w1, const float* b1, const float* g1, const float* be1, const float* w2,
+                         const float* b2, const float* g2, const float* be2, const float* ws, const float* bs, int32_t ein,
+                         int32_t hidden, int32_t cout, int32_t dtype, void* packed, wcn_stream_t stream);
+int wcn_pointconv16_edge_forward(const void* in_feats, const void* q_feats, const float* in_xyz, const float* q_xyz,
+                                 const int32_t* nbr, int64_t n_query, int32_t k, int32_t cin, int32_t cq, int32_t nrel,
+                                 const void* packed, int32_t hidden, int32_t cout, float eps1, float eps2, int32_t mean,
+                                 int32_t linear_shortcut, int32_t dtype, float* out, wcn_stream_t stream);
+int wcn_pointconv16_edge_backward(const void* in_feats, const void* q_feats, const float* in_xyz, const float* q_xyz,
+                                  const int32_t* nbr, int64_t n_query, int32_t k, int32_t cin, int32_t cq, int32_t nrel,
+                                  const void* packed, int32_t hidden, int32_t cout, float eps1, float eps2, int32_t mean,
+                                  int32_t linear_shortcut, int32_t dtype, const float* grad_out, float* d_in, float* d_q,
+                                  float* d_params, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 /* Sparse pooling over a kernel map (REDUCE_AND_STRIDE, SparsePool / SparseMaxPool / SparseUnpool): out[m][c] =
  * reduce over the present neighbours k of in[tbl[m][k]][c]; `tbl` is the row-major neighbour table [n_out][row pitch of
  * num_offsets] (-1 = absent) that wcn_kmap_probe / wcn_kmap_from_csr / wcn_kmap_reverse produce.  op: 0 sum, 1 mean,

@@ -263,6 +263,22 @@ SIGNATURES = {
                                                                c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                                c_size_t, c_void_p],
     ),
+    "wcn_pointconv16_supported": (c_int, [c_int32] * 8),
+    "wcn_pointconv16_packed_bytes": (c_int64, [c_int32] * 3),
+    "wcn_pointconv16_grad_floats": (c_int64, [c_int32] * 4),
+    "wcn_pointconv16_backward_workspace": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "wcn_pointconv16_pack": (c_int, [c_void_p] * 10 + [c_int32] * 4 + [c_void_p, c_void_p]),
+    "wcn_pointconv16_edge_forward": (
+        c_int,
+        [c_void_p] * 5 + [c_int64] + [c_int32] * 4 + [c_void_p, c_int32, c_int32, ctypes.c_float, ctypes.c_float, c_int32,
+                                                      c_int32, c_int32, c_void_p, c_void_p],
+    ),
+    "wcn_pointconv16_edge_backward": (
+        c_int,
+        [c_void_p] * 5 + [c_int64] + [c_int32] * 4 + [c_void_p, c_int32, c_int32, ctypes.c_float, ctypes.c_float, c_int32,
+                                                      c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_size_t, c_void_p],
+    ),
     "wcn_attn_varlen_supported": (c_int, [c_int32, c_int32]),
     "wcn_attn_varlen_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "wcn_attn_varlen_fwd": (

@@ -6,6 +6,11 @@ Takes the place of the op sequence in the reference's ``PointConv.forward``
 `warpconvnet/nn/modules/mlp.py:124-177`), the neighbour lists have a uniform power-of-two length (kNN) and the reduction
 is ``mean`` or ``sum``; ragged lists (radius search) run through the same kernels with per-edge query ids.  Forward and
 backward are single HIP kernels; no ``[M*k, C]`` tensor exists in HBM.
+
+Under ``torch.autocast`` to bfloat16 / float16 the uniform-list case runs on the 16-bit kernels of ``csrc/pointconv16.hip``
+(``fused_point_conv_edge16``): feature rows, relative positions, weights and the hidden activation are 16-bit GEMM operands,
+accumulation, LayerNorm, shortcut add and reduction are fp32, the result is fp32 as on the composed path.  Ragged lists,
+deterministic mode and 16-bit parameters keep the composed path there.
 """
 import os
 from typing import Optional
@@ -17,6 +22,13 @@ from torch import Tensor
 from warpconvnet_amd import _lib
 
 _ENABLED = os.environ.get("WARPCONVNET_AMD_POINTCONV_FUSED", "1") != "0"
+_ENABLED16 = os.environ.get("WARPCONVNET_AMD_POINTCONV16", "1") != "0"  # the 16-bit kernels under autocast
+_CODE16 = {torch.bfloat16: _lib.WCN_BF16, torch.float16: _lib.WCN_F16}
+
+
+def autocast16_dtype() -> Optional[torch.dtype]:
+    """The autocast GPU dtype when autocast is on (whatever it is), else None."""
+    return torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None
 
 
 def _mlp_parts(mlp: nn.Module):
@@ -33,8 +45,14 @@ def _mlp_parts(mlp: nn.Module):
     return lin1, ln1, lin2, ln2, (shortcut if isinstance(shortcut, nn.Linear) else None)
 
 
-def fused_edge_supported(mlp: nn.Module, in_feats: Tensor, q_feats: Tensor, nrel: int, k: int, reduction: str) -> bool:
+def fused_edge_supported(mlp: nn.Module, in_feats: Tensor, q_feats: Tensor, nrel: int, k: int, reduction: str,
+                         ragged: bool = False) -> bool:
+    """Whether the one-kernel path takes this call: the fp32 kernels without autocast, the 16-bit kernels under autocast to
+    bf16 / f16 (uniform lists, fp32 parameters, not in deterministic mode)."""
     if not _ENABLED or not in_feats.is_cuda or reduction not in ("mean", "sum"):
+        return False
+    amp = autocast16_dtype()
+    if amp is not None and (not _ENABLED16 or amp not in _CODE16 or ragged or torch.are_deterministic_algorithms_enabled()):
         return False
     if in_feats.shape[0] == 0 or q_feats.shape[0] == 0:  # empty inputs: the composed path returns the empty result
         return False
@@ -45,27 +63,37 @@ def fused_edge_supported(mlp: nn.Module, in_feats: Tensor, q_feats: Tensor, nrel
     cin, cq = in_feats.shape[1], q_feats.shape[1]
     if lin1.in_features != cin + cq + nrel or lin1.weight.dtype != torch.float32:
         return False
-    return bool(_lib.lib().wcn_pointconv_supported(cin, cq, nrel, lin1.out_features, lin2.out_features, k, int(sc is not None)))
+    dims = (cin, cq, nrel, lin1.out_features, lin2.out_features, k, int(sc is not None))
+    if amp is not None:
+        return bool(_lib.lib().wcn_pointconv16_supported(*dims, _CODE16[amp]))
+    return bool(_lib.lib().wcn_pointconv_supported(*dims))
 
 
-def _packed_params(mlp: nn.Module, parts) -> Tensor:
-    """Operand images of the edge MLP, cached on the module per parameter version."""
+def _packed_params(mlp: nn.Module, parts, dtype: Optional[torch.dtype] = None) -> Tensor:
+    """Operand images of the edge MLP, cached on the module per parameter version (and per 16-bit `dtype`: the images of
+    ``csrc/pointconv16.hip``, weights rounded to it once; None: the fp32 images)."""
     lin1, ln1, lin2, ln2, sc = parts
     ps = (lin1.weight, lin1.bias, ln1.weight, ln1.bias, lin2.weight, lin2.bias, ln2.weight, ln2.bias,
           sc.weight if sc is not None else None, sc.bias if sc is not None else None)
     # (in-place writes through p.data leave this key unchanged: hip_gemm.invalidate_packed(module) after such updates)
-    key = tuple((p.data_ptr(), p._version, p.device) if p is not None else None for p in ps)
-    hit = getattr(mlp, "_wcn_pc_packed", None)
+    key = tuple((p.data_ptr(), p._version, p.device) if p is not None else None for p in ps) + (dtype,)
+    attr = "_wcn_pc_packed" if dtype is None else "_wcn_pc_packed16"
+    hit = getattr(mlp, attr, None)
     if hit is not None and hit[0] == key:
         return hit[1]
     L = _lib.lib()
     ein, hid, co = lin1.in_features, lin1.out_features, lin2.out_features
     dev = lin1.weight.device
-    packed = torch.empty(L.wcn_pointconv_packed_floats(ein, hid, co), dtype=torch.float32, device=dev)
-    c = [p.detach().contiguous() if p is not None else None for p in ps]
-    _lib.check(L.wcn_pointconv_pack(*[_lib.ptr(t) for t in c], ein, hid, co, _lib.ptr(packed), _lib.stream_handle(dev)),
-               "wcn_pointconv_pack")
-    mlp._wcn_pc_packed = (key, packed)
+    c = [p.detach().contiguous() if p is not None else None for p in ps]  # kept alive until the pack kernel is enqueued
+    ptrs = [_lib.ptr(t) for t in c]
+    if dtype is None:
+        packed = torch.empty(L.wcn_pointconv_packed_floats(ein, hid, co), dtype=torch.float32, device=dev)
+        _lib.check(L.wcn_pointconv_pack(*ptrs, ein, hid, co, _lib.ptr(packed), _lib.stream_handle(dev)), "wcn_pointconv_pack")
+    else:
+        packed = torch.empty(L.wcn_pointconv16_packed_bytes(ein, hid, co), dtype=torch.uint8, device=dev)
+        _lib.check(L.wcn_pointconv16_pack(*ptrs, ein, hid, co, _CODE16[dtype], _lib.ptr(packed), _lib.stream_handle(dev)),
+                   "wcn_pointconv16_pack")
+    setattr(mlp, attr, (key, packed))
     return packed
 
 
@@ -154,12 +182,82 @@ class _FusedEdge(torch.autograd.Function):
                 dws, dbs if has_bs else None, None, None, None, None, None, None, None, None, None, None)
 
 
+class _FusedEdge16(torch.autograd.Function):
+    """The 16-bit kernels (``csrc/pointconv16.hip``): feature rows cast to bf16 / f16 here (one ``.to()`` each, the rows the
+    backward reads again), fp32 parameters, fp32 result; the feature gradients come back in the callers' dtypes."""
+
+    @staticmethod
+    def forward(ctx, in_feats, q_feats, w1, b1, g1, be1, w2, b2, g2, be2, ws, bs, packed, in_xyz, q_xyz, nbr, k, eps1, eps2,
+                mean, dtype):
+        L = _lib.lib()
+        dev = in_feats.device
+        ctx.grad_dtypes = (in_feats.dtype, q_feats.dtype)
+        in_feats, q_feats = in_feats.to(dtype).contiguous(), q_feats.to(dtype).contiguous()
+        M, cin, cq = q_feats.shape[0], in_feats.shape[1], q_feats.shape[1]
+        nrel = 0 if in_xyz is None else 3
+        ctx.args = (M, k, cin, cq, nrel, _lib.ptr(packed), w1.shape[0], w2.shape[0], eps1, eps2, int(mean), int(ws is not None),
+                    _CODE16[in_feats.dtype])
+        out = torch.empty(M, w2.shape[0], dtype=torch.float32, device=dev)
+        _lib.check(L.wcn_pointconv16_edge_forward(*[_lib.ptr(t) for t in (in_feats, q_feats, in_xyz, q_xyz, nbr)], *ctx.args,
+                                                  _lib.ptr(out), _lib.stream_handle(dev)), "wcn_pointconv16_edge_forward")
+        ctx.save_for_backward(in_feats, q_feats, packed, in_xyz, q_xyz, nbr)
+        ctx.has = (b1 is not None, b2 is not None, bs is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        L = _lib.lib()
+        in_feats, q_feats, packed, in_xyz, q_xyz, nbr = ctx.saved_tensors
+        M, k, cin, cq, nrel, _, hid, co, _, _, _, lin, _ = ctx.args
+        dev = in_feats.device
+        ein = cin + cq + nrel
+        grad_out = grad_out.contiguous().float()
+        grads = torch.empty(L.wcn_pointconv16_grad_floats(ein, hid, co, lin), dtype=torch.float32, device=dev)
+        d_in = torch.zeros(in_feats.shape, dtype=torch.float32, device=dev)  # the kernel's fp32 atomics add to it
+        d_q = torch.empty(q_feats.shape, dtype=torch.float32, device=dev)    # every row stored once
+        ws_bytes = L.wcn_pointconv16_backward_workspace(M, k, ein, hid, co, lin)
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        _lib.check(L.wcn_pointconv16_edge_backward(*[_lib.ptr(t) for t in (in_feats, q_feats, in_xyz, q_xyz, nbr)], *ctx.args,
+                                                   _lib.ptr(grad_out), _lib.ptr(d_in), _lib.ptr(d_q), _lib.ptr(grads),
+                                                   _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev)),
+                   "wcn_pointconv16_edge_backward")
+        sizes = [hid * ein, hid, hid, hid, co * hid, co, co, co] + ([co * ein, co] if lin else [])
+        dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, *short = grads.split(sizes)
+        dws, dbs = (short[0].view(co, ein), short[1]) if lin else (None, None)
+        has_b1, has_b2, has_bs = ctx.has
+        return (d_in.to(ctx.grad_dtypes[0]), d_q.to(ctx.grad_dtypes[1]), dw1.view(hid, ein), db1 if has_b1 else None, dg1, dbe1, dw2.view(co, hid),
+                db2 if has_b2 else None, dg2, dbe2, dws, dbs if has_bs else None, None, None, None, None, None, None, None, None, None)
+
+
+def fused_point_conv_edge16(mlp: nn.Module, in_feats: Tensor, q_feats: Tensor, nbr: Tensor, k: int, reduction: str,
+                            dtype: torch.dtype, in_xyz: Optional[Tensor] = None, q_xyz: Optional[Tensor] = None) -> Tensor:
+    """``fused_point_conv_edge`` for uniform lists with bf16 / f16 GEMM operands and fp32 accumulation, the arithmetic of the
+    composed path under ``torch.autocast(dtype=dtype)`` without its roundings of the Linear outputs; fp32 [M, out].  ``nbr``
+    [M, k] / [M*k], k a power of two up to 32; an id of -1 is an edge that contributes nothing (``mean`` divides by k)."""
+    parts = _mlp_parts(mlp)
+    assert parts is not None and dtype in _CODE16, "fused_point_conv_edge16 needs the default MLPBlock and bf16 / f16"
+    lin1, ln1, lin2, ln2, sc = parts
+    packed = _packed_params(mlp, parts, dtype)
+    if in_xyz is not None:
+        in_xyz, q_xyz = in_xyz.float().contiguous(), q_xyz.float().contiguous()
+    with torch.autocast("cuda", enabled=False):  # the casts below are the only ones
+        return _FusedEdge16.apply(in_feats, q_feats, lin1.weight, lin1.bias, ln1.weight, ln1.bias,
+                                  lin2.weight, lin2.bias, ln2.weight, ln2.bias, sc.weight if sc is not None else None,
+                                  sc.bias if sc is not None else None, packed, in_xyz, q_xyz,
+                                  nbr.reshape(-1).to(torch.int32).contiguous(), int(k), float(ln1.eps), float(ln2.eps),
+                                  reduction == "mean", dtype)
+
+
 def fused_point_conv_edge(mlp: nn.Module, in_feats: Tensor, q_feats: Tensor, nbr: Tensor, k: int, reduction: str,
                           in_xyz: Optional[Tensor] = None, q_xyz: Optional[Tensor] = None,
                           row_splits: Optional[Tensor] = None) -> Tensor:
     """``row_reduction(edge_mlp(cat([in_feats[nbr], q_feats.repeat(k), in_xyz[nbr] - q_xyz.repeat(k)])), reduction)``
     for ``nbr`` [M, k] / [M*k] row indices into ``in_feats`` (uniform lists), or ``nbr`` [E] with ``row_splits`` [M+1]
     (ragged lists, e.g. radius search); fp32."""
+    amp = autocast16_dtype()
+    if amp is not None:  # fused_edge_supported has admitted the call: uniform lists, bf16 / f16
+        assert row_splits is None
+        return fused_point_conv_edge16(mlp, in_feats, q_feats, nbr, k, reduction, amp, in_xyz, q_xyz)
     parts = _mlp_parts(mlp)
     assert parts is not None, "fused_point_conv_edge needs the default MLPBlock (see fused_edge_supported)"
     lin1, ln1, lin2, ln2, sc = parts
@@ -186,8 +284,9 @@ _ARANGE = {}
 
 
 def fused_mlp_block_supported(mlp: nn.Module, x: Tensor) -> bool:
-    """A default ``MLPBlock`` on a plain [M, C] fp32 CUDA tensor = the edge pipeline with one "neighbour" per row."""
-    if x.ndim != 2 or x.dtype != torch.float32 or torch.is_autocast_enabled():
+    """A default ``MLPBlock`` on a plain [M, C] fp32 CUDA tensor = the edge pipeline with one "neighbour" per row (under
+    autocast to bf16 / f16: on the 16-bit kernels)."""
+    if x.ndim != 2 or x.dtype != torch.float32:
         return False
     return fused_edge_supported(mlp, x, x[:, :0], 0, 1, "sum")
 

@@ -1,6 +1,7 @@
 """``MLPBlock``: Linear - LayerNorm - activation - Linear - LayerNorm plus a (projected) shortcut
 (reference `warpconvnet/nn/modules/mlp.py:124-177`).  On fp32 CUDA features whose widths fit (in <= 64, hidden <= 128, out <= 64)
-the whole block runs as one HIP kernel per direction (the PointConv edge kernel with one row per "edge"); otherwise the
+the whole block runs as one HIP kernel per direction (the PointConv edge kernel with one row per "edge"; under autocast to
+bf16 / f16 the 16-bit kernels of ``csrc/pointconv16.hip``); otherwise the
 linears are library GEMMs.  ``Linear`` is the geometry-aware ``nn.Linear`` of the same reference file."""
 from typing import Union
 
