@@ -1510,6 +1510,50 @@ int wcn_attn_d128_bwd(const void* dout, const void* q, int64_t q_stride, const v
                       int64_t dkv_stride, int32_t q_splits, int32_t k_splits, void* workspace, size_t workspace_bytes,
                       wcn_stream_t stream);
 
+/* ---- masked varlen cross-attention (csrc/attn_varlen_masked.hip; additions only, wcn_abi_version() stays 18) ------------------
+ * wcn_attn_varlen_kv_fwd_s / _kv_bwd_s (head_dim 16 / 32 / 64, fp16 / bf16) with a block mask over the (query, key) pairs of
+ * every sequence that all heads share: a blocked pair has p = 0 exactly, in the forward and in every gradient.  Kernels of their
+ * own - the entry points above launch what they always did.
+ * The packed mask.  One bit per pair, 1 = blocked, in two layouts of 32-bit words:
+ *   q_words [total_q, q_pitch]  bit j of word w of query row t: key 32 w + j of t's sequence;   q_pitch >= wcn_attn_mask_words(max_seqlen_k)
+ *   k_words [total_k, k_pitch]  bit j of word w of key row t: query 32 w + j of t's sequence;   k_pitch >= wcn_attn_mask_words(max_seqlen_q)
+ * Bits past the end of a sequence's keys / queries are 0.  Rows outside [cu[0], cu[num_seqs]) are neither written nor read.
+ *   wcn_attn_mask_words   host-only: ceil(max_seqlen / 32) (0 for max_seqlen <= 0).
+ *   wcn_attn_mask_pack    builds both layouts on the device from `src` [src_rows, >= q_cols] with row pitch src_pitch (elements):
+ *                         column j of a key's row is query j of that key's sequence (max_seqlen_q <= q_cols).  src_dtype WCN_F32 /
+ *                         WCN_F16 / WCN_BF16: logits, blocked <=> logit < threshold (a NaN logit is not blocked);
+ *                         WCN_ATTN_MASK_U8: bytes, blocked <=> non-zero.  key_index NULL: key row t of the mask is row t of src
+ *                         (src_rows = total_k); else int32 [total_k], key row t is row key_index[t] of src (a subsample, in any
+ *                         order; an index outside [0, src_rows) is clamped) and cu_k bounds those total_k rows.
+ *                         release_full_rows != 0: a second launch clears, in both layouts, every bit of a query all of whose
+ *                         in-range keys are blocked (it then attends to all its keys).  Integer work in a fixed order, every word of
+ *                         every in-sequence row written exactly once, no atomics, no host read.
+ *   wcn_attn_varlen_kv_fwd_m / _kv_bwd_m   the arguments of _kv_fwd_s / _kv_bwd_s minus `variant` (and minus q_splits: dK/dV
+ *                         runs one wave per 32-key block), plus the two word arrays and their row pitches before k_splits.
+ *                         k_splits (0: wcn_attn_varlen_k_splits) and the workspace (wcn_attn_varlen_ksplit_workspace_bytes with
+ *                         q_splits = 1) are those of the _s entry points, with the same combine and reduce kernels.  A query with no
+ *                         allowed key: out = 0, lse = -inf, dq = 0, nothing added to dk / dv; a key every query blocks: dk = dv =
+ *                         0.  A mask with no bit set gives the bits of the unmasked entry points.  Deterministic.
+ * Before any launch: missing pointers, negative sizes, a pitch below the word count, a short workspace ->
+ * WCN_ERROR_INVALID_PARAMETERS; another head size or dtype -> WCN_ERROR_UNSUPPORTED_CONFIG; nothing to compute -> success. */
+enum wcn_attn_mask_dtype { WCN_ATTN_MASK_U8 = 3 };
+int32_t wcn_attn_mask_words(int32_t max_seqlen);
+int wcn_attn_mask_pack(const void* src, int32_t src_dtype, int64_t src_rows, int64_t src_pitch, int32_t q_cols, float threshold,
+                       const int32_t* key_index, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q,
+                       int64_t total_k, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t release_full_rows, int32_t* q_words,
+                       int64_t q_pitch, int32_t* k_words, int64_t k_pitch, wcn_stream_t stream);
+int wcn_attn_varlen_kv_fwd_m(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs, int64_t total_q, int64_t total_k,
+                             int32_t heads, int32_t head_dim, int32_t max_seqlen_q, int32_t max_seqlen_k, float softmax_scale,
+                             int32_t dtype, void* out, float* lse, const int32_t* q_words, int64_t q_pitch, const int32_t* k_words,
+                             int64_t k_pitch, int32_t k_splits, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+int wcn_attn_varlen_kv_bwd_m(const void* dout, const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride,
+                             const void* out, const float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t num_seqs,
+                             int64_t total_q, int64_t total_k, int32_t heads, int32_t head_dim, int32_t max_seqlen_q,
+                             int32_t max_seqlen_k, float softmax_scale, int32_t dtype, void* dq, int64_t dq_stride, void* dk,
+                             void* dv, int64_t dkv_stride, const int32_t* q_words, int64_t q_pitch, const int32_t* k_words,
+                             int64_t k_pitch, int32_t k_splits, void* workspace, size_t workspace_bytes, wcn_stream_t stream);
+
 /* ---- dense 3-D brick convolution (csrc/dense_conv3d.hip; additions only, wcn_abi_version() stays 18) ------------------------
  * nn.Conv3d with kernel `ks` = 3 (padding 1) or 1, stride 1, on channels-last cubes: x [batch, D, H, W, cin], y
  * [batch, D, H, W, cout], all tensors of one `dtype` (f32 / f16 / bf16), fp32 accumulation, no float atomics (the same call

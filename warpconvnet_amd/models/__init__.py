@@ -9,7 +9,7 @@ from .mink_unet import (BasicBlock, BottleneckBlock, ConvBlock, ConvTrBlock, Min
                         MinkUNet101, MinkUNetBase)
 from .point_transformer_v3 import MLP, PatchAttentionBlock, PointTransformerV3, SerializedUnpooling
 from .pointnet import PointNet, STNkd
-from .spaceformer import SpaCeFormer
+from .spaceformer import SpaCeFormer, SpaCeFormerInstSeg
 from .volt import (Block, ConvBlockTokenizer, Decoder, Detokenizer, DropPath, LayerScale, Mlp, RoPE, RoPEAttention, SparseResBlock,
                    TokenConv, Tokenizer, Volt)
 
@@ -17,4 +17,4 @@ __all__ = ["FIGConvNet", "FIGConvNetDrivAer", "BasicBlock", "BottleneckBlock", "
            "MinkUNet101", "MinkUNetBase", "DGCNN", "DGCNNEncoder", "PointConvBlock", "Block", "ConvBlockTokenizer", "Decoder",
            "Detokenizer", "DropPath", "LayerScale", "Mlp", "CrossAttention", "FFNLayer", "GeometryToPaddedBatchNoMask",
            "MaskFormer", "MaskInnerProduct", "MaskTransformer", "SpatialFeatureCrossAttention", "TransformerDecoderBlock",
-           "PointNet", "STNkd", "MLP", "PatchAttentionBlock", "PointTransformerV3", "SerializedUnpooling", "SpaCeFormer", "RoPE", "RoPEAttention", "SparseResBlock", "TokenConv", "Tokenizer", "Volt"]
+           "PointNet", "STNkd", "MLP", "PatchAttentionBlock", "PointTransformerV3", "SerializedUnpooling", "SpaCeFormer", "SpaCeFormerInstSeg", "RoPE", "RoPEAttention", "SparseResBlock", "TokenConv", "Tokenizer", "Volt"]

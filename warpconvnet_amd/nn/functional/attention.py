@@ -12,8 +12,14 @@ The reference's sparse cross-attention (`nn/modules/sparse_dit_attention.py:265-
 ``flash_attn.flash_attn_varlen_func`` and ``flash_attn.flash_attn_varlen_kvpacked_func``; the functions of those names here
 run the same kernels with separate Q and K/V operands and two boundary arrays.  ``cross_attention_reference`` is their
 per-sequence torch counterpart.  An empty side is defined: a query with no key gets ``out = 0`` and ``lse = -inf``.
+
+Masked cross-attention (`csrc/attn_varlen_masked.hip`): ``pack_attention_mask`` turns mask logits or a bool tensor into a
+``PackedAttentionMask`` - one bit per (query, key) pair of a sequence, shared by all heads - and both separate-operand functions
+take it as ``attn_mask``.  A blocked pair has probability 0 exactly; a query with no allowed key gets zeros like the empty side.
+``backend="torch"`` of the pack function and ``masked_attention_reference`` are the loop-free torch definition of the feature.
 """
 import math
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -25,7 +31,8 @@ from warpconvnet_amd.utils.compile_guard import eager_unless_compiling
 
 __all__ = ["flash_attn_varlen_qkvpacked", "patch_cu_seqlens", "varlen_attention_reference", "hip_attn_varlen_supported",
            "flash_attn_varlen_func", "flash_attn_varlen_kvpacked_func", "cross_attention_reference",
-           "hip_attn_d128_supported"]
+           "hip_attn_d128_supported", "PackedAttentionMask", "pack_attention_mask", "unpack_attention_mask",
+           "masked_attention_reference"]
 
 
 def hip_attn_varlen_supported(head_dim: int, dtype: torch.dtype) -> bool:
@@ -406,6 +413,294 @@ class _CrossVarlenAttention(Function):
         return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
+# ---- masked cross-attention: the packed mask, its torch definition, the HIP kernels ---------------------------------------------
+@dataclass(frozen=True)
+class PackedAttentionMask:
+    """A block mask over the (query, key) pairs of every sequence, 1 bit per pair (1 = blocked), shared by all heads, in the
+    two layouts the kernels read: ``q_words`` int32 [total_q, ceil(max_seqlen_k / 32)] (bit j of word w of a query row: key
+    32 w + j of its sequence) and ``k_words`` int32 [total_k, ceil(max_seqlen_q / 32)] (the transpose).  Bits past a sequence's
+    end are 0.  The four sizes are those it was built for; a call with other sizes is refused."""
+    q_words: Tensor
+    k_words: Tensor
+    total_q: int
+    total_k: int
+    max_seqlen_q: int
+    max_seqlen_k: int
+
+
+def _mask_words(n: int) -> int:
+    return (int(n) + 31) // 32
+
+
+def _to_words(bits: Tensor) -> Tensor:
+    """bool [R, 32 W] -> int32 [R, W], bit j of word w = column 32 w + j."""
+    r = bits.shape[0]
+    x = (bits.reshape(r, -1, 32).to(torch.int64) << torch.arange(32, device=bits.device)).sum(-1)
+    return ((x + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)
+
+
+def _from_words(words: Tensor) -> Tensor:
+    """int32 [R, W] -> bool [R, 32 W]."""
+    return ((words.unsqueeze(-1) >> torch.arange(32, device=words.device, dtype=torch.int32)) & 1).bool().reshape(words.shape[0], -1)
+
+
+def unpack_attention_mask(mask: PackedAttentionMask) -> Tensor:
+    """The blocked pairs as bool [total_q, max_seqlen_k]: element (t, j) is key j of query row t's own sequence."""
+    return _from_words(mask.q_words)[:, :mask.max_seqlen_k]
+
+
+def _row_sequences(cu: Tensor, total: int) -> Tuple[Tensor, Tensor]:
+    """Per row of [0, total): the index of its sequence and its position inside it (int64)."""
+    rows = torch.arange(total, device=cu.device)
+    seq = torch.searchsorted(cu[1:].contiguous(), rows, right=True).clamp_(max=cu.numel() - 2)
+    return seq, rows - cu[seq]
+
+
+def _pack_mask_torch(src: Tensor, cu_q: Tensor, cu_k: Tensor, total_q: int, max_q: int, max_k: int, threshold: float,
+                     key_index: Optional[Tensor], release: bool) -> Tuple[Tensor, Tensor]:
+    """The definition of ``wcn_attn_mask_pack`` in plain torch, no Python loop over sequences or rows."""
+    dev = src.device
+    cu_q, cu_k = cu_q.to(device=dev, dtype=torch.int64), cu_k.to(device=dev, dtype=torch.int64)
+    rows = src if key_index is None else src[key_index.to(device=dev, dtype=torch.int64)]
+    blocked = rows != 0 if rows.dtype in (torch.bool, torch.uint8) else rows.float() < threshold   # [Tk, Q]
+    tk = blocked.shape[0]
+    wq, wk = _mask_words(max_q), _mask_words(max_k)
+    seq_k, pos_k = _row_sequences(cu_k, tk)                              # sequence and position of every key row
+    len_q, len_k = cu_q[1:] - cu_q[:-1], cu_k[1:] - cu_k[:-1]
+    cols = torch.arange(32 * wq, device=dev)
+    in_seq = cols[None, :] < len_q[seq_k][:, None]                       # [Tk, 32 Wq]: column j is a query of the key's sequence
+    kb = torch.zeros(tk, 32 * wq, dtype=torch.bool, device=dev)
+    n = min(blocked.shape[1], 32 * wq)
+    kb[:, :n] = blocked[:, :n]
+    kb &= in_seq
+    # the query layout: pair (key row r, column j) is (query row cu_q[seq] + j, key position r - cu_k[seq])
+    q_row = (cu_q[seq_k][:, None] + cols[None, :]).clamp_(max=max(total_q - 1, 0))
+    qb = torch.zeros(total_q, 32 * wk, dtype=torch.bool, device=dev)
+    r, j = kb.nonzero(as_tuple=True)
+    qb[q_row[r, j], pos_k[r]] = True
+    if release:  # a query whose every key is blocked sees all of them
+        seq_q, _ = _row_sequences(cu_q, total_q)
+        full = (qb.sum(1) == len_k[seq_q]) & (len_k[seq_q] > 0)
+        qb &= ~full[:, None]
+        kb &= ~(full[q_row] & in_seq)
+    return _to_words(qb), _to_words(kb)
+
+
+def pack_attention_mask(logits_or_bool: Tensor, cu_seqlens_k: Tensor, cu_seqlens_q: Tensor, max_seqlen_q: int, max_seqlen_k: int,
+                        threshold: float = 0.0, key_index: Optional[Tensor] = None, release_full_rows: bool = True,
+                        backend: Optional[str] = None, total_q: Optional[int] = None) -> PackedAttentionMask:
+    """The block mask of a masked cross-attention call from ``logits_or_bool`` [Tk, Q]: row t is a key row, column j query j
+    of that key's sequence (``max_seqlen_q`` <= Q) - the rows ``segment_bmm`` / ``MaskInnerProduct`` produce.  fp32 / fp16 /
+    bf16: blocked where ``logit < threshold``; bool / uint8: blocked where set.  ``key_index`` (int [Tk']) selects and reorders
+    the key rows (a training-time key subsample); ``cu_seqlens_k`` then bounds those Tk' rows.  ``release_full_rows``: a query
+    whose every key is blocked is released - it attends to all its keys (the Mask2Former rule).  ``backend``: ``"hip"`` (one
+    kernel through 32 x 32 tiles in LDS, a second one for the release; no host read), ``"torch"`` (the same words from plain
+    loop-free torch, on any device) or None (hip on a GPU tensor).  ``total_q``: the number of query rows; None reads it from
+    ``cu_seqlens_q`` (a host read when that lives on the device)."""
+    src = logits_or_bool
+    if src.ndim != 2:
+        raise ValueError(f"logits_or_bool must be [Tk, Q], got {tuple(src.shape)}")
+    if src.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.bool, torch.uint8):
+        raise TypeError(f"pack_attention_mask: logits must be float32 / float16 / bfloat16 or a bool / uint8 mask, got {src.dtype}")
+    if backend not in (None, "hip", "torch"):
+        raise ValueError(f"backend must be 'hip', 'torch' or None, got {backend!r}")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel() or cu_seqlens_q.numel() < 1:
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must have the same length >= 1")
+    max_q, max_k = int(max_seqlen_q), int(max_seqlen_k)
+    if max_q < 0 or max_k < 0 or max_q > src.shape[1]:
+        raise ValueError(f"max_seqlen_q must be in [0, Q = {src.shape[1]}] and max_seqlen_k >= 0, got {max_q} and {max_k}")
+    if not math.isfinite(float(threshold)):
+        raise ValueError(f"threshold must be finite, got {threshold}")
+    total_q = int(cu_seqlens_q[-1]) if total_q is None else int(total_q)
+    total_k = int(key_index.numel()) if key_index is not None else src.shape[0]
+    if not cu_seqlens_q.is_cuda:
+        _check_host_cu(cu_seqlens_q, total_q, max_q)
+    if not cu_seqlens_k.is_cuda:
+        _check_host_cu(cu_seqlens_k, total_k, max_k)
+    backend = backend or ("hip" if src.is_cuda else "torch")
+    if backend == "torch":
+        qw, kw = _pack_mask_torch(src, cu_seqlens_q, cu_seqlens_k, total_q, max_q, max_k, float(threshold), key_index,
+                                  bool(release_full_rows))
+        return PackedAttentionMask(qw, kw, total_q, total_k, max_q, max_k)
+    _lib.require_gpu_tensor(src.contiguous(), "logits_or_bool")
+    dev = src.device
+    src = src.contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    code = _lib.WCN_ATTN_MASK_U8 if src.dtype == torch.uint8 else _lib.dtype_code(src.dtype)
+    cu_q = cu_seqlens_q.to(device=dev, dtype=torch.int32).contiguous()
+    cu_k = cu_seqlens_k.to(device=dev, dtype=torch.int32).contiguous()
+    ki = None if key_index is None else key_index.to(device=dev, dtype=torch.int32).contiguous()
+    L = _lib.lib()
+    wk, wq = L.wcn_attn_mask_words(max_k), L.wcn_attn_mask_words(max_q)
+    qw = torch.empty(total_q, wk, dtype=torch.int32, device=dev)   # the kernel writes every word of every in-sequence row
+    kw = torch.empty(total_k, wq, dtype=torch.int32, device=dev)
+    _lib.check(
+        L.wcn_attn_mask_pack(_lib.ptr(src), code, src.shape[0], src.stride(0) if src.shape[0] > 1 else src.shape[1], src.shape[1],
+                             float(threshold), _lib.ptr(ki), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, total_q, total_k,
+                             max_q, max_k, int(bool(release_full_rows)), _lib.ptr(qw), wk, _lib.ptr(kw), wq,
+                             _lib.stream_handle(dev)),
+        "wcn_attn_mask_pack",
+    )
+    return PackedAttentionMask(qw, kw, total_q, total_k, max_q, max_k)
+
+
+def masked_attention_reference(q: Tensor, k: Tensor, v: Tensor, cu_q: Tensor, cu_k: Tensor, max_q: int, max_k: int,
+                               mask: PackedAttentionMask, scale: Optional[float] = None,
+                               dtype: Optional[torch.dtype] = None) -> Tuple[Tensor, Tensor]:
+    """Masked softmax attention per sequence as one padded batch, loop-free and differentiable, on any device: the words of
+    ``mask`` unpacked to a bool mask, blocked pairs at probability 0.  ``q`` [Tq, H, D], ``k`` / ``v`` [Tk, H, D] -> ``out``
+    [Tq, H, D], ``lse`` [Tq, H] in ``dtype`` (None: fp32 for 16-bit inputs, else the inputs').  A query with no allowed key
+    gets ``out = 0`` and ``lse = -inf``, and no gradient flows through it."""
+    tq, h, d = q.shape
+    dev = q.device
+    if dtype is None:
+        dtype = torch.float32 if q.dtype in (torch.float16, torch.bfloat16) else q.dtype
+    scale = d ** -0.5 if scale is None else float(scale)
+    cq, ck = cu_q.to(device=dev, dtype=torch.int64), cu_k.to(device=dev, dtype=torch.int64)
+    b = cq.numel() - 1
+    if b == 0 or tq == 0 or max_q == 0:
+        return q.new_zeros(tq, h, d, dtype=dtype), q.new_zeros(tq, h, dtype=dtype)
+    iq, ik = torch.arange(max_q, device=dev), torch.arange(max(max_k, 1), device=dev)
+    ok_q = iq[None, :] < (cq[1:] - cq[:-1])[:, None]                                      # [B, Mq]
+    ok_k = ik[None, :] < (ck[1:] - ck[:-1])[:, None]                                      # [B, Mk]
+    rq = (cq[:-1, None] + iq[None, :]).clamp_(max=tq - 1)                                 # padded row -> row of q
+    rk = (ck[:-1, None] + ik[None, :]).clamp_(max=max(k.shape[0] - 1, 0))
+    blocked = torch.zeros(tq, ik.numel(), dtype=torch.bool, device=dev)
+    blocked[:, :max_k] = unpack_attention_mask(mask).to(dev)
+    allowed = ok_q[:, :, None] & ok_k[:, None, :] & ~blocked[rq]                          # [B, Mq, Mk]
+    if k.shape[0] == 0:
+        k, v = k.new_zeros(1, h, d), v.new_zeros(1, h, d)
+    qp, kp, vp = q.to(dtype)[rq], k.to(dtype)[rk], v.to(dtype)[rk]                        # [B, M, H, D]
+    s = torch.einsum("bqhd,bkhd->bhqk", qp, kp) * scale
+    al = allowed[:, None]
+    s = torch.where(al, s, torch.zeros_like(s))
+    mx = torch.where(al, s, torch.full_like(s, float("-inf"))).amax(-1, keepdim=True).detach()
+    any_key = mx > float("-inf")
+    mx = torch.where(any_key, mx, torch.zeros_like(mx))
+    e = torch.where(al, torch.exp(s - mx), torch.zeros_like(s))
+    den = e.sum(-1, keepdim=True)
+    p = e / torch.where(any_key, den, torch.ones_like(den))
+    outp = torch.einsum("bhqk,bkhd->bqhd", p, vp)
+    lsep = torch.where(any_key, mx + torch.log(torch.where(any_key, den, torch.ones_like(den))),
+                       torch.full_like(mx, float("-inf")))[..., 0].transpose(1, 2)      # [B, Mq, H]
+    out = q.new_zeros(tq, h, d, dtype=dtype).index_put((rq[ok_q],), outp[ok_q])
+    lse = q.new_zeros(tq, h, dtype=dtype).index_put((rq[ok_q],), lsep[ok_q])
+    return out, lse
+
+
+class _MaskedCrossVarlenAttention(Function):
+    """``_CrossVarlenAttention`` on the masked kernels: ``v`` None means ``k`` is kv-packed [Tk, 2, H, D].  The mask words are
+    saved for the backward, which reads ``q_words`` in dQ and ``k_words`` in dK/dV."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Optional[Tensor], cu_q: Tensor, cu_k: Tensor, max_q: int, max_k: int, scale: float,
+                k_splits: int, q_words: Tensor, k_words: Tensor) -> Tensor:
+        packed = v is None
+        kk, vv = (k[:, 0], k[:, 1]) if packed else (k, v)
+        tq, h, d = q.shape
+        dev = q.device
+        L = _lib.lib()
+        if k_splits == 0:  # resolved once: the backward's dQ sweep uses the same count
+            k_splits = L.wcn_attn_varlen_k_splits(cu_q.numel() - 1, max_q, max_k, h, 0)
+        out = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
+        lse = torch.empty(tq, h, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, kk.shape[0], h, d, 1, k_splits, 0), dtype=torch.uint8,
+                         device=dev)
+        _lib.check(
+            L.wcn_attn_varlen_kv_fwd_m(_lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk), _lib.ptr(cu_q),
+                                       _lib.ptr(cu_k), cu_q.numel() - 1, tq, kk.shape[0], h, d, max_q, max_k, scale,
+                                       _lib.dtype_code(q.dtype), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(q_words),
+                                       q_words.shape[1], _lib.ptr(k_words), k_words.shape[1], k_splits,
+                                       _lib.ptr(ws) if ws.numel() else None, ws.numel(), _lib.stream_handle(dev)),
+            "wcn_attn_varlen_kv_fwd_m",
+        )
+        ctx.args = (max_q, max_k, scale, k_splits)
+        ctx.save_for_backward(q, k, v, cu_q, cu_k, out, lse, q_words, k_words)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: Tensor):
+        q, k, v, cu_q, cu_k, out, lse, q_words, k_words = ctx.saved_tensors
+        max_q, max_k, scale, k_splits = ctx.args
+        packed = v is None
+        kk, vv = (k[:, 0], k[:, 1]) if packed else (k, v)
+        tq, h, d = q.shape
+        tk = kk.shape[0]
+        dev = q.device
+        dout = dout.to(q.dtype).contiguous()
+        dq = torch.empty(tq, h, d, dtype=q.dtype, device=dev)
+        if packed:
+            dkv = torch.empty(tk, 2, h, d, dtype=q.dtype, device=dev)
+            dk, dv = dkv[:, 0], dkv[:, 1]
+        else:
+            dk, dv = torch.empty(tk, h, d, dtype=q.dtype, device=dev), torch.empty(tk, h, d, dtype=q.dtype, device=dev)
+        L = _lib.lib()
+        ws = torch.empty(L.wcn_attn_varlen_ksplit_workspace_bytes(tq, tk, h, d, 1, k_splits, 1), dtype=torch.uint8, device=dev)
+        _lib.check(
+            L.wcn_attn_varlen_kv_bwd_m(_lib.ptr(dout), _lib.ptr(q), _row_stride(q), _lib.ptr(kk), _lib.ptr(vv), _row_stride(kk),
+                                       _lib.ptr(out), _lib.ptr(lse), _lib.ptr(cu_q), _lib.ptr(cu_k), cu_q.numel() - 1, tq, tk, h, d,
+                                       max_q, max_k, scale, _lib.dtype_code(q.dtype), _lib.ptr(dq), h * d, _lib.ptr(dk),
+                                       _lib.ptr(dv), (2 if packed else 1) * h * d, _lib.ptr(q_words), q_words.shape[1],
+                                       _lib.ptr(k_words), k_words.shape[1], k_splits, _lib.ptr(ws) if ws.numel() else None,
+                                       ws.numel(), _lib.stream_handle(dev)),
+            "wcn_attn_varlen_kv_bwd_m",
+        )
+        return (dq, dkv if packed else dk, None if packed else dv) + (None,) * 8
+
+
+def _masked_cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_q: int,
+                         max_k: int, dropout_p: float, softmax_scale: Optional[float], kv: Optional[Tensor], variant, k_splits: int,
+                         mask: PackedAttentionMask) -> Tensor:
+    """The masked form of both public functions: its own checks, then the composed path (CPU tensors) or the kernels."""
+    if not isinstance(mask, PackedAttentionMask):
+        raise TypeError(f"{name}: attn_mask must be a PackedAttentionMask (pack_attention_mask), got {type(mask).__name__}")
+    if variant != "auto" and variant != _lib.WCN_ATTN_AUTO:
+        raise NotImplementedError(f"{name}: a masked call runs the masked kernels; variant must be 'auto', got {variant!r}")
+    if not isinstance(k_splits, int) or isinstance(k_splits, bool) or k_splits < 0:
+        raise ValueError(f"k_splits must be an int >= 0 (0: the library's rule, 1: no split), got {k_splits!r}")
+    if dropout_p > 0.0:
+        raise NotImplementedError(f"{name}: dropout is not implemented (dropout_p must be 0)")
+    if q.ndim != 3 or k.ndim != 3 or k.shape != v.shape or k.shape[1:] != q.shape[1:]:
+        raise ValueError(f"q must be [Tq, H, D] and k, v [Tk, H, D], got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    d = q.shape[2]
+    if d == 128:
+        raise NotImplementedError(f"{name}: attn_mask is not implemented for head_dim 128 (16, 32 or 64)")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must have the same length")
+    sizes = (q.shape[0], k.shape[0], int(max_q), int(max_k))
+    built = (mask.total_q, mask.total_k, mask.max_seqlen_q, mask.max_seqlen_k)
+    if sizes != built:
+        raise ValueError(f"{name}: attn_mask was built for (total_q, total_k, max_seqlen_q, max_seqlen_k) = {built}, the call "
+                         f"has {sizes}")
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"softmax_scale must be finite, got {scale}")
+    if not cu_seqlens_q.is_cuda:
+        _check_host_cu(cu_seqlens_q, q.shape[0], int(max_q))
+    if not cu_seqlens_k.is_cuda:
+        _check_host_cu(cu_seqlens_k, k.shape[0], int(max_k))
+    if not q.is_cuda:  # the composed path: the torch definition, in the inputs' dtype
+        out, _ = masked_attention_reference(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_q), int(max_k), mask, scale)
+        return out.to(q.dtype)
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"{name}: q, k and v must share float16 or bfloat16 (cast them first; there is no fp32 kernel), got "
+                        f"{q.dtype}, {k.dtype}, {v.dtype}")
+    if not hip_attn_varlen_supported(d, q.dtype):
+        raise NotImplementedError(f"{name}: head_dim {d} is not supported with attn_mask (16, 32 or 64)")
+    dev = q.device
+    cu_q = cu_seqlens_q.to(device=dev, dtype=torch.int32).contiguous()
+    cu_k = cu_seqlens_k.to(device=dev, dtype=torch.int32).contiguous()
+    qw, kw = mask.q_words.to(dev).contiguous(), mask.k_words.to(dev).contiguous()
+    if not _kernel_rows(q):
+        q = q.contiguous()
+    if kv is not None:
+        return _MaskedCrossVarlenAttention.apply(q, kv.contiguous(), None, cu_q, cu_k, int(max_q), int(max_k), scale, k_splits, qw, kw)
+    if not (_kernel_rows(k) and _kernel_rows(v) and _row_stride(k) == _row_stride(v)):
+        k, v = k.contiguous(), v.contiguous()
+    return _MaskedCrossVarlenAttention.apply(q, k, v, cu_q, cu_k, int(max_q), int(max_k), scale, k_splits, qw, kw)
+
+
 def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                   max_seqlen_k: int, dropout_p: float, softmax_scale: Optional[float], kv: Optional[Tensor],
                   q_splits: int, variant="auto", k_splits: int = 1) -> Tensor:
@@ -460,7 +755,8 @@ def _cross_varlen(name: str, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tens
 @eager_unless_compiling
 def flash_attn_varlen_func(q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                            max_seqlen_k: int, dropout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                           q_splits: int = 0, variant="auto", k_splits: int = 1) -> Tensor:
+                           q_splits: int = 0, variant="auto", k_splits: int = 1,
+                           attn_mask: Optional[PackedAttentionMask] = None) -> Tensor:
     """Attention of the queries of sequence s, rows [cu_q[s], cu_q[s+1]) of ``q`` [Tq, H, D], over its keys, rows
     [cu_k[s], cu_k[s+1]) of ``k`` / ``v`` [Tk, H, D] -> [Tq, H, D]; fp16 / bf16 on the GPU.  The call the reference makes
     into the flash_attn package, minus dropout; differentiable in q, k and v (deterministic backward).  Host boundaries are
@@ -468,7 +764,13 @@ def flash_attn_varlen_func(q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor
     split count of the backward's dK/dV sweep (0: the library's rule), ``variant`` names the kernels as in
     ``flash_attn_varlen_qkvpacked``.  ``k_splits`` cuts the key sweep of the forward and of dQ into that many shares whose
     fp32 partials a second kernel combines in a fixed order - for a few queries against a very long context (1, the default:
-    no split; 0: the library's rule, ``wcn_attn_varlen_k_splits``); the backward uses the forward's count."""
+    no split; 0: the library's rule, ``wcn_attn_varlen_k_splits``); the backward uses the forward's count.  ``attn_mask`` (a
+    ``PackedAttentionMask`` built for these sizes): blocked pairs get probability 0 on the masked kernels of
+    `csrc/attn_varlen_masked.hip` - head_dim 16 / 32 / 64, ``variant="auto"`` only, ``q_splits`` unused (dK/dV runs one wave per
+    key block), ``k_splits`` as above; CPU tensors run ``masked_attention_reference``.  None is the unmasked call, bit for bit."""
+    if attn_mask is not None:
+        return _masked_cross_varlen("flash_attn_varlen_func", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                                    dropout_p, softmax_scale, None, variant, k_splits, attn_mask)
     return _cross_varlen("flash_attn_varlen_func", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
                          dropout_p, softmax_scale, None, q_splits, variant, k_splits)
 
@@ -476,10 +778,14 @@ def flash_attn_varlen_func(q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: Tensor
 @eager_unless_compiling
 def flash_attn_varlen_kvpacked_func(q: Tensor, kv: Tensor, cu_seqlens_q: Tensor, cu_seqlens_k: Tensor, max_seqlen_q: int,
                                     max_seqlen_k: int, dropout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                                    q_splits: int = 0, variant="auto", k_splits: int = 1) -> Tensor:
+                                    q_splits: int = 0, variant="auto", k_splits: int = 1,
+                                    attn_mask: Optional[PackedAttentionMask] = None) -> Tensor:
     """``flash_attn_varlen_func`` with keys and values as the two slots of ``kv`` [Tk, 2, H, D].  The kernels read the
     slots through their strides, and write the gradient of ``kv`` as one [Tk, 2, H, D] tensor the same way (no ``cat``)."""
     if kv.ndim != 4 or kv.shape[1] != 2:
         raise ValueError(f"kv must be [Tk, 2, H, D], got {tuple(kv.shape)}")
+    if attn_mask is not None:
+        return _masked_cross_varlen("flash_attn_varlen_kvpacked_func", q, kv[:, 0], kv[:, 1], cu_seqlens_q, cu_seqlens_k,
+                                    max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, kv, variant, k_splits, attn_mask)
     return _cross_varlen("flash_attn_varlen_kvpacked_func", q, kv[:, 0], kv[:, 1], cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
                          max_seqlen_k, dropout_p, softmax_scale, kv, q_splits, variant, k_splits)
